@@ -676,7 +676,25 @@ class Workload:
                                   buf.data_ptr(), self.stride_bytes, self.stream)
         if ev_pair:
             ev_pair[1].record()
+        self.last_n = n
         return n
+
+    def dump_outputs(self, buf, out_dir, budget_bytes=60_000_000):
+        """What the last launch gave its caller: the packed s16 PCM of every stream, `last_n` sample-frames x out_ch.
+        Written as DIR/pcm.npy, float32 [streams, sample-frames, out_ch] holding the int16 values exactly, for a fixed
+        seeded sample of the streams that keeps the file under `budget_bytes` (all of them when they fit), and
+        DIR/pcm_streams.npy, float64, the stream indices of that sample."""
+        n, ch = self.last_n, self.out_ch
+        per_stream = n * ch * 4
+        k = min(self.S, max(1, budget_bytes // per_stream))
+        n_kept = min(n, budget_bytes // (ch * 4))   # only when one stream alone is over the budget: its first samples
+        ids = np.arange(self.S) if k == self.S else np.sort(np.random.default_rng(0).choice(self.S, k, replace=False))
+        rows = buf[torch.from_numpy(ids).to(buf.device), :n_kept * ch * 2].cpu().numpy()
+        pcm = rows.view(np.int16).reshape(k, n_kept, ch).astype(np.float32)
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "pcm.npy"), pcm)
+        np.save(os.path.join(out_dir, "pcm_streams.npy"), ids.astype(np.float64))
+        return {"dir": out_dir, "pcm": list(pcm.shape), "streams_of": self.S, "sample_frames_of": n}
 
     def verify(self, k=4):
         """After the timed regions: reset the stream state, render ONE more launch of exactly the timed geometry
@@ -875,7 +893,7 @@ def device_info():
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="launches in each timed region")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5,
                     help="timed regions of --steps launches each; value is the MEDIAN region, all are listed")
@@ -918,6 +936,10 @@ def parse_args(argv=None):
                     help="stagger the streams' input regions: stream stride = frames * channels * frame size "
                          "+ this many KiB, so that the workgroups, which advance in step, are not all on the "
                          "same HBM channel at once (0 = the power-of-two stride: -12 %% on the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the headline workload's last timed launch computed (rank 0's "
+                         "packed PCM, a fixed sample of streams as float32: DIR/pcm.npy, DIR/pcm_streams.npy) so that two "
+                         "builds can be compared output for output")
     return ap.parse_args(argv)
 
 
@@ -926,6 +948,8 @@ def main():
     from iac_amd import launch
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and not launch.under_launcher():
         # `python bench.py --gpus N` with no launcher around it: THIS process becomes the launcher.
         # It has made no GPU call (torch is imported, nothing under torch.cuda was called, the HIP
@@ -1022,6 +1046,10 @@ def main():
             same = sum(int(torch.equal(final_recv[r], final_recv[0])) for r in range(1, world))
             assert same == 0, "gather delivered identical PCM from %d other rank(s)" % same
 
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before anything else renders into the PCM buffers
+        dumped = wl.dump_outputs(pipe.buffers[(pipe.i - 1) % 2], args.dump_outputs)
+
     first_alloc = None
     if world == 1 and (wl.x_first is not None or wl.pcm_first is not None):
         # what a deployment that takes its buffers as hipMalloc hands them out gets: one more region on the FIRST
@@ -1093,6 +1121,7 @@ def main():
             "roofline": roof,
             "verified": verified,
             "value_first_allocation": first_alloc["value"] if first_alloc else round(value, 2),
+            "dumped_outputs": dumped,
             "first_allocation": first_alloc or {"note": "the search kept the first allocations: value is the unsearched rate"},
         }
         try:   # the C-side multi-device entry (include/iamf_hip.h iamf_hip_shard_*) finds its RCCL by dlopen

@@ -225,16 +225,25 @@ def shard_rehearsal(request):
     return request.param, _build_shard_rehearsal(request.param)
 
 
-def _run_shard(rehearsal, args, env_extra=None):
+def _spawn_driver(kind, b, args, env, timeout=300):
     import subprocess
+    cmd = [os.path.join(b, "shard_driver")] + [str(a) for a in args]
+    if kind == "tsan":
+        # gcc's TSan runtime assumes less mmap randomisation than newer kernels allow: with more, its shadow layout collides
+        # with the randomised mappings ("unexpected memory mapping", or a SIGSEGV with no report).  The driver runs with
+        # address randomisation off for this one child (a personality flag of the process).
+        cmd = ["setarch", os.uname().machine, "-R"] + cmd
+    return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
+
+
+def _run_shard(rehearsal, args, env_extra=None):
     kind, b = rehearsal
     env = dict(os.environ, IAMF_HIP_RCCL_LIB=os.path.join(b, "librccl_fake.so"), ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",
                TSAN_OPTIONS="halt_on_error=1")
     env.update(env_extra or {})
-    r = subprocess.run([os.path.join(b, "shard_driver")] + [str(a) for a in args], capture_output=True, text=True, timeout=300, env=env)
+    r = _spawn_driver(kind, b, args, env)
     if "LeakSanitizer has encountered a fatal error" in r.stderr:   # LeakSanitizer cannot always stop the world in a container
-        r = subprocess.run([os.path.join(b, "shard_driver")] + [str(a) for a in args], capture_output=True, text=True, timeout=300,
-                           env=dict(env, ASAN_OPTIONS="detect_leaks=0"))
+        r = _spawn_driver(kind, b, args, dict(env, ASAN_OPTIONS="detect_leaks=0"))
     assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
     assert r.returncode == 0 and "MISMATCH" not in r.stdout, (r.returncode, r.stdout[-1500:], r.stderr[-1500:])
     return r.stdout.strip().splitlines()
@@ -279,8 +288,7 @@ def test_shard_failing_peer_is_reported_and_the_shard_goes_on(shard_rehearsal):
 
 def test_shard_refuses_more_devices_than_streams_and_comm_init_failure(shard_rehearsal):
     assert _run_shard(shard_rehearsal, [3, 4, 0, 1, "rows"])[0].startswith("create -1")   # IAMF_HIP_ERR_BAD_ARG
-    import subprocess
     kind, b = shard_rehearsal
     env = dict(os.environ, IAMF_HIP_RCCL_LIB=os.path.join(b, "librccl_fake.so"), FAKE_RCCL_FAIL_INIT="1", ASAN_OPTIONS="detect_leaks=0")
-    r = subprocess.run([os.path.join(b, "shard_driver"), "6", "3", "0", "1", "rows"], capture_output=True, text=True, timeout=120, env=env)
+    r = _spawn_driver(kind, b, [6, 3, 0, 1, "rows"], env, timeout=120)
     assert "MISMATCH gather step 0 returned" in r.stdout and "ncclCommInitAll failed" in r.stderr
