@@ -41,7 +41,7 @@ struct iamf_hip_decoder_group {
    * and a row of ones per stream — element 1's mix gain is applied by `aux` through ramp row 1 */
   iamf_hip_batch *aux;
   float *d_aux_il, *d_aux_pl, *d_ones;
-  iamf_hip_dmx_frame *h_dmx1, *d_dmx1;       /* [n] */
+  iamf_hip_dmx_frame *h_dmx1, *d_dmx1;       /* [n] (h_dmx1: the current slot's, group_use_slot) */
   iamf_hip_demix_frame *h_demix1, *d_demix1; /* [n] */
   /* resampling handles: the stages behind the render batch (as IAMF_Decoder::rs / batch3 / d_mid / d_res, for n streams) */
   iamf_hip_batch *batch3;
@@ -67,7 +67,7 @@ struct iamf_hip_decoder_group {
   int chunk, nchunks;             /* handles per upload chunk; the uploads of chunk c run beside the parsing of chunk c + 1 */
   int *chunk_done;                /* [nchunks]: handles of the chunk the pool has finished (atomic) */
   int job;                        /* what the pool does this time: 0 parse + stage, 1 hand out the PCM */
-  void *const *pcm_out;
+  void **pcm_out;
   float *h_ramp[3], *d_ramp[3];   /* [n][fs] */
   iamf_hip_dmx_frame *h_dmx, *d_dmx;       /* [n] */
   iamf_hip_demix_frame *h_demix, *d_demix; /* [n] */
@@ -81,6 +81,24 @@ struct iamf_hip_decoder_group {
   const uint8_t *const *data;
   const int32_t *sizes;
   uint32_t *rsizes;
+  /* Two rounds in flight (iamf_hip_decoder_group_submit / _complete): everything the host writes in a round and the
+   * device or the copy engine reads later has one copy per slot; round `ticket` uses slot ticket & 1, and the fields
+   * above that name such a buffer (h_raw, h_ramp, h_dmx, h_demix, h_dmx1, h_demix1, h_pcm, action .. te, pcm_out) point
+   * at the slot the call is working on (group_use_slot).  Device buffers stay single: the group's one in-order stream
+   * runs round k + 1's upload and launches after round k's last kernel, so round k + 1 can only overwrite d_raw, d_in,
+   * d_ramp, ... once round k has read them; only what the HOST writes before round k's kernels have run needs two. */
+  struct {
+    uint8_t *h_raw[2];
+    float *h_ramp[3];
+    iamf_hip_dmx_frame *h_dmx, *h_dmx1;
+    iamf_hip_demix_frame *h_demix, *h_demix1;
+    uint8_t *h_pcm;
+    int *action, *keep, *s0, *result, *rampf, *te;
+    void **pcm_out;   /* [n]: the caller's pcm[] of the round, copied at submit */
+    int dev;          /* the round queued device work: its completion is signalled (h_sig) */
+  } slot[2];
+  uint64_t issued, done;      /* tickets: the last submitted, the last completed (issued - done = rounds outstanding) */
+  volatile uint32_t *h_sig;   /* pinned word: iamf_hip_stream_signal writes a round's ticket behind its last launch */
   /* host thread pool: workers take handle indices from `next` */
   int nthreads;
   pthread_t *threads;
@@ -104,6 +122,24 @@ int iamf_hip_decoder_group_times(const iamf_hip_decoder_group *g, double *second
   for (int k = 0; k < 4; ++k) seconds4[k] = g->t_phase[k];
   if (rounds) *rounds = g->rounds;
   return IAMF_OK;
+}
+
+/* the round-local fields name slot `sl`'s buffers from here on (a round's submit, its complete) */
+static void group_use_slot(iamf_hip_decoder_group *g, int sl) {
+  for (int e = 0; e < 2; ++e) g->h_raw[e] = g->slot[sl].h_raw[e];
+  for (int k = 0; k < 3; ++k) g->h_ramp[k] = g->slot[sl].h_ramp[k];
+  g->h_dmx = g->slot[sl].h_dmx;
+  g->h_dmx1 = g->slot[sl].h_dmx1;
+  g->h_demix = g->slot[sl].h_demix;
+  g->h_demix1 = g->slot[sl].h_demix1;
+  g->h_pcm = g->slot[sl].h_pcm;
+  g->action = g->slot[sl].action;
+  g->keep = g->slot[sl].keep;
+  g->s0 = g->slot[sl].s0;
+  g->result = g->slot[sl].result;
+  g->rampf = g->slot[sl].rampf;
+  g->te = g->slot[sl].te;
+  g->pcm_out = g->slot[sl].pcm_out;
 }
 
 static int group_parse_one(iamf_hip_decoder_group *g, int i);
@@ -323,6 +359,8 @@ void iamf_hip_decoder_group_destroy(iamf_hip_decoder_group *g) {
     pthread_cond_destroy(&g->cv_work);
     pthread_cond_destroy(&g->cv_done);
   }
+  /* rounds still outstanding: their device work is waited for, their PCM is never handed out (the caller's pcm buffers
+   * of those rounds stay as they are); their clocks had moved at submit, as they would have by their _complete */
   if (g->stream) (void)hipStreamSynchronize(g->stream);
   for (int i = 0; i < g->n && g->d; ++i)
     if (g->d[i] && g->d[i]->group == g) {
@@ -330,7 +368,8 @@ void iamf_hip_decoder_group_destroy(iamf_hip_decoder_group *g) {
       d->group = 0;
       for (int e = 0; e < 2; ++e)
         for (int s2 = 0; s2 < MAX_SUBSTREAMS; ++s2) {
-          /* a packet of a temporal unit that is still incomplete lives in the row that is about to go: back to the heap */
+          /* a packet of a temporal unit that is still incomplete lives in the row that is about to go (the slot of the
+           * handle's last submit: group_parse_one moves it along): back to the heap */
           if (d->pkt_in_ext[e][s2] && d->pkt_have[e][s2] && d->pkt_ext[e][s2]) {
             const uint32_t len = d->pkt_len[e][s2];
             if (len > d->pkt_cap[e][s2]) {
@@ -354,9 +393,7 @@ void iamf_hip_decoder_group_destroy(iamf_hip_decoder_group *g) {
   if (g->d_aux_il) (void)hipFree(g->d_aux_il);
   if (g->d_aux_pl) (void)hipFree(g->d_aux_pl);
   if (g->d_ones) (void)hipFree(g->d_ones);
-  if (g->h_dmx1) (void)hipHostFree(g->h_dmx1);
   if (g->d_dmx1) (void)hipFree(g->d_dmx1);
-  if (g->h_demix1) (void)hipHostFree(g->h_demix1);
   if (g->d_demix1) (void)hipFree(g->d_demix1);
   if (g->batch3) iamf_hip_batch_destroy(g->batch3);
   if (g->rs) iamf_hip_resampler_destroy(g->rs);
@@ -365,30 +402,37 @@ void iamf_hip_decoder_group_destroy(iamf_hip_decoder_group *g) {
   free(g->pos3);
   free(g->loud3);
   for (int e = 0; e < 2; ++e) {
-    if (g->h_raw[e]) (void)hipHostFree(g->h_raw[e]);
     if (g->d_raw[e]) (void)hipFree(g->d_raw[e]);
     if (g->d_in[e]) (void)hipFree(g->d_in[e]);
   }
   for (int k = 0; k < 3; ++k) free(g->cgain[k]);
   free(g->chunk_done);
-  for (int k = 0; k < 3; ++k) {
-    if (g->h_ramp[k]) (void)hipHostFree(g->h_ramp[k]);
+  for (int k = 0; k < 3; ++k)
     if (g->d_ramp[k]) (void)hipFree(g->d_ramp[k]);
-  }
-  if (g->h_dmx) (void)hipHostFree(g->h_dmx);
   if (g->d_dmx) (void)hipFree(g->d_dmx);
-  if (g->h_demix) (void)hipHostFree(g->h_demix);
   if (g->d_demix) (void)hipFree(g->d_demix);
-  if (g->h_pcm) (void)hipHostFree(g->h_pcm);
+  for (int sl = 0; sl < 2; ++sl) {
+    for (int e = 0; e < 2; ++e)
+      if (g->slot[sl].h_raw[e]) (void)hipHostFree(g->slot[sl].h_raw[e]);
+    for (int k = 0; k < 3; ++k)
+      if (g->slot[sl].h_ramp[k]) (void)hipHostFree(g->slot[sl].h_ramp[k]);
+    if (g->slot[sl].h_dmx) (void)hipHostFree(g->slot[sl].h_dmx);
+    if (g->slot[sl].h_dmx1) (void)hipHostFree(g->slot[sl].h_dmx1);
+    if (g->slot[sl].h_demix) (void)hipHostFree(g->slot[sl].h_demix);
+    if (g->slot[sl].h_demix1) (void)hipHostFree(g->slot[sl].h_demix1);
+    if (g->slot[sl].h_pcm) (void)hipHostFree(g->slot[sl].h_pcm);
+    free(g->slot[sl].action);
+    free(g->slot[sl].keep);
+    free(g->slot[sl].s0);
+    free(g->slot[sl].result);
+    free(g->slot[sl].rampf);
+    free(g->slot[sl].te);
+    free(g->slot[sl].pcm_out);
+  }
+  if (g->h_sig) (void)hipHostFree((void *)g->h_sig);
   if (g->stream) (void)hipStreamDestroy(g->stream);
   free(g->gain_cur);
   free(g->gain_new);
-  free(g->action);
-  free(g->keep);
-  free(g->s0);
-  free(g->result);
-  free(g->rampf);
-  free(g->te);
   free(g->pos);
   free(g->d);
   free(g);
@@ -419,12 +463,20 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
   g->nel = d0->sel->nel;
   g->bytes = (int)d0->bit_depth / 8;
   g->d = (struct IAMF_Decoder **)calloc((size_t)n, sizeof(*g->d));
-  g->action = (int *)calloc((size_t)n, sizeof(int));
-  g->keep = (int *)calloc((size_t)n, sizeof(int));
-  g->s0 = (int *)calloc((size_t)n, sizeof(int));
-  g->result = (int *)calloc((size_t)n, sizeof(int));
-  g->rampf = (int *)calloc((size_t)n, sizeof(int));
-  g->te = (int *)calloc((size_t)n, sizeof(int));
+  for (int sl = 0; sl < 2; ++sl) {
+    g->slot[sl].action = (int *)calloc((size_t)n, sizeof(int));
+    g->slot[sl].keep = (int *)calloc((size_t)n, sizeof(int));
+    g->slot[sl].s0 = (int *)calloc((size_t)n, sizeof(int));
+    g->slot[sl].result = (int *)calloc((size_t)n, sizeof(int));
+    g->slot[sl].rampf = (int *)calloc((size_t)n, sizeof(int));
+    g->slot[sl].te = (int *)calloc((size_t)n, sizeof(int));
+    g->slot[sl].pcm_out = (void **)calloc((size_t)n, sizeof(void *));
+    if (!g->slot[sl].action || !g->slot[sl].keep || !g->slot[sl].s0 || !g->slot[sl].result || !g->slot[sl].rampf ||
+        !g->slot[sl].te || !g->slot[sl].pcm_out) {
+      iamf_hip_decoder_group_destroy(g);
+      return IAMF_ERR_ALLOC_FAIL;
+    }
+  }
   g->lfe[0] = d0->cfg_sig.lfe_hoa;
   g->lfe[1] = d0->aux && d0->aux_sig.lfe_hoa;
   g->pos = (int64_t *)calloc((size_t)n, sizeof(int64_t));
@@ -433,7 +485,7 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
   g->limiter_on = d0->limiter_on;
   g->gain_cur = (float *)malloc(sizeof(float) * 2 * n);
   g->gain_new = (float *)malloc(sizeof(float) * 2 * n);
-  if (!g->d || !g->action || !g->keep || !g->s0 || !g->result || !g->rampf || !g->te || !g->pos || !g->pos3 || !g->gain_cur || !g->gain_new) {
+  if (!g->d || !g->pos || !g->pos3 || !g->gain_cur || !g->gain_new) {
     iamf_hip_decoder_group_destroy(g);
     return IAMF_ERR_ALLOC_FAIL;
   }
@@ -489,9 +541,11 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
       rc = rc || hipMalloc((void **)&g->d_aux_il, sizeof(float) * fr) != hipSuccess ||
            hipMalloc((void **)&g->d_aux_pl, sizeof(float) * fr) != hipSuccess ||
            hipMalloc((void **)&g->d_ones, sizeof(float) * (size_t)n * g->fs) != hipSuccess ||
-           hipHostMalloc((void **)&g->h_dmx1, sizeof(iamf_hip_dmx_frame) * (size_t)n, 0) != hipSuccess ||
+           hipHostMalloc((void **)&g->slot[0].h_dmx1, sizeof(iamf_hip_dmx_frame) * (size_t)n, 0) != hipSuccess ||
+           hipHostMalloc((void **)&g->slot[1].h_dmx1, sizeof(iamf_hip_dmx_frame) * (size_t)n, 0) != hipSuccess ||
            hipMalloc((void **)&g->d_dmx1, sizeof(iamf_hip_dmx_frame) * (size_t)n) != hipSuccess ||
-           hipHostMalloc((void **)&g->h_demix1, sizeof(iamf_hip_demix_frame) * (size_t)n, 0) != hipSuccess ||
+           hipHostMalloc((void **)&g->slot[0].h_demix1, sizeof(iamf_hip_demix_frame) * (size_t)n, 0) != hipSuccess ||
+           hipHostMalloc((void **)&g->slot[1].h_demix1, sizeof(iamf_hip_demix_frame) * (size_t)n, 0) != hipSuccess ||
            hipMalloc((void **)&g->d_demix1, sizeof(iamf_hip_demix_frame) * (size_t)n) != hipSuccess;
       if (!rc) { /* the ones, through the ramp rows' own upload path (h_ramp is not allocated yet: a scratch vector) */
         float *h1 = (float *)malloc(sizeof(float) * (size_t)n * g->fs);
@@ -549,9 +603,11 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
     GCHK(hipMalloc((void **)&g->d_in[e], sizeof(float) * (size_t)n * g->in_ch[e] * g->fs) != hipSuccess);
     /* rows of channels that no sub-stream carries in a projection / demixer element are never written: keep them defined */
     GCHK(hipMemset(g->d_in[e], 0, sizeof(float) * (size_t)n * g->in_ch[e] * g->fs) != hipSuccess);
-    GCHK(hipHostMalloc((void **)&g->h_raw[e], g->raw_stride[e] * (size_t)n, 0) != hipSuccess ||
-         hipMalloc(&g->d_raw[e], g->raw_stride[e] * (size_t)n) != hipSuccess);
-    memset(g->h_raw[e], 0, g->raw_stride[e] * (size_t)n);
+    for (int sl = 0; sl < 2; ++sl) {
+      GCHK(hipHostMalloc((void **)&g->slot[sl].h_raw[e], g->raw_stride[e] * (size_t)n, 0) != hipSuccess);
+      memset(g->slot[sl].h_raw[e], 0, g->raw_stride[e] * (size_t)n);
+    }
+    GCHK(hipMalloc(&g->d_raw[e], g->raw_stride[e] * (size_t)n) != hipSuccess);
   }
   /* One mono-coded ambisonics element in 16-bit little-endian LPCM into one or two channels with the limiter on: the
    * headline kernel reads the packets themselves (iamf_hip_batch_render_lpcm_range, fused: no unpacked copy, no unpack
@@ -567,12 +623,15 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
   g->nchunks = (n + g->chunk - 1) / g->chunk;
   GCHK(!(g->chunk_done = (int *)calloc((size_t)g->nchunks, sizeof(int))));
   for (int k = 0; k < 3; ++k)
-    GCHK(hipHostMalloc((void **)&g->h_ramp[k], sizeof(float) * (size_t)n * g->fs, 0) != hipSuccess ||
-         hipMalloc((void **)&g->d_ramp[k], sizeof(float) * (size_t)n * g->fs) != hipSuccess);
-  GCHK(hipHostMalloc((void **)&g->h_dmx, sizeof(iamf_hip_dmx_frame) * (size_t)n, 0) != hipSuccess ||
-       hipMalloc((void **)&g->d_dmx, sizeof(iamf_hip_dmx_frame) * (size_t)n) != hipSuccess);
-  GCHK(hipHostMalloc((void **)&g->h_demix, sizeof(iamf_hip_demix_frame) * (size_t)n, 0) != hipSuccess ||
+    GCHK(hipMalloc((void **)&g->d_ramp[k], sizeof(float) * (size_t)n * g->fs) != hipSuccess);
+  GCHK(hipMalloc((void **)&g->d_dmx, sizeof(iamf_hip_dmx_frame) * (size_t)n) != hipSuccess ||
        hipMalloc((void **)&g->d_demix, sizeof(iamf_hip_demix_frame) * (size_t)n) != hipSuccess);
+  for (int sl = 0; sl < 2; ++sl) {
+    for (int k = 0; k < 3; ++k)
+      GCHK(hipHostMalloc((void **)&g->slot[sl].h_ramp[k], sizeof(float) * (size_t)n * g->fs, 0) != hipSuccess);
+    GCHK(hipHostMalloc((void **)&g->slot[sl].h_dmx, sizeof(iamf_hip_dmx_frame) * (size_t)n, 0) != hipSuccess ||
+         hipHostMalloc((void **)&g->slot[sl].h_demix, sizeof(iamf_hip_demix_frame) * (size_t)n, 0) != hipSuccess);
+  }
   /* one call emits at most one frame (or the 240-sample tail) per stream */
   g->pcm_cap = (size_t)g->bytes * ((size_t)(g->fs > 240 ? g->fs : 240) * d0->pcm_stride + d0->pcm_extra);
   if (g->rs) { /* a frame through the resampler, or its tail + the limiter's */
@@ -580,7 +639,10 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
     g->pcm_cap = (size_t)g->bytes * ((a > b ? a : b) * d0->pcm_stride + d0->pcm_extra);
   }
   g->pcm_cap = (g->pcm_cap + 255) & ~(size_t)255;
-  GCHK(hipHostMalloc((void **)&g->h_pcm, g->pcm_cap * n, 0) != hipSuccess);
+  for (int sl = 0; sl < 2; ++sl) GCHK(hipHostMalloc((void **)&g->slot[sl].h_pcm, g->pcm_cap * n, 0) != hipSuccess);
+  GCHK(hipHostMalloc((void **)&g->h_sig, 64, 0) != hipSuccess);
+  *g->h_sig = 0;
+  group_use_slot(g, 0);
   for (int i = 0; i < n; ++i) {
     struct IAMF_Decoder *d = (struct IAMF_Decoder *)handles[i];
     g->d[i] = d;
@@ -715,17 +777,28 @@ static int group_prepare_tu(iamf_hip_decoder_group *g, int i) {
   return 1;
 }
 
-/* the end of IAMF_decoder_decode for handle i: its PCM, the parameter clocks (IAMF_decoder.c:3471), the stream time */
+/* the end of IAMF_decoder_decode for handle i: its PCM (the clocks have moved at submit, group_advance_clocks) */
 static void group_copy_out_one(iamf_hip_decoder_group *g, int i) {
-  struct IAMF_Decoder *d = g->d[i];
+  const struct IAMF_Decoder *d = g->d[i];
   if (g->action[i] == GA_NONE || g->action[i] == GA_ADVANCE) return; /* (a unit trimmed away: IAMF_decoder_decode returned 0) */
   if (g->result[i] > 0)
     memcpy(g->pcm_out[i], g->h_pcm + g->pcm_cap * (size_t)i, ((size_t)g->result[i] * d->pcm_stride + d->pcm_extra) * g->bytes);
-  if (g->action[i] == GA_RENDER) {
-    params_time_elapse(d, (uint64_t)g->keep[i]); /* the mixed frame's length */
-    d->timestamp += g->fs;
+}
+
+/* The rest of the end of IAMF_decoder_decode: the parameter clocks (IAMF_decoder.c:3471), the stream time, the metadata
+ * of the output.  Every value is known once the round's launches are queued (g->result is the count a launch returned on
+ * the host), so this runs at the end of the submit: the next round's parse (group_prepare_tu reads d->timestamp and the
+ * parameter queues) must see it, and it may start before this round's PCM is back. */
+static void group_advance_clocks(iamf_hip_decoder_group *g) {
+  for (int i = 0; i < g->n; ++i) {
+    struct IAMF_Decoder *d = g->d[i];
+    if (g->action[i] == GA_NONE || g->action[i] == GA_ADVANCE) continue;
+    if (g->action[i] == GA_RENDER) {
+      params_time_elapse(d, (uint64_t)g->keep[i]); /* the mixed frame's length */
+      d->timestamp += g->fs;
+    }
+    meta_note_output(d, g->result[i]); /* a rendered unit or the flushed tail: IAMF_decoder.c:3521-3522 */
   }
-  meta_note_output(d, g->result[i]); /* a rendered unit or the flushed tail: IAMF_decoder.c:3521-3522 */
 }
 
 /* IAMF_decoder_decode's parsing half for handle i (IAMF_decoder.c:2871-2995): sets g->action[i]; returns the call's
@@ -737,6 +810,16 @@ static int group_parse_one(iamf_hip_decoder_group *g, int i) {
   uint32_t *rsize = g->rsizes ? &g->rsizes[i] : 0;
   int ready = 0, rc;
   g->action[i] = GA_NONE;
+  /* decode_parse writes packets straight into this round's slot of the handle's row.  A temporal unit whose sub-stream
+   * packets arrived over earlier calls has them in the slot of the handle's last submit (which a round in flight may
+   * still upload from: it is only read here): they move along into this slot's row */
+  for (int e = 0; e < g->nel; ++e)
+    for (int s2 = 0; s2 < g->nsub_eff[e]; ++s2) {
+      uint8_t *mine = g->h_raw[e] + (size_t)i * g->raw_stride[e] + g->slot_off[e][s2];
+      if (d->pkt_ext[e][s2] == mine) continue;
+      if (d->pkt_in_ext[e][s2] && d->pkt_have[e][s2]) memcpy(mine, d->pkt_ext[e][s2], d->pkt_len[e][s2]);
+      d->pkt_ext[e][s2] = mine;
+    }
   for (int e = 0; e < g->nel; ++e) ((int32_t *)(g->h_raw[e] + (size_t)i * g->raw_stride[e]))[1] = 0; /* nothing to unpack yet */
   if (rsize) *rsize = 0;
   if (!d->configured || d->need_reconf) return IAMF_ERR_INVALID_STATE;
@@ -759,14 +842,24 @@ static int group_parse_one(iamf_hip_decoder_group *g, int i) {
   return 0;
 }
 
-int iamf_hip_decoder_group_decode(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes,
-                                  uint32_t *rsizes, void *const *pcm, int32_t *results) {
+/* Round `ticket`'s host half: parse, stage into slot ticket & 1, queue the device work, move the clocks.  Every device
+ * call of a round goes to g->stream; the batch and the resampler take what a launch needs by value (the kernels'
+ * parameter structs) or from device buffers they advance in stream order (iamf_render.hip: p.fir_hist / fir_cur,
+ * d_lim, d_lfe_state; iamf_resample.hip: d_hist[cur], whose host-side phase walk is the only host state), so a launch
+ * reads no host memory after it returns — which a round already relied on: it queues several range launches with no
+ * synchronisation between them.  What they read from the host is the group's pinned staging (h_raw through
+ * iamf_hip_upload_by_kernel, h_ramp / h_dmx / h_demix through hipMemcpyAsync), and that has a copy per slot.  The
+ * exceptions synchronise themselves: iamf_hip_batch_set_gains waits for the batch's last render (quiesce) — in a round
+ * whose constant gains change it therefore waits for the round before it, a bubble in the pipeline — and a buffer that
+ * grows with the largest call seen is replaced after a hipStreamSynchronize. */
+static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes, uint32_t *rsizes,
+                              void *const *pcm, int32_t *results) {
   int any_render = 0, any = 0, rampu = 0, gains_changed = 0;
-  const int n = g ? g->n : 0, fs = g ? g->fs : 0;
-  if (!g || !data || !sizes || !pcm || !results) return IAMF_ERR_BAD_ARG;
-  for (int i = 0; i < n; ++i)
-    if (!pcm[i]) return IAMF_ERR_BAD_ARG;
-  if (g->failed) return IAMF_ERR_INVALID_STATE;
+  const int n = g->n, fs = g->fs;
+  const int sl = (int)((g->issued + 1) & 1);
+  group_use_slot(g, sl);
+  memcpy(g->pcm_out, pcm, sizeof(void *) * (size_t)n);
+  g->slot[sl].dev = 0;
   g->data = data;
   g->sizes = sizes;
   g->rsizes = rsizes;
@@ -814,7 +907,10 @@ int iamf_hip_decoder_group_decode(iamf_hip_decoder_group *g, const uint8_t *cons
     }
     any |= g->action[i] != GA_NONE;
   }
-  if (!any) return IAMF_OK;
+  if (!any) {
+    g->t_phase[1] += group_now() - t0;
+    return IAMF_OK;
+  }
   int unpacked = 0; /* the device unpacker has run this round (it is skipped when every launch reads the packets itself) */
   if (any_render) {
     /* a stage that is on a ramp in SOME stream is applied through its rows in all: the others' rows carry their constant */
@@ -1026,20 +1122,82 @@ int iamf_hip_decoder_group_decode(iamf_hip_decoder_group *g, const uint8_t *cons
     }
     i = j;
   }
-  /* the kernels have written the pinned PCM buffer: wait, then every handle's share to its caller's buffer */
-  t1 = group_now();
-  g->t_phase[1] += t1 - t0;
-  t0 = t1;
-  if (hipStreamSynchronize(g->stream) != hipSuccess) return group_fail(g);
+  /* the round is queued: a one-lane kernel behind its last launch writes the ticket into the pinned word (what _complete
+   * and _poll wait for: this round only, not the one submitted after it) */
+  if (iamf_hip_stream_signal(g->stream, g->h_sig, (uint32_t)(g->issued + 1)) != IAMF_HIP_OK) return group_fail(g);
+  g->slot[sl].dev = 1;
+  group_advance_clocks(g);
+  for (int i = 0; i < n; ++i)
+    if (g->action[i] != GA_NONE) results[i] = g->result[i];
+  g->t_phase[1] += group_now() - t0;
+  return IAMF_OK;
+}
+
+int iamf_hip_decoder_group_submit(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes,
+                                  uint32_t *rsizes, void *const *pcm, int32_t *results, uint64_t *ticket) {
+  int rc;
+  if (!g || !data || !sizes || !pcm || !results || !ticket) return IAMF_ERR_BAD_ARG;
+  for (int i = 0; i < g->n; ++i)
+    if (!pcm[i]) return IAMF_ERR_BAD_ARG;
+  if (g->failed || g->issued - g->done >= IAMF_HIP_GROUP_MAX_IN_FLIGHT) return IAMF_ERR_INVALID_STATE;
+  rc = group_submit_round(g, data, sizes, rsizes, pcm, results);
+  if (rc) return rc;
+  *ticket = ++g->issued;
+  return IAMF_OK;
+}
+
+/* the round's device work has completed: the signal word has reached its ticket (an acquire load: the PCM the kernels
+ * wrote before the signal is visible once it reads so) */
+static int group_round_done(const iamf_hip_decoder_group *g, uint64_t ticket) {
+  return !g->slot[ticket & 1].dev || (int32_t)(__atomic_load_n(g->h_sig, __ATOMIC_ACQUIRE) - (uint32_t)ticket) >= 0;
+}
+enum { kGroupWaitUs = 100000 }; /* spin on the signal word at most this long, then hipStreamSynchronize */
+
+int iamf_hip_decoder_group_poll(iamf_hip_decoder_group *g, uint64_t ticket) {
+  if (!g) return IAMF_ERR_BAD_ARG;
+  if (g->failed || ticket <= g->done || ticket > g->issued) return IAMF_ERR_INVALID_STATE;
+  return group_round_done(g, ticket);
+}
+
+int iamf_hip_decoder_group_complete(iamf_hip_decoder_group *g, uint64_t ticket) {
+  double t0, t1;
+  if (!g) return IAMF_ERR_BAD_ARG;
+  if (g->failed || ticket != g->done + 1 || ticket > g->issued) return IAMF_ERR_INVALID_STATE;
+  t0 = group_now();
+  if (!group_round_done(g, ticket)) {
+    /* a bounded spin; a round that takes longer (or a device that has failed: the signal never comes) ends in
+     * hipStreamSynchronize, which also waits for the round after it and reports a device error */
+    for (int spin = 0; !group_round_done(g, ticket); ++spin) {
+      if (spin < kGroupSpin) {
+        group_relax();
+      } else {
+        if (group_now() - t0 > 1e-6 * kGroupWaitUs) {
+          if (hipStreamSynchronize(g->stream) != hipSuccess) return group_fail(g);
+          break;
+        }
+        sched_yield();
+      }
+    }
+  }
   t1 = group_now();
   g->t_phase[2] += t1 - t0;
-  t0 = t1;
-  g->pcm_out = pcm; /* every handle's share to its caller's buffer, and its clocks moved on: on the pool again */
+  /* every handle's share of the pinned PCM to its caller's buffer: on the pool */
+  group_use_slot(g, (int)(ticket & 1));
   group_start(g, 1);
   group_help(g);
   group_join(g);
-  for (int i = 0; i < n; ++i)
-    if (g->action[i] != GA_NONE) results[i] = g->result[i];
-  g->t_phase[3] += group_now() - t0;
+  g->done = ticket;
+  g->t_phase[3] += group_now() - t1;
   return IAMF_OK;
+}
+
+int iamf_hip_decoder_group_decode(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes,
+                                  uint32_t *rsizes, void *const *pcm, int32_t *results) {
+  uint64_t ticket = 0;
+  int rc;
+  if (!g || !data || !sizes || !pcm || !results) return IAMF_ERR_BAD_ARG;
+  if (g->issued != g->done) return IAMF_ERR_INVALID_STATE; /* rounds outstanding: complete them first */
+  rc = iamf_hip_decoder_group_submit(g, data, sizes, rsizes, pcm, results, &ticket);
+  if (rc) return rc;
+  return iamf_hip_decoder_group_complete(g, ticket);
 }

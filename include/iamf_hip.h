@@ -560,11 +560,47 @@ typedef struct iamf_hip_decoder_group iamf_hip_decoder_group;
 int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads, iamf_hip_decoder_group **out);
 /* where the group's calls spent their time so far, seconds: [0] host parsing + packet staging (the thread pool), [1] enqueueing
  * the uploads, the unpack and render launches and the download, [2] waiting for the device, [3] handing every handle its PCM;
- * *rounds (may be NULL) = calls of iamf_hip_decoder_group_decode.  IAMF_OK or IAMF_ERR_BAD_ARG. */
+ * *rounds (may be NULL) = rounds submitted (calls of iamf_hip_decoder_group_decode or _submit).  IAMF_OK or IAMF_ERR_BAD_ARG. */
 int iamf_hip_decoder_group_times(const iamf_hip_decoder_group *g, double *seconds4, int64_t *rounds);
 int iamf_hip_decoder_group_decode(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes,
                                   uint32_t *rsizes, void *const *pcm, int32_t *results);
 void iamf_hip_decoder_group_destroy(iamf_hip_decoder_group *g);
+
+/* ------------------------------------------------------------------------------------------
+ * A group's round in two halves: hand in the next round's packets while the previous round still renders (the send /
+ * receive split of avcodec_send_packet / avcodec_receive_frame).  iamf_hip_decoder_group_decode is _submit followed by
+ * _complete; split, the host's parsing of round k + 1 overlaps the device's rendering of round k.
+ *   Equivalence: any interleaving of _submit and _complete with at most IAMF_HIP_GROUP_MAX_IN_FLIGHT rounds outstanding
+ *     gives every handle exactly the results, rsizes, PCM bytes and metadata that the same rounds through
+ *     iamf_hip_decoder_group_decode give, which is what IAMF_decoder_decode on each handle gives.
+ *   Ordering errors return IAMF_ERR_INVALID_STATE and consume or change nothing: a _submit while
+ *     IAMF_HIP_GROUP_MAX_IN_FLIGHT rounds are outstanding; a _complete of a ticket that is not the oldest outstanding one
+ *     (never issued, already completed, or a later one); iamf_hip_decoder_group_decode while any round is outstanding.
+ *   Destroy with rounds outstanding waits for their device work, writes nothing into those rounds' pcm buffers and
+ *     releases the handles as usual (a temporal unit that is still incomplete keeps its packets).
+ *   Device failure: a failure found by _submit or _complete returns IAMF_ERR_INTERNAL and latches the group; every later
+ *     call returns IAMF_ERR_INVALID_STATE and _destroy is the valid call.  _poll reads a pinned word and nothing else: a
+ *     device that has failed shows as a round that never becomes ready, and its _complete reports the failure.
+ *   Metadata: a handle's clocks and IAMF_decoder_get_last_metadata advance at _submit.  Once every submitted round is
+ *     complete they equal the synchronous path's; while a later round is outstanding they already describe that round.
+ *   Timing (iamf_hip_decoder_group_times): [0] and [1] are accumulated in _submit, [2] (waiting) and [3] (hand-out) in
+ *     _complete; *rounds counts submits.
+ *   Threading: a group's calls must not run concurrently with each other.
+ * ---------------------------------------------------------------------------------------- */
+#define IAMF_HIP_GROUP_MAX_IN_FLIGHT 2
+/* Host half of iamf_hip_decoder_group_decode: parse, stage, move the parameter clocks, enqueue the round's device work.
+ * On return, results[i] and rsizes[i] are final.  data[i] may be reused.  pcm[i] belongs to the library until the
+ * round's _complete returns (the array pcm itself may be reused).  *ticket identifies the round (increasing, from 1).
+ * IAMF_OK, IAMF_ERR_BAD_ARG, IAMF_ERR_INVALID_STATE, IAMF_ERR_INTERNAL. */
+int iamf_hip_decoder_group_submit(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes,
+                                  uint32_t *rsizes, void *const *pcm, int32_t *results, uint64_t *ticket);
+/* 1: the round's PCM is ready (its _complete will not wait).  0: not yet.  IAMF_ERR_INVALID_STATE: the ticket is not
+ * outstanding, or the group has failed.  Never blocks. */
+int iamf_hip_decoder_group_poll(iamf_hip_decoder_group *g, uint64_t ticket);
+/* Waits for the round's device work (that round only, not rounds submitted after it) and copies each handle's PCM into
+ * the pcm[i] given at submit.  Rounds are completed in submit order.  IAMF_OK, IAMF_ERR_BAD_ARG, IAMF_ERR_INVALID_STATE,
+ * IAMF_ERR_INTERNAL. */
+int iamf_hip_decoder_group_complete(iamf_hip_decoder_group *g, uint64_t ticket);
 
 #ifdef __cplusplus
 }
