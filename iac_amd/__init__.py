@@ -25,6 +25,7 @@ from .hipabi import (  # noqa: F401
     DemixState,
     DmxFrame,
     DmxState,
+    FANOUT_MAX,
     RenderArgs,
     Resampler,
     dmx_matrix,
@@ -40,4 +41,5 @@ from .hipabi import (  # noqa: F401
     lib,
     lib_path,
     lpcm_unpack,
+    render_fanout,
 )

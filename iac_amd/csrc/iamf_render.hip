@@ -54,6 +54,8 @@ extern "C" int iamf_hip_lpcm_unpack_frames(const iamf_hip_lpcm_layout *lay, cons
                                            int32_t uniform_count);
 extern "C" int iamf_hip_fast_lpcm_has(int m, int oc);                                   // iamf_render_lpcm.hip
 extern "C" int iamf_hip_fast_lpcm_launch(const void *params, int m, hipStream_t st);   // iamf_render_lpcm.hip
+extern "C" int iamf_hip_fanout_has(int m, int k);                                       // iamf_render_fanout.hip
+extern "C" int iamf_hip_fanout_launch(const void *params, int m, int k, hipStream_t st);  // iamf_render_fanout.hip
 extern "C" int iamf_hip_wide4_has_mix(int m, int c);                                  // iamf_render_wide4_mix.hip
 extern "C" int iamf_hip_wide4_mix_launch(const void *params, int m, hipStream_t st);  // iamf_render_wide4_mix.hip
 extern "C" int iamf_hip_wide4_has_lfe(int m, int c);                                  // iamf_render_wide4_lfe.hip
@@ -71,6 +73,7 @@ namespace {
 #include "render_fir16.hpp"
 #include "render_fir_fft.hpp"
 #include "render_fast.hpp"
+#include "render_fanout.hpp"
 #include "render_generic.hpp"
 #include "render_nolim.hpp"
 #include "render_wide.hpp"
@@ -650,7 +653,22 @@ int lfe_prepass(iamf_hip_batch *b, const float *d_in, int64_t in_stream_stride, 
   return IAMF_HIP_OK;
 }
 
-int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr) {
+// A render call in three steps — prepare (checks, the kernel's parameter block, scratch that grows with the call; the LFE
+// generator's pre-pass is queued here), launch, commit (positions, the FIR history flip, the re-lay of a fixed channel
+// stride, the `done` event, the emitted count) — so that iamf_hip_batch_render_fanout can prepare every member, launch
+// once, and commit each, and restates none of it.
+struct PreparedCall {
+  RenderParams p;
+  iamf_hip_render_args a;
+  int m_eff;
+  size_t lds;
+  bool restride;
+  int sc, bps;
+  int64_t pos;
+  int total, s0, cnt;
+};
+
+int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
   if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || b->has2 || a.d_element_ramp || a.d_element2_ramp ||
              a.d_output_ramp || !b->lp_scale_ok || getenv("IAMF_HIP_LPCM_UNFUSED")))
@@ -667,7 +685,7 @@ int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int
   // per-batch (not per-stream) state: the FIR history ping-pong.  (The LFE generator's pre-pass takes the range: streams
   // outside it keep their filter state, round 4.)
   if (!whole && b->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
-  RenderParams p;
+  RenderParams &p = pc.p;
   memset(&p, 0, sizeof(p));
   p.stream0 = s0;
   p.n_launch = cnt;
@@ -826,8 +844,30 @@ int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int
     p.pcm = b->d_nat;
     p.pcm_stream_stride = (int64_t)per_stream;
   }
-  const int r = launch(p, m_eff, lds, static_cast<hipStream_t>(a.stream));
-  if (r != IAMF_HIP_OK) return r;
+  pc.a = a;
+  pc.m_eff = m_eff;
+  pc.lds = lds;
+  pc.restride = restride;
+  pc.sc = sc;
+  pc.bps = bps;
+  pc.pos = pos;
+  pc.total = total;
+  pc.s0 = s0;
+  pc.cnt = cnt;
+  return IAMF_HIP_OK;
+}
+
+int render_launch(const PreparedCall &pc) {
+  return launch(pc.p, pc.m_eff, pc.lds, static_cast<hipStream_t>(pc.a.stream));
+}
+
+// behind a launch that succeeded: returns the sample-frames the call emitted per stream
+int render_commit(iamf_hip_batch *b, const PreparedCall &pc) {
+  const RenderParams &p = pc.p;
+  const iamf_hip_render_args &a = pc.a;
+  const bool restride = pc.restride;
+  const int sc = pc.sc, bps = pc.bps, total = pc.total, s0 = pc.s0, cnt = pc.cnt;
+  const int64_t pos = pc.pos;
   if (b->fir && p.in) b->fir_cur ^= 1;
   const int64_t before = p.limiter_on ? (pos > kDelay ? pos - kDelay : 0) : pos;
   for (int i = s0; i < s0 + cnt; ++i) b->spos[(size_t)i] = pos + total;
@@ -844,6 +884,15 @@ int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int
   HIPCHK(hipEventRecord(b->done, static_cast<hipStream_t>(a.stream)));
   b->rendered = true;
   return n_emit;
+}
+
+int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr) {
+  PreparedCall pc;
+  int r = render_prepare(b, a, total, s0, cnt, lp, pc);
+  if (r != IAMF_HIP_OK) return r;
+  r = render_launch(pc);
+  if (r != IAMF_HIP_OK) return r;
+  return render_commit(b, pc);
 }
 
 // feed-major copy of a renderer matrix and its output-slot map (h2m_rdr.c:1114-1150 keeps the
@@ -1339,6 +1388,137 @@ int iamf_hip_batch_render(iamf_hip_batch *b, const float *d_in, int64_t in_strea
   a.stream = stream;
   if (b && (b->has2 || b->dmx || b->demix)) return IAMF_HIP_ERR_BAD_ARG;  // those need iamf_hip_batch_render_ex
   return iamf_hip_batch_render_ex(b, &a);
+}
+
+// How many members one launch of render_fanout_kernel takes.  The kernel exists for 2 .. IAMF_HIP_FANOUT_MAX; a count that
+// measures slower than as many single launches at the bench geometry is not fused (tools/fanout_rate.py).  Measured on
+// MI355X, 3rd-order element, 512 / 2048 streams x 64 frames x 1024 (profiles/r06_fanout_rate.json): K = 2 is 1.49 / 1.81
+// times as fast as its single launches, K = 3 1.91 / 2.08, K = 4 1.29 / 1.28, the spread between two series of the
+// single launches at most 0.009 — every count wins, so all are fused: at this value the `k >= kFanFuseMax` test below
+// never holds (a call has at most IAMF_HIP_FANOUT_MAX members); it is where a count that stops winning would be cut.
+static const int kFanFuseMax = IAMF_HIP_FANOUT_MAX;
+
+int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batches, const float *d_in, int64_t in_stream_stride,
+                                 int64_t in_frame_stride, int32_t n_frames, void *const *d_pcm,
+                                 const int64_t *pcm_stream_stride_bytes, void *stream, int32_t *n_emitted, int32_t *n_fused) {
+  // ---- checks that need no device ----
+  if (n_batches < 1 || n_batches > IAMF_HIP_FANOUT_MAX) return IAMF_HIP_ERR_BAD_ARG;
+  if (!batches || !d_in || !d_pcm || !pcm_stream_stride_bytes || !n_emitted) return IAMF_HIP_ERR_BAD_ARG;
+  for (int j = 0; j < n_batches; ++j) {
+    if (!batches[j] || !d_pcm[j]) return IAMF_HIP_ERR_BAD_ARG;
+    for (int i = 0; i < j; ++i)
+      if (batches[i] == batches[j]) return IAMF_HIP_ERR_BAD_ARG;
+  }
+  // ---- every member's own checks, before anything is queued: what iamf_hip_batch_render would refuse ----
+  iamf_hip_render_args args[IAMF_HIP_FANOUT_MAX];
+  int64_t total = 0;
+  const iamf_hip_batch *b0 = batches[0];
+  for (int j = 0; j < n_batches; ++j) {
+    const iamf_hip_batch *b = batches[j];
+    if (b->cfg.n_streams != b0->cfg.n_streams || b->cfg.frame_size != b0->cfg.frame_size || b->m != b0->m ||
+        (b->d_pre ? b->pre_l : b->m) != (b0->d_pre ? b0->pre_l : b0->m))
+      return IAMF_HIP_ERR_BAD_ARG;
+    if (b->has2 || b->dmx || b->demix) return IAMF_HIP_ERR_BAD_ARG;  // those need iamf_hip_batch_render_ex
+    iamf_hip_render_args &a = args[j];
+    memset(&a, 0, sizeof(a));
+    a.d_in = d_in;
+    a.in_stream_stride = in_stream_stride;
+    a.in_frame_stride = in_frame_stride;
+    a.n_frames = n_frames;
+    a.d_pcm = d_pcm[j];
+    a.pcm_stream_stride_bytes = pcm_stream_stride_bytes[j];
+    a.stream = stream;
+    int64_t tj = 0;
+    const int rc = range_args_check(b, &a, 0, b->cfg.n_streams, &tj);
+    if (rc != IAMF_HIP_OK) return rc;
+    total = tj;   // n_frames * frame_size: the same for every member
+  }
+  if (total == 0) {   // n_frames == 0: nothing to do and no state looked at, as the single call
+    if (n_fused) *n_fused = 0;
+    for (int j = 0; j < n_batches; ++j) n_emitted[j] = 0;
+    return IAMF_HIP_OK;
+  }
+  for (int j = 0; j < n_batches; ++j) {
+    const iamf_hip_batch *b = batches[j];
+    if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
+    for (int i = 0; i < b->cfg.n_streams; ++i)
+      if (b->spos[(size_t)i] != b0->spos[0] || b->sflushed[(size_t)i]) return IAMF_HIP_ERR_INVALID_STATE;
+  }
+  if (n_fused) *n_fused = 0;
+  for (int j = 0; j < n_batches; ++j) n_emitted[j] = 0;
+
+  // ---- which members share the input: those the single call would launch as the plain render_fast_kernel<M, OC> ----
+  const int ns = b0->cfg.n_streams;
+  PreparedCall pcs[IAMF_HIP_FANOUT_MAX];
+  bool fuse[IAMF_HIP_FANOUT_MAX];
+  int k = 0;
+  for (int j = 0; j < n_batches; ++j) {
+    iamf_hip_batch *b = batches[j];
+    fuse[j] = false;
+    const int sc = b->cfg.pcm_stride_channels;
+    // (nothing that prepare would queue or allocate for: no HRTF stage, LFE generator, de-mapping, fixed channel stride)
+    if (k >= kFanFuseMax || b->fir || b->lfe || b->d_pre || (sc > 0 && sc != b->cfg.out_channels) || !b->cfg.limiter_enable ||
+        b->cfg.out_channels > 2)
+      continue;
+    const int rc = render_prepare(b, args[j], (int)total, 0, ns, nullptr, pcs[j]);
+    if (rc != IAMF_HIP_OK) return rc;
+    fuse[j] = fast_path_ok(pcs[j].p) && pcs[j].m_eff == b0->m && iamf_hip_fanout_has(pcs[j].m_eff, 2);
+    if (fuse[j]) ++k;
+  }
+  if (k < 2) k = 0;
+  if (k) {
+    FanParams fp;
+    memset(&fp, 0, sizeof(fp));
+    int n = 0;
+    for (int j = 0; j < n_batches; ++j) {
+      if (!fuse[j]) continue;
+      const RenderParams &p = pcs[j].p;
+      if (n == 0) {
+        fp.in = p.in;
+        fp.in_stream_stride = p.in_stream_stride;
+        fp.in_frame_stride = p.in_frame_stride;
+        fp.pos0 = p.pos0;
+        fp.total = p.total;
+        fp.frame_size = p.frame_size;
+        fp.n_streams = p.n_streams;
+        fp.stream0 = 0;
+        fp.n_launch = ns;
+      }
+      FanMember &mb = fp.mem[n++];
+      mb.pcm = p.pcm;
+      mb.pcm_stream_stride = p.pcm_stream_stride;
+      mb.matrix = p.matrix;
+      mb.gains = p.gains;
+      mb.ctab = p.ctab;
+      mb.lim = p.lim;
+      mb.ring_y = p.ring_y;
+      mb.ring_pm = p.ring_pm;
+      mb.src_feed = p.src_feed;
+      mb.out_ch = p.out_ch;
+      mb.out_format = p.out_format;
+      mb.loudness_on = p.loudness_on;
+      mb.n_atk = p.n_atk;
+      mb.n_end = p.n_end;
+      mb.thr = p.thr;
+    }
+    if (!iamf_hip_fanout_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
+    HIPCHK(hipGetLastError());
+    for (int j = 0; j < n_batches; ++j) {
+      if (!fuse[j]) continue;
+      const int r = render_commit(batches[j], pcs[j]);
+      if (r < 0) return r;
+      n_emitted[j] = r;
+    }
+    if (n_fused) *n_fused = k;
+  }
+  // ---- every other member: the single call, in member order, on the same stream ----
+  for (int j = 0; j < n_batches; ++j) {
+    if (k && fuse[j]) continue;
+    const int r = render_call(batches[j], args[j], (int)total, 0, ns);
+    if (r < 0) return r;
+    n_emitted[j] = r;
+  }
+  return IAMF_HIP_OK;
 }
 
 int iamf_hip_batch_flush_range(iamf_hip_batch *b, void *d_pcm, int64_t pcm_stream_stride_bytes, void *stream,

@@ -127,6 +127,9 @@ def lib():
         L.iamf_hip_batch_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                             C.c_void_p, C.c_int64, C.c_void_p]
         L.iamf_hip_batch_flush.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.iamf_hip_batch_render_fanout.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.iamf_hip_batch_reset.argtypes = [C.c_void_p]
         L.iamf_hip_batch_render_range.argtypes = [C.c_void_p, C.POINTER(RenderArgs), C.c_int32, C.c_int32]
         L.iamf_hip_batch_flush_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32]
@@ -237,6 +240,27 @@ def lpcm_unpack(layout, d_raw, raw_stream_stride, d_first_count, d_out, out_stre
     if r < 0:
         raise IamfHipError(r, "iamf_hip_lpcm_unpack")
     return r
+
+
+FANOUT_MAX = 4   # IAMF_HIP_FANOUT_MAX
+
+
+def render_fanout(batches, d_in, in_stream_stride, in_frame_stride, n_frames, d_pcms, pcm_strides, stream=None):
+    """iamf_hip_batch_render_fanout: one element input (device pointer, int) rendered into every Batch of `batches`, the
+    input read once for the members that can share it.  Returns (n_emitted per member, n_fused)."""
+    n = len(batches)
+    if len(d_pcms) != n or len(pcm_strides) != n:   # (a ctypes array would pad the missing entries with NULL / 0)
+        raise ValueError("render_fanout: one PCM buffer and one stride per batch")
+    hs = (C.c_void_p * n)(*[b.h for b in batches])
+    pcms = (C.c_void_p * n)(*d_pcms)
+    strides = (C.c_int64 * n)(*pcm_strides)
+    emitted = (C.c_int32 * max(n, 1))()
+    fused = C.c_int32(0)
+    r = lib().iamf_hip_batch_render_fanout(hs, n, d_in, in_stream_stride, in_frame_stride, n_frames, pcms, strides, stream,
+                                           emitted, C.byref(fused))
+    if r < 0:
+        raise IamfHipError(r, "iamf_hip_batch_render_fanout")
+    return list(emitted[:n]), fused.value
 
 
 def layout_channels(out_id):

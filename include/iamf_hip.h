@@ -327,6 +327,43 @@ int iamf_hip_batch_flush_range(iamf_hip_batch *b, void *d_pcm, int64_t pcm_strea
 int iamf_hip_batch_flush(iamf_hip_batch *b, void *d_pcm, int64_t pcm_stream_stride_bytes,
                          void *stream);
 
+/* One element rendered into several batches (the layouts of a mix presentation; several mix presentations over one
+ * element, each with its own gains and bit depth) with ONE pass over the input where that is possible.
+ *
+ * Meaning: for every j the call leaves batches[j] (device state, position, the event the setters wait for) and d_pcm[j]
+ * exactly as
+ *   n_emitted[j] = iamf_hip_batch_render(batches[j], d_in, in_stream_stride, in_frame_stride, n_frames, d_pcm[j],
+ *                                        pcm_stream_stride_bytes[j], stream)
+ * would, called for j = 0 .. n_batches - 1 in turn: bit for bit, for every output format, gains, threshold, limiter on
+ * or off.  The members keep the persisted state they have, so this call and the single-batch calls may be mixed freely
+ * on the same batches.  The flush stays per batch (iamf_hip_batch_flush reads no input).
+ *
+ * Which members share the input is decided from what the call can observe, not by the caller: a member that
+ * iamf_hip_batch_render would hand to the one- / two-channel limiter kernel as it is (limiter on, one or two output
+ * channels, a call of whole 64-sample blocks on 16-byte aligned buffers, no HRTF stage, projection de-mapping, LFE
+ * generator or fixed PCM channel stride, an element of 4, 9, 16, 6, 8 or 12 channels) is fusable; if at least two are,
+ * they go to one launch that reads the element once (4 * M + sum of the members' output bytes per sample-frame instead
+ * of 4 * M per member).  Every other member is rendered as iamf_hip_batch_render renders it, in member order, on the
+ * same stream.  *n_fused (may be NULL) receives the number of members the shared launch rendered: 0 or
+ * 2 .. IAMF_HIP_FANOUT_MAX — the caller's traffic accounting.
+ *
+ * Returns IAMF_HIP_OK or a negative IAMF_HIP_ERR_*.  Every argument and state check runs before the first launch; a call
+ * they refuse changes no member.
+ *   IAMF_HIP_ERR_BAD_ARG           n_batches outside 1 .. IAMF_HIP_FANOUT_MAX; a NULL pointer (n_fused excepted); the same
+ *                                  batch twice; members that differ in n_streams, frame_size or input channel count;
+ *                                  whatever iamf_hip_batch_render refuses for a member with these arguments (a batch with a
+ *                                  down-mixer, a demixer or a second element needs the records of iamf_hip_batch_render_ex)
+ *   IAMF_HIP_ERR_BUFFER_TOO_SMALL  as the single call, per member
+ *   IAMF_HIP_ERR_INVALID_STATE     wrong current device; members that do not all stand at the same position for every
+ *                                  stream; a flushed stream
+ * The count and NULL checks need no device.  A device error in the middle (IAMF_HIP_ERR_DEVICE) is as for the single
+ * call: members already queued have advanced. */
+#define IAMF_HIP_FANOUT_MAX 4
+int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batches, const float *d_in,
+                                 int64_t in_stream_stride, int64_t in_frame_stride, int32_t n_frames, void *const *d_pcm,
+                                 const int64_t *pcm_stream_stride_bytes, void *stream, int32_t *n_emitted /* host, [n_batches] */,
+                                 int32_t *n_fused /* host, one int, may be NULL */);
+
 /* ------------------------------------------------------------------------------------------
  * Sample-rate converter for a batch of streams (the decoder's speexdsp-derived resampler at
  * quality 4, src/iamf_dec/resample.c; the decoder only creates one when the stream rate differs
