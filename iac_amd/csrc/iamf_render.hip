@@ -11,7 +11,7 @@
 // Rendered samples never touch HBM (LDS ring or registers hold the limiter's 240-sample delay
 // line); HBM sees the planar f32 input once and the packed PCM once.
 //
-// Kernel families (launch() picks one per call; all share the persisted per-stream state, so
+// Kernel families (pick_route() of render_route.hpp picks one per call; all share the persisted per-stream state, so
 // consecutive calls of one stream may take different ones):
 //   render_fast.hpp     1- and 2-channel layouts, 1024-sample chunks, 4 samples per lane (headline);
 //                       variants: FIR (HRTF stage on the f32 MFMA in front, render_fir.hpp), DOWN
@@ -38,32 +38,14 @@
 #include <string.h>
 
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/iamf_hip.h"
 
 #define IAMF_FFT_HOST_TABLES   // render_fir_fft.hpp: the host-side table builder is compiled in this unit
 
-extern "C" int iamf_hip_fir_m2b_has(int m);                                           // iamf_render_fir_m2b.hip
-extern "C" int iamf_hip_fir_m2b_launch(const void *params, int m, hipStream_t st);    // iamf_render_fir_m2b.hip
-extern "C" int iamf_hip_fir_m2b_launch_fft(const void *params, int m, hipStream_t st);  // iamf_render_fir_m2b.hip
-extern "C" int iamf_hip_lpcm_unpack_frames(const iamf_hip_lpcm_layout *lay, const void *d_raw, int64_t raw_stream_stride,   // iamf_unpack.hip
-                                           int64_t raw_frame_stride, int32_t n_frames, const int32_t *d_first_count,
-                                           int64_t first_count_stride, float *d_out, int64_t out_stream_stride,
-                                           int64_t out_frame_stride, int32_t n_streams, void *stream, int32_t uniform_first,
-                                           int32_t uniform_count);
-extern "C" int iamf_hip_fast_lpcm_has(int m, int oc);                                   // iamf_render_lpcm.hip
-extern "C" int iamf_hip_fast_lpcm_launch(const void *params, int m, hipStream_t st);   // iamf_render_lpcm.hip
-extern "C" int iamf_hip_fanout_has(int m, int k);                                       // iamf_render_fanout.hip
-extern "C" int iamf_hip_fanout_launch(const void *params, int m, int k, hipStream_t st);  // iamf_render_fanout.hip
-extern "C" int iamf_hip_wide4_has_mix(int m, int c);                                  // iamf_render_wide4_mix.hip
-extern "C" int iamf_hip_wide4_mix_launch(const void *params, int m, hipStream_t st);  // iamf_render_wide4_mix.hip
-extern "C" int iamf_hip_wide4_has_lfe(int m, int c);                                  // iamf_render_wide4_lfe.hip
-extern "C" int iamf_hip_wide4_lfe_launch(const void *params, int m, hipStream_t st);  // iamf_render_wide4_lfe.hip
-extern "C" int iamf_hip_wide4_has_downmixer(int m, int c);                            // iamf_render_wide4.hip
-extern "C" int iamf_hip_wide4_has_demixer(int m, int c);                              // iamf_render_wide4.hip
-extern "C" int iamf_hip_wide4_has(int m, int c);                                      // iamf_render_wide4.hip
-extern "C" int iamf_hip_wide4_launch(const void *params, int m, hipStream_t st);      // iamf_render_wide4.hip
+#include "render_entry.hpp"
 
 namespace {
 
@@ -73,6 +55,7 @@ namespace {
 #include "render_fir16.hpp"
 #include "render_fir_fft.hpp"
 #include "render_fast.hpp"
+#include "render_fir_launch.hpp"
 #include "render_fanout.hpp"
 #include "render_generic.hpp"
 #include "render_nolim.hpp"
@@ -312,186 +295,41 @@ void launch_nolim_m(const RenderParams &p, hipStream_t st) {
   hipLaunchKernelGGL(render_nolim_kernel<M>, grid, dim3(256), (size_t)kNlChunk * p.out_ch * bytes, st, p);
 }
 
+template <int M, int OC>
+void launch_fast_mc(const RenderParams &p, bool mixing, dim3 grid, hipStream_t st) {
+  const size_t lds = sizeof(float) * (size_t)fast_lds_floats(OC, M);
+  if (mixing) launch_big_lds<&render_fast_kernel<M, OC, 0, false, true>, 80 * 1024>(grid, dim3(256), lds, st, p);
+  else launch_big_lds<&render_fast_kernel<M, OC>, 80 * 1024>(grid, dim3(256), lds, st, p);
+}
 template <int M>
-void launch_fir_m(const RenderParams &p, dim3 grid, hipStream_t st) {
-  static OptIn opted;
-  if (opted.begin()) {
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 2, 1>), 120 * 1024);
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 2, 2>), 120 * 1024);
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 2, 3>), 120 * 1024);
-    opted.end();
-  }
-  // Three stages with one specification (render_fir.hpp): overlap-save FFT on the VALU (default, render_fir_fft.hpp),
-  // split-f16 MFMA (IAMF_HIP_FIR_F16=1, render_fir16.hpp), f32 MFMA (IAMF_HIP_FIR_F32=1); they differ in the last bits
-  const int stage = fir_stage_choice(p);
-  if (stage == 3) {
-    static_assert(fast_lds_floats(2, M, 3) * 4 <= 80 * 1024, "two workgroups per CU");
-    hipLaunchKernelGGL((render_fast_kernel<M, 2, 3>), grid, dim3(256), sizeof(float) * (size_t)fast_lds_floats(2, M, 3), st, p);
-  } else if (stage == 2) {
-    static_assert(fast_lds_floats(2, M, 2) * 4 <= 80 * 1024, "two workgroups per CU");
-    hipLaunchKernelGGL((render_fast_kernel<M, 2, 2>), grid, dim3(256), sizeof(float) * (size_t)fast_lds_floats(2, M, 2), st, p);
-  } else {
-    hipLaunchKernelGGL((render_fast_kernel<M, 2, 1>), grid, dim3(512), sizeof(float) * (size_t)fast_lds_floats(2, M, 1), st, p);
-  }
+void launch_fast_m(const RenderParams &p, bool mixing, dim3 grid, hipStream_t st) {
+  if (p.out_ch == 1) launch_fast_mc<M, 1>(p, mixing, grid, st);
+  else launch_fast_mc<M, 2>(p, mixing, grid, st);
 }
 
-template <int M>
-void launch_fft_m(const RenderParams &p, hipStream_t st) {   // render_fir_fft.hpp: fir_fft_kernel
-  const dim3 g((unsigned)((p.total + kFftSpan - 1) / kFftSpan), (unsigned)p.n_launch);
-  // (whole frames only: past a call that ends inside a frame the two-base fetch would read what the caller left in the rest
-  //  of the frame — harmless to the samples that are kept unless it is a NaN, which a transform spreads over its block)
-  if ((M & 1) == 0 && p.fir_pre && p.fir_pre_next && p.total % p.frame_size == 0 && !getenv("IAMF_HIP_FIR_GENERAL_FETCH"))
-    hipLaunchKernelGGL((fir_fft_kernel<M, (M & 1) == 0>), g, dim3(256), sizeof(float) * (size_t)kFftLdsFloats, st, p, p.fir_y, 2 * (int64_t)p.total);
-  else
-    hipLaunchKernelGGL((fir_fft_kernel<M, false>), g, dim3(256), sizeof(float) * (size_t)kFftLdsFloats, st, p, p.fir_y, 2 * (int64_t)p.total);
-}
-
-template <int M>
-void launch_fast_m(const RenderParams &p, dim3 grid, hipStream_t st) {
-  const size_t lds = sizeof(float) * (size_t)fast_lds_floats(p.out_ch, M);
-  // more than 64 KiB of dynamic LDS has to be opted into per kernel (gfx950 has 160 KiB per CU)
-  static OptIn opted;
-  if (opted.begin()) {
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 1>), 80 * 1024);
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 2>), 80 * 1024);
-    opted.end();
-  }
-  if (p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp) {  // the mixing variant
-    static OptIn opted2;
-    if (opted2.begin()) {
-      opted2.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 1, 0, false, true>), 80 * 1024);
-      opted2.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 2, 0, false, true>), 80 * 1024);
-      opted2.end();
-    }
-    if (p.out_ch == 1)
-      hipLaunchKernelGGL((render_fast_kernel<M, 1, 0, false, true>), grid, dim3(256), lds, st, p);
-    else
-      hipLaunchKernelGGL((render_fast_kernel<M, 2, 0, false, true>), grid, dim3(256), lds, st, p);
-    return;
-  }
-  if (p.out_ch == 1)
-    hipLaunchKernelGGL((render_fast_kernel<M, 1>), grid, dim3(256), lds, st, p);
-  else
-    hipLaunchKernelGGL((render_fast_kernel<M, 2>), grid, dim3(256), lds, st, p);
-}
-
-// parametric down-mixer to mono / stereo: 7.1 -> {2, 1}, 5.1 -> {2, 1}, stereo -> mono
 template <int M, int OC>
 void launch_fast_down_mc(const RenderParams &p, dim3 grid, hipStream_t st) {
   const size_t lds = sizeof(float) * (size_t)fast_lds_floats(OC, M);
-  static OptIn opted;
-  if (opted.begin()) {
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, OC, 0, true>), 80 * 1024);
-    opted.end();
-  }
-  hipLaunchKernelGGL((render_fast_kernel<M, OC, 0, true>), grid, dim3(256), lds, st, p);
-}
-bool launch_fast_down(const RenderParams &p, int m, dim3 grid, hipStream_t st) {
-  if (m == 8 && p.out_ch == 2) launch_fast_down_mc<8, 2>(p, grid, st);
-  else if (m == 8 && p.out_ch == 1) launch_fast_down_mc<8, 1>(p, grid, st);
-  else if (m == 6 && p.out_ch == 2) launch_fast_down_mc<6, 2>(p, grid, st);
-  else if (m == 6 && p.out_ch == 1) launch_fast_down_mc<6, 1>(p, grid, st);
-  else if (m == 2 && p.out_ch == 1) launch_fast_down_mc<2, 1>(p, grid, st);
-  else return false;
-  return true;
+  launch_big_lds<&render_fast_kernel<M, OC, 0, true>, 80 * 1024>(grid, dim3(256), lds, st, p);
 }
 
 template <int M>
 void launch_wide_m(const RenderParams &p, dim3 grid, hipStream_t st) {
   const size_t lds = sizeof(float) * (size_t)wide_lds_floats(p.out_ch, M);
-  static OptIn opted;
-  if (opted.begin()) {
-    opted.set(reinterpret_cast<const void *>(&render_wide_kernel<M, false>), 80 * 1024);
-    opted.set(reinterpret_cast<const void *>(&render_wide_kernel<M, true>), 80 * 1024);
-    opted.end();
-  }
-  if (p.use_mfma)
-    hipLaunchKernelGGL((render_wide_kernel<M, true>), grid, dim3(256), lds, st, p);
-  else
-    hipLaunchKernelGGL((render_wide_kernel<M, false>), grid, dim3(256), lds, st, p);
+  if (p.use_mfma) launch_big_lds<&render_wide_kernel<M, true>, 80 * 1024>(grid, dim3(256), lds, st, p);
+  else launch_big_lds<&render_wide_kernel<M, false>, 80 * 1024>(grid, dim3(256), lds, st, p);
 }
 
-// The fast kernel takes aligned, limiter-on calls into 1- or 2-channel layouts; everything else
-// (odd sizes, flush, limiter off, wide layouts) goes to the generic kernel.  Both are exact.
-bool fast_path_ok(const RenderParams &p, bool down_mixer = false) {
-  if (getenv("IAMF_HIP_FORCE_GENERIC") || p.og_ch < p.out_ch) return false;
-  if (!p.limiter_on || !p.in || p.out_ch > 2 || p.n_end < kFWin) return false;
-  if (p.pre_matrix || p.demix_on) return false;
-  if (p.dmx_on && !(down_mixer && p.dmx_frames)) return false;
-  if (p.elem_ramp || p.elem2_ramp || p.out_ramp) {  // per-sample gains: the mixing variant reads them 4 at a time
-    if (p.dmx_on || p.fir_taps > 0 || (p.ramp_stream_stride & 3) || (p.elem2_ramp && !p.in2)) return false;
-    if ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) |
-         reinterpret_cast<uintptr_t>(p.out_ramp)) & 15)
-      return false;
-  }
-  if (p.in2 && (p.dmx_on || p.fir_taps > 0 || p.m2 > kFIn2 || (reinterpret_cast<uintptr_t>(p.in2) & 15) ||
-                (p.in2_stream_stride & 3) || (p.in2_frame_stride & 3)))
-    return false;  // a second element of up to 4 channels rides along (render_fast_kernel<.., IN2>)
-  // (a position that is not a multiple of 16 — a trimmed first frame — from 240 samples on: render_fast.hpp `base`)
-  if (((p.pos0 & 15) && p.pos0 < kDelay) || (p.total & 63) || (p.frame_size & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  {  // the kernel addresses a stream's input of one call with 32-bit byte offsets (buffer loads, render_fast.hpp)
-    const int64_t frames = (int64_t)p.total / p.frame_size + 2;
-    if (frames * p.in_frame_stride * 4 + 100 * (int64_t)p.frame_size >= (int64_t)1 << 31) return false;
-    if (p.lpcm && frames * p.lpcm_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
-  }
-  return true;
-}
-
-// The wide kernel: 3..24 output channels, limiter on, aligned calls.
-// any_pos: the caller will launch render_wide4_kernel, which (like render_fast_kernel) places its ring per call; the
-// 256-sample kernel of render_wide.hpp keeps absolute ring positions and needs the stream at a multiple of 16
-bool wide_path_ok(const RenderParams &p, int m, bool with_stage = false, bool any_pos = false) {
-  if (getenv("IAMF_HIP_FORCE_GENERIC") || p.og_ch < p.out_ch) return false;
-  if (!p.limiter_on || !p.in || p.out_ch <= 2 || p.out_ch > kMaxOut || p.n_end < kWWin) return false;
-  if (p.pre_matrix) return false;
-  const bool mixing = p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp;
-  if (mixing && !with_stage) return false;
-  if ((p.demix_on || p.dmx_on) && (!with_stage || mixing)) return false;  // demixer / down-mixer / mixer: wide4 variants only
-  if (p.dmx_on && (!p.dmx_frames || p.demix_on)) return false;  // demixer AND down-mixer: generic kernel
-  if (((p.pos0 & 15) && !(any_pos && p.pos0 >= kDelay)) || (p.total & 63)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  return sizeof(float) * (size_t)wide_lds_floats(p.out_ch, m) <= 80 * 1024;
-}
-
-// The 4-samples-per-lane wide kernel (render_wide4.hpp): 16-bit PCM, whole 1024-sample chunks,
-// 16-byte aligned planar input, an instantiated (inputs, outputs) pair.
-bool wide4_path_ok(const RenderParams &p, int m) {
-  if (getenv("IAMF_HIP_NO_WIDE4")) return false;
-  // whole 1024-sample chunks; the last one may be short if it still holds the 256 samples of stream state
-  if (p.out_format != IAMF_HIP_FMT_S16 || ((p.total & 1023) && (p.total & 1023) < 256) ||
-      (p.frame_size & 3) || p.n_end < 1088)
-    return false;
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
-  if (p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp) {  // the mixing variant (render_wide4.hpp, MIX)
-    if (p.in2 && (p.m2 > kFIn2 || (reinterpret_cast<uintptr_t>(p.in2) & 15) || (p.in2_stream_stride & 3) ||
-                  (p.in2_frame_stride & 3)))
-      return false;
-    if ((p.ramp_stream_stride & 3) || (p.elem2_ramp && !p.in2) ||
-        ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) |
-          reinterpret_cast<uintptr_t>(p.out_ramp)) & 15))
-      return false;
-    return iamf_hip_wide4_has_mix(m, p.out_ch) != 0;
-  }
-  if (p.dmx_on) return iamf_hip_wide4_has_downmixer(m, p.out_ch) != 0;
-  if (p.demix_on)  // scalable channel audio: the variant with the demixer in front of the projection
-    return p.demix_w4 && !p.use_mfma && (p.demix_i0 & 3) == 0 && iamf_hip_wide4_has_demixer(m, p.out_ch) != 0;
-  return iamf_hip_wide4_has(m, p.out_ch) != 0;
-}
-
+// Runs the kernel pick_route (render_route.hpp) names.  `launched` is false only if a launcher's instance list and the
+// one the route was picked by disagree, which sharing the lists rules out.
 int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
-  dim3 grid((unsigned)p.n_launch);
-  if (p.lpcm) {  // element 0 as LPCM packets: render_call has checked that this is a call of the fast kernel
-    if (!iamf_hip_fast_lpcm_launch(&p, m, st)) return IAMF_HIP_ERR_INVALID_STATE;
-    HIPCHK(hipGetLastError());
-    return IAMF_HIP_OK;
-  }
-  if (p.fir_taps > 0 && p.in) {  // HRTF renderer: aligned calls only (the flush goes to the generic kernel)
-    if (!fast_path_ok(p)) return IAMF_HIP_ERR_UNIMPLEMENTED;
-    // the FIR stage keeps input offsets of one stream as 32-bit integers
-    if (((int64_t)(p.total / p.frame_size) + 1) * p.in_frame_stride >= (int64_t)1 << 31) return IAMF_HIP_ERR_BAD_ARG;
-    if (fir_stage_choice(p) == 4) {
+  const Route r = pick_route(p, m);
+  const dim3 grid((unsigned)p.n_launch);
+  bool launched = false;
+  switch (r.family) {
+    case Family::Refused: return r.err;
+    case Family::Lpcm: launched = iamf_hip_fast_lpcm_launch(&p, m, r.variant, st); break;
+    case Family::FirSplit: {
       // (1) the FFT stage for every hop of every stream -> y in HBM (overlap-save blocks are independent: one grid); (2)
       // gains, limiter, pack = the two-channel matrix kernel with the identity over y (one "frame" of `total` samples per
       // stream).  1024 streams x 64 frames: 1.5 ms (vector ALU) + 0.6 ms (the limiter's chain, four workgroups a CU).
@@ -499,14 +337,8 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
       // next on a second stream (23.8 against 33.2 Gsamples/s: the limiter kernel takes 0.6 ms for 256 streams as for
       // 1024), and slices of TIME the same way (31.1: four resident limiter workgroups and two stage workgroups each want
       // all 512 VGPRs of a SIMD lane, so the two kernels take turns instead of overlapping).
-      switch (m) {
-        case 1: launch_fft_m<1>(p, st); break;
-        case 4: launch_fft_m<4>(p, st); break;
-        case 9: launch_fft_m<9>(p, st); break;
-        case 16: launch_fft_m<16>(p, st); break;
-        default:
-          if (!iamf_hip_fir_m2b_launch_fft(&p, m, st)) return IAMF_HIP_ERR_UNIMPLEMENTED;
-      }
+      if (!dispatch(FirHomeM{}, m, [&](auto M) { launch_fft_m<M.value>(p, st); }) && !iamf_hip_fir_m2b_launch_fft(&p, m, st))
+        return IAMF_HIP_ERR_INTERNAL;
       HIPCHK(hipGetLastError());
       RenderParams q = p;
       q.in = p.fir_y;                               // planar [2][total]: channel stride = "frame size" = total
@@ -518,69 +350,28 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
       q.n_feeds = 2;
       q.fir_taps = 0;
       q.fir_hist = q.fir_hist_next = nullptr;
-      launch_fast_m<2>(q, grid, st);
-      return hipGetLastError() == hipSuccess ? IAMF_HIP_OK : IAMF_HIP_ERR_DEVICE;
+      launch_fast_m<2>(q, false, grid, st);
+      launched = true;
+      break;
     }
-    switch (m) {
-      case 1: launch_fir_m<1>(p, grid, st); break;
-      case 4: launch_fir_m<4>(p, grid, st); break;
-      case 9: launch_fir_m<9>(p, grid, st); break;
-      case 16: launch_fir_m<16>(p, grid, st); break;
-      default:  // channel-based elements (M2B): the loudspeaker layouts' channel counts
-        if (!iamf_hip_fir_m2b_launch(&p, m, st)) return IAMF_HIP_ERR_UNIMPLEMENTED;
-    }
-    HIPCHK(hipGetLastError());
-    return IAMF_HIP_OK;
+    case Family::FirFused:  // channel-based elements (M2B), the loudspeaker layouts' channel counts: a unit of their own
+      launched = dispatch(FirHomeM{}, m, [&](auto M) { launch_fir_m<M.value>(p, r.variant, st); }) ||
+                 iamf_hip_fir_m2b_launch(&p, m, r.variant, st);
+      break;
+    case Family::FastDown:
+      launched = dispatch(FastDownMC{}, mc(m, p.out_ch), [&](auto V) { launch_fast_down_mc<mc_m(V.value), mc_c(V.value)>(p, grid, st); });
+      break;
+    case Family::Wide4Lfe: launched = iamf_hip_wide4_lfe_launch(&p, m, st); break;
+    case Family::Wide4Mix: launched = iamf_hip_wide4_mix_launch(&p, m, st); break;
+    case Family::Wide4:
+    case Family::Wide4Demix:
+    case Family::Wide4Down: launched = iamf_hip_wide4_launch(&p, m, st); break;
+    case Family::Nolim: launched = dispatch(NolimM{}, m, [&](auto M) { launch_nolim_m<M.value>(p, st); }); break;
+    case Family::Fast: launched = dispatch(FastM{}, m, [&](auto M) { launch_fast_m<M.value>(p, r.variant != 0, grid, st); }); break;
+    case Family::Wide: launched = dispatch(WideM{}, m, [&](auto M) { launch_wide_m<M.value>(p, grid, st); }); break;
+    case Family::Generic: launched = dispatch(GenericM{}, m, [&](auto M) { launch_m<M.value>(p, grid, lds_bytes, st); }); break;
   }
-  if (p.dmx_on && fast_path_ok(p, true) && launch_fast_down(p, m, grid, st)) {
-    HIPCHK(hipGetLastError());
-    return IAMF_HIP_OK;
-  }
-  // an LFE slot is filled by render_wide4_kernel<.., LFE> where that exists, else by the generic kernel
-  if (p.lfe && !p.lfe_k0 && !p.demix_on && !p.dmx_on && !p.in2 && !p.elem_ramp && !p.elem2_ramp && !p.out_ramp && !p.pre_matrix &&
-      wide_path_ok(p, m) && wide4_path_ok(p, m) && iamf_hip_wide4_has_lfe(m, p.out_ch) &&
-      iamf_hip_wide4_lfe_launch(&p, m, st)) {
-    HIPCHK(hipGetLastError());
-    return IAMF_HIP_OK;
-  }
-  const bool fast = !p.lfe && fast_path_ok(p);
-  const bool wide = !p.lfe && !fast && wide_path_ok(p, m);
-  const bool mixing = p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp;
-  const bool wide_any = !p.lfe && !fast && wide_path_ok(p, m, false, true);
-  if (!p.lfe && (wide_any || ((p.demix_on || p.dmx_on || mixing) && wide_path_ok(p, m, true, true))) && wide4_path_ok(p, m) &&
-      (mixing ? iamf_hip_wide4_mix_launch(&p, m, st) : iamf_hip_wide4_launch(&p, m, st))) {
-    HIPCHK(hipGetLastError());
-    return IAMF_HIP_OK;
-  }
-  if (!p.limiter_on && p.in && !p.lfe && !p.pre_matrix && !p.demix_on && !p.dmx_on && !mixing && p.fir_taps == 0 &&
-      p.og_ch >= p.out_ch && !getenv("IAMF_HIP_FORCE_GENERIC") && nolim_shape_ok(p)) {
-    switch (m) {
-#define CASE_N(v) case v: launch_nolim_m<v>(p, st); break;
-      CASE_N(1) CASE_N(2) CASE_N(4) CASE_N(6) CASE_N(8) CASE_N(9) CASE_N(10) CASE_N(11) CASE_N(12) CASE_N(14) CASE_N(16) CASE_N(24)
-#undef CASE_N
-      default: return IAMF_HIP_ERR_UNIMPLEMENTED;
-    }
-    HIPCHK(hipGetLastError());
-    return IAMF_HIP_OK;
-  }
-  switch (m) {
-#define CASE_M(v)                              \
-  case v:                                      \
-    if (fast)                                  \
-      launch_fast_m<v>(p, grid, st);           \
-    else if (wide)                             \
-      launch_wide_m<v>(p, grid, st);           \
-    else                                       \
-      launch_m<v>(p, grid, lds_bytes, st);     \
-    break;
-    CASE_M(1) CASE_M(2) CASE_M(4) CASE_M(6) CASE_M(8) CASE_M(9) CASE_M(10) CASE_M(12) CASE_M(14) CASE_M(16) CASE_M(24)
-#undef CASE_M
-    // 11 inputs: no element of the reference has them, but the stage behind the resampler takes the OUTPUT layout's
-    // channels through the identity, and Sound System E has 11 (found by tests/test_gpu_fuzz_facade.py: resampling into
-    // layout E was refused).  The general kernel only.
-    case 11: launch_m<11>(p, grid, lds_bytes, st); break;
-    default: return IAMF_HIP_ERR_UNIMPLEMENTED;
-  }
+  if (!launched) return IAMF_HIP_ERR_INTERNAL;
   HIPCHK(hipGetLastError());
   return IAMF_HIP_OK;
 }
@@ -752,9 +543,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   int m_eff = b->m;
   if (b->d_pre && a.d_in) {
     const int l = b->pre_l;
-    const bool inst = l == 1 || l == 2 || l == 4 || l == 6 || l == 8 || l == 9 || l == 10 || l == 12 || l == 14 ||
-                      l == 16 || l == 24;
-    if (tolerance && b->d_matrix_pre && inst && !p.in2) {  // one composed matrix, see iamf_hip_batch_set_projection
+    if (tolerance && b->d_matrix_pre && FastM::has(l) && !p.in2) {  // one composed matrix, see iamf_hip_batch_set_projection
       p.matrix = b->d_matrix_pre;
       for (int g = 0; g < 6; ++g) p.nz_mask[g] = b->nz_mask_pre[g];
       p.sparse = getenv("IAMF_HIP_DENSE") ? 0 : b->sparse_pre;
@@ -781,7 +570,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     p.lpcm_stream_stride = lp->stream_stride;
     p.lpcm_frame_stride = lp->frame_stride;
     for (int m = 0; m < 16; ++m) p.lpcm_off[m] = lp->off[m];
-    if (!fast_path_ok(p) || !iamf_hip_fast_lpcm_has(m_eff, p.out_ch)) return kNotFused;
+    if (pick_route(p, m_eff).family != Family::Lpcm) return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -975,7 +764,7 @@ int iamf_hip_batch_create(const iamf_hip_batch_config *cfg, iamf_hip_batch **out
   const bool fir = mx.kind == IAMF_HIP_KIND_FIR;
   if (fir && (cfg->fir_taps < 1 || cfg->fir_taps > 256 || mx.n != 2 || cfg->out_channels != 2 ||
               !cfg->limiter_enable ||
-              (mx.m != 1 && mx.m != 4 && mx.m != 9 && mx.m != 16 && !iamf_hip_fir_m2b_has(mx.m))))
+              (!FirHomeM::has(mx.m) && !FirM2bM::has(mx.m))))
     return IAMF_HIP_ERR_BAD_ARG;
   if (dmx) {
     if (!iamf_hip_dmx_valid(mx.in_id, mx.out_id)) return IAMF_HIP_ERR_BAD_ARG;
@@ -1447,7 +1236,7 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
   if (n_fused) *n_fused = 0;
   for (int j = 0; j < n_batches; ++j) n_emitted[j] = 0;
 
-  // ---- which members share the input: those the single call would launch as the plain render_fast_kernel<M, OC> ----
+  // ---- which members share the input: those the single call would launch as the plain render_fast_kernel<M, OC> (pick_route) ----
   const int ns = b0->cfg.n_streams;
   PreparedCall pcs[IAMF_HIP_FANOUT_MAX];
   bool fuse[IAMF_HIP_FANOUT_MAX];
@@ -1462,7 +1251,8 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
       continue;
     const int rc = render_prepare(b, args[j], (int)total, 0, ns, nullptr, pcs[j]);
     if (rc != IAMF_HIP_OK) return rc;
-    fuse[j] = fast_path_ok(pcs[j].p) && pcs[j].m_eff == b0->m && iamf_hip_fanout_has(pcs[j].m_eff, 2);
+    const Route r = pick_route(pcs[j].p, pcs[j].m_eff);
+    fuse[j] = r.family == Family::Fast && r.variant == 0 && pcs[j].m_eff == b0->m && FanM::has(pcs[j].m_eff);
     if (fuse[j]) ++k;
   }
   if (k < 2) k = 0;

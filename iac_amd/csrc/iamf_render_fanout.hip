@@ -10,7 +10,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/iamf_hip.h"
+#include "render_entry.hpp"
 
 namespace {
 
@@ -26,48 +29,22 @@ namespace {
 static_assert(2 * sizeof(float) * fan_lds_floats(3, 16) <= 160 * 1024, "K = 2 and 3: two workgroups per CU");
 static_assert(sizeof(float) * fan_lds_floats(kFanMax, 16) <= 160 * 1024, "K = 4 fits a CU");
 
+static_assert(FanK::has(2) && FanK::has(kFanMax) && !FanK::has(kFanMax + 1), "FanK is 2..kFanMax");
+
 template <int M, int K>
 void launch_fan_mk(const FanParams &p, hipStream_t st) {
   constexpr size_t lds = sizeof(float) * (size_t)fan_lds_floats(K, M);
-  // more than 64 KiB of dynamic LDS has to be opted into per kernel and device
-  static OptIn opted;
-  if (opted.begin()) {
-    opted.set(reinterpret_cast<const void *>(&render_fanout_kernel<M, K>), (int)lds);
-    opted.end();
-  }
-  hipLaunchKernelGGL((render_fanout_kernel<M, K>), dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
-}
-
-template <int M>
-int launch_fan_m(const FanParams &p, int k, hipStream_t st) {
-  switch (k) {
-    case 2: launch_fan_mk<M, 2>(p, st); return 1;
-    case 3: launch_fan_mk<M, 3>(p, st); return 1;
-    case 4: launch_fan_mk<M, 4>(p, st); return 1;
-    default: return 0;
-  }
+  launch_big_lds<&render_fanout_kernel<M, K>, (int)lds>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
 }
 
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int iamf_hip_fanout_has(int m, int k) {
-  return (m == 4 || m == 9 || m == 16 || m == 6 || m == 8 || m == 12) && k >= 2 && k <= kFanMax;
-}
-
-// returns 1 if launched; params: a FanParams whose first k members are set
-extern "C" __attribute__((visibility("hidden"))) int iamf_hip_fanout_launch(const void *params, int m, int k, hipStream_t st) {
+int iamf_hip_fanout_launch(const void *params, int m, int k, hipStream_t st) {
   FanParams p;
   memcpy(&p, params, sizeof(p));
-  if (!iamf_hip_fanout_has(m, k)) return 0;
-  for (int j = 0; j < k; ++j)
+  for (int j = 0; j < k && j < kFanMax; ++j)
     if (p.mem[j].out_ch < 1 || p.mem[j].out_ch > 2) return 0;
-  switch (m) {
-    case 4: return launch_fan_m<4>(p, k, st);
-    case 6: return launch_fan_m<6>(p, k, st);
-    case 8: return launch_fan_m<8>(p, k, st);
-    case 9: return launch_fan_m<9>(p, k, st);
-    case 12: return launch_fan_m<12>(p, k, st);
-    case 16: return launch_fan_m<16>(p, k, st);
-    default: return 0;
-  }
+  return dispatch(FanM{}, m, [&](auto M) {
+    return dispatch(FanK{}, k, [&](auto K) { launch_fan_mk<M.value, K.value>(p, st); });
+  });
 }

@@ -16,7 +16,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/iamf_hip.h"
+#include "render_entry.hpp"
 
 namespace {
 
@@ -27,46 +30,22 @@ namespace {
 #include "render_fir_fft.hpp"
 #include "render_fast.hpp"
 
-template <int M>
-void launch_lp_m(const RenderParams &p, hipStream_t st) {
-  const size_t lds = sizeof(float) * (size_t)fast_lds_floats(p.out_ch, M);
-  static OptIn opted;
-  if (opted.begin()) {
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 1, 0, false, false, true, true>), 80 * 1024);
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 2, 0, false, false, true, true>), 80 * 1024);
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 1, 0, false, false, true, false>), 80 * 1024);
-    opted.set(reinterpret_cast<const void *>(&render_fast_kernel<M, 2, 0, false, false, true, false>), 80 * 1024);
-    opted.end();
-  }
+template <int M, int OC>
+void launch_lp_mc(const RenderParams &p, bool early, hipStream_t st) {
+  const size_t lds = sizeof(float) * (size_t)fast_lds_floats(OC, M);
   const dim3 grid((unsigned)p.n_launch);
-  // up to four workgroups a CU: the early per-channel prefetch (latency bound); beyond: the plain one (issue bound).
-  // Measured on MI355X, 512 / 4096 streams: 117 against 109 / 136 against 145 Gsamples/s (profiles/r04_ab_fast.txt)
-  const bool early = p.n_launch <= 1024 && !getenv("IAMF_HIP_LP_LATE");
-  if (p.out_ch == 1) {
-    if (early) hipLaunchKernelGGL((render_fast_kernel<M, 1, 0, false, false, true, true>), grid, dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((render_fast_kernel<M, 1, 0, false, false, true, false>), grid, dim3(256), lds, st, p);
-  } else {
-    if (early) hipLaunchKernelGGL((render_fast_kernel<M, 2, 0, false, false, true, true>), grid, dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((render_fast_kernel<M, 2, 0, false, false, true, false>), grid, dim3(256), lds, st, p);
-  }
+  // early: the per-channel prefetch (pick_route says when)
+  if (early) launch_big_lds<&render_fast_kernel<M, OC, 0, false, false, true, true>, 80 * 1024>(grid, dim3(256), lds, st, p);
+  else launch_big_lds<&render_fast_kernel<M, OC, 0, false, false, true, false>, 80 * 1024>(grid, dim3(256), lds, st, p);
 }
 
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int iamf_hip_fast_lpcm_has(int m, int oc) {
-  return (m == 1 || m == 4 || m == 9 || m == 16) && (oc == 1 || oc == 2);
-}
-
-// returns 1 if launched
-extern "C" __attribute__((visibility("hidden"))) int iamf_hip_fast_lpcm_launch(const void *params, int m, hipStream_t st) {
+int iamf_hip_fast_lpcm_launch(const void *params, int m, int early, hipStream_t st) {
   RenderParams p;
   memcpy(&p, params, sizeof(p));
-  if (!p.lpcm || !iamf_hip_fast_lpcm_has(m, p.out_ch)) return 0;
-  switch (m) {
-    case 1: launch_lp_m<1>(p, st); return 1;
-    case 4: launch_lp_m<4>(p, st); return 1;
-    case 9: launch_lp_m<9>(p, st); return 1;
-    case 16: launch_lp_m<16>(p, st); return 1;
-    default: return 0;
-  }
+  if (!p.lpcm) return 0;
+  return dispatch(LpcmM{}, m, [&](auto M) {
+    return dispatch(LpcmOC{}, p.out_ch, [&](auto OC) { launch_lp_mc<M.value, OC.value>(p, early != 0, st); });
+  });
 }

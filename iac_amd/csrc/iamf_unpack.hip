@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/iamf_hip.h"
+#include "render_entry.hpp"
 
 namespace {
 
@@ -106,7 +107,7 @@ extern "C" int iamf_hip_upload_by_kernel(const void *h_pinned, void *d_dst, size
 // general form; one {first, count} pair serves all frames of a stream).  The public entry below is n_frames = 1.
 // d_first_count == nullptr: {uniform_first, uniform_count} for every stream, passed with the launch (no device word to keep
 // coherent with launches still queued: iamf_hip_batch_render_lpcm_range's unfused form).
-extern "C" __attribute__((visibility("hidden"))) int iamf_hip_lpcm_unpack_frames(
+int iamf_hip_lpcm_unpack_frames(   // render_entry.hpp
     const iamf_hip_lpcm_layout *lay, const void *d_raw, int64_t raw_stream_stride, int64_t raw_frame_stride, int32_t n_frames,
     const int32_t *d_first_count, int64_t first_count_stride, float *d_out, int64_t out_stream_stride, int64_t out_frame_stride,
     int32_t n_streams, void *stream, int32_t uniform_first, int32_t uniform_count) {

@@ -1,0 +1,28 @@
+// render_entry.hpp — the launch entry points between the render translation units, each declared exactly once: the caller
+// (iamf_render.hip) and the defining file both include this header at file scope, so a definition that drifts from its
+// declaration does not compile.  Kernel and parameter types live in each unit's anonymous namespace (the kernels' symbol
+// names depend on it), hence `const void *params`: the caller's RenderParams / FanParams, the same definition on both
+// sides (render_params.hpp, render_fanout.hpp).  Each returns 1 if it launched, 0 if (m, the block's channel counts) is
+// not in the instance list the caller has already consulted (render_route.hpp).
+#pragma once
+
+#define IAMF_INTERNAL extern "C" __attribute__((visibility("hidden")))
+
+// iamf_render_wide4.hip: render_wide4_kernel<M, C>, its demixer and its down-mixer variant (by params->demix_on / dmx_on)
+IAMF_INTERNAL int iamf_hip_wide4_launch(const void *params, int m, hipStream_t st);
+// iamf_render_wide4_mix.hip, iamf_render_wide4_lfe.hip
+IAMF_INTERNAL int iamf_hip_wide4_mix_launch(const void *params, int m, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_wide4_lfe_launch(const void *params, int m, hipStream_t st);
+// iamf_render_fanout.hip; params: a FanParams whose first k members are set
+IAMF_INTERNAL int iamf_hip_fanout_launch(const void *params, int m, int k, hipStream_t st);
+// iamf_render_lpcm.hip; early: Route::variant of Family::Lpcm
+IAMF_INTERNAL int iamf_hip_fast_lpcm_launch(const void *params, int m, int early, hipStream_t st);
+// iamf_render_fir_m2b.hip: render_fast_kernel<M, 2, stage> / the FFT stage alone (fir_fft_kernel)
+IAMF_INTERNAL int iamf_hip_fir_m2b_launch(const void *params, int m, int stage, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_fir_m2b_launch_fft(const void *params, int m, hipStream_t st);
+// iamf_unpack.hip
+IAMF_INTERNAL int iamf_hip_lpcm_unpack_frames(const iamf_hip_lpcm_layout *lay, const void *d_raw, int64_t raw_stream_stride,
+                                              int64_t raw_frame_stride, int32_t n_frames, const int32_t *d_first_count,
+                                              int64_t first_count_stride, float *d_out, int64_t out_stream_stride,
+                                              int64_t out_frame_stride, int32_t n_streams, void *stream, int32_t uniform_first,
+                                              int32_t uniform_count);

@@ -1,5 +1,5 @@
 // render_fast.hpp — the hot kernel: mono/stereo/binaural output layouts with the limiter on,
-// aligned calls (see fast_path_ok() on the host).  One workgroup (4 waves) per stream, 1024-sample
+// aligned calls (see fast_shape_ok() on the host, render_route.hpp).  One workgroup (4 waves) per stream, 1024-sample
 // chunks, FOUR consecutive samples per lane:
 //   * planar f32 input read as 16-byte loads (1 KiB per wave-instruction), the next chunk's loads
 //     issued right after the projection so they fly under the limiter work;
@@ -16,7 +16,7 @@
 
 constexpr int kFChunk = 1024;
 constexpr int kFRing = 1280;   // >= chunk + look-ahead, multiple of 16 (not a power of two)
-constexpr int kFWin = 1088;    // staged limiter-table window / head length (> chunk + 1), multiple of 64
+// (kFWin, the staged limiter-table window / head length, and kFIn2: render_route.hpp — the host routes by them)
 constexpr int kBig = 0x7fffffff;
 
 __device__ __forceinline__ float dpp_quad_bcast0(float v) {
@@ -199,7 +199,6 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //      mixed in (iamf_mixer_mix, IAMF_decoder.c:2702-2733), and / or the element and output gains are
 //      per-sample ramps (animated mix-gain parameters, iamf_frame_gain with a gains[] array,
 //      IAMF_decoder.c:1383-1408) instead of constants.
-constexpr int kFIn2 = 4;
 // FIR:  0 = gain matrix; 1 = HRTF stage on the f32 MFMA (render_fir.hpp); 2 = HRTF stage on the f16
 //       MFMA with split operands (render_fir16.hpp); 3 = HRTF stage by overlap-save FFT on the VALU
 //       (render_fir_fft.hpp: one pass per THREE chunks, a wave per 768-sample hop)
@@ -348,7 +347,7 @@ __global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((FIR || (M <=
   // The element's input goes through BUFFER loads: one resource per stream (base = the stream's region), the lane's byte
   // offset in one register for all channels, the channel's offset as the instruction's scalar offset — no address
   // arithmetic per load (a 64-bit pointer per channel cost an add each and, for the packets' sixteen run offsets, sixteen
-  // scalar register pairs that did not fit).  Offsets are 32-bit: the host sends longer calls elsewhere (fast_path_ok).
+  // scalar register pairs that did not fit).  Offsets are 32-bit: the host sends longer calls elsewhere (fast_shape_ok).
   const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void *>(LP ? static_cast<const void *>(lp_s) : static_cast<const void *>(in_s)), 0, 0x7fffffff, 0x00020000);
   // Frames that are whole chunks (frame size a multiple of 1024 — the usual 1024): a chunk lies in ONE frame, its frame

@@ -9,18 +9,7 @@
 // element gain, `0.f + y` (iamf_mixer_mix), output gain, loudness gain, the format's conversion.
 #pragma once
 
-constexpr int kNlChunk = 1024;                       // sample-frames per workgroup
-constexpr int kNlMaxFrameBytes = 60;                 // out_ch * bytes per sample-frame the LDS tile takes (60 KiB)
-
-// what the kernel's addressing needs; the caller has checked that the call is of the plain kind
-__host__ inline bool nolim_shape_ok(const RenderParams &p) {
-  const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
-  if ((p.frame_size & 3) || (p.total & 3) || p.total <= 0) return false;
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  if (((p.out_ch * bytes) & 3) || p.out_ch * bytes > kNlMaxFrameBytes) return false;  // a lane's 4 sample-frames = whole 16-byte pieces
-  return true;
-}
+// (kNlChunk, kNlMaxFrameBytes and nolim_shape_ok, what the kernel's addressing needs: render_route.hpp)
 
 template <int M>
 __global__ __launch_bounds__(256) void render_nolim_kernel(const RenderParams p) {

@@ -1,0 +1,272 @@
+// render_route.hpp — which render kernels are instantiated, and which of them a call takes.  Plain C++ like
+// render_params.hpp (included behind it, inside the unit's namespace; the unit includes <stdlib.h> and <type_traits> in
+// front): the launchers of every translation unit walk these lists, the host asks them whether an instance exists, and
+// pick_route() holds the whole routing decision, so that tests/test_route_host.py can pin it without a GPU.
+#pragma once
+
+#ifdef __HIPCC__
+#define IAMF_HD __host__ __device__
+#else
+#define IAMF_HD
+#endif
+
+// ------------------------------------------------------------------------------------------
+// instance lists
+// ------------------------------------------------------------------------------------------
+
+template <int... V>
+struct Ints {
+  static constexpr bool has(int v) { return ((v == V) || ...); }
+};
+// Calls f(std::integral_constant<int, V>) for the V of the list that equals v; false if v is not in the list.  (An f that
+// returns a value — a dispatch over a second list — decides the result itself.)
+template <int V, class F>
+bool dispatch_hit(F &f) {
+  if constexpr (std::is_void_v<decltype(f(std::integral_constant<int, V>{}))>) {
+    f(std::integral_constant<int, V>{});
+    return true;
+  } else {
+    return f(std::integral_constant<int, V>{});
+  }
+}
+template <int... V, class F>
+bool dispatch(Ints<V...>, int v, F &&f) {
+  return ((v == V && dispatch_hit<V>(f)) || ...);
+}
+// an (inputs, outputs) pair as one list entry
+constexpr int mc(int m, int c) { return m * 32 + c; }
+constexpr int mc_m(int v) { return v / 32; }
+constexpr int mc_c(int v) { return v % 32; }
+
+// inputs of render_kernel (render_generic.hpp) and render_nolim_kernel.  11 inputs: no element of the reference has them,
+// but the stage behind the resampler takes the OUTPUT layout's channels through the identity, and Sound System E has 11
+// (found by tests/test_gpu_fuzz_facade.py: resampling into layout E was refused).  The general kernels only.
+using GenericM = Ints<1, 2, 4, 6, 8, 9, 10, 11, 12, 14, 16, 24>;
+using NolimM = GenericM;
+using FastM = Ints<1, 2, 4, 6, 8, 9, 10, 12, 14, 16, 24>;   // render_fast_kernel<M, 1 | 2> and its mixing variant
+using WideM = FastM;                                        // render_wide_kernel<M, MFMA>
+// render_fast_kernel<M, OC, 0, DOWN>, the parametric down-mixer to mono / stereo: 7.1 -> {2, 1}, 5.1 -> {2, 1}, stereo -> mono
+using FastDownMC = Ints<mc(8, 2), mc(8, 1), mc(6, 2), mc(6, 1), mc(2, 1)>;
+// render_wide4_kernel<M, C>: plain and MFMA projection (C = 14: Sound System G, 4+9+0)
+using Wide4M = Ints<4, 6, 8, 9, 10, 12, 16>;
+using Wide4C = Ints<6, 8, 10, 12, 14, 24>;
+// its demixer variant: M = channels of the scalable element's target layout (5.1 .. 7.1.4)
+using Wide4DemixM = Ints<6, 8, 10, 12>;
+using Wide4DemixC = Ints<6, 8, 10, 12, 24>;
+// its down-mixer variant: 7.1.4 -> {10, 8, 6}, 5.1.4 / 7.1.2 -> {8, 6}, 5.1.2 / 7.1 -> 6 channels
+using Wide4DownMC = Ints<mc(12, 10), mc(12, 8), mc(12, 6), mc(10, 8), mc(10, 6), mc(8, 6)>;
+// its mixing variant: Wide4M inputs of the first element
+using Wide4MixC = Ints<6, 8, 10, 12>;
+// its LFE variant: ambisonics elements of order 1..3, Wide4C outputs
+using Wide4LfeM = Ints<4, 9, 16>;
+// render_fanout_kernel<M, K>: ambisonics of order 1..3 and 5.1 / 7.1 / 7.1.4 into K members
+using FanM = Ints<4, 6, 8, 9, 12, 16>;
+using FanK = Ints<2, 3, 4>;
+// render_fast_kernel<M, OC, .., LP>: mono-coded ambisonics elements as LPCM packets
+using LpcmM = Ints<1, 4, 9, 16>;
+using LpcmOC = Ints<1, 2>;
+// the HRTF stage: ambisonics elements (iamf_render.hip) and channel-based ones, the loudspeaker layouts' channel counts
+// (iamf_render_fir_m2b.hip)
+using FirHomeM = Ints<1, 4, 9, 16>;
+using FirM2bM = Ints<2, 6, 8, 10, 12>;
+
+// ------------------------------------------------------------------------------------------
+// what the routing decision needs of the kernels' geometry
+// ------------------------------------------------------------------------------------------
+
+constexpr int kFWin = 1088;    // render_fast.hpp: staged limiter-table window / head length (> chunk + 1), multiple of 64
+constexpr int kFIn2 = 4;       // channels of a second element the mixing variants take (render_fast.hpp, IN2)
+
+// render_wide.hpp
+constexpr int kWChunk = 256;
+constexpr int kWPos = 512;   // ring positions (power of two >= chunk + look-ahead + 15)
+constexpr int kWWin = 320;   // staged table window / head length (> chunk + 1)
+
+IAMF_HD constexpr int wide_lds_floats(int c, int m) {
+  return kWPos * c + 2 * kWPos + kWPos / 16 + 3 * kWChunk + 2 * kWWin + ((c + 3) & ~3) * m + 16;
+}
+
+// render_nolim.hpp
+constexpr int kNlChunk = 1024;                       // sample-frames per workgroup
+constexpr int kNlMaxFrameBytes = 60;                 // out_ch * bytes per sample-frame the LDS tile takes (60 KiB)
+
+// what render_nolim_kernel's addressing needs; the caller has checked that the call is of the plain kind
+inline bool nolim_shape_ok(const RenderParams &p) {
+  const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
+  if ((p.frame_size & 3) || (p.total & 3) || p.total <= 0) return false;
+  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  if (((p.out_ch * bytes) & 3) || p.out_ch * bytes > kNlMaxFrameBytes) return false;  // a lane's 4 sample-frames = whole 16-byte pieces
+  return true;
+}
+
+// which HRTF stage a FIR call runs (host): 3 = overlap-save FFT (default), 2 = split-f16 MFMA, 1 = f32 MFMA
+// 4 = the FFT stage as a kernel of its own + the two-channel matrix kernel behind it (default); IAMF_HIP_FIR_FUSED=1 keeps
+// the FFT stage inside render_fast_kernel<M, 2, 3> (one pass over HBM, but the hops of a stream run one pass after the other
+// and the limiter stages at two workgroups per CU: 29 instead of the split's rate, NOTEBOOK.md 4.2c)
+inline int fir_stage_choice(const RenderParams &p) {
+  if (getenv("IAMF_HIP_FIR_F32")) return 1;
+  if (getenv("IAMF_HIP_FIR_F16") && p.fir_h16) return 2;
+  if (p.fir_pq && p.fir_tw && p.fir_zero && (p.frame_size & 63) == 0)   // its input runs of 64 must not straddle frames
+    return (p.fir_y && p.fir_id_matrix && !getenv("IAMF_HIP_FIR_FUSED")) ? 4 : 3;
+  return p.fir_h16 ? 2 : 1;
+}
+
+// ------------------------------------------------------------------------------------------
+// the routing decision
+// ------------------------------------------------------------------------------------------
+
+// What the fast kernel's addressing needs: aligned, limiter-on calls into 1- or 2-channel layouts; everything else (odd
+// sizes, flush, limiter off, wide layouts) goes to the generic kernel.  Both are exact.  (Not looked at here: the
+// parametric down-mixer, which only the DOWN variant takes — pick_route.)
+inline bool fast_shape_ok(const RenderParams &p, bool force_generic) {
+  if (force_generic || p.og_ch < p.out_ch) return false;
+  if (!p.limiter_on || !p.in || p.out_ch > 2 || p.n_end < kFWin) return false;
+  if (p.pre_matrix || p.demix_on) return false;
+  if (p.elem_ramp || p.elem2_ramp || p.out_ramp) {  // per-sample gains: the mixing variant reads them 4 at a time
+    if (p.dmx_on || p.fir_taps > 0 || (p.ramp_stream_stride & 3) || (p.elem2_ramp && !p.in2)) return false;
+    if ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) |
+         reinterpret_cast<uintptr_t>(p.out_ramp)) & 15)
+      return false;
+  }
+  if (p.in2 && (p.dmx_on || p.fir_taps > 0 || p.m2 > kFIn2 || (reinterpret_cast<uintptr_t>(p.in2) & 15) ||
+                (p.in2_stream_stride & 3) || (p.in2_frame_stride & 3)))
+    return false;  // a second element of up to 4 channels rides along (render_fast_kernel<.., IN2>)
+  // (a position that is not a multiple of 16 — a trimmed first frame — from 240 samples on: render_fast.hpp `base`)
+  if (((p.pos0 & 15) && p.pos0 < kDelay) || (p.total & 63) || (p.frame_size & 3)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  {  // the kernel addresses a stream's input of one call with 32-bit byte offsets (buffer loads, render_fast.hpp)
+    const int64_t frames = (int64_t)p.total / p.frame_size + 2;
+    if (frames * p.in_frame_stride * 4 + 100 * (int64_t)p.frame_size >= (int64_t)1 << 31) return false;
+    if (p.lpcm && frames * p.lpcm_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
+  }
+  return true;
+}
+
+// What the wide kernels (render_wide.hpp, render_wide4.hpp) share: 3..24 output channels, limiter on, aligned calls.
+// (Not looked at here: the stream position and the stages in front — demixer, down-mixer, mixer — which differ
+// between the two: pick_route.)
+inline bool wide_shape_ok(const RenderParams &p, int m, bool force_generic) {
+  if (force_generic || p.og_ch < p.out_ch) return false;
+  if (!p.limiter_on || !p.in || p.out_ch <= 2 || p.out_ch > kMaxOut || p.n_end < kWWin) return false;
+  if (p.pre_matrix) return false;
+  if (p.total & 63) return false;
+  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  return sizeof(float) * (size_t)wide_lds_floats(p.out_ch, m) <= 80 * 1024;
+}
+
+// What the 4-samples-per-lane wide kernel (render_wide4.hpp) needs on top: 16-bit PCM, whole 1024-sample chunks,
+// 16-byte aligned planar input (and second element and ramps, for the mixing variant).
+inline bool wide4_shape_ok(const RenderParams &p, bool mixing) {
+  if (getenv("IAMF_HIP_NO_WIDE4")) return false;
+  // whole 1024-sample chunks; the last one may be short if it still holds the 256 samples of stream state
+  if (p.out_format != IAMF_HIP_FMT_S16 || ((p.total & 1023) && (p.total & 1023) < 256) ||
+      (p.frame_size & 3) || p.n_end < 1088)
+    return false;
+  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
+  if (mixing) {  // the mixing variant (render_wide4.hpp, MIX)
+    if (p.in2 && (p.m2 > kFIn2 || (reinterpret_cast<uintptr_t>(p.in2) & 15) || (p.in2_stream_stride & 3) ||
+                  (p.in2_frame_stride & 3)))
+      return false;
+    if ((p.ramp_stream_stride & 3) || (p.elem2_ramp && !p.in2) ||
+        ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) |
+          reinterpret_cast<uintptr_t>(p.out_ramp)) & 15))
+      return false;
+  }
+  return true;
+}
+
+// Kernel families (all share the persisted per-stream state, so consecutive calls of one stream may take different
+// ones) and, per family, what Route::variant says.
+enum class Family {
+  Refused,      // no kernel takes the call: Route::err
+  Lpcm,         // render_fast_kernel<.., LP>; variant 1: the early per-channel prefetch, 0: the late one
+  FirSplit,     // fir_fft_kernel, then render_fast_kernel<2, 2> with the identity over its output
+  FirFused,     // render_fast_kernel<M, 2, FIR>; variant = FIR: 3 FFT, 2 split-f16 MFMA, 1 f32 MFMA
+  FastDown,     // render_fast_kernel<M, OC, 0, DOWN>
+  Wide4Lfe,     // render_wide4_kernel<.., LFE>; variant 1: MFMA projection          } iamf_render_wide4_lfe.hip
+  Wide4,        // render_wide4_kernel<M, C>; variant 1: MFMA projection             } iamf_render_wide4.hip
+  Wide4Demix,   // render_wide4_kernel<.., DMX>                                      }
+  Wide4Down,    // render_wide4_kernel<.., DOWN>                                     }
+  Wide4Mix,     // render_wide4_kernel<.., MIX>; variant 1: MFMA projection          } iamf_render_wide4_mix.hip
+  Nolim,        // render_nolim_kernel<M>
+  Fast,         // render_fast_kernel<M, OC>; variant 1: the mixing one (IN2)
+  Wide,         // render_wide_kernel<M, MFMA>; variant 1: MFMA projection
+  Generic,      // render_kernel<M>
+};
+struct Route {
+  Family family;
+  int variant;
+  int err;   // IAMF_HIP_OK unless family == Refused
+};
+
+// Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
+// kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
+// rules.  The environment switches are read at every call (the tests set and unset them within one process).
+inline Route pick_route(const RenderParams &p, int m) {
+  const auto take = [](Family f, int variant = 0) { return Route{f, variant, IAMF_HIP_OK}; };
+  const auto refuse = [](int err) { return Route{Family::Refused, 0, err}; };
+  const bool force_generic = getenv("IAMF_HIP_FORCE_GENERIC") != nullptr;
+  const bool mixing = p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp;
+  const bool staged = p.demix_on || p.dmx_on || mixing;   // a stage in front of or beside the projection
+  const bool fast_shape = fast_shape_ok(p, force_generic);
+
+  // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
+  if (p.lpcm) {
+    if (!LpcmM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+    // up to four workgroups a CU: the early per-channel prefetch (latency bound); beyond: the plain one (issue bound).
+    // Measured on MI355X, 512 / 4096 streams: 117 against 109 / 136 against 145 Gsamples/s (profiles/r04_ab_fast.txt)
+    return take(Family::Lpcm, p.n_launch <= 1024 && !getenv("IAMF_HIP_LP_LATE"));
+  }
+  // HRTF renderer: aligned calls only (the flush goes to the generic kernel)
+  if (p.fir_taps > 0 && p.in) {
+    if (!fast_shape || p.dmx_on) return refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
+    // the FIR stage keeps input offsets of one stream as 32-bit integers
+    if (((int64_t)(p.total / p.frame_size) + 1) * p.in_frame_stride >= (int64_t)1 << 31) return refuse(IAMF_HIP_ERR_BAD_ARG);
+    if (!FirHomeM::has(m) && !FirM2bM::has(m)) return refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
+    // Three stages with one specification (render_fir.hpp): overlap-save FFT on the VALU (default, render_fir_fft.hpp),
+    // split-f16 MFMA (IAMF_HIP_FIR_F16=1, render_fir16.hpp), f32 MFMA (IAMF_HIP_FIR_F32=1); they differ in the last bits
+    const int stage = fir_stage_choice(p);
+    return stage == 4 ? take(Family::FirSplit) : take(Family::FirFused, stage);
+  }
+  // the parametric down-mixer to mono / stereo, with the frames' parameters at hand
+  if (p.dmx_on && p.dmx_frames && fast_shape && FastDownMC::has(mc(m, p.out_ch))) return take(Family::FastDown);
+
+  const bool fast = !p.lfe && fast_shape && !p.dmx_on;
+  const bool wide_shape = wide_shape_ok(p, m, force_generic);
+  const bool wide4_shape = wide_shape && wide4_shape_ok(p, mixing);
+  // render_wide4_kernel (like render_fast_kernel) places its ring per call and takes a position that is not a multiple
+  // of 16 from 240 samples on; the 256-sample kernel of render_wide.hpp keeps absolute ring positions and needs the
+  // stream at a multiple of 16
+  const bool pos16 = !(p.pos0 & 15);
+  const bool pos_any = pos16 || p.pos0 >= kDelay;
+
+  // an LFE slot is filled by render_wide4_kernel<.., LFE> where that exists, else by the generic kernel
+  if (p.lfe) {
+    if (!p.lfe_k0 && !staged && wide4_shape && pos16 && Wide4LfeM::has(m) && Wide4C::has(p.out_ch))
+      return take(Family::Wide4Lfe, p.use_mfma != 0);
+  } else if (wide4_shape && pos_any) {
+    // demixer / down-mixer / mixer: wide4 variants only, and one of them at a time
+    if (mixing) {
+      if (!p.demix_on && !p.dmx_on && Wide4M::has(m) && Wide4MixC::has(p.out_ch)) return take(Family::Wide4Mix, p.use_mfma != 0);
+    } else if (p.dmx_on) {  // (demixer AND down-mixer: generic kernel)
+      if (p.dmx_frames && !p.demix_on && Wide4DownMC::has(mc(m, p.out_ch))) return take(Family::Wide4Down);
+    } else if (p.demix_on) {  // scalable channel audio: the variant with the demixer in front of the projection
+      if (p.demix_w4 && !p.use_mfma && (p.demix_i0 & 3) == 0 && Wide4DemixM::has(m) && Wide4DemixC::has(p.out_ch))
+        return take(Family::Wide4Demix);
+    } else if (Wide4M::has(m) && Wide4C::has(p.out_ch)) {
+      return take(Family::Wide4, p.use_mfma != 0);
+    }
+  }
+  // limiter off, one matrix-rendered element, constant gains (render_nolim.hpp)
+  if (!p.limiter_on && p.in && !p.lfe && !p.pre_matrix && !staged && p.fir_taps == 0 && p.og_ch >= p.out_ch && !force_generic &&
+      nolim_shape_ok(p))
+    return NolimM::has(m) ? take(Family::Nolim) : refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
+  // aligned calls of one matrix-rendered element (the fast kernel: with a small second element or ramps, too)
+  if (fast && FastM::has(m)) return take(Family::Fast, mixing);
+  if (!p.lfe && wide_shape && !staged && pos16 && WideM::has(m)) return take(Family::Wide, p.use_mfma != 0);
+  // everything else: ragged calls, flush, wide second elements, exact two-stage projection, demixer + down-mixer
+  // together, other PCM formats of the stages above
+  return GenericM::has(m) ? take(Family::Generic) : refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
+}

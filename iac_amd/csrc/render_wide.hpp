@@ -22,15 +22,9 @@
 //     can reach without a trigger plus the table head that follows a trigger.
 #pragma once
 
-constexpr int kWChunk = 256;
-constexpr int kWPos = 512;   // ring positions (power of two >= chunk + look-ahead + 15)
-constexpr int kWWin = 320;   // staged table window / head length (> chunk + 1)
+// (kWChunk, kWPos, kWWin and wide_lds_floats: render_route.hpp — the host routes by the LDS a layout needs)
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-__host__ __device__ constexpr int wide_lds_floats(int c, int m) {
-  return kWPos * c + 2 * kWPos + kWPos / 16 + 3 * kWChunk + 2 * kWWin + ((c + 3) & ~3) * m + 16;
-}
 
 // DPP helpers inside a 16-lane row; lanes shifted in from outside the row read 0
 template <int N>

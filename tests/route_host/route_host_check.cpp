@@ -1,0 +1,214 @@
+// Host-only check of the render dispatch (iac_amd/csrc/render_route.hpp): a table of parameter blocks against the kernel
+// family, variant and return code pick_route() must give, and the instance-list helper.  Every kernel is exact, so a
+// wrong route shows in no parity test, only as a slower rate: this table is what pins it.  The expectations were read
+// from launch() as it stood before the decision was gathered in pick_route().  Driven by tests/test_route_host.py.
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <type_traits>
+
+#include "../../include/iamf_hip.h"
+
+namespace {
+#include "../../iac_amd/csrc/render_params.hpp"
+#include "../../iac_amd/csrc/render_route.hpp"
+
+const char *family_name(Family f) {
+  static const char *const names[] = {"Refused", "Lpcm",      "FirSplit", "FirFused", "FastDown", "Wide4Lfe", "Wide4",
+                                      "Wide4Demix", "Wide4Down", "Wide4Mix", "Nolim",    "Fast",     "Wide",     "Generic"};
+  return names[(int)f];
+}
+
+float *const kIn = reinterpret_cast<float *>(0x10000);       // never dereferenced: routing looks at alignment only
+float *const kIn2 = reinterpret_cast<float *>(0x20000);
+float *const kTab = reinterpret_cast<float *>(0x30000);
+uint8_t *const kPcm = reinterpret_cast<uint8_t *>(0x40000);
+const iamf_hip_dmx_frame *const kDmxFrames = reinterpret_cast<const iamf_hip_dmx_frame *>(0x50000);
+
+// "aligned": limiter on, 16-byte-aligned pointers, strides that are multiples of 4 floats / 16 bytes, total % 64 == 0,
+// pos0 % 16 == 0, n_end large enough (the 48 kHz table: 9651); four whole 1024-sample frames of 64 streams
+RenderParams aligned(int m, int out_ch, int fmt = IAMF_HIP_FMT_S16) {
+  RenderParams p;
+  memset(&p, 0, sizeof(p));
+  p.frame_size = 1024;
+  p.total = 4096;
+  p.in = kIn;
+  p.in_frame_stride = (int64_t)m * p.frame_size;
+  p.in_stream_stride = 4 * p.in_frame_stride;
+  p.pcm = kPcm;
+  p.out_ch = p.og_ch = out_ch;
+  p.out_format = fmt;
+  p.pcm_stream_stride = (int64_t)(p.total + 1024) * out_ch * 4;
+  p.n_streams = p.n_launch = 64;
+  p.limiter_on = 1;
+  p.n_atk = 241;
+  p.n_end = 9651;
+  return p;
+}
+void set_total(RenderParams &p, int total) { p.total = total; }
+void second_element(RenderParams &p) {
+  p.in2 = kIn2;
+  p.m2 = 2;
+  p.in2_frame_stride = 2 * p.frame_size;
+  p.in2_stream_stride = 4 * p.in2_frame_stride;
+}
+void down_mixer(RenderParams &p) {
+  p.dmx_on = 1;
+  p.dmx_frames = kDmxFrames;
+}
+void demixer(RenderParams &p) {
+  p.demix_on = 1;
+  p.demix_w4 = 1;
+}
+void lfe(RenderParams &p) { p.lfe = kTab; }
+void fir(RenderParams &p) {   // with the FFT stage's tables and the split form's scratch
+  p.fir_taps = 256;
+  p.fir_pq = p.fir_tw = p.fir_zero = p.fir_id_matrix = kTab;
+  p.fir_y = kTab;
+}
+void lpcm(RenderParams &p) {
+  p.lpcm = kPcm;
+  p.lpcm_frame_stride = 16 * 2048;
+  p.lpcm_stream_stride = 4 * p.lpcm_frame_stride;
+}
+
+int g_failed = 0, g_cases = 0;
+
+// env: one switch set to "1" for this case, or null
+void expect(const char *what, RenderParams p, int m, const char *env, Family family, int variant, int err = IAMF_HIP_OK) {
+  if (env) setenv(env, "1", 1);
+  const Route r = pick_route(p, m);
+  if (env) unsetenv(env);
+  const bool ok = r.family == family && r.variant == variant && r.err == err;
+  printf("%-72s %s/%d/%d %s\n", what, family_name(r.family), r.variant, r.err, ok ? "ok" : "WRONG");
+  if (!ok) printf("    expected %s/%d/%d\n", family_name(family), variant, err);
+  ++g_cases;
+  g_failed += ok ? 0 : 1;
+}
+template <class F>
+RenderParams with(RenderParams p, F f) {
+  f(p);
+  return p;
+}
+
+void list_checks() {
+  static_assert(GenericM::has(11) && NolimM::has(11) && !FastM::has(11) && !WideM::has(11), "11 inputs: generic and nolim only");
+  static_assert(Wide4DownMC::has(mc(12, 10)) && Wide4DownMC::has(mc(10, 8)) && Wide4DownMC::has(mc(8, 6)) &&
+                    !Wide4DownMC::has(mc(10, 10)) && !Wide4DownMC::has(mc(8, 8)) && !Wide4DownMC::has(mc(6, 6)),
+                "the down-mixer's pairs");
+  static_assert(mc_m(mc(24, 24)) == 24 && mc_c(mc(24, 24)) == 24 && mc(1, 0) > mc(0, 24), "pairs of up to 24 channels do not collide");
+  static_assert(!Wide4MixC::has(14) && Wide4C::has(14) && !Wide4DemixC::has(14), "14 channels: plain and LFE only");
+  int got = 0, calls = 0;
+  const bool hit = dispatch(FirHomeM{}, 9, [&](auto M) { got = M.value; ++calls; });
+  const bool miss = dispatch(FirHomeM{}, 3, [&](auto) { ++calls; });
+  int gm = 0, gc = 0;
+  const bool nested = dispatch(Wide4M{}, 12, [&](auto M) { return dispatch(Wide4MixC{}, 10, [&](auto C) { gm = M.value; gc = C.value; }); });
+  const bool nested_miss = dispatch(Wide4M{}, 12, [&](auto) { return dispatch(Wide4MixC{}, 14, [&](auto) { ++calls; }); });
+  const bool ok = hit && got == 9 && !miss && calls == 1 && nested && gm == 12 && gc == 10 && !nested_miss;
+  printf("%-72s %s\n", "dispatch: the matching constant once, false outside the list", ok ? "ok" : "WRONG");
+  ++g_cases;
+  g_failed += ok ? 0 : 1;
+}
+
+}  // namespace
+
+int main() {
+  const char *const switches[] = {"IAMF_HIP_FORCE_GENERIC", "IAMF_HIP_NO_WIDE4", "IAMF_HIP_FIR_F16", "IAMF_HIP_FIR_F32",
+                                  "IAMF_HIP_FIR_FUSED", "IAMF_HIP_LP_LATE"};
+  for (const char *e : switches) unsetenv(e);
+  list_checks();
+  const int UNIMPL = IAMF_HIP_ERR_UNIMPLEMENTED;
+
+  // ---- stereo ----
+  const RenderParams st = aligned(16, 2);
+  expect("aligned stereo, m = 16", st, 16, nullptr, Family::Fast, 0);
+  expect("  pos0 = 8", with(st, [](RenderParams &p) { p.pos0 = 8; }), 16, nullptr, Family::Generic, 0);
+  expect("  pos0 = 248 (>= 240, not a multiple of 16)", with(st, [](RenderParams &p) { p.pos0 = 248; }), 16, nullptr, Family::Fast, 0);
+  expect("  total % 64 != 0", with(st, [](RenderParams &p) { set_total(p, 4096 + 32); }), 16, nullptr, Family::Generic, 0);
+  expect("  in == nullptr (flush)", with(st, [](RenderParams &p) { p.in = nullptr; p.total = 240; }), 16, nullptr, Family::Generic, 0);
+  expect("  IAMF_HIP_FORCE_GENERIC", st, 16, "IAMF_HIP_FORCE_GENERIC", Family::Generic, 0);
+  expect("  m = 11", aligned(11, 2), 11, nullptr, Family::Generic, 0);
+  expect("  m = 7", aligned(7, 2), 7, nullptr, Family::Refused, 0, UNIMPL);
+
+  // ---- 12 channels ----
+  const RenderParams w = aligned(16, 12);
+  expect("aligned, 12 channels, s16, whole chunks, m = 16", w, 16, nullptr, Family::Wide4, 0);
+  expect("  use_mfma", with(w, [](RenderParams &p) { p.use_mfma = 1; }), 16, nullptr, Family::Wide4, 1);
+  expect("  s24", aligned(16, 12, IAMF_HIP_FMT_S24), 16, nullptr, Family::Wide, 0);
+  expect("  s24, use_mfma", with(aligned(16, 12, IAMF_HIP_FMT_S24), [](RenderParams &p) { p.use_mfma = 1; }), 16, nullptr, Family::Wide, 1);
+  expect("  a last chunk of 128", with(w, [](RenderParams &p) { set_total(p, 4096 + 128); }), 16, nullptr, Family::Wide, 0);
+  expect("  a last chunk of 256", with(w, [](RenderParams &p) { set_total(p, 4096 + 256); }), 16, nullptr, Family::Wide4, 0);
+  expect("  pos0 = 248: wide4 places its ring per call", with(w, [](RenderParams &p) { p.pos0 = 248; }), 16, nullptr, Family::Wide4, 0);
+  expect("  pos0 = 248, s24: the 256-sample kernel needs a multiple of 16",
+         with(aligned(16, 12, IAMF_HIP_FMT_S24), [](RenderParams &p) { p.pos0 = 248; }), 16, nullptr, Family::Generic, 0);
+  expect("  IAMF_HIP_NO_WIDE4", w, 16, "IAMF_HIP_NO_WIDE4", Family::Wide, 0);
+  expect("  IAMF_HIP_FORCE_GENERIC", w, 16, "IAMF_HIP_FORCE_GENERIC", Family::Generic, 0);
+  expect("  m = 24: no wide4 instance", aligned(24, 12), 24, nullptr, Family::Wide, 0);
+  expect("  m = 11", aligned(11, 12), 11, nullptr, Family::Generic, 0);
+
+  // ---- second element or ramps ----
+  expect("second element into stereo", with(st, second_element), 16, nullptr, Family::Fast, 1);
+  expect("output ramp into stereo", with(st, [](RenderParams &p) { p.out_ramp = kTab; }), 16, nullptr, Family::Fast, 1);
+  expect("second element into 12 channels", with(w, second_element), 16, nullptr, Family::Wide4Mix, 0);
+  expect("  use_mfma", with(w, [](RenderParams &p) { second_element(p); p.use_mfma = 1; }), 16, nullptr, Family::Wide4Mix, 1);
+  expect("second element into 14 channels: no mix instance", with(aligned(16, 14), second_element), 16, nullptr, Family::Generic, 0);
+  expect("second element of 6 channels into stereo", with(st, [](RenderParams &p) { second_element(p); p.m2 = 6; }), 16, nullptr,
+         Family::Generic, 0);
+
+  // ---- down-mixer with per-frame parameters ----
+  expect("down-mixer 8 -> 2", with(aligned(8, 2), down_mixer), 8, nullptr, Family::FastDown, 0);
+  expect("down-mixer 12 -> 6", with(aligned(12, 6), down_mixer), 12, nullptr, Family::Wide4Down, 0);
+  expect("down-mixer 10 -> 10: no pair", with(aligned(10, 10), down_mixer), 10, nullptr, Family::Generic, 0);
+  expect("down-mixer without frames 8 -> 2", with(aligned(8, 2), [](RenderParams &p) { p.dmx_on = 1; }), 8, nullptr, Family::Generic, 0);
+  expect("demixer and down-mixer together 12 -> 6", with(aligned(12, 6), [](RenderParams &p) { down_mixer(p); demixer(p); }), 12, nullptr,
+         Family::Generic, 0);
+
+  // ---- demixer of scalable channel audio ----
+  const RenderParams dx = with(aligned(12, 12), demixer);
+  expect("demixer with demix_w4, 12 -> 12", dx, 12, nullptr, Family::Wide4Demix, 0);
+  expect("  use_mfma", with(dx, [](RenderParams &p) { p.use_mfma = 1; }), 12, nullptr, Family::Generic, 0);
+  expect("  demix_i0 % 4 != 0", with(dx, [](RenderParams &p) { p.demix_i0 = 2; }), 12, nullptr, Family::Generic, 0);
+  expect("  without demix_w4", with(dx, [](RenderParams &p) { p.demix_w4 = 0; }), 12, nullptr, Family::Generic, 0);
+
+  // ---- HOA LFE generator ----
+  expect("LFE buffer, m = 16, 12 channels", with(w, lfe), 16, nullptr, Family::Wide4Lfe, 0);
+  expect("  use_mfma", with(w, [](RenderParams &p) { lfe(p); p.use_mfma = 1; }), 16, nullptr, Family::Wide4Lfe, 1);
+  expect("  lfe_k0 > 0", with(w, [](RenderParams &p) { lfe(p); p.lfe_k0 = 3; }), 16, nullptr, Family::Generic, 0);
+  expect("  stereo output", with(st, lfe), 16, nullptr, Family::Generic, 0);
+  expect("  m = 6: no LFE instance", with(aligned(6, 12), lfe), 6, nullptr, Family::Generic, 0);
+
+  // ---- limiter off ----
+  const RenderParams nl = with(st, [](RenderParams &p) { p.limiter_on = 0; });
+  expect("limiter off, a shape nolim_shape_ok accepts", nl, 16, nullptr, Family::Nolim, 0);
+  expect("  IAMF_HIP_FORCE_GENERIC", nl, 16, "IAMF_HIP_FORCE_GENERIC", Family::Generic, 0);
+  expect("  m = 11", with(aligned(11, 2), [](RenderParams &p) { p.limiter_on = 0; }), 11, nullptr, Family::Nolim, 0);
+  expect("  total % 4 != 0", with(nl, [](RenderParams &p) { set_total(p, 4098); }), 16, nullptr, Family::Generic, 0);
+
+  // ---- HRTF stage ----
+  const RenderParams f16 = with(st, fir);
+  expect("FIR, m = 16, spectra tables and scratch", f16, 16, nullptr, Family::FirSplit, 0);
+  expect("  IAMF_HIP_FIR_FUSED", f16, 16, "IAMF_HIP_FIR_FUSED", Family::FirFused, 3);
+  expect("  IAMF_HIP_FIR_F32", f16, 16, "IAMF_HIP_FIR_F32", Family::FirFused, 1);
+  expect("  IAMF_HIP_FIR_F16 with its tables", with(f16, [](RenderParams &p) { p.fir_h16 = kTab; }), 16, "IAMF_HIP_FIR_F16", Family::FirFused, 2);
+  expect("  without scratch", with(f16, [](RenderParams &p) { p.fir_y = nullptr; }), 16, nullptr, Family::FirFused, 3);
+  expect("  m = 6 (channel-based set)", with(aligned(6, 2), fir), 6, nullptr, Family::FirSplit, 0);
+  expect("  m = 6, IAMF_HIP_FIR_FUSED", with(aligned(6, 2), fir), 6, "IAMF_HIP_FIR_FUSED", Family::FirFused, 3);
+  expect("  m = 3", with(aligned(3, 2), fir), 3, nullptr, Family::Refused, 0, UNIMPL);
+  expect("  misaligned (total % 64 != 0)", with(f16, [](RenderParams &p) { set_total(p, 4096 + 32); }), 16, nullptr, Family::Refused, 0, UNIMPL);
+  expect("  flush (in == nullptr)", with(f16, [](RenderParams &p) { p.in = nullptr; p.total = 240; }), 16, nullptr, Family::Generic, 0);
+
+  // ---- element 0 as LPCM packets ----
+  const RenderParams lp = with(st, lpcm);
+  expect("LPCM input, n_launch = 1024", with(lp, [](RenderParams &p) { p.n_launch = p.n_streams = 1024; }), 16, nullptr, Family::Lpcm, 1);
+  expect("  n_launch = 1025", with(lp, [](RenderParams &p) { p.n_launch = p.n_streams = 1025; }), 16, nullptr, Family::Lpcm, 0);
+  expect("  IAMF_HIP_LP_LATE", lp, 16, "IAMF_HIP_LP_LATE", Family::Lpcm, 0);
+  expect("  m = 6: no instance", with(aligned(6, 2), lpcm), 6, nullptr, Family::Refused, 0, IAMF_HIP_ERR_INVALID_STATE);
+  expect("  pos0 = 8: not a call of the fast kernel", with(lp, [](RenderParams &p) { p.pos0 = 8; }), 16, nullptr, Family::Refused, 0,
+         IAMF_HIP_ERR_INVALID_STATE);
+
+  printf("%d cases, %d wrong\n", g_cases, g_failed);
+  if (!g_failed) printf("OK\n");
+  return g_failed ? 1 : 0;
+}

@@ -1,0 +1,26 @@
+"""Which kernel a render call takes is decided by pick_route() in iac_amd/csrc/render_route.hpp, a plain C++ header:
+tests/route_host/route_host_check.cpp compiles it with the host compiler and checks a table of parameter blocks against
+the expected kernel family, variant and return code (and the instance-list helper the launchers walk).  Every render
+kernel is exact, so a wrong routing decision is invisible to the parity tests and shows only as a slower rate; this
+is the test that sees it.  (That the routes are what gets launched: launch() in iamf_render.hip is a switch over them,
+and the GPU suites cover each family's results.)"""
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+
+
+def test_routing_table_on_the_host(tmp_path):
+    exe = os.path.join(str(tmp_path), "route_host_check")
+    src = os.path.join(ROOT, "tests", "route_host", "route_host_check.cpp")
+    cc = CLANG if os.path.exists(CLANG) else "clang++"
+    subprocess.check_call([cc, "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-o", exe, src])
+    env = {k: v for k, v in os.environ.items() if not k.startswith("IAMF_HIP_")}
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
+    assert p.returncode == 0, p.stdout + p.stderr
+    out = p.stdout
+    m = re.search(r"(\d+) cases, (\d+) wrong", out)
+    assert m and int(m.group(1)) >= 55 and int(m.group(2)) == 0, out
+    assert "WRONG" not in out and out.strip().endswith("OK"), out
