@@ -373,6 +373,9 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
   }
   if (!launched) return IAMF_HIP_ERR_INTERNAL;
   HIPCHK(hipGetLastError());
+  const RouteKey k = route_key(r, p, m);   // the tally of iamf_hip_route_tally
+  iamf_hip_route_count(k.family, k.variant, k.m, k.c, k.k);
+  if (r.family == Family::FirSplit) iamf_hip_route_count(IAMF_HIP_ROUTE_FAST, 0, 2, 2, 0);
   return IAMF_HIP_OK;
 }
 
@@ -1293,6 +1296,7 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
     }
     if (!iamf_hip_fanout_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
     HIPCHK(hipGetLastError());
+    iamf_hip_route_count(IAMF_HIP_ROUTE_FANOUT, 0, b0->m, 0, k);
     for (int j = 0; j < n_batches; ++j) {
       if (!fuse[j]) continue;
       const int r = render_commit(batches[j], pcs[j]);

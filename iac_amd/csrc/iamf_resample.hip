@@ -19,12 +19,16 @@
 #include <string.h>
 
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/iamf_hip.h"
 #include "../data/resample_window_q4.h"
+#include "render_entry.hpp"
 
 namespace {
+
+#include "resample_route.hpp"
 
 struct RsParams {
   const float *in;        // [stream][ns][ch] or nullptr (zeros)
@@ -319,25 +323,26 @@ __global__ __launch_bounds__(512) void resample_block_kernel(const RsParams p, i
   }
 }
 
-// R for a channel count: 4 R C accumulators per thread in interpolated mode
-constexpr int rs_block_r(int c) { return c <= 2 ? 4 : (c <= 8 ? 2 : 1); }
 template <int C, int R>
 void rs_block_launch_cr(const RsParams &p, int G, dim3 grid, unsigned block, size_t lds, hipStream_t st) {
   hipLaunchKernelGGL((resample_block_kernel<C, R>), grid, dim3(block), lds, st, p, G);
 }
-// mono, stereo / binaural, 5.1 / 3.1.2, 7.1 / 5.1.2; `r` is one of 1, 2, 4 and at most rs_block_r(ch).  false: no instantiation
-bool rs_block_launch(int ch, int r, const RsParams &p, int G, dim3 grid, unsigned block, size_t lds, hipStream_t st) {
-#define RS_CASE(C_)                                                                   \
-  case C_:                                                                            \
-    if (r >= 4 && rs_block_r(C_) >= 4) rs_block_launch_cr<C_, rs_block_r(C_) >= 4 ? 4 : 1>(p, G, grid, block, lds, st);      \
-    else if (r >= 2 && rs_block_r(C_) >= 2) rs_block_launch_cr<C_, rs_block_r(C_) >= 2 ? 2 : 1>(p, G, grid, block, lds, st); \
-    else rs_block_launch_cr<C_, 1>(p, G, grid, block, lds, st);                        \
-    return true;
-  switch (ch) {
-    RS_CASE(1) RS_CASE(2) RS_CASE(6) RS_CASE(8) RS_CASE(10) RS_CASE(12) RS_CASE(14) RS_CASE(24)
-    default: return false;
-  }
-#undef RS_CASE
+// `r` is one of RsBlockR; the instance launched has the largest R of the list that is at most r and rs_block_r(ch), and
+// *r_used says which.  false: no instantiation for `ch` (RsBlockC, resample_route.hpp)
+bool rs_block_launch(int ch, int r, const RsParams &p, int G, dim3 grid, unsigned block, size_t lds, hipStream_t st, int *r_used) {
+  return dispatch(RsBlockC{}, ch, [&](auto C) {
+    int rr = r >= 4 ? 4 : (r >= 2 ? 2 : 1);
+    while (rr > rs_block_r(C.value)) rr >>= 1;
+    *r_used = rr;
+    return dispatch(RsBlockR{}, rr, [&](auto R) {
+      if constexpr (R.value <= rs_block_r(C.value)) {
+        rs_block_launch_cr<C.value, R.value>(p, G, grid, block, lds, st);
+        return true;
+      } else {
+        return false;
+      }
+    });
+  });
 }
 
 // DIRECT mode (small denominators: 2:1, 3:1, 1:2, 1:3, 2:3, 3:2 ...; resample.c:273-281) with the phase's filter row in
@@ -464,30 +469,16 @@ __global__ __launch_bounds__(256, 2) void resample_direct_kernel(const RsParams 
   }
 }
 
-// outputs a thread works on at once
-constexpr int rs_direct_r(int c) { return c <= 2 ? 4 : (c <= 8 ? 2 : 1); }
-template <int C>
-bool rs_direct_launch_c(int n, int nump, const RsParams &p, int G, dim3 grid, unsigned block, size_t lds, hipStream_t st) {
-  constexpr int R = rs_direct_r(C);
-  if (n == 64 && nump == 1) hipLaunchKernelGGL((resample_direct_kernel<C, 64, 1, R>), grid, dim3(block), lds, st, p, G);
-  else if (n == 96 && nump == 1) hipLaunchKernelGGL((resample_direct_kernel<C, 96, 1, R>), grid, dim3(block), lds, st, p, G);
-  else if (n == 128 && nump == 2) hipLaunchKernelGGL((resample_direct_kernel<C, 128, 2, R>), grid, dim3(block), lds, st, p, G);
-  else if (n == 192 && nump == 3 && (C == 6 || C >= 10))   // (192 taps + accumulators: two waves per SIMD; 1, 2 and 8 channels measured 0.8 of the tiled kernel)
-    hipLaunchKernelGGL((resample_direct_kernel<C, 192, 3, R>), grid, dim3(block), lds, st, p, G);
-  else return false;
-  return true;
-}
-// filter lengths of quality 4: 64 (up-sampling), 96 (3:2), 128 (2:1), 192 (3:1).  false: no instantiation
+// (N, NUMP) of RsDirectNP for the channel counts of RsDirectC, where rs_direct_takes (resample_route.hpp) lets the call in.
+// false: no instantiation, or one the rule keeps for the tiled kernel
 bool rs_direct_launch(int ch, int n, int nump, const RsParams &p, int G, dim3 grid, unsigned block, size_t lds, hipStream_t st) {
-  switch (ch) {
-    case 1: return rs_direct_launch_c<1>(n, nump, p, G, grid, block, lds, st);
-    case 2: return rs_direct_launch_c<2>(n, nump, p, G, grid, block, lds, st);
-    case 6: return rs_direct_launch_c<6>(n, nump, p, G, grid, block, lds, st);
-    case 8: return rs_direct_launch_c<8>(n, nump, p, G, grid, block, lds, st);
-    case 10: return rs_direct_launch_c<10>(n, nump, p, G, grid, block, lds, st);
-    case 12: return rs_direct_launch_c<12>(n, nump, p, G, grid, block, lds, st);
-    default: return false;
-  }
+  if (nump < 1 || nump > 3 || !rs_direct_takes(ch, n)) return false;
+  return dispatch(RsDirectC{}, ch, [&](auto C) {
+    return dispatch(RsDirectNP{}, rs_np(n, nump), [&](auto V) {
+      hipLaunchKernelGGL((resample_direct_kernel<C.value, rs_np_n(V.value), rs_np_p(V.value), rs_direct_r(C.value)>), grid, dim3(block),
+                         lds, st, p, G);
+    });
+  });
 }
 
 // ---- filter design on the host: resample.c:194-231 (window, sinc) and :527-611 ----
@@ -604,6 +595,7 @@ int rs_run(iamf_hip_resampler *r, const float *d_in, int64_t in_stride, int ns, 
   const size_t tab_floats = r->direct ? (size_t)r->den * (r->filt_len + 4) : (size_t)4 * r->oversample * (r->filt_len + 1);
   const size_t lds = sizeof(float) * ((((size_t)win_cap * r->ch + 3) & ~(size_t)3) + tab_floats);
   bool blocked = false;
+  struct { int family, variant, m, c, k; } ran = {IAMF_HIP_ROUTE_RS_PLAIN, 0, 0, 0, 0};   // the tally of iamf_hip_route_tally
   // direct mode: a thread = one phase with its filter row in registers (resample_direct_kernel)
   if (r->direct && r->den <= 16 && !getenv("IAMF_HIP_RESAMPLE_PLAIN") && !getenv("IAMF_HIP_RESAMPLE_TILE")) {
     const int nump = r->den == 1 ? (int)r->num : 1;
@@ -620,6 +612,7 @@ int rs_run(iamf_hip_resampler *r, const float *d_in, int64_t in_stride, int ns, 
         const unsigned blk = (unsigned)(((int)r->den * G + 63) & ~63);
         dim3 dgrid((unsigned)(n_out > 0 ? (n_out + T - 1) / T : 1), (unsigned)cnt);
         blocked = rs_direct_launch(r->ch, (int)r->filt_len, nump, p, G, dgrid, blk, dlds, static_cast<hipStream_t>(stream));
+        if (blocked) ran = {IAMF_HIP_ROUTE_RS_DIRECT, nump, (int)r->filt_len, r->ch, R};
         break;
       }
     }
@@ -649,7 +642,9 @@ int rs_run(iamf_hip_resampler *r, const float *d_in, int64_t in_stride, int ns, 
         p.win_cap = (int)wcap;
         const unsigned blk = (unsigned)(((int)r->den * G + 63) & ~63);
         dim3 bgrid((unsigned)(n_out > 0 ? (n_out + T - 1) / T : 1), (unsigned)cnt);
-        blocked = rs_block_launch(r->ch, R, p, G, bgrid, blk, blds, static_cast<hipStream_t>(stream));
+        int r_used = 0;
+        blocked = rs_block_launch(r->ch, R, p, G, bgrid, blk, blds, static_cast<hipStream_t>(stream), &r_used);
+        if (blocked) ran = {IAMF_HIP_ROUTE_RS_BLOCK, 0, 0, r->ch, r_used};
         break;
       }
       if (R > 1) R >>= 1;
@@ -663,10 +658,12 @@ int rs_run(iamf_hip_resampler *r, const float *d_in, int64_t in_stride, int ns, 
     p.win_cap = (int)win_cap;
     dim3 tgrid((unsigned)((work + kRsTile - 1) / kRsTile), (unsigned)cnt);
     hipLaunchKernelGGL(resample_tile_kernel, tgrid, dim3(256), lds, static_cast<hipStream_t>(stream), p);
+    ran = {IAMF_HIP_ROUTE_RS_TILE, r->direct ? 1 : 0, 0, 0, 0};
   } else {
     hipLaunchKernelGGL(resample_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
   }
   RS_HIPCHK(hipGetLastError());
+  iamf_hip_route_count(ran.family, ran.variant, ran.m, ran.c, ran.k);
   for (int i = s0; i < s0 + cnt; ++i) {
     r->last_sample[(size_t)i] = ls - consumed;
     r->frac[(size_t)i] = fr;

@@ -1,0 +1,106 @@
+// iamf_route.hip — which kernel ran (include/iamf_hip.h: iamf_hip_route_instances, iamf_hip_route_tally).  Host code only.
+// The table is built by walking the lists the launchers dispatch over (render_route.hpp, resample_route.hpp), so a kernel
+// instance added to a list is listed and counted without a change here.  Counting is one relaxed atomic add per launch on a
+// fixed array: no lock and no allocation on the call path (the decoder groups launch from several threads).
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <type_traits>
+
+#include "../../include/iamf_hip.h"
+#include "render_entry.hpp"
+
+namespace {
+
+#include "render_params.hpp"
+#include "render_route.hpp"
+#include "resample_route.hpp"
+
+constexpr int kRouteCap = 1024;   // rows the table can hold; slot kRouteCap counts launches outside the table
+
+constexpr uint32_t pack_key(int family, int variant, int m, int c, int k) {
+  return (uint32_t)family << 24 | (uint32_t)variant << 20 | (uint32_t)m << 12 | (uint32_t)c << 4 | (uint32_t)k;
+}
+
+struct RouteTable {
+  iamf_hip_route_row rows[kRouteCap];
+  uint32_t key[kRouteCap];     // sorted
+  int32_t index[kRouteCap];    // row of key[i]
+  int n = 0, dropped = 0;
+  RouteTable() {
+    const auto add = [&](int family, int variant, int m, int c, int k) {
+      if (n == kRouteCap) {
+        ++dropped;
+        return;
+      }
+      iamf_hip_route_row &r = rows[n];
+      memset(&r, 0, sizeof(r));
+      r.family = family;
+      r.variant = variant;
+      r.m = m;
+      r.c = c;
+      r.k = k;
+      key[n] = pack_key(family, variant, m, c, k);
+      index[n] = n;
+      ++n;
+    };
+    for_each_render_instance(add);
+    for_each_resample_instance(add);
+    int32_t order[kRouteCap];
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::sort(order, order + n, [&](int a, int b) { return key[a] < key[b]; });
+    uint32_t sorted[kRouteCap];
+    for (int i = 0; i < n; ++i) sorted[i] = key[order[i]];
+    memcpy(key, sorted, sizeof(uint32_t) * n);
+    memcpy(index, order, sizeof(int32_t) * n);
+  }
+  int find(uint32_t k) const {
+    const uint32_t *e = key + n, *p = std::lower_bound(key, e, k);
+    return (p != e && *p == k) ? index[p - key] : kRouteCap;
+  }
+};
+
+const RouteTable &route_table() {
+  static const RouteTable t;
+  return t;
+}
+
+std::atomic<int64_t> g_launches[kRouteCap + 1];
+
+}  // namespace
+
+void iamf_hip_route_count(int family, int variant, int m, int c, int k) {
+  g_launches[route_table().find(pack_key(family, variant, m, c, k))].fetch_add(1, std::memory_order_relaxed);
+}
+
+extern "C" {
+
+int iamf_hip_route_instances(iamf_hip_route_row *rows, int cap) {
+  const RouteTable &t = route_table();
+  for (int i = 0; rows && i < t.n && i < cap; ++i) rows[i] = t.rows[i];
+  return t.n + t.dropped;
+}
+
+int iamf_hip_route_tally(iamf_hip_route_row *rows, int cap, int reset) {
+  const RouteTable &t = route_table();
+  int cnt = 0;
+  for (int i = 0; i <= kRouteCap; ++i) {
+    if (i >= t.n && i != kRouteCap) continue;
+    const int64_t v = reset ? g_launches[i].exchange(0, std::memory_order_relaxed) : g_launches[i].load(std::memory_order_relaxed);
+    if (v == 0) continue;
+    if (rows && cnt < cap) {
+      if (i < t.n) rows[cnt] = t.rows[i];
+      else memset(&rows[cnt], 0, sizeof(rows[cnt]));   // IAMF_HIP_ROUTE_NONE
+      rows[cnt].launches = v;
+    }
+    ++cnt;
+  }
+  return cnt;
+}
+
+}  // extern "C"

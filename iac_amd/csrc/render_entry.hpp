@@ -26,3 +26,5 @@ IAMF_INTERNAL int iamf_hip_lpcm_unpack_frames(const iamf_hip_lpcm_layout *lay, c
                                               int64_t first_count_stride, float *d_out, int64_t out_stream_stride,
                                               int64_t out_frame_stride, int32_t n_streams, void *stream, int32_t uniform_first,
                                               int32_t uniform_count);
+// iamf_route.hip: one launch of the instance (family, variant, m, c, k) of iamf_hip_route_row succeeded
+IAMF_INTERNAL void iamf_hip_route_count(int family, int variant, int m, int c, int k);

@@ -14,29 +14,7 @@
 // instance lists
 // ------------------------------------------------------------------------------------------
 
-template <int... V>
-struct Ints {
-  static constexpr bool has(int v) { return ((v == V) || ...); }
-};
-// Calls f(std::integral_constant<int, V>) for the V of the list that equals v; false if v is not in the list.  (An f that
-// returns a value — a dispatch over a second list — decides the result itself.)
-template <int V, class F>
-bool dispatch_hit(F &f) {
-  if constexpr (std::is_void_v<decltype(f(std::integral_constant<int, V>{}))>) {
-    f(std::integral_constant<int, V>{});
-    return true;
-  } else {
-    return f(std::integral_constant<int, V>{});
-  }
-}
-template <int... V, class F>
-bool dispatch(Ints<V...>, int v, F &&f) {
-  return ((v == V && dispatch_hit<V>(f)) || ...);
-}
-// an (inputs, outputs) pair as one list entry
-constexpr int mc(int m, int c) { return m * 32 + c; }
-constexpr int mc_m(int v) { return v / 32; }
-constexpr int mc_c(int v) { return v % 32; }
+#include "instance_lists.hpp"
 
 // inputs of render_kernel (render_generic.hpp) and render_nolim_kernel.  11 inputs: no element of the reference has them,
 // but the stage behind the resampler takes the OUTPUT layout's channels through the identity, and Sound System E has 11
@@ -44,6 +22,7 @@ constexpr int mc_c(int v) { return v % 32; }
 using GenericM = Ints<1, 2, 4, 6, 8, 9, 10, 11, 12, 14, 16, 24>;
 using NolimM = GenericM;
 using FastM = Ints<1, 2, 4, 6, 8, 9, 10, 12, 14, 16, 24>;   // render_fast_kernel<M, 1 | 2> and its mixing variant
+using FastOC = Ints<1, 2>;
 using WideM = FastM;                                        // render_wide_kernel<M, MFMA>
 // render_fast_kernel<M, OC, 0, DOWN>, the parametric down-mixer to mono / stereo: 7.1 -> {2, 1}, 5.1 -> {2, 1}, stereo -> mono
 using FastDownMC = Ints<mc(8, 2), mc(8, 1), mc(6, 2), mc(6, 1), mc(2, 1)>;
@@ -269,4 +248,64 @@ inline Route pick_route(const RenderParams &p, int m) {
   // everything else: ragged calls, flush, wide second elements, exact two-stage projection, demixer + down-mixer
   // together, other PCM formats of the stages above
   return GenericM::has(m) ? take(Family::Generic) : refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
+}
+
+// ------------------------------------------------------------------------------------------
+// the instance table: every render kernel instance of the build, as rows of include/iamf_hip.h
+// ------------------------------------------------------------------------------------------
+
+// f(family, variant, m, c, k) — family: IAMF_HIP_ROUTE_*, the other fields as iamf_hip.h says per family — for every
+// instance the launchers can name, walking the lists they dispatch over.  iamf_route.hip numbers the rows in this order.
+template <class F>
+void for_each_render_instance(F &&f) {
+  for_each_int(GenericM{}, [&](int m) { f(IAMF_HIP_ROUTE_GENERIC, 0, m, 0, 0); });
+  for_each_int(NolimM{}, [&](int m) { f(IAMF_HIP_ROUTE_NOLIM, 0, m, 0, 0); });
+  for (int mixing = 0; mixing < 2; ++mixing)
+    for_each_int(FastM{}, [&](int m) { for_each_int(FastOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_FAST, mixing, m, oc, 0); }); });
+  for_each_int(FastDownMC{}, [&](int v) { f(IAMF_HIP_ROUTE_FAST_DOWN, 0, mc_m(v), mc_c(v), 0); });
+  for (int mfma = 0; mfma < 2; ++mfma) for_each_int(WideM{}, [&](int m) { f(IAMF_HIP_ROUTE_WIDE, mfma, m, 0, 0); });
+  for (int mfma = 0; mfma < 2; ++mfma)
+    for_each_int(Wide4M{}, [&](int m) { for_each_int(Wide4C{}, [&](int c) { f(IAMF_HIP_ROUTE_WIDE4, mfma, m, c, 0); }); });
+  for_each_int(Wide4DemixM{}, [&](int m) { for_each_int(Wide4DemixC{}, [&](int c) { f(IAMF_HIP_ROUTE_WIDE4_DEMIX, 0, m, c, 0); }); });
+  for_each_int(Wide4DownMC{}, [&](int v) { f(IAMF_HIP_ROUTE_WIDE4_DOWN, 0, mc_m(v), mc_c(v), 0); });
+  for (int mfma = 0; mfma < 2; ++mfma)
+    for_each_int(Wide4M{}, [&](int m) { for_each_int(Wide4MixC{}, [&](int c) { f(IAMF_HIP_ROUTE_WIDE4_MIX, mfma, m, c, 0); }); });
+  for (int mfma = 0; mfma < 2; ++mfma)
+    for_each_int(Wide4LfeM{}, [&](int m) { for_each_int(Wide4C{}, [&](int c) { f(IAMF_HIP_ROUTE_WIDE4_LFE, mfma, m, c, 0); }); });
+  for (int early = 0; early < 2; ++early)
+    for_each_int(LpcmM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM, early, m, oc, 0); }); });
+  for_each_int(FanM{}, [&](int m) { for_each_int(FanK{}, [&](int k) { f(IAMF_HIP_ROUTE_FANOUT, 0, m, 0, k); }); });
+  for (int home = 1; home >= 0; --home) {
+    const auto firs = [&](int m) {
+      f(IAMF_HIP_ROUTE_FIR_SPLIT, 0, m, 0, 0);
+      for (int stage = 1; stage <= 3; ++stage) f(IAMF_HIP_ROUTE_FIR_FUSED, stage, m, 0, 0);
+    };
+    if (home) for_each_int(FirHomeM{}, firs);
+    else for_each_int(FirM2bM{}, firs);
+  }
+}
+
+// the row of the kernel launch() runs for a route (a FirSplit call launches render_fast_kernel<2, 2> behind it as well:
+// launch() counts that row too)
+struct RouteKey {
+  int family, variant, m, c, k;
+};
+inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
+  switch (r.family) {
+    case Family::Refused: break;
+    case Family::Lpcm: return {IAMF_HIP_ROUTE_LPCM, r.variant, m, p.out_ch, 0};
+    case Family::FirSplit: return {IAMF_HIP_ROUTE_FIR_SPLIT, 0, m, 0, 0};
+    case Family::FirFused: return {IAMF_HIP_ROUTE_FIR_FUSED, r.variant, m, 0, 0};
+    case Family::FastDown: return {IAMF_HIP_ROUTE_FAST_DOWN, 0, m, p.out_ch, 0};
+    case Family::Wide4Lfe: return {IAMF_HIP_ROUTE_WIDE4_LFE, r.variant, m, p.out_ch, 0};
+    case Family::Wide4: return {IAMF_HIP_ROUTE_WIDE4, r.variant, m, p.out_ch, 0};
+    case Family::Wide4Demix: return {IAMF_HIP_ROUTE_WIDE4_DEMIX, 0, m, p.out_ch, 0};
+    case Family::Wide4Down: return {IAMF_HIP_ROUTE_WIDE4_DOWN, 0, m, p.out_ch, 0};
+    case Family::Wide4Mix: return {IAMF_HIP_ROUTE_WIDE4_MIX, r.variant, m, p.out_ch, 0};
+    case Family::Nolim: return {IAMF_HIP_ROUTE_NOLIM, 0, m, 0, 0};
+    case Family::Fast: return {IAMF_HIP_ROUTE_FAST, r.variant, m, p.out_ch, 0};
+    case Family::Wide: return {IAMF_HIP_ROUTE_WIDE, r.variant, m, 0, 0};
+    case Family::Generic: return {IAMF_HIP_ROUTE_GENERIC, 0, m, 0, 0};
+  }
+  return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

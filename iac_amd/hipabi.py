@@ -70,6 +70,17 @@ class LpcmInput(C.Structure):   # iamf_hip_lpcm_input
                 ("first_sample", C.c_int32), ("layout", LpcmLayout)]
 
 
+class RouteRow(C.Structure):   # iamf_hip_route_row
+    _fields_ = [("family", C.c_int32), ("variant", C.c_int32), ("m", C.c_int32), ("c", C.c_int32), ("k", C.c_int32),
+                ("reserved", C.c_int32), ("launches", C.c_int64)]
+
+
+# IAMF_HIP_ROUTE_*: the kernel families of iamf_hip_route_row::family
+ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, WIDE4_DEMIX=7, WIDE4_DOWN=8, WIDE4_MIX=9,
+             WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23)
+ROUTE_NAME = {v: k for k, v in ROUTE.items()}
+
+
 class DemixConfig(C.Structure):
     _fields_ = [("layout", C.c_int32), ("n_in", C.c_int32), ("chs_in", C.c_int32 * 12), ("n_gain", C.c_int32),
                 ("gain_ch", C.c_int32 * 12), ("gain", C.c_float * 12), ("frame_offset", C.c_uint32)]
@@ -172,6 +183,8 @@ def lib():
         L.iamf_hip_dmx_set_mode_weight.argtypes = [C.POINTER(DmxState), C.c_int, C.c_int]
         L.iamf_hip_dmx_coefficients.argtypes = [C.POINTER(DmxState), FP]
         L.iamf_hip_dmx_coefficients.restype = None
+        L.iamf_hip_route_instances.argtypes = [C.POINTER(RouteRow), C.c_int]
+        L.iamf_hip_route_tally.argtypes = [C.POINTER(RouteRow), C.c_int, C.c_int]
         L.iamf_hip_shard_split.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.iamf_hip_shard_create.argtypes = [C.POINTER(BatchConfig), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_shard_destroy.argtypes = [C.c_void_p]
@@ -240,6 +253,28 @@ def lpcm_unpack(layout, d_raw, raw_stream_stride, d_first_count, d_out, out_stre
     if r < 0:
         raise IamfHipError(r, "iamf_hip_lpcm_unpack")
     return r
+
+
+def route_instances():
+    """iamf_hip_route_instances: every kernel instance of the build as (family name, variant, m, c, k); needs no GPU"""
+    L = lib()
+    n = L.iamf_hip_route_instances(None, 0)
+    rows = (RouteRow * max(n, 1))()
+    n = min(n, L.iamf_hip_route_instances(rows, n))
+    return [(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k) for r in rows[:n]]
+
+
+def route_tally(reset=True):
+    """iamf_hip_route_tally: {(family name, variant, m, c, k): launches} since the last reset"""
+    L = lib()
+    cap = L.iamf_hip_route_instances(None, 0) + 1
+    rows = (RouteRow * cap)()
+    n = L.iamf_hip_route_tally(rows, cap, 1 if reset else 0)
+    return {(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k): r.launches for r in rows[:min(n, cap)]}
+
+
+def route_reset():
+    lib().iamf_hip_route_tally(None, 0, 1)
 
 
 FANOUT_MAX = 4   # IAMF_HIP_FANOUT_MAX

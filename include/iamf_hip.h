@@ -576,6 +576,59 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
                               int32_t n_samples, float *d_dst, int64_t dst_stream_stride, int64_t dst_channel_stride, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Which kernel ran.  Every render kernel is exact and the general kernel takes what the others refuse, so results alone
+ * do not show which instance a call launched.  The library lists the kernel instances it holds and counts, process-wide,
+ * every launch per instance: a test resets the tally, makes its calls and reads which instances ran.
+ *   family: IAMF_HIP_ROUTE_* below (stable numbers).  The other fields, per family (0 where not named):
+ *     GENERIC, NOLIM       m = inputs
+ *     FAST                 variant 1 = mixing (second element / ramps), m, c = output channels (1, 2)
+ *     FAST_DOWN, WIDE4_DEMIX, WIDE4_DOWN   m, c = output channels
+ *     WIDE                 variant 1 = MFMA projection, m
+ *     WIDE4, WIDE4_MIX, WIDE4_LFE          variant 1 = MFMA projection, m, c
+ *     LPCM                 variant 1 = early per-channel prefetch, 0 = late; m, c
+ *     FANOUT               m, k = members of the fused launch
+ *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
+ *     FIR_FUSED            variant = stage (3 FFT, 2 split-f16 MFMA, 1 f32 MFMA), m
+ *     RS_PLAIN             resample_kernel
+ *     RS_TILE              resample_tile_kernel, variant 1 = direct mode, 0 = interpolated
+ *     RS_BLOCK             resample_block_kernel<C, R>: c = C, k = R
+ *     RS_DIRECT            resample_direct_kernel<C, N, NUMP, R>: m = N, c = C, variant = NUMP, k = R
+ *   A launch counts after it succeeded.  Counters are relaxed atomics: any thread may launch while another reads.
+ * ---------------------------------------------------------------------------------------- */
+enum {
+  IAMF_HIP_ROUTE_NONE = 0,   /* tally only: launches of an instance the listing does not hold (a defect) */
+  IAMF_HIP_ROUTE_GENERIC = 1,
+  IAMF_HIP_ROUTE_NOLIM = 2,
+  IAMF_HIP_ROUTE_FAST = 3,
+  IAMF_HIP_ROUTE_FAST_DOWN = 4,
+  IAMF_HIP_ROUTE_WIDE = 5,
+  IAMF_HIP_ROUTE_WIDE4 = 6,
+  IAMF_HIP_ROUTE_WIDE4_DEMIX = 7,
+  IAMF_HIP_ROUTE_WIDE4_DOWN = 8,
+  IAMF_HIP_ROUTE_WIDE4_MIX = 9,
+  IAMF_HIP_ROUTE_WIDE4_LFE = 10,
+  IAMF_HIP_ROUTE_LPCM = 11,
+  IAMF_HIP_ROUTE_FANOUT = 12,
+  IAMF_HIP_ROUTE_FIR_SPLIT = 13,
+  IAMF_HIP_ROUTE_FIR_FUSED = 14,
+  IAMF_HIP_ROUTE_RS_PLAIN = 20,
+  IAMF_HIP_ROUTE_RS_TILE = 21,
+  IAMF_HIP_ROUTE_RS_BLOCK = 22,
+  IAMF_HIP_ROUTE_RS_DIRECT = 23
+};
+typedef struct {
+  int32_t family, variant, m, c, k;
+  int32_t reserved;
+  int64_t launches;   /* iamf_hip_route_instances: 0 */
+} iamf_hip_route_row;
+/* Every kernel instance this build holds, in a fixed order; needs no device.  Writes min(cap, count) rows (rows may be NULL
+ * with cap 0) and returns the count. */
+int iamf_hip_route_instances(iamf_hip_route_row *rows, int cap);
+/* The instances launched since the last reset, with their counts, in the listing's order; reset != 0 zeroes the counters
+ * as it reads them.  Writes min(cap, count) rows and returns the count (rows NULL, cap 0, reset 1: just reset). */
+int iamf_hip_route_tally(iamf_hip_route_row *rows, int cap, int reset);
+
+/* ------------------------------------------------------------------------------------------
  * A group of decoder handles: callers of the reference API get the batch renderer's throughput.
  * The reference renders one handle, one frame per call (IAMF_decoder_decode, include/IAMF_decoder.h:82-99, driver loop
  * src/iamf_dec/IAMF_decoder.c:3303-3525).  N configured handles (IAMF_DecoderHandle of this library's IAMF_decoder.h) of ONE

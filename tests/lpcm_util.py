@@ -1,0 +1,98 @@
+"""LPCM packet rows for iamf_hip_batch_render_lpcm and the loop that renders them (shared by tests/test_gpu_lpcm.py and
+tests/route_cases.py)."""
+import numpy as np
+
+import iac_amd as A
+
+
+def pack(v, bps, le):
+    """int samples [..., n] -> bytes [..., n * bps] in the reference's byte orders (24-bit big-endian: bitstream.c:204-208:
+    byte 1 is the top one, then byte 2, byte 0 is the low one)"""
+    v = v.astype(np.int64)
+    u = v & ((1 << (8 * bps)) - 1)
+    b = [((u >> (8 * k)) & 0xff).astype(np.uint8) for k in range(bps)]   # b[0] = low byte
+    if le:
+        order = b
+    elif bps == 3:
+        order = [b[1], b[2], b[0]]   # reads24be: p[2] | p[0] << 8 | p[1] << 16
+    else:
+        order = b[::-1]
+    return np.stack(order, axis=-1).reshape(v.shape[:-1] + (v.shape[-1] * bps,))
+
+
+def rows(ints, bps, le, widths, perm, head, pad, frame_size):
+    """ints [S][F][ch][fs] -> packet rows [S][F][row bytes] + layout.  Sub-stream j carries widths[j] channels (1 = mono
+    packet, 2 = coupled: samples interleaved); perm[c] = the decoded channel output channel c takes."""
+    S, F, ch, fs = ints.shape
+    assert sum(widths) == ch and fs == frame_size
+    off = head
+    ch_off, ch_step = [], []
+    pieces = []
+    c = 0
+    for w in widths:
+        blk = ints[:, :, c:c + w, :]                       # [S][F][w][fs]
+        inter = np.ascontiguousarray(blk.transpose(0, 1, 3, 2)).reshape(S, F, fs * w)
+        pieces.append((off, pack(inter, bps, le)))
+        for k in range(w):
+            ch_off.append(off + k * bps)
+            ch_step.append(w * bps)
+        off += w * bps * fs + pad
+        c += w
+    row = (off + 15) & ~15
+    raw = np.zeros((S, F, row), dtype=np.uint8)
+    for o, data in pieces:
+        raw[:, :, o:o + data.shape[-1]] = data
+    L = A.LpcmLayout()
+    L.sample_bytes, L.little_endian, L.channels, L.frame_size = bps, 1 if le else 0, ch, fs
+    for p in range(ch):
+        L.src_offset[p] = ch_off[perm[p]]
+        L.src_step[p] = ch_step[perm[p]]
+    return raw, L, row
+
+
+def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_samples=0, fmt=A.FMT_S16):
+    S, F, _ = raw.shape
+    import torch
+    d_raw = torch.from_numpy(raw).cuda()
+    bps_out = {A.FMT_S16: 2, A.FMT_S24: 3, A.FMT_S32: 4}[fmt]
+    b = A.Batch(S, matrix, out_ch, frame_size=frame_size, out_format=fmt, limiter=True)
+    st = torch.cuda.current_stream().cuda_stream
+    outs = [[] for _ in range(S)]
+    f0 = 0
+    for nf in calls:
+        cap = max(nf * frame_size, 240) * out_ch * bps_out
+        pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
+        inp = A.LpcmInput()
+        inp.d_raw = d_raw.data_ptr() + f0 * row
+        inp.raw_stream_stride = F * row
+        inp.raw_frame_stride = row
+        inp.first_sample = first
+        inp.layout = L
+        a = A.RenderArgs()
+        a.n_frames = nf
+        a.n_samples = n_samples
+        a.d_pcm = pcm.data_ptr()
+        a.pcm_stream_stride_bytes = cap
+        a.stream = st
+        n = b.render_lpcm(inp, a)
+        torch.cuda.synchronize()
+        h = pcm.cpu().numpy()
+        for s in range(S):
+            outs[s].append(h[s][:n * out_ch * bps_out].copy())
+        f0 += nf
+    cap = 240 * out_ch * bps_out
+    pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
+    n = b.flush(pcm.data_ptr(), cap, st)
+    torch.cuda.synchronize()
+    h = pcm.cpu().numpy()
+    for s in range(S):
+        outs[s].append(h[s][:n * out_ch * bps_out].copy())
+    b.close()
+    return [np.concatenate(o) for o in outs]
+
+
+def ints(rng, S, F, ch, fs, bps, level=0.35):
+    full = float(1 << (8 * bps - 1))
+    v = rng.standard_normal((S, F, ch, fs)) * level * full
+    v[:, :, :, ::97] *= 3.0   # peaks: the limiter works
+    return np.clip(np.rint(v), -full, full - 1).astype(np.int64)

@@ -81,7 +81,13 @@ void expect(const char *what, RenderParams p, int m, const char *env, Family fam
   if (env) setenv(env, "1", 1);
   const Route r = pick_route(p, m);
   if (env) unsetenv(env);
-  const bool ok = r.family == family && r.variant == variant && r.err == err;
+  // a route that launches names an instance of the listing (iamf_hip_route_instances walks the same lists)
+  bool listed = r.family == Family::Refused;
+  const RouteKey k = route_key(r, p, m);
+  for_each_render_instance([&](int f, int v, int km, int kc, int kk) {
+    listed = listed || (f == k.family && v == k.variant && km == k.m && kc == k.c && kk == k.k);
+  });
+  const bool ok = r.family == family && r.variant == variant && r.err == err && listed;
   printf("%-72s %s/%d/%d %s\n", what, family_name(r.family), r.variant, r.err, ok ? "ok" : "WRONG");
   if (!ok) printf("    expected %s/%d/%d\n", family_name(family), variant, err);
   ++g_cases;

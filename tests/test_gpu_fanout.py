@@ -174,11 +174,19 @@ def test_shared_kernel_parity(element, K):
     x = programme(ELEMENTS[element][0], S, sum(calls) * fs)
     assert_condition(element, specs, x)
     got, twin = Drive(element, specs, x, fs), Drive(element, specs, x, fs)
+    m = ELEMENTS[element][0]
+    A.route_reset()
     for nf in calls:
         assert got.fan(nf) == K
-        twin.single(nf)
     got.flush()
+    # one launch of render_fanout_kernel<m, K> per call and nothing beside it; each member's flush on the generic kernel
+    assert A.route_tally() == {("FANOUT", 0, m, 0, K): len(calls), ("GENERIC", 0, m, 0, 0): K}
+    for nf in calls:
+        twin.single(nf)
     twin.flush()
+    single = A.route_tally()
+    assert single.pop(("GENERIC", 0, m, 0, 0)) == K and sum(single.values()) == K * len(calls)
+    assert all(k[0] == "FAST" and k[1] == 0 and k[2] == m for k in single), single   # the twin: render_fast_kernel<m, OC> per member
     assert_same(got, twin)
     assert_oracle(got, element, specs, x, fs)
     got.close()

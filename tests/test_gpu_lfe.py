@@ -81,10 +81,13 @@ def test_wide4_lfe_variant_bit_exact_vs_oracle_and_generic(order, lay, ch, monke
     m, F = (order + 1) ** 2, 6
     x = np.stack([LC.programme(500 + 7 * s + order, m, fs * F) * np.float32(2.5) for s in range(3)])
     mx, omx = A.get_h2m_matrix(order, A.SS[lay]), O.get_h2m(order, O.SS[lay])
+    A.route_reset()
     got = G.hip_render(mx, ch, x, frame_size=fs, frames_per_call=calls, lfe_hoa=True, projection=A.PROJ_EXACT)
+    assert A.route_tally() == {("WIDE4_LFE", 0, m, ch, 0): 3, ("GENERIC", 0, m, 0, 0): 1}   # three calls and the flush
     monkeypatch.setenv("IAMF_HIP_NO_WIDE4", "1")
     gen = G.hip_render(mx, ch, x, frame_size=fs, frames_per_call=calls, lfe_hoa=True, projection=A.PROJ_EXACT)
     monkeypatch.delenv("IAMF_HIP_NO_WIDE4")
+    assert A.route_tally() == {("GENERIC", 0, m, 0, 0): 4}
     for s in range(3):
         want = O.stream_run(omx, ch, x[s], fs, lfe_rate=48000)
         assert np.array_equal(got[s], want), s

@@ -16,93 +16,9 @@ import torch
 
 import iac_amd as A
 from gpu_util import hip_render
+from lpcm_util import ints as _ints, render_lpcm as _render_lpcm, rows as _rows
 
 pytestmark = pytest.mark.gpu
-
-
-def _pack(v, bps, le):
-    """int samples [..., n] -> bytes [..., n * bps] in the reference's byte orders (24-bit big-endian: bitstream.c:204-208:
-    byte 1 is the top one, then byte 2, byte 0 is the low one)"""
-    v = v.astype(np.int64)
-    u = v & ((1 << (8 * bps)) - 1)
-    b = [((u >> (8 * k)) & 0xff).astype(np.uint8) for k in range(bps)]   # b[0] = low byte
-    if le:
-        order = b
-    elif bps == 3:
-        order = [b[1], b[2], b[0]]   # reads24be: p[2] | p[0] << 8 | p[1] << 16
-    else:
-        order = b[::-1]
-    return np.stack(order, axis=-1).reshape(v.shape[:-1] + (v.shape[-1] * bps,))
-
-
-def _rows(ints, bps, le, widths, perm, head, pad, frame_size):
-    """ints [S][F][ch][fs] -> packet rows [S][F][row bytes] + layout.  Sub-stream j carries widths[j] channels (1 = mono
-    packet, 2 = coupled: samples interleaved); perm[c] = the decoded channel output channel c takes."""
-    S, F, ch, fs = ints.shape
-    assert sum(widths) == ch and fs == frame_size
-    off = head
-    ch_off, ch_step = [], []
-    pieces = []
-    c = 0
-    for w in widths:
-        blk = ints[:, :, c:c + w, :]                       # [S][F][w][fs]
-        inter = np.ascontiguousarray(blk.transpose(0, 1, 3, 2)).reshape(S, F, fs * w)
-        pieces.append((off, _pack(inter, bps, le)))
-        for k in range(w):
-            ch_off.append(off + k * bps)
-            ch_step.append(w * bps)
-        off += w * bps * fs + pad
-        c += w
-    row = (off + 15) & ~15
-    raw = np.zeros((S, F, row), dtype=np.uint8)
-    for o, data in pieces:
-        raw[:, :, o:o + data.shape[-1]] = data
-    L = A.LpcmLayout()
-    L.sample_bytes, L.little_endian, L.channels, L.frame_size = bps, 1 if le else 0, ch, fs
-    for p in range(ch):
-        L.src_offset[p] = ch_off[perm[p]]
-        L.src_step[p] = ch_step[perm[p]]
-    return raw, L, row
-
-
-def _render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_samples=0, fmt=A.FMT_S16):
-    S, F, _ = raw.shape
-    d_raw = torch.from_numpy(raw).cuda()
-    bps_out = {A.FMT_S16: 2, A.FMT_S24: 3, A.FMT_S32: 4}[fmt]
-    b = A.Batch(S, matrix, out_ch, frame_size=frame_size, out_format=fmt, limiter=True)
-    st = torch.cuda.current_stream().cuda_stream
-    outs = [[] for _ in range(S)]
-    f0 = 0
-    for nf in calls:
-        cap = max(nf * frame_size, 240) * out_ch * bps_out
-        pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
-        inp = A.LpcmInput()
-        inp.d_raw = d_raw.data_ptr() + f0 * row
-        inp.raw_stream_stride = F * row
-        inp.raw_frame_stride = row
-        inp.first_sample = first
-        inp.layout = L
-        a = A.RenderArgs()
-        a.n_frames = nf
-        a.n_samples = n_samples
-        a.d_pcm = pcm.data_ptr()
-        a.pcm_stream_stride_bytes = cap
-        a.stream = st
-        n = b.render_lpcm(inp, a)
-        torch.cuda.synchronize()
-        h = pcm.cpu().numpy()
-        for s in range(S):
-            outs[s].append(h[s][:n * out_ch * bps_out].copy())
-        f0 += nf
-    cap = 240 * out_ch * bps_out
-    pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
-    n = b.flush(pcm.data_ptr(), cap, st)
-    torch.cuda.synchronize()
-    h = pcm.cpu().numpy()
-    for s in range(S):
-        outs[s].append(h[s][:n * out_ch * bps_out].copy())
-    b.close()
-    return [np.concatenate(o) for o in outs]
 
 
 def _reference_bytes(matrix, out_ch, ints, bps, perm, frame_size, calls, fmt=A.FMT_S16):
@@ -114,13 +30,6 @@ def _reference_bytes(matrix, out_ch, ints, bps, perm, frame_size, calls, fmt=A.F
     planar = np.ascontiguousarray(x.transpose(0, 2, 1, 3)).reshape(S, ch, F * fs)
     outs = hip_render(matrix, out_ch, planar, frame_size, fmt=fmt, frames_per_call=calls)
     return [np.ascontiguousarray(o).view(np.uint8).reshape(-1) for o in outs]
-
-
-def _ints(rng, S, F, ch, fs, bps, level=0.35):
-    full = float(1 << (8 * bps - 1))
-    v = rng.standard_normal((S, F, ch, fs)) * level * full
-    v[:, :, :, ::97] *= 3.0   # peaks: the limiter works
-    return np.clip(np.rint(v), -full, full - 1).astype(np.int64)
 
 
 @pytest.mark.parametrize("order,out", [(3, "binaural"), (2, "binaural"), (1, "stereo"), (0, "stereo")])
@@ -138,7 +47,14 @@ def test_mono_coded_ambisonics_s16_equals_the_f32_path(order, out, unfused, monk
     perm = list(rng.permutation(ch))
     raw, L, row = _rows(ints, 2, True, [1] * ch, perm, head=16, pad=0, frame_size=fs)
     calls = [2, 1, 3]
+    A.route_reset()
     got = _render_lpcm(mx, 2, raw, L, row, fs, calls)
+    tally = A.route_tally()
+    if unfused:   # the device unpacker, then the f32 kernel
+        assert not [k for k in tally if k[0] == "LPCM"], tally
+        assert tally == {("FAST", 0, ch, 2, 0): 3, ("GENERIC", 0, ch, 0, 0): 1}
+    else:         # render_fast_kernel<ch, 2, .., LP> with the early prefetch (5 streams), the flush on the generic kernel
+        assert tally == {("LPCM", 1, ch, 2, 0): 3, ("GENERIC", 0, ch, 0, 0): 1}
     want = _reference_bytes(mx, 2, ints, 2, perm, fs, calls)
     for s in range(S):
         assert np.array_equal(got[s], want[s]), "stream %d" % s

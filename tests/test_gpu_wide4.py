@@ -44,8 +44,11 @@ def test_wide4_exact_multi_stream_multi_call(hip, src, out):
     x = np.stack([synth.hot(900 + 7 * s, m, F * fs, sigma=0.22, burst_phase=150 + 400 * s, burst_period=2300)
                   for s in range(S)])
     eg, og = [0.8, 1.0, 1.2], [1.0, 0.9, 1.0]
+    A.route_reset()
     got = G.hip_render(mx, ch, x, frame_size=fs, flush=True, frames_per_call=[1, 2, 1, 1],
                        gains=dict(element=eg, output=og), projection=A.PROJ_EXACT)
+    # the four calls ran render_wide4_kernel<m, ch>, the flush the generic kernel
+    assert A.route_tally() == {("WIDE4", 0, m, ch, 0): 4, ("GENERIC", 0, m, 0, 0): 1}
     for s in range(S):
         want = O.stream_run(omx, ch, x[s], fs, element_gain=eg[s], output_gain=og[s])
         assert got[s].shape == want.shape
