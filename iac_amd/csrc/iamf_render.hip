@@ -61,6 +61,7 @@ namespace {
 #include "render_nolim.hpp"
 #include "render_wide.hpp"
 #include "render_lfe.hpp"
+#include "stream_state.hpp"
 
 // PCM with a fixed channel stride (the -DSAMSUNG_TV build: iamf_decoder_plane2stride_out with
 // stride = SAMSUNG_SPECIFIC_CHANNELS = 12, IAMF_decoder.c:121-167,3492-3495).  The reference zeroes
@@ -1024,10 +1025,14 @@ int iamf_hip_batch_set_gains(iamf_hip_batch *b, const float *eg, const float *og
     if (q != IAMF_HIP_OK) return q;
   }
   const int ns = b->cfg.n_streams;
-  if (eg) memcpy(&b->h_gains[0], eg, sizeof(float) * ns);
-  if (og) memcpy(&b->h_gains[(size_t)ns], og, sizeof(float) * ns);
-  if (lg) memcpy(&b->h_gains[(size_t)2 * ns], lg, sizeof(float) * ns);
-  HIPCHK(hipMemcpy(b->d_gains, b->h_gains.data(), sizeof(float) * 3 * ns, hipMemcpyHostToDevice));
+  // Only the rows given are uploaded: a row left NULL keeps what the device holds, which since iamf_hip_batch_import_range
+  // may be newer than the host mirror (an imported stream's gains arrive in its blob, on the device).
+  const float *rows[3] = {eg, og, lg};
+  for (int k = 0; k < 3; ++k) {
+    if (!rows[k]) continue;
+    memcpy(&b->h_gains[(size_t)k * ns], rows[k], sizeof(float) * ns);
+    HIPCHK(hipMemcpy(b->d_gains + (size_t)k * ns, rows[k], sizeof(float) * ns, hipMemcpyHostToDevice));
+  }
   return IAMF_HIP_OK;
 }
 
@@ -1659,6 +1664,222 @@ void iamf_hip_dmx_coefficients(const iamf_hip_dmx_state *st, float out[5]) {
   out[2] = st->gamma;
   out[3] = st->delta;
   out[4] = st->gamma_w;
+}
+
+/* ---- per-stream lifecycle: restart, range gains, export, import (stream_state.hpp) ---- */
+
+namespace {
+
+// Field numbers of a batch's list: the bits of the kernels' field mask
+enum { kFldLim = 0, kFldRingY, kFldRingPm, kFldLfeState, kFldLfeNext, kFldFirHist0, kFldFirHist1, kFldFirPre0, kFldFirPre1,
+       kFldGain0, kFldGain1, kFldGain2, kFldGainE2, kFldCount };
+constexpr uint32_t kFldGainMask = (1u << kFldGain0) | (1u << kFldGain1) | (1u << kFldGain2) | (1u << kFldGainE2);
+
+// THE list: what reset_state touches, plus the gains.  *bytes (may be NULL) = bytes of one stream's blob.
+StateFields batch_fields(const iamf_hip_batch *b, int64_t *bytes) {
+  StateFields fl;
+  memset(&fl, 0, sizeof(fl));
+  const int ns = b->cfg.n_streams;
+  fl.lim_n = b->n_end;
+  static_assert(sizeof(LimState) == 4 * sizeof(float), "LimState travels as one 16-byte row");
+  static_assert(kFldCount <= kStateMaxFields, "field list too long");
+  state_add(fl, reinterpret_cast<float *>(b->d_lim), 4, kFreshLim, 0, true);
+  state_add(fl, b->d_ring_y, b->cfg.out_channels * kSave, kFreshZero, 0, true);
+  state_add(fl, b->d_ring_pm, kSave, kFreshZero, 0, true);
+  const bool own_lfe = b->lfe && !b->lfe_shared;   // a borrowed filter state is its owner's to restart and to move
+  state_add(fl, own_lfe ? b->d_lfe_state : nullptr, 4, kFreshZero, 0, true);
+  state_add(fl, own_lfe ? b->d_lfe_next : nullptr, 2, kFreshZero, 0, true);
+  // FIR: restart only (the history is a batch-wide ping-pong, fir_cur: both buffers are cleared)
+  const int fm = b->m * 256;
+  state_add(fl, b->fir ? b->d_fir_hist[0] : nullptr, fm, kFreshZero, 0, false);
+  state_add(fl, b->fir ? b->d_fir_hist[1] : nullptr, fm, kFreshZero, 0, false);
+  {  // the same history at the input's channel stride (RenderParams::fir_pre): G streams share the rows of a slab
+    const int fs = b->cfg.frame_size, g = fs >= 256 ? fs / 256 : 1;
+    for (int k = 0; k < 2; ++k)
+      state_add_rows(fl, b->fir ? b->d_fir_pre[k] : nullptr, g, (int64_t)b->m * fs, 256, b->m, 256, fs, kFreshZero, 0, false);
+  }
+  for (int k = 0; k < 3; ++k) state_add(fl, b->d_gains + (size_t)k * ns, 1, kFreshValue, k, true);
+  state_add(fl, b->has2 ? b->d_gains2 : nullptr, 1, kFreshValue, 3, true);
+  const int64_t n = state_layout(fl);
+  if (bytes) *bytes = n;
+  return fl;
+}
+
+// everything the blob's layout and meaning depend on; not the matrices
+uint32_t batch_signature(const iamf_hip_batch *b) {
+  uint32_t thr_bits;
+  memcpy(&thr_bits, &b->thr, 4);
+  const uint32_t w[] = {kStateVersion, 1u /* kind */, (uint32_t)kSave, (uint32_t)sizeof(LimState), (uint32_t)b->cfg.out_channels,
+                        b->cfg.limiter_enable ? 1u : 0u, thr_bits, (uint32_t)b->n_end, (uint32_t)b->n_atk,
+                        (uint32_t)b->cfg.sample_rate, (b->lfe && !b->lfe_shared) ? 1u : 0u, b->has2 ? 1u : 0u};
+  return state_hash(w, (int)(sizeof(w) / sizeof(w[0])));
+}
+
+bool range_ok(const iamf_hip_batch *b, int32_t s0, int32_t cnt) {
+  return s0 >= 0 && cnt > 0 && (int64_t)s0 + cnt <= b->cfg.n_streams;
+}
+
+// `st` behind everything queued on the batch so far, whatever stream that used
+int lifecycle_enter(iamf_hip_batch *b, hipStream_t st) {
+  if (b->rendered) HIPCHK(hipStreamWaitEvent(st, b->done, 0));
+  return IAMF_HIP_OK;
+}
+// ... and the synchronous setters and destroy behind this call
+int lifecycle_leave(iamf_hip_batch *b, hipStream_t st) {
+  HIPCHK(hipEventRecord(b->done, st));
+  b->rendered = true;
+  return IAMF_HIP_OK;
+}
+
+// Restart job over [s0, s0 + cnt) with the field mask `mask`; the gains of `g` (rows NULL or not part of the mask are not
+// read) travel in the kernel arguments, kStateChunk streams a launch.  Without gain fields: one launch.
+int restart_launches(const StateFields &fl, uint32_t mask, int s0, int cnt, const iamf_hip_stream_gains *g, hipStream_t st) {
+  StateValues vals;
+  memset(&vals, 0, sizeof(vals));
+  if (!(mask & kFldGainMask)) {
+    stream_state_launch<StateJob::Restart>(fl, mask, s0, cnt, nullptr, 0, vals, st);
+    HIPCHK(hipGetLastError());
+    return IAMF_HIP_OK;
+  }
+  const float *rows[4] = {g->element_gain, g->output_gain, g->loudness_gain, g->element2_gain};
+  for (int c0 = 0; c0 < cnt; c0 += kStateChunk) {
+    const int c = cnt - c0 < kStateChunk ? cnt - c0 : kStateChunk;
+    for (int k = 0; k < 4; ++k)
+      if (rows[k]) memcpy(vals.v[k], rows[k] + c0, sizeof(float) * c);
+    stream_state_launch<StateJob::Restart>(fl, mask, s0 + c0, c, nullptr, 0, vals, st);
+    HIPCHK(hipGetLastError());
+  }
+  return IAMF_HIP_OK;
+}
+
+uint32_t gain_mask(const iamf_hip_stream_gains *g) {
+  if (!g) return 0;
+  return (g->element_gain ? 1u << kFldGain0 : 0u) | (g->output_gain ? 1u << kFldGain1 : 0u) |
+         (g->loudness_gain ? 1u << kFldGain2 : 0u) | (g->element2_gain ? 1u << kFldGainE2 : 0u);
+}
+
+void gains_to_mirror(iamf_hip_batch *b, const iamf_hip_stream_gains *g, int s0, int cnt) {
+  if (!g) return;
+  const size_t ns = (size_t)b->cfg.n_streams;
+  const float *rows[3] = {g->element_gain, g->output_gain, g->loudness_gain};
+  for (int k = 0; k < 3; ++k)   // (the second element's gains have no host mirror: no setter re-uploads them)
+    if (rows[k]) memcpy(&b->h_gains[k * ns + (size_t)s0], rows[k], sizeof(float) * cnt);
+}
+
+// the checks export and import share; *bytes = one stream's blob
+int blob_args_check(const iamf_hip_batch *b, int32_t s0, int32_t cnt, const void *d_state, int64_t stride, const void *tickets,
+                    int64_t *bytes) {
+  if (!b || !d_state || !tickets) return IAMF_HIP_ERR_BAD_ARG;
+  if (b->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
+  if (!range_ok(b, s0, cnt)) return IAMF_HIP_ERR_BAD_ARG;
+  (void)batch_fields(b, bytes);
+  if (stride < *bytes || (stride & 15) || (reinterpret_cast<uintptr_t>(d_state) & 15)) return IAMF_HIP_ERR_BAD_ARG;
+  if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
+  return IAMF_HIP_OK;
+}
+
+}  // namespace
+
+int iamf_hip_batch_set_gains_range(iamf_hip_batch *b, int32_t stream0, int32_t n_streams, const iamf_hip_stream_gains *gains,
+                                   void *stream) {
+  if (!b || !gains || !range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
+  if (gains->element2_gain && !b->has2) return IAMF_HIP_ERR_BAD_ARG;
+  if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
+  const uint32_t mask = gain_mask(gains);
+  if (!mask) return IAMF_HIP_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int r = lifecycle_enter(b, st);
+  if (r != IAMF_HIP_OK) return r;
+  r = restart_launches(batch_fields(b, nullptr), mask, stream0, n_streams, gains, st);
+  if (r != IAMF_HIP_OK) return r;
+  gains_to_mirror(b, gains, stream0, n_streams);
+  return lifecycle_leave(b, st);
+}
+
+int iamf_hip_batch_restart_range(iamf_hip_batch *b, int32_t stream0, int32_t n_streams, const iamf_hip_stream_gains *gains,
+                                 void *stream) {
+  if (!b || !range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
+  if (gains && gains->element2_gain && !b->has2) return IAMF_HIP_ERR_BAD_ARG;
+  if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int r = lifecycle_enter(b, st);
+  if (r != IAMF_HIP_OK) return r;
+  const uint32_t mask = (((1u << kFldCount) - 1u) & ~kFldGainMask) | gain_mask(gains);
+  r = restart_launches(batch_fields(b, nullptr), mask, stream0, n_streams, gains, st);
+  if (r != IAMF_HIP_OK) return r;
+  gains_to_mirror(b, gains, stream0, n_streams);
+  for (int i = stream0; i < stream0 + n_streams; ++i) {
+    b->spos[(size_t)i] = 0;
+    b->sflushed[(size_t)i] = 0;
+  }
+  return lifecycle_leave(b, st);
+}
+
+int64_t iamf_hip_batch_stream_state_bytes(const iamf_hip_batch *b) {
+  if (!b) return IAMF_HIP_ERR_BAD_ARG;
+  if (b->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
+  int64_t bytes = 0;
+  (void)batch_fields(b, &bytes);
+  return bytes;
+}
+
+int iamf_hip_batch_export_range(iamf_hip_batch *b, int32_t stream0, int32_t n_streams, void *d_state,
+                                int64_t state_stream_stride_bytes, iamf_hip_stream_state *tickets, void *stream) {
+  int64_t bytes = 0;
+  int r = blob_args_check(b, stream0, n_streams, d_state, state_stream_stride_bytes, tickets, &bytes);
+  if (r != IAMF_HIP_OK) return r;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  r = lifecycle_enter(b, st);
+  if (r != IAMF_HIP_OK) return r;
+  StateValues vals;
+  memset(&vals, 0, sizeof(vals));
+  const StateFields fl = batch_fields(b, nullptr);
+  stream_state_launch<StateJob::Export>(fl, (1u << kFldCount) - 1u, stream0, n_streams, static_cast<float *>(d_state),
+                                        state_stream_stride_bytes / 4, vals, st);
+  HIPCHK(hipGetLastError());
+  const uint32_t sig = batch_signature(b);
+  for (int i = 0; i < n_streams; ++i) {   // the batch tracks the positions on the host, at enqueue
+    iamf_hip_stream_state &t = tickets[i];
+    memset(&t, 0, sizeof(t));
+    t.magic = kStateMagic;
+    t.version = kStateVersion;
+    t.kind = 1;
+    t.signature = sig;
+    t.bytes = bytes;
+    t.cursor[0] = b->spos[(size_t)(stream0 + i)];
+    t.cursor[1] = b->sflushed[(size_t)(stream0 + i)];
+  }
+  return lifecycle_leave(b, st);
+}
+
+int iamf_hip_batch_import_range(iamf_hip_batch *b, int32_t stream0, int32_t n_streams, const void *d_state,
+                                int64_t state_stream_stride_bytes, const iamf_hip_stream_state *tickets, void *stream) {
+  int64_t bytes = 0;
+  int r = blob_args_check(b, stream0, n_streams, d_state, state_stream_stride_bytes, tickets, &bytes);
+  if (r != IAMF_HIP_OK) return r;
+  const uint32_t sig = batch_signature(b);
+  for (int i = 0; i < n_streams; ++i) {
+    const iamf_hip_stream_state &t = tickets[i];
+    if (t.magic != kStateMagic || t.version != kStateVersion || t.kind != 1 || t.signature != sig || t.bytes != bytes ||
+        t.cursor[0] < 0 || (t.cursor[1] != 0 && t.cursor[1] != 1))
+      return IAMF_HIP_ERR_BAD_ARG;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  r = lifecycle_enter(b, st);
+  if (r != IAMF_HIP_OK) return r;
+  StateValues vals;
+  memset(&vals, 0, sizeof(vals));
+  const StateFields fl = batch_fields(b, nullptr);
+  stream_state_launch<StateJob::Import>(fl, (1u << kFldCount) - 1u, stream0, n_streams,
+                                        const_cast<float *>(static_cast<const float *>(d_state)), state_stream_stride_bytes / 4,
+                                        vals, st);
+  HIPCHK(hipGetLastError());
+  for (int i = 0; i < n_streams; ++i) {
+    b->spos[(size_t)(stream0 + i)] = tickets[i].cursor[0];
+    b->sflushed[(size_t)(stream0 + i)] = (uint8_t)tickets[i].cursor[1];
+  }
+  b->any_rendered = true;
+  return lifecycle_leave(b, st);
 }
 
 int iamf_hip_batch_reset(iamf_hip_batch *b) {

@@ -29,6 +29,7 @@
 namespace {
 
 #include "resample_route.hpp"
+#include "stream_state.hpp"
 
 struct RsParams {
   const float *in;        // [stream][ns][ch] or nullptr (zeros)
@@ -798,6 +799,122 @@ int iamf_hip_resampler_same_state(const iamf_hip_resampler *r, int32_t a, int32_
   if (!r || a < 0 || b < 0 || a >= r->n_streams || b >= r->n_streams) return 0;
   return r->last_sample[(size_t)a] == r->last_sample[(size_t)b] && r->frac[(size_t)a] == r->frac[(size_t)b] &&
          r->cur[(size_t)a] == r->cur[(size_t)b];
+}
+
+/* ---- per-stream lifecycle (stream_state.hpp): restart, export, import ---- */
+
+namespace {
+
+// THE list of a resampler stream: its row of both history buffers for restart, the row of buffer `blob_buf` for export
+// and import (-1: neither in the blob).  *bytes (may be NULL) = bytes of one stream's blob.
+StateFields rs_fields(const iamf_hip_resampler *r, int blob_buf, int64_t *bytes) {
+  StateFields fl;
+  memset(&fl, 0, sizeof(fl));
+  const int row = (int)(r->filt_len - 1) * r->ch;
+  for (int k = 0; k < 2; ++k) state_add(fl, r->d_hist[k], row, kFreshZero, 0, k == blob_buf);
+  const int64_t n = state_layout(fl);
+  if (bytes) *bytes = n;
+  return fl;
+}
+
+uint32_t rs_signature(const iamf_hip_resampler *r) {
+  const uint32_t w[] = {kStateVersion, 2u /* kind */, (uint32_t)r->ch, (uint32_t)r->in_rate, (uint32_t)r->out_rate, r->filt_len};
+  return state_hash(w, (int)(sizeof(w) / sizeof(w[0])));
+}
+
+int rs_blob_args_check(const iamf_hip_resampler *r, int32_t s0, int32_t cnt, const void *d_state, int64_t stride,
+                       const void *tickets, int64_t *bytes) {
+  if (!r || !d_state || !tickets) return IAMF_HIP_ERR_BAD_ARG;
+  if (s0 < 0 || cnt <= 0 || (int64_t)s0 + cnt > r->n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  (void)rs_fields(r, 0, bytes);
+  if (stride < *bytes || (stride & 15) || (reinterpret_cast<uintptr_t>(d_state) & 15)) return IAMF_HIP_ERR_BAD_ARG;
+  return IAMF_HIP_OK;
+}
+
+}  // namespace
+
+int iamf_hip_resampler_restart_range(iamf_hip_resampler *r, int32_t stream0, int32_t n_streams, void *stream) {
+  if (!r || stream0 < 0 || n_streams <= 0 || (int64_t)stream0 + n_streams > r->n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  StateValues vals;
+  memset(&vals, 0, sizeof(vals));
+  stream_state_launch<StateJob::Restart>(rs_fields(r, -1, nullptr), 3u, stream0, n_streams, nullptr, 0, vals,
+                                         static_cast<hipStream_t>(stream));
+  RS_HIPCHK(hipGetLastError());
+  for (int i = stream0; i < stream0 + n_streams; ++i) {   // as iamf_hip_resampler_create
+    r->last_sample[(size_t)i] = (int)(r->filt_len / 2);
+    r->frac[(size_t)i] = 0u;
+    r->cur[(size_t)i] = 0;
+  }
+  return IAMF_HIP_OK;
+}
+
+int64_t iamf_hip_resampler_stream_state_bytes(const iamf_hip_resampler *r) {
+  if (!r) return IAMF_HIP_ERR_BAD_ARG;
+  int64_t bytes = 0;
+  (void)rs_fields(r, 0, &bytes);
+  return bytes;
+}
+
+int iamf_hip_resampler_export_range(iamf_hip_resampler *r, int32_t stream0, int32_t n_streams, void *d_state,
+                                    int64_t state_stream_stride_bytes, iamf_hip_stream_state *tickets, void *stream) {
+  int64_t bytes = 0;
+  const int rc = rs_blob_args_check(r, stream0, n_streams, d_state, state_stream_stride_bytes, tickets, &bytes);
+  if (rc != IAMF_HIP_OK) return rc;
+  StateValues vals;
+  memset(&vals, 0, sizeof(vals));
+  // one launch per maximal run of streams whose past lies in the same buffer
+  for (int a = stream0; a < stream0 + n_streams;) {
+    int e = a + 1;
+    while (e < stream0 + n_streams && r->cur[(size_t)e] == r->cur[(size_t)a]) ++e;
+    stream_state_launch<StateJob::Export>(rs_fields(r, r->cur[(size_t)a], nullptr), 3u, a, e - a,
+                                          reinterpret_cast<float *>(static_cast<uint8_t *>(d_state) +
+                                                                    (int64_t)(a - stream0) * state_stream_stride_bytes),
+                                          state_stream_stride_bytes / 4, vals, static_cast<hipStream_t>(stream));
+    RS_HIPCHK(hipGetLastError());
+    a = e;
+  }
+  const uint32_t sig = rs_signature(r);
+  for (int i = 0; i < n_streams; ++i) {
+    iamf_hip_stream_state &t = tickets[i];
+    memset(&t, 0, sizeof(t));
+    t.magic = kStateMagic;
+    t.version = kStateVersion;
+    t.kind = 2;
+    t.signature = sig;
+    t.bytes = bytes;
+    t.cursor[0] = r->last_sample[(size_t)(stream0 + i)];
+    t.cursor[1] = r->frac[(size_t)(stream0 + i)];
+  }
+  return IAMF_HIP_OK;
+}
+
+int iamf_hip_resampler_import_range(iamf_hip_resampler *r, int32_t stream0, int32_t n_streams, const void *d_state,
+                                    int64_t state_stream_stride_bytes, const iamf_hip_stream_state *tickets, void *stream) {
+  int64_t bytes = 0;
+  const int rc = rs_blob_args_check(r, stream0, n_streams, d_state, state_stream_stride_bytes, tickets, &bytes);
+  if (rc != IAMF_HIP_OK) return rc;
+  const uint32_t sig = rs_signature(r);
+  for (int i = 0; i < n_streams; ++i) {
+    const iamf_hip_stream_state &t = tickets[i];
+    if (t.magic != kStateMagic || t.version != kStateVersion || t.kind != 2 || t.signature != sig || t.bytes != bytes ||
+        t.cursor[0] < 0 || t.cursor[0] > INT32_MAX || t.cursor[1] < 0 || t.cursor[1] >= (int64_t)r->den)
+      return IAMF_HIP_ERR_BAD_ARG;
+  }
+  // the buffer a neighbour's past lies in, so that the imported streams can share its launches
+  const int buf = stream0 > 0 ? r->cur[(size_t)stream0 - 1]
+                              : (stream0 + n_streams < r->n_streams ? r->cur[(size_t)(stream0 + n_streams)] : r->cur[(size_t)stream0]);
+  StateValues vals;
+  memset(&vals, 0, sizeof(vals));
+  stream_state_launch<StateJob::Import>(rs_fields(r, buf, nullptr), 3u, stream0, n_streams,
+                                        const_cast<float *>(static_cast<const float *>(d_state)), state_stream_stride_bytes / 4, vals,
+                                        static_cast<hipStream_t>(stream));
+  RS_HIPCHK(hipGetLastError());
+  for (int i = 0; i < n_streams; ++i) {
+    r->last_sample[(size_t)(stream0 + i)] = (int)tickets[i].cursor[0];
+    r->frac[(size_t)(stream0 + i)] = (unsigned)tickets[i].cursor[1];
+    r->cur[(size_t)(stream0 + i)] = (uint8_t)buf;
+  }
+  return IAMF_HIP_OK;
 }
 
 }  // extern "C"

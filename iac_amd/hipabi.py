@@ -81,6 +81,15 @@ ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, W
 ROUTE_NAME = {v: k for k, v in ROUTE.items()}
 
 
+class StreamGains(C.Structure):   # iamf_hip_stream_gains: host arrays of the RANGE's length, NULL = leave that gain
+    _fields_ = [("element_gain", FP), ("output_gain", FP), ("loudness_gain", FP), ("element2_gain", FP)]
+
+
+class StreamState(C.Structure):   # iamf_hip_stream_state: the ticket of one exported stream
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("kind", C.c_uint32), ("signature", C.c_uint32),
+                ("bytes", C.c_int64), ("cursor", C.c_int64 * 2)]
+
+
 class DemixConfig(C.Structure):
     _fields_ = [("layout", C.c_int32), ("n_in", C.c_int32), ("chs_in", C.c_int32 * 12), ("n_gain", C.c_int32),
                 ("gain_ch", C.c_int32 * 12), ("gain", C.c_float * 12), ("frame_offset", C.c_uint32)]
@@ -144,6 +153,17 @@ def lib():
         L.iamf_hip_batch_reset.argtypes = [C.c_void_p]
         L.iamf_hip_batch_render_range.argtypes = [C.c_void_p, C.POINTER(RenderArgs), C.c_int32, C.c_int32]
         L.iamf_hip_batch_flush_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32]
+        L.iamf_hip_batch_set_gains_range.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(StreamGains), C.c_void_p]
+        L.iamf_hip_batch_restart_range.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(StreamGains), C.c_void_p]
+        L.iamf_hip_batch_stream_state_bytes.argtypes = [C.c_void_p]
+        L.iamf_hip_batch_stream_state_bytes.restype = C.c_int64
+        for name in ("iamf_hip_batch_export_range", "iamf_hip_batch_import_range", "iamf_hip_resampler_export_range",
+                     "iamf_hip_resampler_import_range"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(StreamState),
+                                         C.c_void_p]
+        L.iamf_hip_resampler_restart_range.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.iamf_hip_resampler_stream_state_bytes.argtypes = [C.c_void_p]
+        L.iamf_hip_resampler_stream_state_bytes.restype = C.c_int64
         L.iamf_hip_format_bytes.argtypes = [C.c_int]
         L.iamf_hip_version.restype = C.c_char_p
         L.iamf_hip_batch_render_ex.argtypes = [C.c_void_p, C.POINTER(RenderArgs)]
@@ -309,6 +329,31 @@ def _fparr(a):
     return arr
 
 
+def stream_gains(element=None, output=None, loudness=None, element2=None):
+    """a StreamGains over sequences of the range's length (None = leave that gain as it is); keeps the arrays alive"""
+    g = StreamGains()
+    g._keep = [_fparr(a) for a in (element, output, loudness, element2)]
+    for name, arr in zip(("element_gain", "output_gain", "loudness_gain", "element2_gain"), g._keep):
+        if arr is not None:
+            setattr(g, name, C.cast(arr, FP))
+    return g
+
+
+def _export(fn, what, h, s0, cnt, d_state, stride, stream):
+    tickets = (StreamState * max(cnt, 1))()
+    r = fn(h, s0, cnt, d_state, stride, tickets, stream)
+    if r != 0:
+        raise IamfHipError(r, what)
+    return list(tickets[:cnt])
+
+
+def _import(fn, what, h, s0, cnt, d_state, stride, tickets, stream):
+    arr = (StreamState * max(len(tickets), 1))(*tickets)
+    r = fn(h, s0, cnt, d_state, stride, arr if len(tickets) >= cnt else None, stream)
+    if r != 0:
+        raise IamfHipError(r, what)
+
+
 class Batch:
     """Thin handle on iamf_hip_batch_*; pointers are raw device addresses (ints)."""
 
@@ -410,6 +455,33 @@ class Batch:
         if r != 0:
             raise IamfHipError(r, "iamf_hip_batch_reset")
 
+    def set_gains_range(self, s0, cnt, gains, stream=None):
+        """iamf_hip_batch_set_gains_range; gains: a StreamGains (stream_gains(...)) over the range"""
+        r = lib().iamf_hip_batch_set_gains_range(self.h, s0, cnt, C.byref(gains) if gains is not None else None, stream)
+        if r != 0:
+            raise IamfHipError(r, "iamf_hip_batch_set_gains_range")
+
+    def restart_range(self, s0, cnt, gains=None, stream=None):
+        """iamf_hip_batch_restart_range: a fresh stream in every slot of the range, its neighbours untouched"""
+        r = lib().iamf_hip_batch_restart_range(self.h, s0, cnt, C.byref(gains) if gains is not None else None, stream)
+        if r != 0:
+            raise IamfHipError(r, "iamf_hip_batch_restart_range")
+
+    def stream_state_bytes(self):
+        r = lib().iamf_hip_batch_stream_state_bytes(self.h)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_stream_state_bytes")
+        return r
+
+    def export_range(self, s0, cnt, d_state, stride_bytes, stream=None):
+        """iamf_hip_batch_export_range -> the tickets (StreamState) of the range's streams"""
+        return _export(lib().iamf_hip_batch_export_range, "iamf_hip_batch_export_range", self.h, s0, cnt, d_state,
+                       stride_bytes, stream)
+
+    def import_range(self, s0, cnt, d_state, stride_bytes, tickets, stream=None):
+        _import(lib().iamf_hip_batch_import_range, "iamf_hip_batch_import_range", self.h, s0, cnt, d_state, stride_bytes,
+                tickets, stream)
+
     def close(self):
         if self.h:
             lib().iamf_hip_batch_destroy(self.h)
@@ -459,6 +531,25 @@ class Resampler:
 
     def same_state(self, a, b):
         return bool(lib().iamf_hip_resampler_same_state(self.h, a, b))
+
+    def restart_range(self, s0, cnt, stream=None):
+        r = lib().iamf_hip_resampler_restart_range(self.h, s0, cnt, stream)
+        if r != 0:
+            raise IamfHipError(r, "iamf_hip_resampler_restart_range")
+
+    def stream_state_bytes(self):
+        r = lib().iamf_hip_resampler_stream_state_bytes(self.h)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_resampler_stream_state_bytes")
+        return r
+
+    def export_range(self, s0, cnt, d_state, stride_bytes, stream=None):
+        return _export(lib().iamf_hip_resampler_export_range, "iamf_hip_resampler_export_range", self.h, s0, cnt, d_state,
+                       stride_bytes, stream)
+
+    def import_range(self, s0, cnt, d_state, stride_bytes, tickets, stream=None):
+        _import(lib().iamf_hip_resampler_import_range, "iamf_hip_resampler_import_range", self.h, s0, cnt, d_state,
+                stride_bytes, tickets, stream)
 
     def close(self):
         if self.h:

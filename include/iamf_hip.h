@@ -155,7 +155,8 @@ void iamf_hip_batch_destroy(iamf_hip_batch *b);
  * (IAMF_decoder.c:1392-1397: only if != 1 and > 0), and the loudness gain
  * db2lin(target - loudness) of iamf_loudness_process (IAMF_decoder.c:3206-3221).  Synchronous, and ordered after the renders already queued: it
  * first waits for the batch's last render / flush call (an event the batch itself records behind every call, so the
- * caller's stream need not outlive the call). */
+ * caller's stream need not outlive the call).  Only the rows given are uploaded: a NULL row keeps what the device holds,
+ * the values of iamf_hip_batch_set_gains_range, _restart_range and _import_range included. */
 int iamf_hip_batch_set_gains(iamf_hip_batch *b, const float *element_gain,
                              const float *output_gain, const float *loudness_gain);
 
@@ -400,6 +401,84 @@ int iamf_hip_resampler_same_state(const iamf_hip_resampler *r, int32_t stream_a,
 /* Forgets all stream state (new IA sequence: limiter re-initialised as in
  * iamf_decoder_internal_configure, IAMF_decoder.c:3809-3815).  Synchronous. */
 int iamf_hip_batch_reset(iamf_hip_batch *b);
+
+/* ------------------------------------------------------------------------------------------
+ * Per-stream lifecycle: streams of one batch need not live and die in step.
+ * The range calls above let the streams of a batch ADVANCE independently; these let them start, end and move
+ * independently: a slot whose stream ended is restarted for the next programme while its neighbours go on rendering
+ * (each reference handle is closed and opened on its own, IAMF_decoder.c:3809-3815), its gains are set without stopping
+ * anybody, and a live stream's state is exported into a blob of plain bytes and imported into another slot, another
+ * batch, or a batch on another device, where it continues bit for bit.
+ *
+ * All entries below are STREAM-ORDERED and never make the host wait for the device: `stream` first waits (on the
+ * device) for the event the batch records behind every call, so the entry is ordered behind every render or flush
+ * already queued on the batch whatever stream that used; the entry then records the event behind itself, so that the
+ * synchronous setters and destroy wait for it in turn.  Renders queued AFTER an entry are ordered behind it the way
+ * renders are ordered among themselves: by being issued on the same stream (or behind an event of the caller's).
+ * Every argument is checked before the first device call; a refused call changes nothing, on the host or the device.
+ * IAMF_HIP_ERR_INVALID_STATE unless the batch's device is current.
+ *
+ * What travels: the limiter's state and look-ahead rings, the HOA LFE generator's filter state when the batch OWNS it
+ * (a batch that borrowed it through iamf_hip_batch_share_lfe_state leaves it alone, as iamf_hip_batch_reset does), the
+ * stream's gains, its position.  What does not: the matrices and every other per-batch constant (the target batch has
+ * its own), and the stage state the CALLER holds — iamf_hip_dmx_state and iamf_hip_demix_state are the caller's own
+ * host data and travel with the caller.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {            /* host arrays of n_streams (of the RANGE) floats each; NULL = leave that gain as it is */
+  const float *element_gain, *output_gain, *loudness_gain, *element2_gain;
+} iamf_hip_stream_gains;
+
+/* iamf_hip_batch_set_gains for the streams [stream0, stream0 + n_streams), without the host wait: the new values hold
+ * for every render queued after the call and for none queued before it; the host arrays may be reused on return (the
+ * values travel in kernel arguments).  element2_gain on a batch without a second element: IAMF_HIP_ERR_BAD_ARG. */
+int iamf_hip_batch_set_gains_range(iamf_hip_batch *b, int32_t stream0, int32_t n_streams,
+                                   const iamf_hip_stream_gains *gains, void *stream);
+/* Leaves the streams of the range exactly as iamf_hip_batch_create leaves them (position 0, not flushed, limiter idle,
+ * rings and filter histories zero) and stores the new gains where `gains` names some; streams outside the range and
+ * batch-wide state are not touched.  Over the whole batch it is iamf_hip_batch_reset without the device-wide wait.
+ * Serves batches of kind FIR too (both history buffers of the range are cleared). */
+int iamf_hip_batch_restart_range(iamf_hip_batch *b, int32_t stream0, int32_t n_streams,
+                                 const iamf_hip_stream_gains *gains /* may be NULL */, void *stream);
+
+typedef struct {            /* host-side ticket of one exported stream; plain data, may be stored or sent */
+  uint32_t magic, version;  /* layout of this struct and of the blob */
+  uint32_t kind;            /* 1 = batch stream, 2 = resampler stream */
+  uint32_t signature;       /* hash of everything the blob's layout and meaning depend on */
+  int64_t bytes;            /* bytes of the device blob for this stream */
+  int64_t cursor[2];        /* batch: {samples consumed, flushed}; resampler: {last_sample, frac} */
+} iamf_hip_stream_state;
+
+/* Bytes of one stream's blob, a multiple of 16; negative IAMF_HIP_ERR_UNIMPLEMENTED for batches of kind FIR (their
+ * history is a batch-wide ping-pong and their parity is unpinned), IAMF_HIP_ERR_BAD_ARG for NULL.  Needs no device. */
+int64_t iamf_hip_batch_stream_state_bytes(const iamf_hip_batch *b);
+/* Export reads only: stream stream0 + i of the batch -> the blob at d_state + i * state_stream_stride_bytes (device,
+ * 16-byte aligned, stride a multiple of 16 and >= the blob's bytes), gathered on `stream`; tickets[i] is filled at call
+ * time (the batch tracks positions on the host).  The blob holds no pointers: the caller may copy it anywhere.
+ * Import writes the range of any batch whose signature equals the tickets' — same output channel count, limiter
+ * setting / threshold / sample rate, owned LFE state or none, second element or none; the matrices, the frame size and
+ * the PCM format may differ — sets the streams' positions from the tickets and counts as a first render for the setters
+ * that must precede it.  The streams then continue bit for bit as the source would have, and a neighbour that stands at
+ * the same position may share a range launch with them.  The blob is the caller's buffer: import reads it on `stream`,
+ * behind whatever the caller queued there.
+ * IAMF_HIP_ERR_BAD_ARG: a ticket whose magic, version, kind, signature or bytes do not match the target, a stride
+ * smaller than the blob, a range outside the batch — nothing is written.  IAMF_HIP_ERR_UNIMPLEMENTED: kind FIR. */
+int iamf_hip_batch_export_range(iamf_hip_batch *b, int32_t stream0, int32_t n_streams, void *d_state,
+                                int64_t state_stream_stride_bytes, iamf_hip_stream_state *tickets /* host, [n_streams] */, void *stream);
+int iamf_hip_batch_import_range(iamf_hip_batch *b, int32_t stream0, int32_t n_streams, const void *d_state,
+                                int64_t state_stream_stride_bytes, const iamf_hip_stream_state *tickets, void *stream);
+
+/* The same for the resampler (tickets of kind 2; the signature covers channels, both rates and the filter length).
+ * The resampler keeps no event of its own: like its process calls, these are ordered by the stream they are issued on.
+ * Restart: the host phase goes back to what iamf_hip_resampler_create sets and both history rows of the range are
+ * zeroed.  Import writes the range's rows into ONE of the two history buffers — the one the stream below the range uses,
+ * else the one above it, else the range's first stream's own — so that an imported stream can join its neighbour's
+ * launches (iamf_hip_resampler_same_state) when their phases agree. */
+int iamf_hip_resampler_restart_range(iamf_hip_resampler *r, int32_t stream0, int32_t n_streams, void *stream);
+int64_t iamf_hip_resampler_stream_state_bytes(const iamf_hip_resampler *r);
+int iamf_hip_resampler_export_range(iamf_hip_resampler *r, int32_t stream0, int32_t n_streams, void *d_state,
+                                    int64_t state_stream_stride_bytes, iamf_hip_stream_state *tickets, void *stream);
+int iamf_hip_resampler_import_range(iamf_hip_resampler *r, int32_t stream0, int32_t n_streams, const void *d_state,
+                                    int64_t state_stream_stride_bytes, const iamf_hip_stream_state *tickets, void *stream);
 
 /* bytes one output sample occupies for a format (2, 3, 4) */
 int iamf_hip_format_bytes(int out_format);
