@@ -68,6 +68,11 @@ __device__ __forceinline__ float to_scaled(float x, float scale, float lo, float
   return rintf(x);  // v_rndne_f32: ties to even, like lrintf in the default rounding mode
 }
 
+// float -> the integer render_wide.hpp and render_wide4.hpp hand to v_cvt_pk_i16 (rint, then saturate == the reference's
+// clamp, then lrintf: the bounds are integers).  NaN: the reference's clamp `x > lo ? x : lo` (IAMF_decoder.c:100-119) makes
+// it lo, the conversion alone 0; maxnum returns its other operand for a NaN and leaves every other value's result alone.
+__device__ __forceinline__ int to_s16_sat(float x) { return (int)rintf(__builtin_fmaxf(x, -32768.f)); }
+
 // Quotients that share a divisor (the demixer of scalable channel audio divides 8 numerators each by delta, beta and
 // gamma of the frame: demixer.c:205-214,255-267,357-366).  With r = RN(1 / d) — ONE IEEE division per divisor —
 //     q = n * r;  e = fma(-d, q, n);  q' = fma(e, r, q)

@@ -336,18 +336,18 @@ __global__ __launch_bounds__(256) void render_wide_kernel(const RenderParams p) 
         const float4 v1 = *reinterpret_cast<const float4 *>(&ring[rf + 4]);
         const float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
         int o[8];
-        // rint then saturate == the reference's clamp then lrintf (the bounds are integers)
+        // rint then saturate == the reference's clamp then lrintf (the bounds are integers; NaN -> lower bound: to_s16_sat)
         if (C >= 8) {  // a piece of 8 spans at most two sample-frames
           const float g0 = arr_g[srel];
           const float g1 = arr_g[srel + 1 < kWChunk ? srel + 1 : kWChunk - 1];
           const int cross = C - r;  // elements of the piece that belong to the first sample-frame
 #pragma unroll
-          for (int i = 0; i < 8; ++i) o[i] = (int)rintf(vv[i] * (i < cross ? g0 : g1));
+          for (int i = 0; i < 8; ++i) o[i] = to_s16_sat(vv[i] * (i < cross ? g0 : g1));
         } else {
           float gq = arr_g[srel];
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
-            o[i] = (int)rintf(vv[i] * gq);
+            o[i] = to_s16_sat(vv[i] * gq);
             ++r;
             if (r == C) {  // next sample-frame: next gain
               r = 0;

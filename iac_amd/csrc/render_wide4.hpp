@@ -950,17 +950,17 @@ __global__ __launch_bounds__(256, (M <= 12 && C <= 12 && !(DMX || DOWN || MIX)) 
 #else
     {
       // Pack to s16 (rint then saturate == the reference's clamp then lrintf: the bounds are
-      // integers).  Piece k of a lane = dwords 4k..4k+3 of its 8*C bytes; dword d = sample
+      // integers; NaN becomes the lower bound: to_s16_sat).  Piece k of a lane = dwords 4k..4k+3 of its 8*C bytes; dword d = sample
       // d / (C/2), channels 2*(d % (C/2)) and +1.
       constexpr int H2 = C / 2, S = wide4_stage_stride(C), LR = wide4_stage_lanes(C, M, kExtra);
       uint32_t od[4 * H2];  // filled channel pair by channel pair so that y dies as od is born
 #pragma unroll
       for (int c = 0; c < C; c += 2) {
         const float4 ya = y[c], yb = y[c + 1];
-        od[0 * H2 + c / 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16((int)rintf(ya.x * gs4[0]), (int)rintf(yb.x * gs4[0])));
-        od[1 * H2 + c / 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16((int)rintf(ya.y * gs4[1]), (int)rintf(yb.y * gs4[1])));
-        od[2 * H2 + c / 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16((int)rintf(ya.z * gs4[2]), (int)rintf(yb.z * gs4[2])));
-        od[3 * H2 + c / 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16((int)rintf(ya.w * gs4[3]), (int)rintf(yb.w * gs4[3])));
+        od[0 * H2 + c / 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(to_s16_sat(ya.x * gs4[0]), to_s16_sat(yb.x * gs4[0])));
+        od[1 * H2 + c / 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(to_s16_sat(ya.y * gs4[1]), to_s16_sat(yb.y * gs4[1])));
+        od[2 * H2 + c / 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(to_s16_sat(ya.z * gs4[2]), to_s16_sat(yb.z * gs4[2])));
+        od[3 * H2 + c / 2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(to_s16_sat(ya.w * gs4[3]), to_s16_sat(yb.w * gs4[3])));
       }
       __builtin_amdgcn_sched_barrier(0);
       // Through the wave's staging area so that every store instruction writes one contiguous run:

@@ -233,14 +233,17 @@ static float ease(float x) {
 }
 
 /* audio_effect_peak_limiter.c:237-265 */
-static float limiter_gain_step(orc_limiter *l, float peak) {
+static float limiter_gain_step(orc_limiter *l, float peak, unsigned char *trace) {
+  int phase = ORC_LIM_IDLE, trig = 0;
   if (l->tc != -1 && l->tc < l->atk) {
     float r;
+    phase = ORC_LIM_ATTACK;
     l->tc += l->inc;
     r = ease(l->tc / l->atk);
     l->g = l->gs - r * (l->gs - l->ge);
   } else if (l->tc != -1 && l->tc < l->rel + l->atk) {
     float r;
+    phase = ORC_LIM_RELEASE;
     l->tc += l->inc;
     r = ease((l->tc - l->atk) / l->rel);
     l->g = l->ge + r * (1.0f - l->ge);
@@ -251,7 +254,9 @@ static float limiter_gain_step(orc_limiter *l, float peak) {
     l->gs = l->g;
     l->ge = l->thr / peak;
     l->tc = 0.0f;
+    trig = ORC_LIM_TRIGGER;
   }
+  if (trace) *trace = (unsigned char)(phase | trig);
   return l->g;
 }
 
@@ -259,7 +264,7 @@ static float limiter_gain_step(orc_limiter *l, float peak) {
  * new sample enters, gain step, emit delayed sample * gain, store the new sample and its
  * cross-channel |x| maximum.  The reference's peak_pos cache (:117-133,171-176) always yields
  * the true ring maximum; it is kept here (same rescan order) so the CPU cost is comparable. */
-int orc_limiter_process(orc_limiter *lim, const float *in, float *out, int ns) {
+static int limiter_process(orc_limiter *lim, const float *in, float *out, int ns, unsigned char *trace) {
   const int D = lim->delay;
   if (!in) return 0;
   for (int k = 0; k < ns; ++k) {
@@ -276,7 +281,7 @@ int orc_limiter_process(orc_limiter *lim, const float *in, float *out, int ns) {
     } else {
       peak = lim->pk[lim->maxpos];
     }
-    gain = limiter_gain_step(lim, peak);
+    gain = limiter_gain_step(lim, peak, trace ? trace + k : NULL);
     for (int c = 0; c < lim->ch; ++c) {
       float a;
       out[(size_t)c * ns + k] = lim->dl[c][idx] * gain;
@@ -306,6 +311,16 @@ int orc_limiter_process(orc_limiter *lim, const float *in, float *out, int ns) {
     }
   }
   return ns;
+}
+
+int orc_limiter_process(orc_limiter *lim, const float *in, float *out, int ns) {
+  return limiter_process(lim, in, out, ns, NULL);
+}
+
+/* the same call, and what each of its ns gain steps did: trace[k] = phase the step took (ORC_LIM_IDLE / _ATTACK /
+ * _RELEASE) | ORC_LIM_TRIGGER if the step ended with peak * gain > threshold.  Step k is the one input sample k enters at. */
+int orc_limiter_process_trace(orc_limiter *lim, const float *in, float *out, int ns, unsigned char *trace) {
+  return limiter_process(lim, in, out, ns, trace);
 }
 
 /* ------------------------------------------------------------------------------------------

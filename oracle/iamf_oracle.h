@@ -90,6 +90,9 @@ void orc_limiter_init(orc_limiter *lim, float threshold_db, int rate, int channe
                       float atk_sec, float rel_sec, int delay);
 /* in/out planar [ch][ns]; returns the number of samples emitted (ns, or ns - pad once) */
 int orc_limiter_process(orc_limiter *lim, const float *in, float *out, int ns);
+/* orc_limiter_process, reporting per gain step (trace[0..ns)) the phase it took and whether it triggered */
+enum { ORC_LIM_IDLE = 0, ORC_LIM_ATTACK = 1, ORC_LIM_RELEASE = 2, ORC_LIM_TRIGGER = 4 };
+int orc_limiter_process_trace(orc_limiter *lim, const float *in, float *out, int ns, unsigned char *trace);
 
 /* ---- float -> interleaved PCM ---- reference src/iamf_dec/IAMF_decoder.c:100-167 */
 void orc_pack(void *dst, const float *src, int ns, int channels, int bit_depth, int stride);

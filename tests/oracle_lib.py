@@ -58,6 +58,7 @@ def lib():
         L.orc_limiter_init.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float,
                                        C.c_int]
         L.orc_limiter_process.argtypes = [C.c_void_p, FP, FP, C.c_int]
+        L.orc_limiter_process_trace.argtypes = [C.c_void_p, FP, FP, C.c_int, C.c_void_p]
         L.orc_pack.argtypes = [C.c_void_p, FP, C.c_int, C.c_int, C.c_int, C.c_int]
         L.orc_dmx_open.restype = C.c_void_p
         L.orc_dmx_open.argtypes = [C.c_int, C.c_int]
@@ -159,6 +160,30 @@ def limiter_run(x, sizes, flush=True, **kw):
         outs.append(o)
         rets.append(r)
     return np.concatenate(outs, axis=1), rets
+
+
+LIM_IDLE, LIM_ATTACK, LIM_RELEASE, LIM_TRIGGER = 0, 1, 2, 4
+
+
+def limiter_trace(x, sizes, flush=True, **kw):
+    """limiter_run, and per gain step (input samples, then the flush's 240) the phase the step took (LIM_IDLE / LIM_ATTACK /
+    LIM_RELEASE) with LIM_TRIGGER or-ed in where it triggered: (y [ch][n_out], trace uint8 [steps])"""
+    lim = Limiter(x.shape[0], **kw)
+    blocks, pos = [], 0
+    for n in sizes:
+        blocks.append(np.ascontiguousarray(x[:, pos:pos + n], dtype=np.float32))
+        pos += n
+    if flush:
+        blocks.append(np.zeros((x.shape[0], 240), dtype=np.float32))
+    outs, traces = [], []
+    for b in blocks:
+        n = b.shape[1]
+        o = np.zeros((lim.ch, max(n, 1)), dtype=np.float32)
+        t = np.zeros(max(n, 1), dtype=np.uint8)
+        r = lib().orc_limiter_process_trace(lim.buf, fp(b), fp(o), n, t.ctypes.data_as(C.c_void_p))
+        outs.append(o.reshape(-1)[:lim.ch * r].reshape(lim.ch, r).copy())
+        traces.append(t[:n])
+    return np.concatenate(outs, axis=1), np.concatenate(traces)
 
 
 def pack(x, bit_depth, stride=None):
