@@ -200,9 +200,10 @@ inline Route pick_route(const RenderParams &p, int m) {
   }
   // HRTF renderer: aligned calls only (the flush goes to the generic kernel)
   if (p.fir_taps > 0 && p.in) {
-    if (!fast_shape || p.dmx_on) return refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
-    // the FIR stage keeps input offsets of one stream as 32-bit integers
+    // the FIR stage keeps input offsets of one stream as 32-bit integers.  (In front of the fast kernel's own, tighter
+    // bound on byte offsets, which would shadow it: a frame stride no stage can address is a bad argument.)
     if (((int64_t)(p.total / p.frame_size) + 1) * p.in_frame_stride >= (int64_t)1 << 31) return refuse(IAMF_HIP_ERR_BAD_ARG);
+    if (!fast_shape || p.dmx_on) return refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
     if (!FirHomeM::has(m) && !FirM2bM::has(m)) return refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
     // Three stages with one specification (render_fir.hpp): overlap-save FFT on the VALU (default, render_fir_fft.hpp),
     // split-f16 MFMA (IAMF_HIP_FIR_F16=1, render_fir16.hpp), f32 MFMA (IAMF_HIP_FIR_F32=1); they differ in the last bits

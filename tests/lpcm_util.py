@@ -2,6 +2,7 @@
 tests/route_cases.py)."""
 import numpy as np
 
+import gpu_util as G
 import iac_amd as A
 
 
@@ -50,7 +51,8 @@ def rows(ints, bps, le, widths, perm, head, pad, frame_size):
     return raw, L, row
 
 
-def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_samples=0, fmt=A.FMT_S16):
+def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_samples=0, fmt=A.FMT_S16, layout=G.DENSE):
+    """layout: of the PCM rows only (gpu_util.pcm_rows); the packet rows have head, pad and perm"""
     S, F, _ = raw.shape
     import torch
     d_raw = torch.from_numpy(raw).cuda()
@@ -61,7 +63,7 @@ def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_sampl
     f0 = 0
     for nf in calls:
         cap = max(nf * frame_size, 240) * out_ch * bps_out
-        pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
+        pcm, d_pcm, stride = G.pcm_rows(S, cap, layout, bps_out)
         inp = A.LpcmInput()
         inp.d_raw = d_raw.data_ptr() + f0 * row
         inp.raw_stream_stride = F * row
@@ -71,22 +73,22 @@ def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_sampl
         a = A.RenderArgs()
         a.n_frames = nf
         a.n_samples = n_samples
-        a.d_pcm = pcm.data_ptr()
-        a.pcm_stream_stride_bytes = cap
+        a.d_pcm = d_pcm
+        a.pcm_stream_stride_bytes = stride
         a.stream = st
         n = b.render_lpcm(inp, a)
         torch.cuda.synchronize()
-        h = pcm.cpu().numpy()
+        h = G.rows_and_rest(pcm, layout, n * out_ch * bps_out)
         for s in range(S):
-            outs[s].append(h[s][:n * out_ch * bps_out].copy())
+            outs[s].append(h[s])
         f0 += nf
     cap = 240 * out_ch * bps_out
-    pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
-    n = b.flush(pcm.data_ptr(), cap, st)
+    pcm, d_pcm, stride = G.pcm_rows(S, cap, layout, bps_out)
+    n = b.flush(d_pcm, stride, st)
     torch.cuda.synchronize()
-    h = pcm.cpu().numpy()
+    h = G.rows_and_rest(pcm, layout, n * out_ch * bps_out)
     for s in range(S):
-        outs[s].append(h[s][:n * out_ch * bps_out].copy())
+        outs[s].append(h[s])
     b.close()
     return [np.concatenate(o) for o in outs]
 

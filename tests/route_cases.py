@@ -7,7 +7,8 @@ calls were expected to take, and every stream equals the oracle.  Exact kernels 
 within 1 LSB; the HRTF stages against the float64 convolution with the tolerance of tests/test_gpu_fir.py.
 
 tests/test_route_coverage_cpu.py holds the cases against the library's listing (no GPU);
-tests/test_gpu_route_coverage.py runs them.  Importing this module needs neither a GPU nor the library.
+tests/test_gpu_route_coverage.py runs them, tests/test_gpu_layouts.py runs some of them again with their buffers under
+the layouts of tests/gpu_util.py (kw["layout"], default: dense).  Importing this module needs neither a GPU nor the library.
 
 Matrices: the reference's own table where it has one for the (inputs, outputs) pair, else a seeded dense matrix whose
 columns sum to 1.4, so that the bursts of the hot programme (1.5 on every channel) drive the limiter.
@@ -135,8 +136,9 @@ def compare(got, want, lsb, what):
 
 
 def check_tally(tally, expected):
+    """expected: {instance: launches} or [(instance, launches)], where an instance may appear more than once"""
     exp = {}
-    for k, v in expected.items():
+    for k, v in (expected.items() if isinstance(expected, dict) else expected):
         exp[k] = exp.get(k, 0) + v
     assert tally == exp, "launched %s, expected %s" % (sorted(tally.items()), sorted(exp.items()))
 
@@ -148,7 +150,7 @@ def check_tally(tally, expected):
 def run_matrix(c):
     """one matrix-rendered element: Generic, Nolim, Fast, Wide, Wide4, Wide4Lfe, and with a 1-channel second element the
     mixing variants of Fast and Wide4.  kw: m, oc, fs, calls (frames per call), fmt (16 / 24 / 32), limiter, mfma, second,
-    lfe, env, streams (+ check: the streams compared), expect: [(instance, calls that take it)]"""
+    lfe, env, streams (+ check: the streams compared), expect: [(instance, calls that take it)], layout (gpu_util.Layout)"""
     import torch
     import gpu_util as G
     import iac_amd as A
@@ -162,6 +164,7 @@ def run_matrix(c):
     limiter, mfma, second, lfe = k.get("limiter", True), k.get("mfma", False), k.get("second", False), k.get("lfe", False)
     ns = k.get("streams", S)
     check = k.get("check", list(range(ns)))
+    layout = k.get("layout", G.DENSE)
     F = sum(calls)
     mx, omx = matrices(m, oc)
     if lfe:
@@ -182,11 +185,11 @@ def run_matrix(c):
             b = A.Batch(ns, mx, oc, frame_size=fs, out_format=fmt, projection=proj)
             b.set_gains(element=eg, output=og)
             b.set_second_element(mx2, eg2)
-            got = G.run_ex(A, G, torch, b, ns, m, x, fs, oc, fmt, x2=x2, m2=1, calls=calls)
+            got = G.run_ex(A, G, torch, b, ns, m, x, fs, oc, fmt, x2=x2, m2=1, calls=calls, layout=layout)
             b.close()
         else:
             got = G.hip_render(mx, oc, x, frame_size=fs, fmt=fmt, limiter=limiter, flush=True, frames_per_call=calls,
-                               gains=dict(element=eg, output=og), projection=proj, lfe_hoa=lfe)
+                               gains=dict(element=eg, output=og), projection=proj, lfe_hoa=lfe, layout=layout)
         tally = A.route_tally()
     for s in check:
         if second:
@@ -211,7 +214,7 @@ def run_matrix(c):
 
 def run_lpcm(c):
     """a mono-coded ambisonics element as 16-bit LPCM packets (render_fast_kernel<M, OC, .., LP>); kw: m, oc, env, streams,
-    check, calls"""
+    check, calls, layout (the PCM side)"""
     import iac_amd as A
     import lpcm_util as LP
     import oracle_lib as O
@@ -233,23 +236,26 @@ def run_lpcm(c):
     raw, L, row = LP.rows(ints, 2, True, [1] * m, perm, head=16, pad=0, frame_size=fs)
     with environment(k.get("env", {})):
         A.route_reset()
-        got = LP.render_lpcm(mx, oc, raw, L, row, fs, calls)
+        got = LP.render_lpcm(mx, oc, raw, L, row, fs, calls, layout=k.get("layout", LP.G.DENSE))
         tally = A.route_tally()
     for s in check:
         want = O.stream_run(omx, oc, planar[s], fs)
         assert float(np.abs(O.render(omx, planar[s], oc)).max()) > 0.95, "the programme does not drive the limiter"
         compare(got[s].view(np.int16).reshape(-1, oc), want, 0, (c.id, s))
-    check_tally(tally, {c.inst: len(calls), gen(m): 1})
+    check_tally(tally, [(c.inst, len(calls)), (gen(m), 1)])
 
 
 def run_fanout(c):
-    """one element into K one- and two-channel batches in one launch (render_fanout_kernel<M, K>); kw: m, k"""
+    """one element into K one- and two-channel batches in one launch (render_fanout_kernel<M, K>); kw: m, k, calls, layout,
+    fused: the members a call renders in the shared launch (K, or 0 where every member is rendered singly: c.inst then
+    names the kernel each of them takes)"""
     import torch
     import gpu_util as G
     import iac_amd as A
     import oracle_lib as O
     m, K = c.kw["m"], c.kw["k"]
-    fs, calls = 1024, [1, 3, 2]
+    fs, calls = 1024, c.kw.get("calls", [1, 3, 2])
+    layout, n_fused = c.kw.get("layout", G.DENSE), c.kw.get("fused", K)
     F = sum(calls)
     ocs = [2, 1, 2, 1][:K]
     mxs = [matrices(m, oc, table=(j < 2), salt=j) for j, oc in enumerate(ocs)]   # members 2, 3: the same layouts, other weights
@@ -257,7 +263,7 @@ def run_fanout(c):
     x = hot(m, F, fs)
     for j in range(K):   # every member's limiter must work
         x = drive_limiter(O, mxs[j][1], ocs[j], x, gains[j][0], gains[j][1])
-    xin = torch.from_numpy(G.to_frames(x, fs)).cuda()
+    xf = G.to_frames(x, fs)
     st = torch.cuda.current_stream().cuda_stream
     batches = []
     for j in range(K):
@@ -266,68 +272,85 @@ def run_fanout(c):
         batches.append(b)
     outs = [[[] for _ in range(S)] for _ in range(K)]
 
-    def take(j, pcm, n):
+    def take(j, rows, n):
         torch.cuda.synchronize()
-        h = pcm.cpu().numpy()
+        h = G.rows_and_rest(rows, layout, n * ocs[j] * 2)
         for s in range(S):
-            outs[j][s].append(h[s][:n * ocs[j] * 2].view(np.int16).reshape(n, ocs[j]).copy())
+            outs[j][s].append(h[s].view(np.int16).reshape(n, ocs[j]).copy())
 
     A.route_reset()
     f0 = 0
-    for nf in calls:
-        caps = [(nf * fs * oc * 2 + 15) & ~15 for oc in ocs]
-        pcms = [torch.zeros((S, cap), dtype=torch.uint8, device="cuda") for cap in caps]
-        n_emitted, fused = A.render_fanout(batches, xin.data_ptr() + 4 * f0 * m * fs, F * m * fs, m * fs, nf,
-                                           [p.data_ptr() for p in pcms], caps, st)
-        assert fused == K, (fused, K)
-        for j in range(K):
-            take(j, pcms[j], n_emitted[j])
-        f0 += nf
-    for j, b in enumerate(batches):
-        cap = 240 * ocs[j] * 2
-        pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
-        take(j, pcm, b.flush(pcm.data_ptr(), cap, st))
-        b.close()
+    keep = pcms = rows = None
+    try:
+        for nf in calls:
+            caps = [(nf * fs * oc * 2 + 15) & ~15 for oc in ocs]
+            pcms = [G.pcm_rows(S, cap, layout) for cap in caps]
+            pl = G.place_input(xf, layout, f0, nf, keep=keep)
+            keep = pl.keep
+            n_emitted, fused = A.render_fanout(batches, pl.d_in, pl.stream_stride, pl.frame_stride, nf,
+                                               [p[1] for p in pcms], [p[2] for p in pcms], st)
+            assert fused == n_fused, (fused, n_fused)
+            for j in range(K):
+                take(j, pcms[j][0], n_emitted[j])
+            pcms = None
+            f0 += nf
+        for j, b in enumerate(batches):
+            cap = 240 * ocs[j] * 2
+            rows, d_pcm, stride = G.pcm_rows(S, cap, layout)
+            take(j, rows, b.flush(d_pcm, stride, st))
+            rows = None
+    finally:
+        keep = pcms = rows = pl = None
+        for b in batches:
+            b.close()
     tally = A.route_tally()
     for j in range(K):
         for s in range(S):
             want = O.stream_run(mxs[j][1], ocs[j], x[s], fs, element_gain=gains[j][0][s], output_gain=gains[j][1][s])
             compare(np.concatenate(outs[j][s]), want, 0, (c.id, j, s))
-    check_tally(tally, {c.inst: len(calls), gen(m): K})
+    check_tally(tally, [(c.inst, len(calls) * (1 if n_fused else K)), (gen(m), K)])
 
 
-def _ex_loop(A, b, x, per_call_extra, calls, oc):
+def _ex_loop(A, b, x, per_call_extra, calls, oc, layout=None):
     """x [S][F][m][fs]; render_ex per entry of calls (frames), then the flush; per_call_extra(a, f0, nf) fills the stage's
     fields of the call's RenderArgs and returns what must stay alive.  Returns per stream [n][oc] int16."""
     import torch
+    import gpu_util as G
+    layout = layout or G.DENSE
     ns, F, m, fs = x.shape
-    xin = torch.from_numpy(np.ascontiguousarray(x)).cuda()
     st = torch.cuda.current_stream().cuda_stream
     outs = [[] for _ in range(ns)]
     f0 = 0
-    for nf in calls + [0]:
-        cap = max(nf * fs, 240) * oc * 2
-        pcm = torch.zeros((ns, cap), dtype=torch.uint8, device="cuda")
-        if nf:
-            a = A.RenderArgs()
-            a.d_in, a.in_stream_stride, a.in_frame_stride = xin.data_ptr() + 4 * f0 * m * fs, F * m * fs, m * fs
-            a.n_frames, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, pcm.data_ptr(), cap, st
-            keep = per_call_extra(a, f0, nf)
-            n = b.render_ex(a)
-        else:
-            keep = None
-            n = b.flush(pcm.data_ptr(), cap, st)
-        torch.cuda.synchronize()
-        del keep
-        h = pcm.cpu().numpy()
-        for s in range(ns):
-            outs[s].append(h[s][:n * oc * 2].view(np.int16).reshape(n, oc).copy())
-        f0 += nf
+    placed = rows = pl = keep = None
+    try:
+        for nf in calls + [0]:
+            cap = max(nf * fs, 240) * oc * 2
+            rows, d_pcm, stride = G.pcm_rows(ns, cap, layout)
+            if nf:
+                a = A.RenderArgs()
+                pl = G.place_input(x, layout, f0, nf, keep=placed)
+                placed = pl.keep
+                a.d_in, a.in_stream_stride, a.in_frame_stride = pl.d_in, pl.stream_stride, pl.frame_stride
+                a.n_frames, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, d_pcm, stride, st
+                keep = per_call_extra(a, f0, nf)
+                n = b.render_ex(a)
+            else:
+                keep = None
+                n = b.flush(d_pcm, stride, st)
+            torch.cuda.synchronize()
+            del keep
+            h = G.rows_and_rest(rows, layout, n * oc * 2)
+            rows = None
+            for s in range(ns):
+                outs[s].append(h[s].view(np.int16).reshape(n, oc).copy())
+            f0 += nf
+    finally:
+        placed = rows = pl = None
     return [np.concatenate(o, axis=0) for o in outs]
 
 
 def run_down(c):
-    """the parametric down-mixer: render_fast_kernel<.., DOWN> (mono / stereo) and render_wide4_kernel<.., DOWN>; kw: m, oc"""
+    """the parametric down-mixer: render_fast_kernel<.., DOWN> (mono / stereo) and render_wide4_kernel<.., DOWN>; kw: m, oc, calls, layout"""
     import torch
     import iac_amd as A
     import oracle_lib as O
@@ -336,7 +359,7 @@ def run_down(c):
     m, oc = c.kw["m"], c.kw["oc"]
     il, ol = _DOWN_PAIR[(m, oc)]
     assert L.iamf_hip_dmx_valid(il, ol) == 1 and O.LAYOUT_CH[il] == m and O.LAYOUT_CH[ol] == oc
-    fs, calls = 1024, [1, 3, 2]
+    fs, calls = 1024, c.kw.get("calls", [1, 3, 2])
     F = sum(calls)
     sched = [((-1, 1, 2, 4, 5, 6, 0, 2)[f % 8], (0, 0, 37, 128, 0, fs - 3, 4, 0)[f % 8]) for f in range(F)]
     x = np.stack([np.stack([synth.hot(500 + 31 * s + f, m, fs, sigma=0.3, burst_phase=100 + 50 * f, burst_period=700)
@@ -362,7 +385,7 @@ def run_down(c):
 
     A.route_reset()
     b = A.Batch(S, A.dmx_matrix(il, ol), oc, frame_size=fs, out_format=A.FMT_S16, limiter=True)
-    got = _ex_loop(A, b, x, extra, calls, oc)
+    got = _ex_loop(A, b, x, extra, calls, oc, c.kw.get("layout"))
     b.close()
     tally = A.route_tally()
     for s in range(S):
@@ -371,7 +394,7 @@ def run_down(c):
         assert float(np.abs(yd).max()) > 1.2, "the programme does not drive the limiter"
         z, _ = O.limiter_run(yd, [fs] * F)
         compare(got[s], O.pack(z, 16), 0, (c.id, s))
-    check_tally(tally, {c.inst: len(calls), gen(m): 1})
+    check_tally(tally, [(c.inst, len(calls)), (gen(m), 1)])
 
 
 def demix_frames(A, c, ns):
@@ -395,14 +418,14 @@ def demix_frames(A, c, ns):
 
 
 def run_demix(c):
-    """scalable channel audio: the demixer in front of the projection (render_wide4_kernel<.., DMX>); kw: m, oc"""
+    """scalable channel audio: the demixer in front of the projection (render_wide4_kernel<.., DMX>); kw: m, oc, calls, layout"""
     import torch
     import demix_cases as D
     import iac_amd as A
     import oracle_lib as O
     import synth
     m, oc = c.kw["m"], c.kw["oc"]
-    fs, calls = 1024, [1, 2, 1]
+    fs, calls = 1024, c.kw.get("calls", [1, 2, 1])
     F = sum(calls)
     dc = D.make_case(_DEMIX_LAYERS[m], default=(1, 3), offset=8, fs=fs, seed=770 + m)
     dc["schedule"] = dc["schedule"][:F]
@@ -423,7 +446,7 @@ def run_demix(c):
     A.route_reset()
     b = A.Batch(S, mx, oc, frame_size=fs, out_format=A.FMT_S16, limiter=True, projection=A.PROJ_EXACT)
     b.set_demixer(dc["layout"], dc["order"], dc["gains"], dc["offset"])
-    got = _ex_loop(A, b, x, extra, calls, oc)
+    got = _ex_loop(A, b, x, extra, calls, oc, c.kw.get("layout"))
     b.close()
     tally = A.route_tally()
     for s in range(S):
@@ -431,24 +454,26 @@ def run_demix(c):
         xd = np.ascontiguousarray(dem.transpose(1, 0, 2).reshape(m, F * fs))
         assert float(np.abs(O.render(omx, xd, oc)).max()) > 1.2, "the programme does not drive the limiter"
         compare(got[s], O.stream_run(omx, oc, xd, fs), 0, (c.id, s))
-    check_tally(tally, {c.inst: len(calls), gen(m): 1})
+    check_tally(tally, [(c.inst, len(calls)), (gen(m), 1)])
 
 
 def run_fir(c):
-    """the HRTF stage against the float64 convolution, tolerance and set-up of tests/test_gpu_fir.py; kw: m, env"""
+    """the HRTF stage against the float64 convolution, tolerance and set-up of tests/test_gpu_fir.py; kw: m, env, calls, layout,
+    refused: (layout, error code, frames) of a first call that must be refused and change nothing (gpu_util.hip_render)"""
     import gpu_util as G
     import iac_amd as A
     import synth
     from test_gpu_fir import F32_TOL, fir64, hrir_set
     m = c.kw["m"]
-    fs, calls, taps = 1024, [1, 3, 2], 256
+    fs, calls, taps = 1024, c.kw.get("calls", [1, 3, 2]), 256
     F = sum(calls)
     x = np.stack([synth.gaussian(800 + s, m, F * fs, 0.1) for s in range(S)])
     h = hrir_set(5 + m, m, taps)
     with environment(c.kw.get("env", {})):
         A.route_reset()
         got = G.hip_render(A.fir_matrix(h), 2, x, frame_size=fs, fmt=A.FMT_F32, limiter=True, flush=True,
-                           frames_per_call=calls, fir_taps=taps)
+                           frames_per_call=calls, fir_taps=taps, layout=c.kw.get("layout", G.DENSE),
+                           refused=c.kw.get("refused"))
         tally = A.route_tally()
     for s in range(S):
         y = fir64(h, x[s])
@@ -462,12 +487,15 @@ def run_fir(c):
 
 
 def run_resample(c):
-    """kw: rates, ch, streams, env.  Three calls of unequal length and the drain, streams 0, the middle and the last one
+    """kw: rates, ch, streams, env, layout (input rows as one frame of one channel each, output rows as PCM rows of
+    floats).  Three calls of unequal length and the drain, streams 0, the middle and the last one
     bit for bit against the oracle."""
     import torch
+    import gpu_util as G
     import iac_amd as A
     import oracle_lib as O
     k = c.kw
+    layout = k.get("layout", G.DENSE)
     (r_in, r_out), ch, ns = k["rates"], k["ch"], k["streams"]
     sizes = [700, 1300, 333]
     rng = np.random.default_rng(ch * 1000 + ns)
@@ -479,20 +507,21 @@ def run_resample(c):
         r = A.Resampler(ns, ch, r_in, r_out)
         outs, pos = [], 0
         for n_in in sizes:
-            inter = torch.from_numpy(np.ascontiguousarray(x[:, pos:pos + n_in])).cuda()
+            inter = G.place_input(x[:, pos:pos + n_in].reshape(ns, 1, 1, n_in * ch), layout)
             pos += n_in
             cap = max(r.out_capacity(n_in), 1)
-            o = torch.full((ns, cap, ch), 9.0, dtype=torch.float32, device="cuda")
-            n = r.process(inter.data_ptr(), n_in * ch, n_in, o.data_ptr(), cap * ch, st)
+            rows, d_out, stride = G.pcm_rows(ns, cap * ch * 4, layout, bps=4)
+            n = r.process(inter.d_in, inter.stream_stride, n_in, d_out, stride // 4, st)
             torch.cuda.synchronize()
             assert n >= 0, n
-            outs.append(o[:, :n].cpu().numpy())
-            assert bool((o[:, n:] == 9.0).all()), "nothing is written past the call's outputs"
+            # (rows_and_rest: nothing is written past the call's outputs)
+            outs.append(np.stack(G.rows_and_rest(rows, layout, n * ch * 4)).view(np.float32).reshape(ns, n, ch))
         cap = max(r.flush_capacity(), 1)
-        o = torch.zeros((ns, cap, ch), dtype=torch.float32, device="cuda")
-        n = r.flush(o.data_ptr(), cap * ch, st)
+        rows, d_out, stride = G.pcm_rows(ns, cap * ch * 4, layout, bps=4)
+        n = r.flush(d_out, stride // 4, st)
         torch.cuda.synchronize()
-        outs.append(o[:, :n].cpu().numpy())
+        outs.append(np.stack(G.rows_and_rest(rows, layout, n * ch * 4)).view(np.float32).reshape(ns, n, ch))
+        del rows, inter
         r.close()
         tally = A.route_tally()
     got = np.concatenate(outs, axis=1)

@@ -118,6 +118,113 @@ void list_checks() {
   g_failed += ok ? 0 : 1;
 }
 
+// ---- the address rules: pointers, strides and the 32-bit bounds ----
+// Each row is a block of the table above with exactly one field changed.  The vector kernels load 16 bytes at a time and
+// keep 32-bit byte offsets, so these rules are all that stands between a legal call and a misaligned or wrapped access:
+// the expectation of every row is the family as pick_route() gives it today.
+template <class T>
+T *bytes_on(T *ptr, int n) {
+  return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(ptr) + n);
+}
+template <class F>
+void one_change(const char *block, const char *change, const RenderParams &base, int m, F f, Family family, int variant,
+                int err = IAMF_HIP_OK) {
+  char what[96];
+  snprintf(what, sizeof(what), "%s: %s", block, change);
+  expect(what, with(base, f), m, nullptr, family, variant, err);
+}
+// the three rules of the first element's input
+void input_rules(const char *block, const RenderParams &base, int m, Family family, int variant, int err = IAMF_HIP_OK) {
+  one_change(block, "in + 4 B", base, m, [](RenderParams &p) { p.in = bytes_on(p.in, 4); }, family, variant, err);
+  one_change(block, "in_stream_stride + 1", base, m, [](RenderParams &p) { p.in_stream_stride += 1; }, family, variant, err);
+  one_change(block, "in_frame_stride + 2", base, m, [](RenderParams &p) { p.in_frame_stride += 2; }, family, variant, err);
+}
+void pcm_rules(const char *block, const RenderParams &base, int m, Family family, int variant) {
+  one_change(block, "pcm + 2 B", base, m, [](RenderParams &p) { p.pcm = bytes_on(p.pcm, 2); }, family, variant);
+  one_change(block, "pcm_stream_stride + 2", base, m, [](RenderParams &p) { p.pcm_stream_stride += 2; }, family, variant);
+}
+void second_rules(const char *block, const RenderParams &base, int m, Family family, int variant) {
+  one_change(block, "in2 + 4 B", base, m, [](RenderParams &p) { p.in2 = bytes_on(p.in2, 4); }, family, variant);
+  one_change(block, "in2_stream_stride + 1", base, m, [](RenderParams &p) { p.in2_stream_stride += 1; }, family, variant);
+  one_change(block, "in2_frame_stride + 1", base, m, [](RenderParams &p) { p.in2_frame_stride += 1; }, family, variant);
+}
+void ramp_rules(const char *block, const RenderParams &base, int m, Family family, int variant) {
+  one_change(block, "elem_ramp + 4 B", base, m, [](RenderParams &p) { p.elem_ramp = bytes_on(p.elem_ramp, 4); }, family, variant);
+  one_change(block, "out_ramp + 4 B", base, m, [](RenderParams &p) { p.out_ramp = bytes_on(p.out_ramp, 4); }, family, variant);
+  one_change(block, "ramp_stream_stride + 1", base, m, [](RenderParams &p) { p.ramp_stream_stride += 1; }, family, variant);
+}
+
+void address_rules(const RenderParams &st, const RenderParams &w, const RenderParams &nl, const RenderParams &f16,
+                   const RenderParams &lp) {
+  const int UNIMPL = IAMF_HIP_ERR_UNIMPLEMENTED;
+  const RenderParams st_mix = with(st, second_element), w_mix = with(w, second_element);
+  const RenderParams w24 = aligned(16, 12, IAMF_HIP_FMT_S24);
+  // 11 channels (Sound System E): no wide4 layout.  render_wide_kernel loads its input as scalars, so wide_shape_ok looks
+  // at the PCM only and an unaligned input keeps the kernel
+  const RenderParams e11 = aligned(12, 11);
+  expect("aligned, 11 channels, m = 12", e11, 12, nullptr, Family::Wide, 0);
+
+  // ---- the first element's pointer and strides ----
+  input_rules("stereo", st, 16, Family::Generic, 0);
+  input_rules("limiter off", nl, 16, Family::Generic, 0);
+  // (the fused LPCM kernel does not read `in`, but it is a call of the fast kernel's shape or none)
+  input_rules("LPCM", lp, 16, Family::Refused, 0, IAMF_HIP_ERR_INVALID_STATE);
+  input_rules("12 channels", w, 16, Family::Wide, 0);             // the scalar loads of render_wide_kernel take it
+  input_rules("12 channels + second element", w_mix, 16, Family::Generic, 0);
+  input_rules("FIR", f16, 16, Family::Refused, 0, UNIMPL);
+  input_rules("11 channels", e11, 12, Family::Wide, 0);
+
+  // ---- the PCM pointer and stride ----
+  pcm_rules("stereo", st, 16, Family::Generic, 0);
+  pcm_rules("12 channels, s24 (Wide)", w24, 16, Family::Generic, 0);
+  pcm_rules("12 channels (Wide4)", w, 16, Family::Generic, 0);
+  pcm_rules("limiter off", nl, 16, Family::Generic, 0);
+  pcm_rules("11 channels", e11, 12, Family::Generic, 0);
+
+  // ---- the second element ----
+  expect("12 channels + second element, aligned", w_mix, 16, nullptr, Family::Wide4Mix, 0);
+  second_rules("stereo + second element", st_mix, 16, Family::Generic, 0);
+  second_rules("12 channels + second element", w_mix, 16, Family::Generic, 0);
+
+  // ---- the ramps ----
+  const auto ramps = [](RenderParams &p) {
+    p.elem_ramp = kTab;
+    p.out_ramp = kTab + 4096;
+    p.ramp_stream_stride = 4096;
+  };
+  expect("stereo + ramps, aligned", with(st, ramps), 16, nullptr, Family::Fast, 1);
+  expect("12 channels + ramps, aligned", with(w, ramps), 16, nullptr, Family::Wide4Mix, 0);
+  ramp_rules("stereo + ramps", with(st, ramps), 16, Family::Generic, 0);
+  ramp_rules("12 channels + ramps", with(w, ramps), 16, Family::Generic, 0);
+
+  // ---- the 32-bit rules, one step to either side of each bound ----
+  // render_fast_kernel: (total / frame_size + 2) * in_frame_stride * 4 + 100 * frame_size < 2^31, here 6 frames of 1024
+  constexpr int64_t k31 = (int64_t)1 << 31;
+  constexpr int64_t kFastMax = 89474216;    // the largest multiple of 4 within the bound
+  static_assert(6 * kFastMax * 4 + 100 * 1024 < k31 && 6 * (kFastMax + 4) * 4 + 100 * 1024 >= k31, "in_frame_stride bound");
+  one_change("stereo", "in_frame_stride at the 32-bit bound", st, 16, [](RenderParams &p) { p.in_frame_stride = kFastMax; },
+             Family::Fast, 0);
+  one_change("stereo", "in_frame_stride 4 floats beyond", st, 16, [](RenderParams &p) { p.in_frame_stride = kFastMax + 4; },
+             Family::Generic, 0);
+  // the packets of its LPCM variant: (total / frame_size + 2) * lpcm_frame_stride + 2^24 < 2^31
+  constexpr int64_t kLpMax = 355117736;     // the largest multiple of 8 within the bound
+  static_assert(6 * kLpMax + (1 << 24) < k31 && 6 * (kLpMax + 8) + (1 << 24) >= k31, "lpcm_frame_stride bound");
+  one_change("LPCM", "lpcm_frame_stride at the 32-bit bound", lp, 16, [](RenderParams &p) { p.lpcm_frame_stride = kLpMax; },
+             Family::Lpcm, 1);
+  one_change("LPCM", "lpcm_frame_stride 8 bytes beyond", lp, 16, [](RenderParams &p) { p.lpcm_frame_stride = kLpMax + 8; },
+             Family::Refused, 0, IAMF_HIP_ERR_INVALID_STATE);
+  // the FIR stage: (total / frame_size + 1) * in_frame_stride < 2^31 floats, else BAD_ARG.  Below the bound the call is
+  // still beyond the fast kernel's byte offsets, which is the UNIMPLEMENTED of any call that kernel does not take
+  constexpr int64_t kFirMax = 429496728;    // the largest multiple of 4 within the bound
+  static_assert(5 * kFirMax < k31 && 5 * (kFirMax + 4) >= k31, "FIR in_frame_stride bound");
+  one_change("FIR", "in_frame_stride at the fast kernel's bound", f16, 16, [](RenderParams &p) { p.in_frame_stride = kFastMax; },
+             Family::FirSplit, 0);
+  one_change("FIR", "in_frame_stride at the stage's 32-bit bound", f16, 16, [](RenderParams &p) { p.in_frame_stride = kFirMax; },
+             Family::Refused, 0, UNIMPL);
+  one_change("FIR", "in_frame_stride 4 floats beyond", f16, 16, [](RenderParams &p) { p.in_frame_stride = kFirMax + 4; },
+             Family::Refused, 0, IAMF_HIP_ERR_BAD_ARG);
+}
+
 }  // namespace
 
 int main() {
@@ -213,6 +320,8 @@ int main() {
   expect("  m = 6: no instance", with(aligned(6, 2), lpcm), 6, nullptr, Family::Refused, 0, IAMF_HIP_ERR_INVALID_STATE);
   expect("  pos0 = 8: not a call of the fast kernel", with(lp, [](RenderParams &p) { p.pos0 = 8; }), 16, nullptr, Family::Refused, 0,
          IAMF_HIP_ERR_INVALID_STATE);
+
+  address_rules(st, w, nl, f16, lp);
 
   printf("%d cases, %d wrong\n", g_cases, g_failed);
   if (!g_failed) printf("OK\n");
