@@ -57,6 +57,7 @@ namespace {
 #include "render_fast.hpp"
 #include "render_fir_launch.hpp"
 #include "render_fanout.hpp"
+#include "render_fanout_lp.hpp"
 #include "render_generic.hpp"
 #include "render_nolim.hpp"
 #include "render_wide.hpp"
@@ -1086,19 +1087,17 @@ int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in,
 
 // the same for the streams [stream0, stream0 + n_streams) only (as iamf_hip_batch_render_range: buffers and strides are
 // still indexed by the stream's number in the batch)
-int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
-                                     int32_t stream0, int32_t n_streams) {
-  if (!b || !in || !args || !in->d_raw || args->d_in || !args->d_pcm || args->n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
-  if (stream0 < 0 || n_streams <= 0 || stream0 + n_streams > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
-  if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
-  if (args->n_frames == 0) return 0;
+// The packet-form checks of an LPCM call of nf frames (n_samples as iamf_hip_render_args::n_samples): an error, or
+// IAMF_HIP_OK with the trim {first, count} and whether the packets have the form the fused kernels read
+static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int n_samples, bool *fusable_out,
+                           int *first_out, int *count_out) {
   const iamf_hip_lpcm_layout &L = in->layout;
-  const int fs = b->cfg.frame_size, ch = b->d_pre ? b->pre_l : b->m, ns = b->cfg.n_streams, nf = args->n_frames;
+  const int fs = b->cfg.frame_size, ch = b->d_pre ? b->pre_l : b->m;
   if (L.sample_bytes < 2 || L.sample_bytes > 4 || L.channels != ch || ch > IAMF_HIP_LPCM_MAX_CHANNELS || L.frame_size != fs ||
       (fs & 3) || in->raw_frame_stride <= 0 || in->raw_stream_stride < (int64_t)nf * in->raw_frame_stride)
     return IAMF_HIP_ERR_BAD_ARG;
-  const int first = in->first_sample, count = args->n_samples > 0 ? args->n_samples : fs;
-  if (first < 0 || (first > 0 && (nf != 1 || args->n_samples <= 0)) || first + count > fs) return IAMF_HIP_ERR_BAD_ARG;
+  const int first = in->first_sample, count = n_samples > 0 ? n_samples : fs;
+  if (first < 0 || (first > 0 && (nf != 1 || n_samples <= 0)) || first + count > fs) return IAMF_HIP_ERR_BAD_ARG;
   bool fusable = L.sample_bytes == 2 && L.little_endian && ch <= 16 && (in->raw_frame_stride & 7) == 0 &&
                  (in->raw_stream_stride & 7) == 0 && (reinterpret_cast<uintptr_t>(in->d_raw) & 15) == 0;
   for (int c = 0; c < ch; ++c) {   // every byte a kernel may read lies inside the frame's packet row (as iamf_hip_lpcm_unpack)
@@ -1111,30 +1110,28 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
       return IAMF_HIP_ERR_BAD_ARG;
     if (L.src_step[c] != 2 || ((L.src_offset[c] + 2 * first) & 7)) fusable = false;
   }
-  iamf_hip_render_args a = *args;
-  if (fusable) {
-    LpcmIn lp;
-    memset(&lp, 0, sizeof(lp));
-    lp.raw = static_cast<const uint8_t *>(in->d_raw);
-    lp.stream_stride = in->raw_stream_stride;
-    lp.frame_stride = in->raw_frame_stride;
-    for (int c = 0; c < ch; ++c) lp.off[c] = L.src_offset[c] + 2 * first;
-    a.d_in = reinterpret_cast<const float *>(in->d_raw);   // not read by the fused kernel; non-null = "not a flush"
-    a.in_stream_stride = a.in_frame_stride = 0;
-    const int r = render_range_impl(b, &a, stream0, n_streams, &lp);
-    if (r != kNotFused) return r;
-  }
-  // Unfused: the RANGE's packets -> planar f32 in a buffer of the batch (rows indexed by the stream's number in the batch, as
-  // every buffer of a range call), then the f32 path.  Everything the render call would refuse is refused here first, so
-  // that no unpack launch precedes an error; {first, count} travel in the unpacker's kernel arguments (a device
-  // word updated by a blocking copy cost K host synchronisations per round of a group with K divergent runs).
-  {
-    a.d_in = reinterpret_cast<const float *>(in->d_raw);   // placeholder for the checks: set below
-    int64_t total = 0;
-    const int rc = range_args_check(b, &a, stream0, n_streams, &total);
-    if (rc != IAMF_HIP_OK || total == 0) return rc;
-  }
-  hipStream_t st = static_cast<hipStream_t>(args->stream);
+  *fusable_out = fusable;
+  *first_out = first;
+  *count_out = count;
+  return IAMF_HIP_OK;
+}
+
+// packets of the fusable form as the fused kernels take them
+static void lpcm_in_of(const iamf_hip_lpcm_input *in, int ch, int first, LpcmIn &lp) {
+  memset(&lp, 0, sizeof(lp));
+  lp.raw = static_cast<const uint8_t *>(in->d_raw);
+  lp.stream_stride = in->raw_stream_stride;
+  lp.frame_stride = in->raw_frame_stride;
+  for (int c = 0; c < ch; ++c) lp.off[c] = in->layout.src_offset[c] + 2 * first;
+}
+
+// The RANGE's packets -> planar f32 in a buffer of the batch (rows indexed by the stream's number in the batch, as every
+// buffer of a range call); a's input fields then name that buffer.  {first, count} travel in the unpacker's kernel arguments
+// (a device word updated by a blocking copy cost K host synchronisations per round of a group with K divergent runs).
+static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int first, int count, int32_t stream0,
+                             int32_t n_streams, hipStream_t st, iamf_hip_render_args &a) {
+  const iamf_hip_lpcm_layout &L = in->layout;
+  const int fs = b->cfg.frame_size, ch = b->d_pre ? b->pre_l : b->m, ns = b->cfg.n_streams;
   const size_t need = (size_t)ns * nf * ch * fs;
   if (need > b->lp_in_floats) {   // grows with the largest call seen
     const int q = quiesce(b);     // a render queued earlier may still be reading the old buffer
@@ -1163,6 +1160,39 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
   a.d_in = b->d_lp_in;
   a.in_stream_stride = lp_stream_stride;
   a.in_frame_stride = (int64_t)ch * fs;
+  return IAMF_HIP_OK;
+}
+
+int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
+                                     int32_t stream0, int32_t n_streams) {
+  if (!b || !in || !args || !in->d_raw || args->d_in || !args->d_pcm || args->n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
+  if (stream0 < 0 || n_streams <= 0 || stream0 + n_streams > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
+  if (args->n_frames == 0) return 0;
+  const int ch = b->d_pre ? b->pre_l : b->m, nf = args->n_frames;
+  bool fusable = false;
+  int first = 0, count = 0;
+  const int fc = lpcm_form_check(b, in, nf, args->n_samples, &fusable, &first, &count);
+  if (fc != IAMF_HIP_OK) return fc;
+  iamf_hip_render_args a = *args;
+  if (fusable) {
+    LpcmIn lp;
+    lpcm_in_of(in, ch, first, lp);
+    a.d_in = reinterpret_cast<const float *>(in->d_raw);   // not read by the fused kernel; non-null = "not a flush"
+    a.in_stream_stride = a.in_frame_stride = 0;
+    const int r = render_range_impl(b, &a, stream0, n_streams, &lp);
+    if (r != kNotFused) return r;
+  }
+  // Unfused: unpack, then the f32 path.  Everything the render call would refuse is refused here first, so that no unpack
+  // launch precedes an error.
+  {
+    a.d_in = reinterpret_cast<const float *>(in->d_raw);   // placeholder for the checks: set below
+    int64_t total = 0;
+    const int rc = range_args_check(b, &a, stream0, n_streams, &total);
+    if (rc != IAMF_HIP_OK || total == 0) return rc;
+  }
+  const int ur = lpcm_unpack_range(b, in, nf, first, count, stream0, n_streams, static_cast<hipStream_t>(args->stream), a);
+  if (ur != IAMF_HIP_OK) return ur;
   return render_range_impl(b, &a, stream0, n_streams, nullptr);
 }
 
@@ -1195,12 +1225,17 @@ int iamf_hip_batch_render(iamf_hip_batch *b, const float *d_in, int64_t in_strea
 // never holds (a call has at most IAMF_HIP_FANOUT_MAX members); it is where a count that stops winning would be cut.
 static const int kFanFuseMax = IAMF_HIP_FANOUT_MAX;
 
-int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batches, const float *d_in, int64_t in_stream_stride,
-                                 int64_t in_frame_stride, int32_t n_frames, void *const *d_pcm,
-                                 const int64_t *pcm_stream_stride_bytes, void *stream, int32_t *n_emitted, int32_t *n_fused) {
+// iamf_hip_batch_render_fanout over the streams [stream0, stream0 + n_streams) of every member; whole: every stream of the
+// members, whatever their count (the range arguments are not looked at).  n_samples: iamf_hip_render_args::n_samples of
+// every member's call (0 for the public f32 entries).
+static int fanout_range_impl(iamf_hip_batch *const *batches, int32_t n_batches, const float *d_in, int64_t in_stream_stride,
+                             int64_t in_frame_stride, int32_t n_frames, int32_t n_samples, void *const *d_pcm,
+                             const int64_t *pcm_stream_stride_bytes, void *stream, int32_t *n_emitted, int32_t *n_fused,
+                             bool whole, int32_t stream0, int32_t n_streams) {
   // ---- checks that need no device ----
   if (n_batches < 1 || n_batches > IAMF_HIP_FANOUT_MAX) return IAMF_HIP_ERR_BAD_ARG;
   if (!batches || !d_in || !d_pcm || !pcm_stream_stride_bytes || !n_emitted) return IAMF_HIP_ERR_BAD_ARG;
+  if (!whole && (stream0 < 0 || n_streams <= 0)) return IAMF_HIP_ERR_BAD_ARG;
   for (int j = 0; j < n_batches; ++j) {
     if (!batches[j] || !d_pcm[j]) return IAMF_HIP_ERR_BAD_ARG;
     for (int i = 0; i < j; ++i)
@@ -1210,6 +1245,8 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
   iamf_hip_render_args args[IAMF_HIP_FANOUT_MAX];
   int64_t total = 0;
   const iamf_hip_batch *b0 = batches[0];
+  const int ns = b0->cfg.n_streams;
+  if (whole) stream0 = 0, n_streams = ns;
   for (int j = 0; j < n_batches; ++j) {
     const iamf_hip_batch *b = batches[j];
     if (b->cfg.n_streams != b0->cfg.n_streams || b->cfg.frame_size != b0->cfg.frame_size || b->m != b0->m ||
@@ -1222,13 +1259,14 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
     a.in_stream_stride = in_stream_stride;
     a.in_frame_stride = in_frame_stride;
     a.n_frames = n_frames;
+    a.n_samples = n_samples;
     a.d_pcm = d_pcm[j];
     a.pcm_stream_stride_bytes = pcm_stream_stride_bytes[j];
     a.stream = stream;
     int64_t tj = 0;
-    const int rc = range_args_check(b, &a, 0, b->cfg.n_streams, &tj);
+    const int rc = range_args_check(b, &a, stream0, n_streams, &tj);
     if (rc != IAMF_HIP_OK) return rc;
-    total = tj;   // n_frames * frame_size: the same for every member
+    total = tj;   // the call's samples per stream: the same for every member
   }
   if (total == 0) {   // n_frames == 0: nothing to do and no state looked at, as the single call
     if (n_fused) *n_fused = 0;
@@ -1238,14 +1276,17 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
   for (int j = 0; j < n_batches; ++j) {
     const iamf_hip_batch *b = batches[j];
     if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
-    for (int i = 0; i < b->cfg.n_streams; ++i)
-      if (b->spos[(size_t)i] != b0->spos[0] || b->sflushed[(size_t)i]) return IAMF_HIP_ERR_INVALID_STATE;
+    for (int i = stream0; i < stream0 + n_streams; ++i)
+      if (b->spos[(size_t)i] != b0->spos[(size_t)stream0] || b->sflushed[(size_t)i]) return IAMF_HIP_ERR_INVALID_STATE;
   }
+  // the HRTF stage's history is per batch, not per stream: a proper sub-range is not built (as the single call)
+  if (stream0 != 0 || n_streams != ns)
+    for (int j = 0; j < n_batches; ++j)
+      if (batches[j]->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
   if (n_fused) *n_fused = 0;
   for (int j = 0; j < n_batches; ++j) n_emitted[j] = 0;
 
   // ---- which members share the input: those the single call would launch as the plain render_fast_kernel<M, OC> (pick_route) ----
-  const int ns = b0->cfg.n_streams;
   PreparedCall pcs[IAMF_HIP_FANOUT_MAX];
   bool fuse[IAMF_HIP_FANOUT_MAX];
   int k = 0;
@@ -1257,7 +1298,7 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
     if (k >= kFanFuseMax || b->fir || b->lfe || b->d_pre || (sc > 0 && sc != b->cfg.out_channels) || !b->cfg.limiter_enable ||
         b->cfg.out_channels > 2)
       continue;
-    const int rc = render_prepare(b, args[j], (int)total, 0, ns, nullptr, pcs[j]);
+    const int rc = render_prepare(b, args[j], (int)total, stream0, n_streams, nullptr, pcs[j]);
     if (rc != IAMF_HIP_OK) return rc;
     const Route r = pick_route(pcs[j].p, pcs[j].m_eff);
     fuse[j] = r.family == Family::Fast && r.variant == 0 && pcs[j].m_eff == b0->m && FanM::has(pcs[j].m_eff);
@@ -1279,8 +1320,8 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
         fp.total = p.total;
         fp.frame_size = p.frame_size;
         fp.n_streams = p.n_streams;
-        fp.stream0 = 0;
-        fp.n_launch = ns;
+        fp.stream0 = stream0;
+        fp.n_launch = n_streams;
       }
       FanMember &mb = fp.mem[n++];
       mb.pcm = p.pcm;
@@ -1313,10 +1354,217 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
   // ---- every other member: the single call, in member order, on the same stream ----
   for (int j = 0; j < n_batches; ++j) {
     if (k && fuse[j]) continue;
-    const int r = render_call(batches[j], args[j], (int)total, 0, ns);
+    const int r = render_call(batches[j], args[j], (int)total, stream0, n_streams);
     if (r < 0) return r;
     n_emitted[j] = r;
   }
+  return IAMF_HIP_OK;
+}
+
+int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batches, const float *d_in, int64_t in_stream_stride,
+                                 int64_t in_frame_stride, int32_t n_frames, void *const *d_pcm,
+                                 const int64_t *pcm_stream_stride_bytes, void *stream, int32_t *n_emitted, int32_t *n_fused) {
+  return fanout_range_impl(batches, n_batches, d_in, in_stream_stride, in_frame_stride, n_frames, 0, d_pcm, pcm_stream_stride_bytes,
+                           stream, n_emitted, n_fused, true, 0, 0);
+}
+
+int iamf_hip_batch_render_fanout_range(iamf_hip_batch *const *batches, int32_t n_batches, const float *d_in,
+                                       int64_t in_stream_stride, int64_t in_frame_stride, int32_t n_frames, void *const *d_pcm,
+                                       const int64_t *pcm_stream_stride_bytes, void *stream, int32_t *n_emitted, int32_t *n_fused,
+                                       int32_t stream0, int32_t n_streams) {
+  return fanout_range_impl(batches, n_batches, d_in, in_stream_stride, in_frame_stride, n_frames, 0, d_pcm, pcm_stream_stride_bytes,
+                           stream, n_emitted, n_fused, false, stream0, n_streams);
+}
+
+// How many members one launch of render_fanout_lp_kernel takes for a range of `workgroups` streams: a (K, size) that does
+// not beat K single packet-fed calls by more than the spread of two series of those calls is not fused
+// (tools/fanout_lpcm_rate.py).  The rule may look at K and at the number of workgroups only.
+static int fan_lp_fuse_max(int workgroups) {
+  (void)workgroups;
+  return IAMF_HIP_FANOUT_MAX;
+}
+
+int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_batches, const iamf_hip_lpcm_input *in,
+                                      int32_t n_frames, int32_t n_samples, void *const *d_pcm,
+                                      const int64_t *pcm_stream_stride_bytes, void *stream, int32_t stream0, int32_t n_streams,
+                                      int32_t *n_emitted, iamf_hip_fanout_report *report) {
+  // ---- checks that need no device ----
+  if (n_batches < 1 || n_batches > IAMF_HIP_FANOUT_MAX) return IAMF_HIP_ERR_BAD_ARG;
+  if (!batches || !in || !in->d_raw || !d_pcm || !pcm_stream_stride_bytes || !n_emitted || n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
+  if (stream0 < 0 || n_streams <= 0) return IAMF_HIP_ERR_BAD_ARG;
+  for (int j = 0; j < n_batches; ++j) {
+    if (!batches[j] || !d_pcm[j]) return IAMF_HIP_ERR_BAD_ARG;
+    for (int i = 0; i < j; ++i)
+      if (batches[i] == batches[j]) return IAMF_HIP_ERR_BAD_ARG;
+  }
+  // ---- the members against each other and the range (as the f32 entry), the device (as the single LPCM call) ----
+  iamf_hip_batch *b0 = batches[0];
+  const int ns = b0->cfg.n_streams, ch = b0->d_pre ? b0->pre_l : b0->m;
+  for (int j = 0; j < n_batches; ++j) {
+    const iamf_hip_batch *b = batches[j];
+    if (b->cfg.n_streams != ns || b->cfg.frame_size != b0->cfg.frame_size || b->m != b0->m || (b->d_pre ? b->pre_l : b->m) != ch)
+      return IAMF_HIP_ERR_BAD_ARG;
+    if (b->has2 || b->dmx || b->demix) return IAMF_HIP_ERR_BAD_ARG;  // those need iamf_hip_batch_render_ex
+  }
+  if (stream0 + n_streams > ns) return IAMF_HIP_ERR_BAD_ARG;
+  for (int j = 0; j < n_batches; ++j)
+    if (!on_batch_device(batches[j])) return IAMF_HIP_ERR_INVALID_STATE;
+  iamf_hip_fanout_report rep;
+  memset(&rep, 0, sizeof(rep));
+  if (n_frames == 0) {   // nothing to do and no state looked at, as the single call
+    for (int j = 0; j < n_batches; ++j) n_emitted[j] = 0;
+    if (report) *report = rep;
+    return IAMF_HIP_OK;
+  }
+  // ---- the packets (channels and frame size are the same for every member), then every member's own argument checks ----
+  bool pk_form = false;
+  int first = 0, count = 0;
+  const int fc = lpcm_form_check(b0, in, n_frames, n_samples, &pk_form, &first, &count);
+  if (fc != IAMF_HIP_OK) return fc;
+  iamf_hip_render_args args[IAMF_HIP_FANOUT_MAX];
+  int64_t total = 0;
+  for (int j = 0; j < n_batches; ++j) {
+    iamf_hip_render_args &a = args[j];
+    memset(&a, 0, sizeof(a));
+    a.d_in = reinterpret_cast<const float *>(in->d_raw);   // not read by the fused kernels; non-null = "not a flush"
+    a.n_frames = n_frames;
+    a.n_samples = n_samples;
+    a.d_pcm = d_pcm[j];
+    a.pcm_stream_stride_bytes = pcm_stream_stride_bytes[j];
+    a.stream = stream;
+    int64_t tj = 0;
+    const int rc = range_args_check(batches[j], &a, stream0, n_streams, &tj);
+    if (rc != IAMF_HIP_OK) return rc;
+    total = tj;
+  }
+  // ---- state: the range at one position in every member, unflushed; no proper sub-range of an HRTF batch ----
+  for (int j = 0; j < n_batches; ++j) {
+    const iamf_hip_batch *b = batches[j];
+    for (int i = stream0; i < stream0 + n_streams; ++i)
+      if (b->spos[(size_t)i] != b0->spos[(size_t)stream0] || b->sflushed[(size_t)i]) return IAMF_HIP_ERR_INVALID_STATE;
+  }
+  if (stream0 != 0 || n_streams != ns)
+    for (int j = 0; j < n_batches; ++j)
+      if (batches[j]->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
+
+  // ---- what each member runs: 2 = the shared packet-fed launch, 1 = its single packet-fed call, 0 = f32 ----
+  PreparedCall pcs[IAMF_HIP_FANOUT_MAX];
+  int cls[IAMF_HIP_FANOUT_MAX];
+  int k = 0, n_f32 = 0;
+  const int k_max = fan_lp_fuse_max(n_streams);
+  for (int j = 0; j < n_batches; ++j) {
+    iamf_hip_batch *b = batches[j];
+    cls[j] = 0;
+    if (pk_form) {
+      LpcmIn lp;
+      lpcm_in_of(in, ch, first, lp);
+      const int rc = render_prepare(b, args[j], (int)total, stream0, n_streams, &lp, pcs[j]);
+      if (rc != kNotFused && rc != IAMF_HIP_OK) return rc;
+      if (rc == IAMF_HIP_OK) {   // the member's single call takes Family::Lpcm (render_prepare has asked pick_route)
+        // what the f32 fan-out asks on top: nothing re-laid behind the kernel; then an instance of this kernel
+        cls[j] = (!pcs[j].restride && k < k_max && pcs[j].m_eff == b0->m && FanLpM::has(pcs[j].m_eff)) ? 2 : 1;
+        if (cls[j] == 2) ++k;
+      }
+    }
+    if (cls[j] == 0) ++n_f32;
+  }
+  if (k < 2 || !FanLpK::has(k)) {
+    for (int j = 0; j < n_batches; ++j)
+      if (cls[j] == 2) cls[j] = 1;
+    k = 0;
+  }
+  if (n_f32 && 65535 / n_streams == 0) return IAMF_HIP_ERR_UNIMPLEMENTED;   // the unpacker's grid (lpcm_unpack_range)
+  int32_t emitted[IAMF_HIP_FANOUT_MAX] = {0, 0, 0, 0};
+
+  // ---- 1. the members that share the packets ----
+  if (k) {
+    FanLpParams fp;
+    memset(&fp, 0, sizeof(fp));
+    int n = 0;
+    for (int j = 0; j < n_batches; ++j) {
+      if (cls[j] != 2) continue;
+      const RenderParams &p = pcs[j].p;
+      if (n == 0) {
+        fp.lpcm = p.lpcm;
+        fp.lpcm_stream_stride = p.lpcm_stream_stride;
+        fp.lpcm_frame_stride = p.lpcm_frame_stride;
+        for (int m = 0; m < 16; ++m) fp.lpcm_off[m] = p.lpcm_off[m];
+        fp.pos0 = p.pos0;
+        fp.total = p.total;
+        fp.frame_size = p.frame_size;
+        fp.n_streams = p.n_streams;
+        fp.stream0 = p.stream0;
+        fp.n_launch = p.n_launch;
+      }
+      FanMember &mb = fp.mem[n++];
+      mb.pcm = p.pcm;
+      mb.pcm_stream_stride = p.pcm_stream_stride;
+      mb.matrix = p.matrix;
+      mb.gains = p.gains;
+      mb.ctab = p.ctab;
+      mb.lim = p.lim;
+      mb.ring_y = p.ring_y;
+      mb.ring_pm = p.ring_pm;
+      mb.src_feed = p.src_feed;
+      mb.out_ch = p.out_ch;
+      mb.out_format = p.out_format;
+      mb.loudness_on = p.loudness_on;
+      mb.n_atk = p.n_atk;
+      mb.n_end = p.n_end;
+      mb.thr = p.thr;
+    }
+    if (!iamf_hip_fanout_lp_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
+    HIPCHK(hipGetLastError());
+    iamf_hip_route_count_ext(IAMF_HIP_ROUTE_FANOUT_LPCM, 0, b0->m, 0, k);
+    for (int j = 0; j < n_batches; ++j) {
+      if (cls[j] != 2) continue;
+      const int r = render_commit(batches[j], pcs[j]);
+      if (r < 0) return r;
+      emitted[j] = r;
+    }
+    rep.n_fused = k;
+    rep.input_fused = 1;
+  }
+  // ---- 2. the members whose single call reads the packets itself, in member order ----
+  for (int j = 0; j < n_batches; ++j) {
+    if (cls[j] != 1) continue;
+    int r = render_launch(pcs[j]);
+    if (r != IAMF_HIP_OK) return r;
+    r = render_commit(batches[j], pcs[j]);
+    if (r < 0) return r;
+    emitted[j] = r;
+  }
+  // ---- 3. the members that need f32: one unpack pass into the first one's buffer, then the f32 fan-out over it ----
+  if (n_f32) {
+    iamf_hip_batch *sub_b[IAMF_HIP_FANOUT_MAX];
+    void *sub_pcm[IAMF_HIP_FANOUT_MAX];
+    int64_t sub_stride[IAMF_HIP_FANOUT_MAX];
+    int32_t sub_emitted[IAMF_HIP_FANOUT_MAX] = {0, 0, 0, 0};
+    int n = 0;
+    for (int j = 0; j < n_batches; ++j) {
+      if (cls[j] != 0) continue;
+      sub_b[n] = batches[j];
+      sub_pcm[n] = d_pcm[j];
+      sub_stride[n] = pcm_stream_stride_bytes[j];
+      ++n;
+    }
+    iamf_hip_render_args a = args[0];
+    const int ur = lpcm_unpack_range(sub_b[0], in, n_frames, first, count, stream0, n_streams, static_cast<hipStream_t>(stream), a);
+    if (ur != IAMF_HIP_OK) return ur;
+    rep.n_unpacks = 1;
+    int32_t f32_fused = 0;
+    const int r = fanout_range_impl(sub_b, n, a.d_in, a.in_stream_stride, a.in_frame_stride, n_frames, n_samples, sub_pcm, sub_stride,
+                                    stream, sub_emitted, &f32_fused, false, stream0, n_streams);
+    if (r != IAMF_HIP_OK) return r;
+    // the other members read the first one's buffer: it must not be re-used by that batch before they are done
+    if (n > 1) HIPCHK(hipEventRecord(sub_b[0]->done, static_cast<hipStream_t>(stream)));
+    if (!k) rep.n_fused = f32_fused;
+    n = 0;
+    for (int j = 0; j < n_batches; ++j)
+      if (cls[j] == 0) emitted[j] = sub_emitted[n++];
+  }
+  for (int j = 0; j < n_batches; ++j) n_emitted[j] = emitted[j];
+  if (report) *report = rep;
   return IAMF_HIP_OK;
 }
 

@@ -32,7 +32,7 @@ struct RouteTable {
   uint32_t key[kRouteCap];     // sorted
   int32_t index[kRouteCap];    // row of key[i]
   int n = 0, dropped = 0;
-  RouteTable() {
+  explicit RouteTable(bool ext) {
     const auto add = [&](int family, int variant, int m, int c, int k) {
       if (n == kRouteCap) {
         ++dropped;
@@ -49,8 +49,12 @@ struct RouteTable {
       index[n] = n;
       ++n;
     };
-    for_each_render_instance(add);
-    for_each_resample_instance(add);
+    if (ext) {
+      for_each_render_instance_ext(add);
+    } else {
+      for_each_render_instance(add);
+      for_each_resample_instance(add);
+    }
     int32_t order[kRouteCap];
     for (int i = 0; i < n; ++i) order[i] = i;
     std::sort(order, order + n, [&](int a, int b) { return key[a] < key[b]; });
@@ -66,32 +70,29 @@ struct RouteTable {
 };
 
 const RouteTable &route_table() {
-  static const RouteTable t;
+  static const RouteTable t(false);
+  return t;
+}
+
+// the extension table: the same row type and semantics, its own rows and its own counters (iamf_hip_route_instances_ext)
+const RouteTable &route_table_ext() {
+  static const RouteTable t(true);
   return t;
 }
 
 std::atomic<int64_t> g_launches[kRouteCap + 1];
+std::atomic<int64_t> g_launches_ext[kRouteCap + 1];
 
-}  // namespace
-
-void iamf_hip_route_count(int family, int variant, int m, int c, int k) {
-  g_launches[route_table().find(pack_key(family, variant, m, c, k))].fetch_add(1, std::memory_order_relaxed);
-}
-
-extern "C" {
-
-int iamf_hip_route_instances(iamf_hip_route_row *rows, int cap) {
-  const RouteTable &t = route_table();
+int list_instances(const RouteTable &t, iamf_hip_route_row *rows, int cap) {
   for (int i = 0; rows && i < t.n && i < cap; ++i) rows[i] = t.rows[i];
   return t.n + t.dropped;
 }
 
-int iamf_hip_route_tally(iamf_hip_route_row *rows, int cap, int reset) {
-  const RouteTable &t = route_table();
+int tally_of(const RouteTable &t, std::atomic<int64_t> *launches, iamf_hip_route_row *rows, int cap, int reset) {
   int cnt = 0;
   for (int i = 0; i <= kRouteCap; ++i) {
     if (i >= t.n && i != kRouteCap) continue;
-    const int64_t v = reset ? g_launches[i].exchange(0, std::memory_order_relaxed) : g_launches[i].load(std::memory_order_relaxed);
+    const int64_t v = reset ? launches[i].exchange(0, std::memory_order_relaxed) : launches[i].load(std::memory_order_relaxed);
     if (v == 0) continue;
     if (rows && cnt < cap) {
       if (i < t.n) rows[cnt] = t.rows[i];
@@ -101,6 +102,30 @@ int iamf_hip_route_tally(iamf_hip_route_row *rows, int cap, int reset) {
     ++cnt;
   }
   return cnt;
+}
+
+}  // namespace
+
+void iamf_hip_route_count(int family, int variant, int m, int c, int k) {
+  g_launches[route_table().find(pack_key(family, variant, m, c, k))].fetch_add(1, std::memory_order_relaxed);
+}
+
+void iamf_hip_route_count_ext(int family, int variant, int m, int c, int k) {
+  g_launches_ext[route_table_ext().find(pack_key(family, variant, m, c, k))].fetch_add(1, std::memory_order_relaxed);
+}
+
+extern "C" {
+
+int iamf_hip_route_instances(iamf_hip_route_row *rows, int cap) { return list_instances(route_table(), rows, cap); }
+
+int iamf_hip_route_tally(iamf_hip_route_row *rows, int cap, int reset) {
+  return tally_of(route_table(), g_launches, rows, cap, reset);
+}
+
+int iamf_hip_route_instances_ext(iamf_hip_route_row *rows, int cap) { return list_instances(route_table_ext(), rows, cap); }
+
+int iamf_hip_route_tally_ext(iamf_hip_route_row *rows, int cap, int reset) {
+  return tally_of(route_table_ext(), g_launches_ext, rows, cap, reset);
 }
 
 }  // extern "C"

@@ -15,6 +15,8 @@ IAMF_INTERNAL int iamf_hip_wide4_mix_launch(const void *params, int m, hipStream
 IAMF_INTERNAL int iamf_hip_wide4_lfe_launch(const void *params, int m, hipStream_t st);
 // iamf_render_fanout.hip; params: a FanParams whose first k members are set
 IAMF_INTERNAL int iamf_hip_fanout_launch(const void *params, int m, int k, hipStream_t st);
+// iamf_render_fanout_lp.hip; params: a FanLpParams (render_fanout_lp.hpp) whose first k members are set
+IAMF_INTERNAL int iamf_hip_fanout_lp_launch(const void *params, int m, int k, hipStream_t st);
 // iamf_render_lpcm.hip; early: Route::variant of Family::Lpcm
 IAMF_INTERNAL int iamf_hip_fast_lpcm_launch(const void *params, int m, int early, hipStream_t st);
 // iamf_render_fir_m2b.hip: render_fast_kernel<M, 2, stage> / the FFT stage alone (fir_fft_kernel)
@@ -28,3 +30,5 @@ IAMF_INTERNAL int iamf_hip_lpcm_unpack_frames(const iamf_hip_lpcm_layout *lay, c
                                               int32_t uniform_count);
 // iamf_route.hip: one launch of the instance (family, variant, m, c, k) of iamf_hip_route_row succeeded
 IAMF_INTERNAL void iamf_hip_route_count(int family, int variant, int m, int c, int k);
+// ... of an instance of the extension table (iamf_hip_route_instances_ext)
+IAMF_INTERNAL void iamf_hip_route_count_ext(int family, int variant, int m, int c, int k);

@@ -44,6 +44,10 @@ using FanK = Ints<2, 3, 4>;
 // render_fast_kernel<M, OC, .., LP>: mono-coded ambisonics elements as LPCM packets
 using LpcmM = Ints<1, 4, 9, 16>;
 using LpcmOC = Ints<1, 2>;
+// render_fanout_lp_kernel<M, K>: the fan-out fed with LPCM packets.  M: what LpcmM and FanM share (mono-coded ambisonics
+// elements are the only ones whose channels are contiguous 16-bit runs), K within FanK
+using FanLpM = Ints<4, 9, 16>;
+using FanLpK = Ints<2, 3, 4>;
 // the HRTF stage: ambisonics elements (iamf_render.hip) and channel-based ones, the loudspeaker layouts' channel counts
 // (iamf_render_fir_m2b.hip)
 using FirHomeM = Ints<1, 4, 9, 16>;
@@ -284,6 +288,12 @@ void for_each_render_instance(F &&f) {
     if (home) for_each_int(FirHomeM{}, firs);
     else for_each_int(FirM2bM{}, firs);
   }
+}
+
+// The extension table (iamf_hip_route_instances_ext): instances added behind the table above, whose row set is pinned.
+template <class F>
+void for_each_render_instance_ext(F &&f) {
+  for_each_int(FanLpM{}, [&](int m) { for_each_int(FanLpK{}, [&](int k) { f(IAMF_HIP_ROUTE_FANOUT_LPCM, 0, m, 0, k); }); });
 }
 
 // the row of the kernel launch() runs for a route (a FirSplit call launches render_fast_kernel<2, 2> behind it as well:

@@ -70,6 +70,10 @@ class LpcmInput(C.Structure):   # iamf_hip_lpcm_input
                 ("first_sample", C.c_int32), ("layout", LpcmLayout)]
 
 
+class FanoutReport(C.Structure):   # iamf_hip_fanout_report
+    _fields_ = [("n_fused", C.c_int32), ("input_fused", C.c_int32), ("n_unpacks", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RouteRow(C.Structure):   # iamf_hip_route_row
     _fields_ = [("family", C.c_int32), ("variant", C.c_int32), ("m", C.c_int32), ("c", C.c_int32), ("k", C.c_int32),
                 ("reserved", C.c_int32), ("launches", C.c_int64)]
@@ -77,7 +81,7 @@ class RouteRow(C.Structure):   # iamf_hip_route_row
 
 # IAMF_HIP_ROUTE_*: the kernel families of iamf_hip_route_row::family
 ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, WIDE4_DEMIX=7, WIDE4_DOWN=8, WIDE4_MIX=9,
-             WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23)
+             WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23)
 ROUTE_NAME = {v: k for k, v in ROUTE.items()}
 
 
@@ -150,6 +154,10 @@ def lib():
         L.iamf_hip_batch_render_fanout.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
                                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p,
                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.iamf_hip_batch_render_fanout_range.argtypes = L.iamf_hip_batch_render_fanout.argtypes + [C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_fanout_lpcm.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(LpcmInput), C.c_int32, C.c_int32,
+                                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.c_int32, C.c_int32,
+                                                        C.POINTER(C.c_int32), C.POINTER(FanoutReport)]
         L.iamf_hip_batch_reset.argtypes = [C.c_void_p]
         L.iamf_hip_batch_render_range.argtypes = [C.c_void_p, C.POINTER(RenderArgs), C.c_int32, C.c_int32]
         L.iamf_hip_batch_flush_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32]
@@ -168,6 +176,7 @@ def lib():
         L.iamf_hip_version.restype = C.c_char_p
         L.iamf_hip_batch_render_ex.argtypes = [C.c_void_p, C.POINTER(RenderArgs)]
         L.iamf_hip_batch_render_lpcm.argtypes = [C.c_void_p, C.POINTER(LpcmInput), C.POINTER(RenderArgs)]
+        L.iamf_hip_batch_render_lpcm_range.argtypes = [C.c_void_p, C.POINTER(LpcmInput), C.POINTER(RenderArgs), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_resampler_destroy.argtypes = [C.c_void_p]
@@ -205,6 +214,8 @@ def lib():
         L.iamf_hip_dmx_coefficients.restype = None
         L.iamf_hip_route_instances.argtypes = [C.POINTER(RouteRow), C.c_int]
         L.iamf_hip_route_tally.argtypes = [C.POINTER(RouteRow), C.c_int, C.c_int]
+        L.iamf_hip_route_instances_ext.argtypes = [C.POINTER(RouteRow), C.c_int]
+        L.iamf_hip_route_tally_ext.argtypes = [C.POINTER(RouteRow), C.c_int, C.c_int]
         L.iamf_hip_shard_split.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.iamf_hip_shard_create.argtypes = [C.POINTER(BatchConfig), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_shard_destroy.argtypes = [C.c_void_p]
@@ -297,6 +308,24 @@ def route_reset():
     lib().iamf_hip_route_tally(None, 0, 1)
 
 
+def route_instances_ext():
+    """iamf_hip_route_instances_ext: the instances of the extension table, as route_instances lists the others; needs no GPU"""
+    L = lib()
+    n = L.iamf_hip_route_instances_ext(None, 0)
+    rows = (RouteRow * max(n, 1))()
+    n = min(n, L.iamf_hip_route_instances_ext(rows, n))
+    return [(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k) for r in rows[:n]]
+
+
+def route_tally_ext(reset=True):
+    """iamf_hip_route_tally_ext: {(family name, variant, m, c, k): launches} of the extension table since its last reset"""
+    L = lib()
+    cap = L.iamf_hip_route_instances_ext(None, 0) + 1
+    rows = (RouteRow * cap)()
+    n = L.iamf_hip_route_tally_ext(rows, cap, 1 if reset else 0)
+    return {(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k): r.launches for r in rows[:min(n, cap)]}
+
+
 FANOUT_MAX = 4   # IAMF_HIP_FANOUT_MAX
 
 
@@ -316,6 +345,48 @@ def render_fanout(batches, d_in, in_stream_stride, in_frame_stride, n_frames, d_
     if r < 0:
         raise IamfHipError(r, "iamf_hip_batch_render_fanout")
     return list(emitted[:n]), fused.value
+
+
+def render_fanout_range(batches, d_in, in_stream_stride, in_frame_stride, n_frames, d_pcms, pcm_strides, stream0, n_streams,
+                        stream=None):
+    """iamf_hip_batch_render_fanout_range: render_fanout for the streams [stream0, stream0 + n_streams) of every member.
+    Returns (n_emitted per member, n_fused)."""
+    n = len(batches)
+    if len(d_pcms) != n or len(pcm_strides) != n:
+        raise ValueError("render_fanout_range: one PCM buffer and one stride per batch")
+    hs = (C.c_void_p * n)(*[b.h for b in batches])
+    pcms = (C.c_void_p * n)(*d_pcms)
+    strides = (C.c_int64 * n)(*pcm_strides)
+    emitted = (C.c_int32 * max(n, 1))()
+    fused = C.c_int32(0)
+    r = lib().iamf_hip_batch_render_fanout_range(hs, n, d_in, in_stream_stride, in_frame_stride, n_frames, pcms, strides, stream,
+                                                 emitted, C.byref(fused), stream0, n_streams)
+    if r < 0:
+        raise IamfHipError(r, "iamf_hip_batch_render_fanout_range")
+    return list(emitted[:n]), fused.value
+
+
+def render_fanout_lpcm(batches, lpcm_input, n_frames, d_pcms, pcm_strides, stream=None, n_samples=0, stream0=0, n_streams=None,
+                       report=None):
+    """iamf_hip_batch_render_fanout_lpcm: one element as LPCM packets (LpcmInput) rendered into every Batch of `batches`, the
+    packets read once for the members that can share them; n_streams None = every stream of the first batch; report: a
+    FanoutReport to be written instead of a fresh one (a refused call leaves it alone).  Returns (n_emitted per member,
+    (n_fused, input_fused, n_unpacks))."""
+    n = len(batches)
+    if len(d_pcms) != n or len(pcm_strides) != n:
+        raise ValueError("render_fanout_lpcm: one PCM buffer and one stride per batch")
+    if n_streams is None:
+        n_streams = batches[0].cfg.n_streams if n else 1
+    hs = (C.c_void_p * n)(*[b.h for b in batches])
+    pcms = (C.c_void_p * n)(*d_pcms)
+    strides = (C.c_int64 * n)(*pcm_strides)
+    emitted = (C.c_int32 * max(n, 1))()
+    rep = FanoutReport() if report is None else report
+    r = lib().iamf_hip_batch_render_fanout_lpcm(hs, n, C.byref(lpcm_input), n_frames, n_samples, pcms, strides, stream, stream0,
+                                                n_streams, emitted, C.byref(rep))
+    if r < 0:
+        raise IamfHipError(r, "iamf_hip_batch_render_fanout_lpcm")
+    return list(emitted[:n]), (rep.n_fused, rep.input_fused, rep.n_unpacks)
 
 
 def layout_channels(out_id):
@@ -406,6 +477,12 @@ class Batch:
         r = lib().iamf_hip_batch_render_lpcm(self.h, C.byref(lpcm_input), C.byref(args))
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_lpcm")
+        return r
+
+    def render_lpcm_range(self, lpcm_input, args, stream0, n_streams):
+        r = lib().iamf_hip_batch_render_lpcm_range(self.h, C.byref(lpcm_input), C.byref(args), stream0, n_streams)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_lpcm_range")
         return r
 
     def render_range(self, args, stream0, n_streams):

@@ -364,6 +364,15 @@ int iamf_hip_batch_render_fanout(iamf_hip_batch *const *batches, int32_t n_batch
                                  int64_t in_stream_stride, int64_t in_frame_stride, int32_t n_frames, void *const *d_pcm,
                                  const int64_t *pcm_stream_stride_bytes, void *stream, int32_t *n_emitted /* host, [n_batches] */,
                                  int32_t *n_fused /* host, one int, may be NULL */);
+/* ... for the streams [stream0, stream0 + n_streams) of every member only: iamf_hip_batch_render_range per member.  The
+ * streams of the range must stand at one position in every member and be unflushed (IAMF_HIP_ERR_INVALID_STATE); a member
+ * of kind FIR with a proper sub-range is IAMF_HIP_ERR_UNIMPLEMENTED, as for the single call; stream0 < 0, n_streams <= 0
+ * (checked without a device) or a range outside the members IAMF_HIP_ERR_BAD_ARG.  Buffers and strides are still indexed
+ * by the stream's number in the batch; PCM rows outside the range are not written. */
+int iamf_hip_batch_render_fanout_range(iamf_hip_batch *const *batches, int32_t n_batches, const float *d_in,
+                                       int64_t in_stream_stride, int64_t in_frame_stride, int32_t n_frames, void *const *d_pcm,
+                                       const int64_t *pcm_stream_stride_bytes, void *stream, int32_t *n_emitted /* host, [n_batches] */,
+                                       int32_t *n_fused /* host, one int, may be NULL */, int32_t stream0, int32_t n_streams);
 
 /* ------------------------------------------------------------------------------------------
  * Sample-rate converter for a batch of streams (the decoder's speexdsp-derived resampler at
@@ -634,6 +643,42 @@ int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in,
 int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
                                      int32_t stream0, int32_t n_streams);
 
+/* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
+ * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
+ *
+ * Meaning: for every j the call leaves batches[j] and d_pcm[j] exactly as
+ *   n_emitted[j] = iamf_hip_batch_render_lpcm_range(batches[j], in, &args_j, stream0, n_streams)
+ * with args_j = {n_frames, n_samples, d_pcm[j], pcm_stream_stride_bytes[j], stream} would, called for j = 0 .. in turn: bit
+ * for bit, for every packet form (16 / 24 / 32 bit, either byte order, coupled sub-streams), every PCM format, gains,
+ * threshold, limiter on or off.  in->first_sample and n_samples follow the single call's rules.  This call, the f32
+ * fan-out and the single-batch calls may be mixed freely on the same batches.
+ *
+ * What runs is decided from what the call can observe, in this order:
+ *   1. A member is packet-fusable when the packets have the form the single call fuses (see above), the member's single
+ *      call would run the packet-fed kernel, the element has 4, 9 or 16 channels, and the member is one the f32 fan-out
+ *      would fuse (no fixed PCM channel stride).  If at least two members are packet-fusable they share one launch that
+ *      reads the packets once: 2 * M + sum of the members' output bytes per sample-frame instead of 2 * M per member.
+ *   2. A remaining member whose single call runs the packet-fed kernel gets that call.
+ *   3. All other members need f32: the range's packets are unpacked ONCE (iamf_hip_lpcm_unpack), into the buffer of the
+ *      first such member, and those members go through iamf_hip_batch_render_fanout_range on it — so 24-bit packets and
+ *      coupled 5.1 / 7.1 / 7.1.4 elements get the f32 fan-out's saving and one unpack pass instead of one per member.
+ * *report (may be NULL) says what ran.
+ *
+ * Errors: those of iamf_hip_batch_render_fanout_range plus those of iamf_hip_batch_render_lpcm_range.  Every argument and
+ * state check runs before the first launch; a refused call changes no member and writes neither n_emitted nor *report.
+ * The count, NULL and n_streams <= 0 checks need no device. */
+typedef struct iamf_hip_fanout_report {
+  int32_t n_fused;      /* members the shared launch rendered: 0 or 2..IAMF_HIP_FANOUT_MAX (the packet launch's where both
+                           a packet launch and an f32 launch ran) */
+  int32_t input_fused;  /* 1: that launch read the packets itself; 0: it read f32 (or there was none) */
+  int32_t n_unpacks;    /* passes of iamf_hip_lpcm_unpack over the range's packets queued by this call: 0 or 1 */
+  int32_t reserved;
+} iamf_hip_fanout_report;
+int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_batches, const iamf_hip_lpcm_input *in,
+                                      int32_t n_frames, int32_t n_samples, void *const *d_pcm,
+                                      const int64_t *pcm_stream_stride_bytes, void *stream, int32_t stream0, int32_t n_streams,
+                                      int32_t *n_emitted /* host, [n_batches] */, iamf_hip_fanout_report *report /* may be NULL */);
+
 /* Host -> device by a kernel that reads pinned host memory (hipHostMalloc) over PCIe, 16 bytes per lane: the bytes of a
  * hipMemcpyAsync without leaving the compute queue, for callers that put a small upload between kernels (a pinned
  * hipMemcpyAsync costs ~9 us per call and the hand-over between copy engine and compute queue ~12 us each way on
@@ -666,6 +711,7 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *     WIDE4, WIDE4_MIX, WIDE4_LFE          variant 1 = MFMA projection, m, c
  *     LPCM                 variant 1 = early per-channel prefetch, 0 = late; m, c
  *     FANOUT               m, k = members of the fused launch
+ *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
  *     FIR_FUSED            variant = stage (3 FFT, 2 split-f16 MFMA, 1 f32 MFMA), m
  *     RS_PLAIN             resample_kernel
@@ -690,6 +736,7 @@ enum {
   IAMF_HIP_ROUTE_FANOUT = 12,
   IAMF_HIP_ROUTE_FIR_SPLIT = 13,
   IAMF_HIP_ROUTE_FIR_FUSED = 14,
+  IAMF_HIP_ROUTE_FANOUT_LPCM = 15,   /* extension table only */
   IAMF_HIP_ROUTE_RS_PLAIN = 20,
   IAMF_HIP_ROUTE_RS_TILE = 21,
   IAMF_HIP_ROUTE_RS_BLOCK = 22,
@@ -706,6 +753,11 @@ int iamf_hip_route_instances(iamf_hip_route_row *rows, int cap);
 /* The instances launched since the last reset, with their counts, in the listing's order; reset != 0 zeroes the counters
  * as it reads them.  Writes min(cap, count) rows and returns the count (rows NULL, cap 0, reset 1: just reset). */
 int iamf_hip_route_tally(iamf_hip_route_row *rows, int cap, int reset);
+/* The extension table: kernel instances added after the listing above was pinned by its callers (FANOUT_LPCM).  The same
+ * row type and the same semantics, rows and counters of its own: a launch of one of these instances shows in
+ * iamf_hip_route_tally_ext only, never as a NONE row of iamf_hip_route_tally. */
+int iamf_hip_route_instances_ext(iamf_hip_route_row *rows, int cap);
+int iamf_hip_route_tally_ext(iamf_hip_route_row *rows, int cap, int reset);
 
 /* ------------------------------------------------------------------------------------------
  * A group of decoder handles: callers of the reference API get the batch renderer's throughput.
