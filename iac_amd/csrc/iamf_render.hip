@@ -57,7 +57,6 @@ namespace {
 #include "render_fast.hpp"
 #include "render_fir_launch.hpp"
 #include "render_fanout.hpp"
-#include "render_fanout_lp.hpp"
 #include "render_generic.hpp"
 #include "render_nolim.hpp"
 #include "render_wide.hpp"
@@ -1225,6 +1224,62 @@ int iamf_hip_batch_render(iamf_hip_batch *b, const float *d_in, int64_t in_strea
 // never holds (a call has at most IAMF_HIP_FANOUT_MAX members); it is where a count that stops winning would be cut.
 static const int kFanFuseMax = IAMF_HIP_FANOUT_MAX;
 
+// ---- what iamf_hip_batch_render_fanout* and iamf_hip_batch_render_fanout_lpcm check alike.  Each entry calls these in its
+//      own order (which check answers a bad call first is part of the ABI); none of them needs a device. ----
+
+// every member and every member's buffer given, no member given twice (pointers are compared, no member is looked at)
+static bool fan_members_distinct(iamf_hip_batch *const *batches, void *const *d_pcm, int n_batches) {
+  for (int j = 0; j < n_batches; ++j) {
+    if (!batches[j] || !d_pcm[j]) return false;
+    for (int i = 0; i < j; ++i)
+      if (batches[i] == batches[j]) return false;
+  }
+  return true;
+}
+
+// member b against the first one: the same streams, frame size, element and input channels, and nothing that needs
+// iamf_hip_batch_render_ex
+static bool fan_member_like(const iamf_hip_batch *b, const iamf_hip_batch *b0) {
+  return b->cfg.n_streams == b0->cfg.n_streams && b->cfg.frame_size == b0->cfg.frame_size && b->m == b0->m &&
+         (b->d_pre ? b->pre_l : b->m) == (b0->d_pre ? b0->pre_l : b0->m) && !(b->has2 || b->dmx || b->demix);
+}
+
+// state: the range at one position in every member, unflushed; the HRTF stage's history is per batch, not per stream, so
+// a proper sub-range of an HRTF batch is not built (as the single call)
+static int fan_state_check(iamf_hip_batch *const *batches, int n_batches, int stream0, int n_streams) {
+  const iamf_hip_batch *b0 = batches[0];
+  for (int j = 0; j < n_batches; ++j) {
+    const iamf_hip_batch *b = batches[j];
+    for (int i = stream0; i < stream0 + n_streams; ++i)
+      if (b->spos[(size_t)i] != b0->spos[(size_t)stream0] || b->sflushed[(size_t)i]) return IAMF_HIP_ERR_INVALID_STATE;
+  }
+  if (stream0 != 0 || n_streams != b0->cfg.n_streams)
+    for (int j = 0; j < n_batches; ++j)
+      if (batches[j]->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
+  return IAMF_HIP_OK;
+}
+
+// what differs between the renditions of one fused launch, from a member's prepared call
+static FanMember fan_member_of(const RenderParams &p) {
+  FanMember mb;
+  mb.pcm = p.pcm;
+  mb.pcm_stream_stride = p.pcm_stream_stride;
+  mb.matrix = p.matrix;
+  mb.gains = p.gains;
+  mb.ctab = p.ctab;
+  mb.lim = p.lim;
+  mb.ring_y = p.ring_y;
+  mb.ring_pm = p.ring_pm;
+  mb.src_feed = p.src_feed;
+  mb.out_ch = p.out_ch;
+  mb.out_format = p.out_format;
+  mb.loudness_on = p.loudness_on;
+  mb.n_atk = p.n_atk;
+  mb.n_end = p.n_end;
+  mb.thr = p.thr;
+  return mb;
+}
+
 // iamf_hip_batch_render_fanout over the streams [stream0, stream0 + n_streams) of every member; whole: every stream of the
 // members, whatever their count (the range arguments are not looked at).  n_samples: iamf_hip_render_args::n_samples of
 // every member's call (0 for the public f32 entries).
@@ -1236,23 +1291,15 @@ static int fanout_range_impl(iamf_hip_batch *const *batches, int32_t n_batches, 
   if (n_batches < 1 || n_batches > IAMF_HIP_FANOUT_MAX) return IAMF_HIP_ERR_BAD_ARG;
   if (!batches || !d_in || !d_pcm || !pcm_stream_stride_bytes || !n_emitted) return IAMF_HIP_ERR_BAD_ARG;
   if (!whole && (stream0 < 0 || n_streams <= 0)) return IAMF_HIP_ERR_BAD_ARG;
-  for (int j = 0; j < n_batches; ++j) {
-    if (!batches[j] || !d_pcm[j]) return IAMF_HIP_ERR_BAD_ARG;
-    for (int i = 0; i < j; ++i)
-      if (batches[i] == batches[j]) return IAMF_HIP_ERR_BAD_ARG;
-  }
+  if (!fan_members_distinct(batches, d_pcm, n_batches)) return IAMF_HIP_ERR_BAD_ARG;
   // ---- every member's own checks, before anything is queued: what iamf_hip_batch_render would refuse ----
   iamf_hip_render_args args[IAMF_HIP_FANOUT_MAX];
   int64_t total = 0;
   const iamf_hip_batch *b0 = batches[0];
-  const int ns = b0->cfg.n_streams;
-  if (whole) stream0 = 0, n_streams = ns;
+  if (whole) stream0 = 0, n_streams = b0->cfg.n_streams;
   for (int j = 0; j < n_batches; ++j) {
     const iamf_hip_batch *b = batches[j];
-    if (b->cfg.n_streams != b0->cfg.n_streams || b->cfg.frame_size != b0->cfg.frame_size || b->m != b0->m ||
-        (b->d_pre ? b->pre_l : b->m) != (b0->d_pre ? b0->pre_l : b0->m))
-      return IAMF_HIP_ERR_BAD_ARG;
-    if (b->has2 || b->dmx || b->demix) return IAMF_HIP_ERR_BAD_ARG;  // those need iamf_hip_batch_render_ex
+    if (!fan_member_like(b, b0)) return IAMF_HIP_ERR_BAD_ARG;
     iamf_hip_render_args &a = args[j];
     memset(&a, 0, sizeof(a));
     a.d_in = d_in;
@@ -1273,16 +1320,10 @@ static int fanout_range_impl(iamf_hip_batch *const *batches, int32_t n_batches, 
     for (int j = 0; j < n_batches; ++j) n_emitted[j] = 0;
     return IAMF_HIP_OK;
   }
-  for (int j = 0; j < n_batches; ++j) {
-    const iamf_hip_batch *b = batches[j];
-    if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
-    for (int i = stream0; i < stream0 + n_streams; ++i)
-      if (b->spos[(size_t)i] != b0->spos[(size_t)stream0] || b->sflushed[(size_t)i]) return IAMF_HIP_ERR_INVALID_STATE;
-  }
-  // the HRTF stage's history is per batch, not per stream: a proper sub-range is not built (as the single call)
-  if (stream0 != 0 || n_streams != ns)
-    for (int j = 0; j < n_batches; ++j)
-      if (batches[j]->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
+  for (int j = 0; j < n_batches; ++j)
+    if (!on_batch_device(batches[j])) return IAMF_HIP_ERR_INVALID_STATE;   // (the same answer as a member out of position)
+  const int state = fan_state_check(batches, n_batches, stream0, n_streams);
+  if (state != IAMF_HIP_OK) return state;
   if (n_fused) *n_fused = 0;
   for (int j = 0; j < n_batches; ++j) n_emitted[j] = 0;
 
@@ -1323,22 +1364,7 @@ static int fanout_range_impl(iamf_hip_batch *const *batches, int32_t n_batches, 
         fp.stream0 = stream0;
         fp.n_launch = n_streams;
       }
-      FanMember &mb = fp.mem[n++];
-      mb.pcm = p.pcm;
-      mb.pcm_stream_stride = p.pcm_stream_stride;
-      mb.matrix = p.matrix;
-      mb.gains = p.gains;
-      mb.ctab = p.ctab;
-      mb.lim = p.lim;
-      mb.ring_y = p.ring_y;
-      mb.ring_pm = p.ring_pm;
-      mb.src_feed = p.src_feed;
-      mb.out_ch = p.out_ch;
-      mb.out_format = p.out_format;
-      mb.loudness_on = p.loudness_on;
-      mb.n_atk = p.n_atk;
-      mb.n_end = p.n_end;
-      mb.thr = p.thr;
+      fp.mem[n++] = fan_member_of(p);
     }
     if (!iamf_hip_fanout_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
     HIPCHK(hipGetLastError());
@@ -1376,8 +1402,8 @@ int iamf_hip_batch_render_fanout_range(iamf_hip_batch *const *batches, int32_t n
                            stream, n_emitted, n_fused, false, stream0, n_streams);
 }
 
-// How many members one launch of render_fanout_lp_kernel takes for a range of `workgroups` streams: a (K, size) that does
-// not beat K single packet-fed calls by more than the spread of two series of those calls is not fused
+// How many members one launch of render_fanout_kernel<.., LP> takes for a range of `workgroups` streams: a (K, size) that
+// does not beat K single packet-fed calls by more than the spread of two series of those calls is not fused
 // (tools/fanout_lpcm_rate.py).  The rule may look at K and at the number of workgroups only.
 static int fan_lp_fuse_max(int workgroups) {
   (void)workgroups;
@@ -1392,21 +1418,13 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
   if (n_batches < 1 || n_batches > IAMF_HIP_FANOUT_MAX) return IAMF_HIP_ERR_BAD_ARG;
   if (!batches || !in || !in->d_raw || !d_pcm || !pcm_stream_stride_bytes || !n_emitted || n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
   if (stream0 < 0 || n_streams <= 0) return IAMF_HIP_ERR_BAD_ARG;
-  for (int j = 0; j < n_batches; ++j) {
-    if (!batches[j] || !d_pcm[j]) return IAMF_HIP_ERR_BAD_ARG;
-    for (int i = 0; i < j; ++i)
-      if (batches[i] == batches[j]) return IAMF_HIP_ERR_BAD_ARG;
-  }
+  if (!fan_members_distinct(batches, d_pcm, n_batches)) return IAMF_HIP_ERR_BAD_ARG;
   // ---- the members against each other and the range (as the f32 entry), the device (as the single LPCM call) ----
   iamf_hip_batch *b0 = batches[0];
-  const int ns = b0->cfg.n_streams, ch = b0->d_pre ? b0->pre_l : b0->m;
-  for (int j = 0; j < n_batches; ++j) {
-    const iamf_hip_batch *b = batches[j];
-    if (b->cfg.n_streams != ns || b->cfg.frame_size != b0->cfg.frame_size || b->m != b0->m || (b->d_pre ? b->pre_l : b->m) != ch)
-      return IAMF_HIP_ERR_BAD_ARG;
-    if (b->has2 || b->dmx || b->demix) return IAMF_HIP_ERR_BAD_ARG;  // those need iamf_hip_batch_render_ex
-  }
-  if (stream0 + n_streams > ns) return IAMF_HIP_ERR_BAD_ARG;
+  const int ch = b0->d_pre ? b0->pre_l : b0->m;
+  for (int j = 0; j < n_batches; ++j)
+    if (!fan_member_like(batches[j], b0)) return IAMF_HIP_ERR_BAD_ARG;
+  if (stream0 + n_streams > b0->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
   for (int j = 0; j < n_batches; ++j)
     if (!on_batch_device(batches[j])) return IAMF_HIP_ERR_INVALID_STATE;
   iamf_hip_fanout_report rep;
@@ -1438,14 +1456,8 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
     total = tj;
   }
   // ---- state: the range at one position in every member, unflushed; no proper sub-range of an HRTF batch ----
-  for (int j = 0; j < n_batches; ++j) {
-    const iamf_hip_batch *b = batches[j];
-    for (int i = stream0; i < stream0 + n_streams; ++i)
-      if (b->spos[(size_t)i] != b0->spos[(size_t)stream0] || b->sflushed[(size_t)i]) return IAMF_HIP_ERR_INVALID_STATE;
-  }
-  if (stream0 != 0 || n_streams != ns)
-    for (int j = 0; j < n_batches; ++j)
-      if (batches[j]->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
+  const int state = fan_state_check(batches, n_batches, stream0, n_streams);
+  if (state != IAMF_HIP_OK) return state;
 
   // ---- what each member runs: 2 = the shared packet-fed launch, 1 = its single packet-fed call, 0 = f32 ----
   PreparedCall pcs[IAMF_HIP_FANOUT_MAX];
@@ -1496,22 +1508,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
         fp.stream0 = p.stream0;
         fp.n_launch = p.n_launch;
       }
-      FanMember &mb = fp.mem[n++];
-      mb.pcm = p.pcm;
-      mb.pcm_stream_stride = p.pcm_stream_stride;
-      mb.matrix = p.matrix;
-      mb.gains = p.gains;
-      mb.ctab = p.ctab;
-      mb.lim = p.lim;
-      mb.ring_y = p.ring_y;
-      mb.ring_pm = p.ring_pm;
-      mb.src_feed = p.src_feed;
-      mb.out_ch = p.out_ch;
-      mb.out_format = p.out_format;
-      mb.loudness_on = p.loudness_on;
-      mb.n_atk = p.n_atk;
-      mb.n_end = p.n_end;
-      mb.thr = p.thr;
+      fp.mem[n++] = fan_member_of(p);
     }
     if (!iamf_hip_fanout_lp_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
     HIPCHK(hipGetLastError());

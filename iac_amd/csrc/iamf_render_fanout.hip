@@ -1,6 +1,7 @@
-// iamf_render_fanout.hip — render_fanout_kernel<M, K> (render_fanout.hpp): one element rendered into K = 2..4 member
-// batches of one or two output channels each with ONE pass over the input, in a translation unit of its own (compiled
-// beside iamf_render.hip; render_fast_kernel is not instantiated here and its code generation does not move).
+// iamf_render_fanout.hip — render_fanout_kernel<M, K, false> (render_fanout.hpp), the f32-fed form: one element rendered
+// into K = 2..4 member batches of one or two output channels each with ONE pass over the input, in a translation unit of
+// its own (compiled beside iamf_render.hip and iamf_render_fanout_lp.hip, which instantiates the packet-fed form;
+// render_fast_kernel is not instantiated here and its code generation does not move).
 // M: ambisonics of order 1..3 (4, 9, 16 channels) and 5.1 / 7.1 / 7.1.4 (6, 8, 12).  Entry: iamf_hip_batch_render_fanout
 // (iamf_render.hip), which renders every member this kernel does not take exactly as iamf_hip_batch_render does.
 #include <hip/hip_runtime.h>
@@ -34,7 +35,7 @@ static_assert(FanK::has(2) && FanK::has(kFanMax) && !FanK::has(kFanMax + 1), "Fa
 template <int M, int K>
 void launch_fan_mk(const FanParams &p, hipStream_t st) {
   constexpr size_t lds = sizeof(float) * (size_t)fan_lds_floats(K, M);
-  launch_big_lds<&render_fanout_kernel<M, K>, (int)lds>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
+  launch_big_lds<&render_fanout_kernel<M, K, false>, (int)lds>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
-// iamf_render_fanout_lp.hip — render_fanout_lp_kernel<M, K> (render_fanout_lp.hpp): one mono-coded ambisonics element,
-// held as 16-bit LPCM packets, rendered into K = 2..4 member batches of one or two output channels each with ONE pass over
-// the packets, in a translation unit of its own (compiled beside iamf_render_fanout.hip and iamf_render_lpcm.hip; neither
-// render_fanout_kernel nor render_fast_kernel is instantiated here and their code generation does not move).
+// iamf_render_fanout_lp.hip — render_fanout_kernel<M, K, true> (render_fanout.hpp), the packet-fed form: one mono-coded
+// ambisonics element, held as 16-bit LPCM packets, rendered into K = 2..4 member batches of one or two output channels each
+// with ONE pass over the packets, in a translation unit of its own (compiled beside iamf_render_fanout.hip, which
+// instantiates the f32-fed form, and iamf_render_lpcm.hip; render_fast_kernel is not instantiated here and its code
+// generation does not move).
 // M: ambisonics of order 1..3 (4, 9, 16 channels), the element sizes both the packet-fed kernel and the fan-out take.
 // Entry: iamf_hip_batch_render_fanout_lpcm (iamf_render.hip), which renders every member this kernel does not take
 // exactly as iamf_hip_batch_render_lpcm does.
@@ -26,9 +27,8 @@ namespace {
 #include "render_fir_fft.hpp"
 #include "render_fast.hpp"
 #include "render_fanout.hpp"
-#include "render_fanout_lp.hpp"
 
-// LDS per workgroup is the f32 kernel's (fan_lds_floats): two, two, one workgroup per CU for K = 2 / 3 / 4
+// LDS per workgroup is the f32-fed form's (fan_lds_floats): two, two, one workgroup per CU for K = 2 / 3 / 4
 static_assert(FanLpK::has(2) && FanLpK::has(kFanMax) && !FanLpK::has(kFanMax + 1), "FanLpK is 2..kFanMax");
 static_assert(!FanLpM::has(17), "one run offset per channel: at most sixteen");
 
@@ -36,7 +36,7 @@ template <int M, int K>
 void launch_fan_lp_mk(const FanLpParams &p, hipStream_t st) {
   static_assert(LpcmM::has(M) && FanM::has(M) && FanK::has(K), "FanLpM x FanLpK lies inside LpcmM x FanM x FanK");
   constexpr size_t lds = sizeof(float) * (size_t)fan_lds_floats(K, M);
-  launch_big_lds<&render_fanout_lp_kernel<M, K>, (int)lds>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
+  launch_big_lds<&render_fanout_kernel<M, K, true>, (int)lds>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
 }
 
 }  // namespace

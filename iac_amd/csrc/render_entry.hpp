@@ -15,7 +15,7 @@ IAMF_INTERNAL int iamf_hip_wide4_mix_launch(const void *params, int m, hipStream
 IAMF_INTERNAL int iamf_hip_wide4_lfe_launch(const void *params, int m, hipStream_t st);
 // iamf_render_fanout.hip; params: a FanParams whose first k members are set
 IAMF_INTERNAL int iamf_hip_fanout_launch(const void *params, int m, int k, hipStream_t st);
-// iamf_render_fanout_lp.hip; params: a FanLpParams (render_fanout_lp.hpp) whose first k members are set
+// iamf_render_fanout_lp.hip; params: a FanLpParams whose first k members are set
 IAMF_INTERNAL int iamf_hip_fanout_lp_launch(const void *params, int m, int k, hipStream_t st);
 // iamf_render_lpcm.hip; early: Route::variant of Family::Lpcm
 IAMF_INTERNAL int iamf_hip_fast_lpcm_launch(const void *params, int m, int early, hipStream_t st);

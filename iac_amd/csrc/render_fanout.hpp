@@ -1,25 +1,47 @@
-// render_fanout.hpp — one element, several renditions, one pass over the input: render_fanout_kernel<M, K> renders the
-// M-channel element of a stream into K member batches (iamf_hip_batch_render_fanout, iamf_render.hip), each with its own
-// matrix, gains, limiter and PCM format, and reads the element ONCE.  Every workload of the plain kernel
-// (render_fast.hpp) is bound by the 4 * M bytes per sample-frame it reads; K renditions of one element cost
-// 4 * M + sum(out bytes) here instead of K * 4 * M + sum(out bytes).
+// render_fanout.hpp — one element, several renditions, one pass over the input: render_fanout_kernel<M, K, LP> renders the
+// M-channel element of a stream into K member batches, each with its own matrix, gains, limiter and PCM format, and reads
+// the element ONCE.  ONE kernel body with two input paths, chosen at compile time as in render_fast_kernel<.., LP>:
+//   LP = false  planar f32 element PCM (FanParams; iamf_hip_batch_render_fanout, iamf_render.hip).  Every workload of the
+//               plain kernel (render_fast.hpp) is bound by the 4 * M bytes per sample-frame it reads; K renditions of one
+//               element cost 4 * M + sum(out bytes) here instead of K * 4 * M + sum(out bytes).
+//   LP = true   the 16-bit LPCM packets of a mono-coded ambisonics element, read by the kernel itself (FanLpParams;
+//               iamf_hip_batch_render_fanout_lpcm): 2 * M + sum(out bytes) instead of K * 2 * M + sum(out bytes) for K
+//               calls of render_fast_kernel<.., LP>, or 2 * M + 8 * M + sum(out bytes) for an unpack pass and LP = false.
+// The two differ in six places, each an `if constexpr (LP)` below: the staged weights' scale, the stream's base pointer,
+// the per-channel input registers, load_one, the fill of lanes past the end of the call, and where channel m is consumed.
+// Everything else — member state, rings, window maximum, limiter rounds, PCM stores, persistence — is written once.
 //
 // The geometry is render_fast_kernel's — one workgroup of 256 lanes per stream, 1024-sample chunks, four consecutive
 // samples per lane — so the persisted state (LimState, ring_y, ring_pm: the generic kernel's format) is read and written
-// by the same lane <-> sample mapping, and a batch may go through this kernel in one call and through the plain one in
-// the next.  Per chunk:
-//   1. the element's channels are consumed one by one (16-byte non-temporal buffer loads, one resource per stream); while
+// by the same lane <-> sample mapping, and a batch may go through either form of this kernel, render_fast_kernel with or
+// without LP and the generic kernel in any order.  Per chunk:
+//   1. the element's channels are consumed one by one (non-temporal buffer loads, one resource per stream); while
 //      channel m is live every output slot of every member adds its product — ascending channel order, one rounding per
 //      product and per sum: the plain kernel's and the reference's arithmetic — and channel m of the NEXT chunk is
-//      requested as soon as channel m has been consumed, so the loads fly under everything below;
+//      requested as soon as channel m has been consumed, so the loads fly under everything below.  When there is no next
+//      chunk the requests go through a resource of zero records, which answers every load with zeros; lanes past the end
+//      of the call hold zeros;
 //   2. member by member: gains in the reference's order, max |y|, the member's LDS rings, the 240-sample window
 //      maximum, the limiter gains (hypothesis, workgroup vote, limiter_wave for the blocks that trigger), delayed
 //      samples * gain -> the member's PCM in the member's format.
-// A member has one or two output channels (a run-time property: the instantiations are <M, K> only; a mono member's
+// The input path of LP = false: one 16-byte load per channel and lane, a float4 per channel.  Of LP = true
+// (render_fast_kernel<.., LP>'s, render_fast.hpp):
+//   - the resource lies over the stream's packet region, the lane's byte offset is in one register for all channels and
+//     the channel's run offset (lpcm_off[m]) is the load's scalar offset: one 8-byte load per channel and lane;
+//   - two dwords are kept per channel (four 16-bit samples as they lie in memory) instead of a float4 — half the live
+//     input registers — and (float)(int16) happens where channel m is consumed;
+//   - the decoder's "/ 32768" is folded into every slot's staged weights: (w * 2^-15) * (float)s has the bits of
+//     w * (s * 2^-15) for the matrices the host admits (iamf_hip_batch::lp_scale_ok: a power of two commutes with
+//     rounding as long as neither the scaled weight nor a product leaves the normal range), so each product and each sum
+//     is rounded once, in ascending channel order: the reference's arithmetic.
+// A member has one or two output channels (a run-time property: the instantiations are <M, K, LP> only; a mono member's
 // second slot carries zero weights).  The rings and the staged limiter-table window / head are per member; the array of
 // window maxima the limiter walk reads — and overwrites, block by block, with its gains — is transient and serves the
 // members in turn.  Of max |y| only what the next call needs is kept (the last 256 samples; the window maximum reads the
 // per-16 suffix and block maxima): 25.7 KB per member, so that THREE members still run two workgroups per CU.
+//
+// The parameter block is passed by value and read in place (p.x): no reference or pointer to `p` as a whole is taken and
+// it is passed to no function, so that its fields stay scalar loads from the kernel-argument segment where they are used.
 #pragma once
 
 constexpr int kFanMax = IAMF_HIP_FANOUT_MAX;
@@ -53,6 +75,19 @@ struct FanParams {          // what the renditions share, then the members
   FanMember mem[kFanMax];
 };
 
+struct FanLpParams {        // LP: the packets, what the renditions share, then the members
+  const uint8_t *lpcm;      // packet rows (device): stream s, frame f at lpcm + s * stream stride + f * frame stride
+  int64_t lpcm_stream_stride;  // bytes, a multiple of 8
+  int64_t lpcm_frame_stride;   // bytes, a multiple of 8
+  int32_t lpcm_off[16];     // byte offset of channel m's run of little-endian 16-bit samples in a row, a multiple of 8
+  int64_t pos0;             // samples of each stream consumed before this call (the same for every member)
+  int32_t total;            // samples to process in this call: a multiple of 64
+  int32_t frame_size;
+  int32_t n_streams;        // streams of every member batch (the per-stream arrays' extent)
+  int32_t stream0, n_launch;  // workgroup i takes stream stream0 + i
+  FanMember mem[kFanMax];
+};
+
 // LDS floats of one member: ring_y [2][R], ring_suf [R], ring_bm [2][R/16], pm_tail [kSave], win [kFWin], head [kFWin]
 __host__ __device__ constexpr int fan_member_floats() { return 3 * kFRing + 2 * (kFRing / 16) + kSave + 2 * kFWin; }
 // ... and of a workgroup: the members, arr_p [1024], the 2 * K slots' matrix rows, misc [16]
@@ -60,8 +95,9 @@ __host__ __device__ constexpr int fan_lds_floats(int k, int m) {
   return k * fan_member_floats() + kFChunk + ((2 * k * m + 15) & ~15) + 16;
 }
 
-template <int M, int K>
-__global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(const FanParams p) {
+template <int M, int K, bool LP>
+__global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(const std::conditional_t<LP, FanLpParams, FanParams> p) {
+  static_assert(!LP || M <= 16, "one run offset per channel");
   static_assert(K >= 2 && K <= kFanMax, "two to four members");
   extern __shared__ float lds[];
   constexpr int R = kFRing;
@@ -118,7 +154,10 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
     if (t < 2 * M) {
       const int c = t / M, m = t - c * M;
       const int f = c < oc ? mb.src_feed[c] : -1;
-      mat[2 * j * M + t] = f >= 0 ? mb.matrix[f * M + m] : 0.f;
+      if constexpr (LP)   // the LPCM decoder's "sample / 32768.f" folded into the weight (the host has checked lp_scale_ok)
+        mat[2 * j * M + t] = (f >= 0 ? mb.matrix[f * M + m] : 0.f) * (1.0f / 32768.0f);
+      else
+        mat[2 * j * M + t] = f >= 0 ? mb.matrix[f * M + m] : 0.f;
     }
     const LimState ls = mb.lim[s];
     g_cur[j] = ls.g, gs[j] = ls.gs, ge[j] = ls.ge, n_st[j] = ls.n;
@@ -134,15 +173,19 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
   chain_wave_publish(misc + 12);
 
   const int64_t out_base = p.pos0 > kDelay ? p.pos0 - kDelay : 0;
-  const float *in_s = p.in + (int64_t)s * p.in_stream_stride;
+  const void *in_s;
+  if constexpr (LP)
+    in_s = p.lpcm + (int64_t)s * p.lpcm_stream_stride;
+  else
+    in_s = p.in + (int64_t)s * p.in_stream_stride;
 
-  // ---- the element's input: buffer loads, one resource per stream (render_fast.hpp) ----
-  float4 x[M];
-  const __amdgpu_buffer_rsrc_t rs_in =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(static_cast<const void *>(in_s)), 0, 0x7fffffff, 0x00020000);
+  // ---- the element's input: buffer loads, one resource per stream (render_fast.hpp).  Per channel a float4, or (LP) the
+  //      packets' samples as they lie in memory: four 16-bit samples in two dwords ----
+  using lp_u2 = __attribute__((ext_vector_type(2))) unsigned;
+  std::conditional_t<LP, lp_u2, float4> x[M];
+  const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(in_s), 0, 0x7fffffff, 0x00020000);
   // (zero records: every load through it is answered with zeros — the requests for "the next chunk" when there is none)
-  const __amdgpu_buffer_rsrc_t rs_none =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(static_cast<const void *>(in_s)), 0, 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_none = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(in_s), 0, 0, 0x00020000);
   const bool fr_uni = (fs & (kFChunk - 1)) == 0;   // a chunk lies in ONE frame: workgroup-uniform counters
   int fu = 0, iu = 0;
   auto frame_pos = [&](int kq, int &f, int &i) {
@@ -155,9 +198,15 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
     }
   };
   auto load_one = [&](int m, int f, int i, __amdgpu_buffer_rsrc_t rs) {
-    const int vo = 4 * (f * (int)p.in_frame_stride + i);
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 4 * m * fs, 2 /* nt */);
-    x[m] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+    if constexpr (LP) {
+      const int vo = f * (int)p.lpcm_frame_stride + 2 * i;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, p.lpcm_off[m], 2 /* nt */);
+      x[m] = lp_u2{v[0], v[1]};
+    } else {
+      const int vo = 4 * (f * (int)p.in_frame_stride + i);
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 4 * m * fs, 2 /* nt */);
+      x[m] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
+    }
   };
   {
     const int k = 4 * t;
@@ -168,7 +217,12 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
       for (int m = 0; m < M; ++m) load_one(m, f, i, rs_in);
     } else {
 #pragma unroll
-      for (int m = 0; m < M; ++m) x[m] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int m = 0; m < M; ++m) {
+        if constexpr (LP)
+          x[m] = lp_u2{0u, 0u};
+        else
+          x[m] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
     }
   }
   __syncthreads();
@@ -238,13 +292,21 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
             }
           }
         }
-        // channel m is taken up when channel m - 1 has been added up: the weights of one group of four channels are all
-        // that is live beside the samples and the sums
+        // channel m is taken up — LP: its packets converted — when channel m - 1 has been added up: the weights of one
+        // group of four channels (LP: and ONE converted channel) are all that is live beside the samples and the sums
 #pragma unroll
         for (int c = 0; c < 2 * NS; ++c) asm volatile("" : "+v"(prj[c]));
-        asm volatile("" : "+v"(x[m].x), "+v"(x[m].y), "+v"(x[m].z), "+v"(x[m].w));
-        const f2 xa = f2{x[m].x, x[m].y};
-        const f2 xb = f2{x[m].z, x[m].w};
+        f2 xa, xb;
+        if constexpr (LP) {
+          asm volatile("" : "+v"(x[m].x), "+v"(x[m].y));
+          const unsigned pa = x[m].x, pb = x[m].y;   // (the scale 2^-15 sits in the weights: see where `mat` is filled)
+          xa = f2{(float)(int)(short)(pa & 0xffffu), (float)((int)pa >> 16)};
+          xb = f2{(float)(int)(short)(pb & 0xffffu), (float)((int)pb >> 16)};
+        } else {
+          asm volatile("" : "+v"(x[m].x), "+v"(x[m].y), "+v"(x[m].z), "+v"(x[m].w));
+          xa = f2{x[m].x, x[m].y};
+          xb = f2{x[m].z, x[m].w};
+        }
 #pragma unroll
         for (int c = 0; c < NS; ++c) {
           const float w = kWG ? wg[c][m & 3] : mat[c * M + m];

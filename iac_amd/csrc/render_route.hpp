@@ -44,7 +44,7 @@ using FanK = Ints<2, 3, 4>;
 // render_fast_kernel<M, OC, .., LP>: mono-coded ambisonics elements as LPCM packets
 using LpcmM = Ints<1, 4, 9, 16>;
 using LpcmOC = Ints<1, 2>;
-// render_fanout_lp_kernel<M, K>: the fan-out fed with LPCM packets.  M: what LpcmM and FanM share (mono-coded ambisonics
+// render_fanout_kernel<M, K, LP>: the fan-out fed with LPCM packets.  M: what LpcmM and FanM share (mono-coded ambisonics
 // elements are the only ones whose channels are contiguous 16-bit runs), K within FanK
 using FanLpM = Ints<4, 9, 16>;
 using FanLpK = Ints<2, 3, 4>;

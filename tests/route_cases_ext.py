@@ -13,7 +13,7 @@ FAN_LP_K = [2, 3, 4]
 
 def run_fanout_lpcm(c):
     """a mono-coded ambisonics element as 16-bit LPCM packets into K one- and two-channel batches in one launch
-    (render_fanout_lp_kernel<M, K>); kw: m, k"""
+    (render_fanout_kernel<M, K, LP>); kw: m, k"""
     import torch
     import iac_amd as A
     import lpcm_util as LP

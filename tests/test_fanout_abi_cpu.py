@@ -65,6 +65,23 @@ def test_null_pointers_are_refused_without_a_device():
     assert L.iamf_hip_batch_render_fanout(hs, 1, 0x1000, 0, 0, 1, pcms, st, None, em, None) == BAD_ARG
 
 
+def test_a_member_given_twice_is_refused_without_a_device():
+    """the members are compared as pointers, in member order, before any of them is looked at: with every other argument
+    good the call is refused at the first repeat, whichever members repeat"""
+    L = _lib()
+    pcms = (C.c_void_p * 4)(0x3000, 0x3100, 0x3200, 0x3300)
+    st = (C.c_int64 * 4)(*([1 << 20] * 4))
+    for hs in ((0x2000, 0x2000), (0x2000, 0x2100, 0x2000), (0x2000, 0x2100, 0x2100), (0x2000, 0x2100, 0x2200, 0x2100)):
+        em = (C.c_int32 * 4)(*([-9] * 4))
+        fused = C.c_int32(-7)
+        r = L.iamf_hip_batch_render_fanout((C.c_void_p * len(hs))(*hs), len(hs), 0x1000, 0, 0, 1, pcms, st, None, em, C.byref(fused))
+        assert r == BAD_ARG and fused.value == -7 and list(em) == [-9] * 4, hs
+    # ... and with n_frames == 0 too: the member list is checked before the early return
+    em = (C.c_int32 * 4)(*([-9] * 4))
+    assert L.iamf_hip_batch_render_fanout((C.c_void_p * 2)(0x2000, 0x2000), 2, 0x1000, 0, 0, 0, pcms, st, None, em, None) == BAD_ARG
+    assert list(em) == [-9] * 4
+
+
 def test_python_binding_raises_like_its_neighbours():
     import pytest
 

@@ -93,6 +93,47 @@ def test_an_empty_or_negative_range_is_refused_without_a_device():
         assert call(L, "ok", 2, stream0=-1) == BAD_ARG
 
 
+def _members(L, entry, hs, pcms, n_frames=1):
+    """every argument good but the member list: the handles are fakes that the member-list check compares and never reads"""
+    import iac_amd
+    n = len(hs)
+    st = (C.c_int64 * n)(*([1 << 20] * n))
+    em = (C.c_int32 * n)(*([-9] * n))
+    if entry == "lpcm":
+        li = iac_amd.LpcmInput()
+        li.d_raw = 0x1000
+        rep = iac_amd.FanoutReport(-7, -7, -7, -7)
+        r = L.iamf_hip_batch_render_fanout_lpcm((C.c_void_p * n)(*hs), n, C.byref(li), n_frames, 0, (C.c_void_p * n)(*pcms), st, None,
+                                                0, 4, em, C.byref(rep))
+        assert (rep.n_fused, rep.input_fused, rep.n_unpacks, rep.reserved) == (-7, -7, -7, -7)
+    else:
+        fused = C.c_int32(-7)
+        r = L.iamf_hip_batch_render_fanout_range((C.c_void_p * n)(*hs), n, 0x1000, 0, 0, n_frames, (C.c_void_p * n)(*pcms), st, None,
+                                                 em, C.byref(fused), 0, 4)
+        assert fused.value == -7
+    assert list(em) == [-9] * n
+    return r
+
+
+def test_the_member_list_is_checked_without_a_device():
+    """a NULL member, a NULL member buffer and a member given twice are refused in member order, by pointer comparison
+    alone, before any member is looked at and before the n_frames == 0 early return"""
+    L = _lib()
+    ok = [0x3000, 0x3100, 0x3200, 0x3300]
+    for entry in ("lpcm", "range"):
+        for n_frames in (1, 0):
+            assert _members(L, entry, [None], ok[:1], n_frames) == BAD_ARG
+            assert _members(L, entry, [0x2000, None], ok[:2], n_frames) == BAD_ARG
+            assert _members(L, entry, [0x2000], [None], n_frames) == BAD_ARG
+            assert _members(L, entry, [0x2000, 0x2000], ok[:2], n_frames) == BAD_ARG
+            assert _members(L, entry, [0x2000, 0x2100, 0x2000], ok[:3], n_frames) == BAD_ARG
+            assert _members(L, entry, [0x2000, 0x2100, 0x2100], ok[:3], n_frames) == BAD_ARG
+            assert _members(L, entry, [0x2000, 0x2100, 0x2200, 0x2100], ok, n_frames) == BAD_ARG
+            # the buffer of member 1 is looked at before member 2 is compared with member 0, and the other way round
+            assert _members(L, entry, [0x2000, 0x2100, 0x2000], [0x3000, None, 0x3200], n_frames) == BAD_ARG
+            assert _members(L, entry, [0x2000, 0x2000, 0x2200], [0x3000, 0x3100, None], n_frames) == BAD_ARG
+
+
 def test_python_bindings_raise_like_their_neighbours():
     import pytest
 

@@ -1,5 +1,5 @@
 """iamf_hip_batch_render_fanout_lpcm and iamf_hip_batch_render_fanout_range: one element held as LPCM packets rendered into
-several batches, the packets read once (render_fanout_lp_kernel, iac_amd/csrc/render_fanout_lp.hpp).
+several batches, the packets read once (render_fanout_kernel<M, K, LP>, iac_amd/csrc/render_fanout.hpp).
 
 Expected bytes come from two independent sources and both are asserted: (a) TWIN batches of the same configuration driven
 by K single iamf_hip_batch_render_lpcm_range calls on the same packets; (b) for s16 members the oracle

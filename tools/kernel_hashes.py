@@ -5,6 +5,9 @@ block alone.  Local label numbers (they count functions and blocks in file order
 
     for f in iac_amd/csrc/*.hip; do hipcc $HIPFLAGS --cuda-device-only -S $f -o out/$(basename $f).s; done
     tools/kernel_hashes.py out/*.s > kernels.txt
+
+--anon hashes each body with the kernel's own symbol replaced by a fixed token, so that a kernel that was only renamed
+(a template argument added, two templates folded into one) keeps its hash and can be paired with the other tree's.
 """
 import hashlib
 import re
@@ -14,10 +17,14 @@ BODY = re.compile(r"^\t\.type\t(\S+),@function\n(.*?)^\.Lfunc_end\d+:", re.M | r
 LOCAL = re.compile(r"\.(LBB|Ltmp|Lfunc_begin|Lfunc_end)\d+")
 COMMENT = re.compile(r"\s*;.*$", re.M)
 
+args = sys.argv[1:]
+anon = "--anon" in args
 rows = []
-for path in sys.argv[1:]:
+for path in (a for a in args if a != "--anon"):
     for sym, body in BODY.findall(open(path).read()):
         if ".amdhsa_kernel " + sym + "\n" in body:   # kernels only: device functions have no descriptor
+            if anon:
+                body = body.replace(sym, "@KERNEL@")
             rows.append((sym, hashlib.sha1(LOCAL.sub(r".\1", COMMENT.sub("", body)).encode()).hexdigest()))
 for sym, h in sorted(rows):
     print(h, sym)
