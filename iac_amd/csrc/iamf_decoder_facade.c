@@ -1419,20 +1419,22 @@ static int setup_pipeline(struct IAMF_Decoder *d) {
     const Element *e0 = d->sel_el[0];
     iamf_hip_lpcm_layout *L = &d->lp_layout;
     d->lp_ok = p->nel == 1 && e0->type == AUDIO_ELEMENT_SCENE_BASED && !e0->amb_projection && !d->pre[0].use_dmx && !d->pre[0].use_demix &&
-               !resample && d->sample_size == 16 && d->little_endian && d->limiter_on && d->out_channels <= 2 &&
+               !resample && (d->sample_size == 16 || d->sample_size == 24) && d->little_endian && d->limiter_on && d->out_channels <= 2 &&
                d->pcm_stride == d->out_channels && (d->frame_size & 63) == 0 && e0->nsub > 0 && e0->nsub <= MAX_SUBSTREAMS &&
                (e0->channels == 1 || e0->channels == 4 || e0->channels == 9 || e0->channels == 16) && !getenv("IAMF_HIP_FACADE_UNPACK");
+    /* (16 or 24 bit: sub-stream s at s * frame_size * bytes, a multiple of 8 / of 4 with the frame size one of 64) */
+    const int lp_bytes = d->sample_size == 24 ? 3 : 2;
     memset(L, 0, sizeof(*L));
-    L->sample_bytes = 2;
+    L->sample_bytes = lp_bytes;
     L->little_endian = 1;
     L->channels = e0->channels;
     L->frame_size = (int32_t)d->frame_size;
     for (int c = 0; c < e0->channels && d->lp_ok; ++c) {
       if (e0->amb_map[c] >= e0->nsub) d->lp_ok = 0; /* a channel no sub-stream carries: the f32 form zeroes it */
-      L->src_offset[c] = (int32_t)(e0->amb_map[c] * d->frame_size * 2);
-      L->src_step[c] = 2;
+      L->src_offset[c] = (int32_t)(e0->amb_map[c] * d->frame_size * lp_bytes);
+      L->src_step[c] = lp_bytes;
     }
-    if (d->lp_ok && hipHostMalloc((void **)&d->h_raw, (size_t)e0->nsub * d->frame_size * 2 + 256, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
+    if (d->lp_ok && hipHostMalloc((void **)&d->h_raw, (size_t)e0->nsub * d->frame_size * lp_bytes + 256, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   }
   d->pcm_cap = (size_t)4 * ((size_t)d->info.max_frame_size * d->pcm_stride + d->pcm_extra);
   if (hipHostMalloc(&d->h_pcm, d->pcm_cap, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
@@ -1633,17 +1635,18 @@ static int unpack_element(struct IAMF_Decoder *d, int ei) {
   return ns;
 }
 
-/* element 0's packets as they are -> the pinned raw row (sub-stream s at s * frame_size * 2); unpack_element's checks;
- * returns samples per channel */
+/* element 0's packets as they are -> the pinned raw row (sub-stream s at s * frame_size * sample bytes); unpack_element's
+ * checks; returns samples per channel */
 static int stage_lpcm_row(struct IAMF_Decoder *d) {
   const Element *e = d->sel_el[0];
   const int fs = (int)d->frame_size;
+  const unsigned bps = (unsigned)d->lp_layout.sample_bytes;
   int ns = -1;
   for (int s = 0; s < e->nsub; ++s) {
-    const int n = (int)(d->pkt_len[0][s] / 2u);
+    const int n = (int)(d->pkt_len[0][s] / bps);
     if (ns < 0) ns = n;
     if (n != ns || n > fs) return IAMF_ERR_INVALID_PACKET;
-    memcpy(d->h_raw + (size_t)s * fs * 2, d->pkt[0][s], (size_t)n * 2);
+    memcpy(d->h_raw + (size_t)s * fs * bps, d->pkt[0][s], (size_t)n * bps);
   }
   return ns < 0 ? IAMF_ERR_INVALID_PACKET : ns;
 }
@@ -1854,7 +1857,7 @@ static int render_tu(struct IAMF_Decoder *d, void *pcm) {
     iamf_hip_lpcm_input in;
     memset(&in, 0, sizeof(in));
     in.d_raw = d->h_raw;
-    in.raw_stream_stride = in.raw_frame_stride = (int64_t)d->sel_el[0]->nsub * fs * 2;
+    in.raw_stream_stride = in.raw_frame_stride = (int64_t)d->sel_el[0]->nsub * fs * d->lp_layout.sample_bytes;
     in.first_sample = s0;
     in.layout = d->lp_layout;
     a.d_pcm = d->h_pcm;

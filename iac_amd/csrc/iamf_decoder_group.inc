@@ -609,14 +609,18 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
     }
     GCHK(hipMalloc(&g->d_raw[e], g->raw_stride[e] * (size_t)n) != hipSuccess);
   }
-  /* One mono-coded ambisonics element in 16-bit little-endian LPCM into one or two channels with the limiter on: the
+  /* One mono-coded ambisonics element in 16-bit or 24-bit little-endian LPCM into one or two channels with the limiter on: the
    * headline kernel reads the packets themselves (iamf_hip_batch_render_lpcm_range, fused: no unpacked copy, no unpack
    * launch).  The library decides per call (and falls back to its own unpacker); this only says when asking is worth it. */
-  g->lp_ok = g->nel == 1 && !d0->pre[0].use_dmx && !d0->pre[0].use_demix && !d0->sel_el[0]->amb_projection && d0->sample_size == 16 &&
+  g->lp_ok = g->nel == 1 && !d0->pre[0].use_dmx && !d0->pre[0].use_demix && !d0->sel_el[0]->amb_projection &&
+             (d0->sample_size == 16 || d0->sample_size == 24) &&
              d0->little_endian && d0->limiter_on && d0->out_channels <= 2 && d0->pcm_stride == d0->out_channels &&
              d0->sel_el[0]->type == AUDIO_ELEMENT_SCENE_BASED && (g->fs & 63) == 0 && !d0->rs && !getenv("IAMF_HIP_GROUP_UNPACK");
+  /* (contiguous runs on the form's grid: 8 bytes for 16-bit samples, 4 for 24-bit ones) */
   for (int c = 0; c < g->lay[0].channels && g->lp_ok; ++c)
-    if (g->lay[0].src_step[c] != 2 || g->lay[0].src_offset[c] < 0 || (g->lay[0].src_offset[c] & 7)) g->lp_ok = 0;
+    if (g->lay[0].src_step[c] != g->lay[0].sample_bytes || g->lay[0].src_offset[c] < 0 ||
+        (g->lay[0].src_offset[c] & (g->lay[0].sample_bytes == 3 ? 3 : 7)))
+      g->lp_ok = 0;
   for (int k = 0; k < 3; ++k) GCHK(!(g->cgain[k] = (float *)calloc((size_t)n, sizeof(float))));
   /* upload chunks: at most eight per round, at least eight handles each (an upload call costs ~4 us of host time) */
   g->chunk = (n + 7) / 8 < 8 ? 8 : (n + 7) / 8;

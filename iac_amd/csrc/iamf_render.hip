@@ -62,6 +62,7 @@ namespace {
 #include "render_wide.hpp"
 #include "render_lfe.hpp"
 #include "stream_state.hpp"
+#include "lpcm_form.hpp"
 
 // PCM with a fixed channel stride (the -DSAMSUNG_TV build: iamf_decoder_plane2stride_out with
 // stride = SAMSUNG_SPECIFIC_CHANNELS = 12, IAMF_decoder.c:121-167,3492-3495).  The reference zeroes
@@ -330,6 +331,7 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
   switch (r.family) {
     case Family::Refused: return r.err;
     case Family::Lpcm: launched = iamf_hip_fast_lpcm_launch(&p, m, r.variant, st); break;
+    case Family::Lpcm24: launched = iamf_hip_fast_lpcm24_launch(&p, m, r.variant, st); break;
     case Family::FirSplit: {
       // (1) the FFT stage for every hop of every stream -> y in HBM (overlap-save blocks are independent: one grid); (2)
       // gains, limiter, pack = the two-channel matrix kernel with the identity over y (one "frame" of `total` samples per
@@ -375,7 +377,8 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
   if (!launched) return IAMF_HIP_ERR_INTERNAL;
   HIPCHK(hipGetLastError());
   const RouteKey k = route_key(r, p, m);   // the tally of iamf_hip_route_tally
-  iamf_hip_route_count(k.family, k.variant, k.m, k.c, k.k);
+  if (r.family == Family::Lpcm24) iamf_hip_route_count_table(2, k.family, k.variant, k.m, k.c, k.k);   // its own table
+  else iamf_hip_route_count(k.family, k.variant, k.m, k.c, k.k);
   if (r.family == Family::FirSplit) iamf_hip_route_count(IAMF_HIP_ROUTE_FAST, 0, 2, 2, 0);
   return IAMF_HIP_OK;
 }
@@ -405,6 +408,7 @@ struct LpcmIn {
   const uint8_t *raw;
   int64_t stream_stride, frame_stride;
   int32_t off[16];
+  int32_t bytes;   // per sample: 2 or 3 (lpcm_form.hpp)
 };
 constexpr int kNotFused = INT32_MIN;
 
@@ -574,7 +578,9 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     p.lpcm_stream_stride = lp->stream_stride;
     p.lpcm_frame_stride = lp->frame_stride;
     for (int m = 0; m < 16; ++m) p.lpcm_off[m] = lp->off[m];
-    if (pick_route(p, m_eff).family != Family::Lpcm) return kNotFused;
+    p.lpcm_bytes = lp->bytes;
+    if (lp->bytes == 3 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
+    if (pick_route(p, m_eff).family != (lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm)) return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -816,6 +822,11 @@ int iamf_hip_batch_create(const iamf_hip_batch_config *cfg, iamf_hip_batch **out
     // w * (s * 2^-15) as long as neither the scaled weight nor a product leaves the normal range — scaling by a power of two
     // commutes with rounding there.  True of every table of the reference (|w| in 1e-4 .. 2); a caller's own matrix with
     // weights below 2^-100 takes the unfused path.
+    // The 24-bit form (render_fast_kernel<.., LPB = 3>) folds "/ 2^23" (pcm/IAMF_pcm_decoder.c:71-76, 144-148) the same way,
+    // and the same check suffices: a 24-bit integer is exact in f32 and s * 2^-23 is exact; for a non-zero |w| in
+    // [2^-100, 2^100] the staged weight w * 2^-23 >= 2^-123 is normal (no bit of w is lost), and with |s| >= 1 the product
+    // (w * 2^-23) * s is at least 2^-123 and at most 2^100: normal, so it has the bits of w * (s * 2^-23).  s == 0 gives a
+    // zero of the same sign either way.  (Not so for 32-bit samples: w * 2^-31 may be subnormal, and (float)s rounds.)
     b->lp_scale_ok = true;
     for (float w : fm)
       if (w != 0.f && !(fabsf(w) >= 0x1p-100f && fabsf(w) <= 0x1p100f)) b->lp_scale_ok = false;
@@ -1075,10 +1086,11 @@ int iamf_hip_batch_render_range(iamf_hip_batch *b, const iamf_hip_render_args *a
   return render_range_impl(b, a, stream0, n_streams, nullptr);
 }
 
-// Element 0 as LPCM packets.  Fused (render_fast_kernel<.., LP>: the packets' 16-bit samples are converted where the
-// render kernel loads them) when the call is one of the headline kernel's and every channel is a contiguous run of
-// little-endian 16-bit samples; in every other case exactly what the caller would do itself: iamf_hip_lpcm_unpack into a
-// buffer of the batch, then the f32 path.  Both give the same PCM bit for bit.
+// Element 0 as LPCM packets.  Fused (render_fast_kernel<.., LP>: the packets' samples are converted where the render
+// kernel loads them) when the call is one of the headline kernel's and every channel is a contiguous run of little-endian
+// 16-bit or 24-bit samples on the form's grid (lpcm_form.hpp: 8 bytes / 4 bytes); in every other case exactly what the
+// caller would do itself: iamf_hip_lpcm_unpack into a buffer of the batch, then the f32 path.  Both give the same PCM
+// and leave the same stream state, bit for bit.
 int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args) {
   if (!b) return IAMF_HIP_ERR_BAD_ARG;
   return iamf_hip_batch_render_lpcm_range(b, in, args, 0, b->cfg.n_streams);
@@ -1088,7 +1100,7 @@ int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in,
 // still indexed by the stream's number in the batch)
 // The packet-form checks of an LPCM call of nf frames (n_samples as iamf_hip_render_args::n_samples): an error, or
 // IAMF_HIP_OK with the trim {first, count} and whether the packets have the form the fused kernels read
-static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int n_samples, bool *fusable_out,
+static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int n_samples, LpcmForm *form_out,
                            int *first_out, int *count_out) {
   const iamf_hip_lpcm_layout &L = in->layout;
   const int fs = b->cfg.frame_size, ch = b->d_pre ? b->pre_l : b->m;
@@ -1097,19 +1109,14 @@ static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *i
     return IAMF_HIP_ERR_BAD_ARG;
   const int first = in->first_sample, count = n_samples > 0 ? n_samples : fs;
   if (first < 0 || (first > 0 && (nf != 1 || n_samples <= 0)) || first + count > fs) return IAMF_HIP_ERR_BAD_ARG;
-  bool fusable = L.sample_bytes == 2 && L.little_endian && ch <= 16 && (in->raw_frame_stride & 7) == 0 &&
-                 (in->raw_stream_stride & 7) == 0 && (reinterpret_cast<uintptr_t>(in->d_raw) & 15) == 0;
   for (int c = 0; c < ch; ++c) {   // every byte a kernel may read lies inside the frame's packet row (as iamf_hip_lpcm_unpack)
-    if (L.src_offset[c] < 0) {
-      fusable = false;
-      continue;
-    }
+    if (L.src_offset[c] < 0) continue;
     if (L.src_step[c] < L.sample_bytes ||
         (int64_t)L.src_offset[c] + (int64_t)(fs - 1) * L.src_step[c] + L.sample_bytes > in->raw_frame_stride)
       return IAMF_HIP_ERR_BAD_ARG;
-    if (L.src_step[c] != 2 || ((L.src_offset[c] + 2 * first) & 7)) fusable = false;
   }
-  *fusable_out = fusable;
+  // which form, if any, the fused kernels can load as it lies (lpcm_form.hpp; pinned by tests/route_host)
+  *form_out = lpcm_form(L, ch, in->raw_stream_stride, in->raw_frame_stride, reinterpret_cast<uintptr_t>(in->d_raw), first);
   *first_out = first;
   *count_out = count;
   return IAMF_HIP_OK;
@@ -1121,7 +1128,8 @@ static void lpcm_in_of(const iamf_hip_lpcm_input *in, int ch, int first, LpcmIn 
   lp.raw = static_cast<const uint8_t *>(in->d_raw);
   lp.stream_stride = in->raw_stream_stride;
   lp.frame_stride = in->raw_frame_stride;
-  for (int c = 0; c < ch; ++c) lp.off[c] = in->layout.src_offset[c] + 2 * first;
+  lp.bytes = in->layout.sample_bytes;
+  for (int c = 0; c < ch; ++c) lp.off[c] = in->layout.src_offset[c] + lp.bytes * first;
 }
 
 // The RANGE's packets -> planar f32 in a buffer of the batch (rows indexed by the stream's number in the batch, as every
@@ -1169,12 +1177,12 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
   if (args->n_frames == 0) return 0;
   const int ch = b->d_pre ? b->pre_l : b->m, nf = args->n_frames;
-  bool fusable = false;
+  LpcmForm form = LpcmForm::None;
   int first = 0, count = 0;
-  const int fc = lpcm_form_check(b, in, nf, args->n_samples, &fusable, &first, &count);
+  const int fc = lpcm_form_check(b, in, nf, args->n_samples, &form, &first, &count);
   if (fc != IAMF_HIP_OK) return fc;
   iamf_hip_render_args a = *args;
-  if (fusable) {
+  if (form != LpcmForm::None) {
     LpcmIn lp;
     lpcm_in_of(in, ch, first, lp);
     a.d_in = reinterpret_cast<const float *>(in->d_raw);   // not read by the fused kernel; non-null = "not a flush"
@@ -1435,10 +1443,13 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
     return IAMF_HIP_OK;
   }
   // ---- the packets (channels and frame size are the same for every member), then every member's own argument checks ----
-  bool pk_form = false;
+  LpcmForm form = LpcmForm::None;
   int first = 0, count = 0;
-  const int fc = lpcm_form_check(b0, in, n_frames, n_samples, &pk_form, &first, &count);
+  const int fc = lpcm_form_check(b0, in, n_frames, n_samples, &form, &first, &count);
   if (fc != IAMF_HIP_OK) return fc;
+  // "the form the single call fuses" is the 16-bit one here: render_fanout_kernel<.., LP> reads no other, and 24-bit
+  // packets keep sharing one unpack pass and the f32 fan-out (include/iamf_hip.h)
+  const bool pk_form = form == LpcmForm::S16;
   iamf_hip_render_args args[IAMF_HIP_FANOUT_MAX];
   int64_t total = 0;
   for (int j = 0; j < n_batches; ++j) {

@@ -32,7 +32,7 @@ struct RouteTable {
   uint32_t key[kRouteCap];     // sorted
   int32_t index[kRouteCap];    // row of key[i]
   int n = 0, dropped = 0;
-  explicit RouteTable(bool ext) {
+  explicit RouteTable(int table) {
     const auto add = [&](int family, int variant, int m, int c, int k) {
       if (n == kRouteCap) {
         ++dropped;
@@ -49,7 +49,9 @@ struct RouteTable {
       index[n] = n;
       ++n;
     };
-    if (ext) {
+    if (table == 2) {
+      for_each_render_instance_lpcm24(add);
+    } else if (table == 1) {
       for_each_render_instance_ext(add);
     } else {
       for_each_render_instance(add);
@@ -70,18 +72,34 @@ struct RouteTable {
 };
 
 const RouteTable &route_table() {
-  static const RouteTable t(false);
+  static const RouteTable t(0);
   return t;
 }
 
 // the extension table: the same row type and semantics, its own rows and its own counters (iamf_hip_route_instances_ext)
 const RouteTable &route_table_ext() {
-  static const RouteTable t(true);
+  static const RouteTable t(1);
+  return t;
+}
+
+// table 2: the 24-bit LPCM form (iamf_hip_route_table_instances)
+const RouteTable &route_table_lpcm24() {
+  static const RouteTable t(2);
   return t;
 }
 
 std::atomic<int64_t> g_launches[kRouteCap + 1];
 std::atomic<int64_t> g_launches_ext[kRouteCap + 1];
+std::atomic<int64_t> g_launches_lpcm24[kRouteCap + 1];
+
+// the indexed form: table 0 and 1 ARE the base and the extension listing (rows and counters), 2 onwards have their own
+constexpr int kRouteTables = 3;
+const RouteTable *table_of(int table) {
+  return table == 0 ? &route_table() : table == 1 ? &route_table_ext() : table == 2 ? &route_table_lpcm24() : nullptr;
+}
+std::atomic<int64_t> *launches_of(int table) {
+  return table == 0 ? g_launches : table == 1 ? g_launches_ext : table == 2 ? g_launches_lpcm24 : nullptr;
+}
 
 int list_instances(const RouteTable &t, iamf_hip_route_row *rows, int cap) {
   for (int i = 0; rows && i < t.n && i < cap; ++i) rows[i] = t.rows[i];
@@ -114,7 +132,24 @@ void iamf_hip_route_count_ext(int family, int variant, int m, int c, int k) {
   g_launches_ext[route_table_ext().find(pack_key(family, variant, m, c, k))].fetch_add(1, std::memory_order_relaxed);
 }
 
+void iamf_hip_route_count_table(int table, int family, int variant, int m, int c, int k) {
+  const RouteTable *t = table_of(table);
+  if (t) launches_of(table)[t->find(pack_key(family, variant, m, c, k))].fetch_add(1, std::memory_order_relaxed);
+}
+
 extern "C" {
+
+int iamf_hip_route_tables(void) { return kRouteTables; }
+
+int iamf_hip_route_table_instances(int table, iamf_hip_route_row *rows, int cap) {
+  const RouteTable *t = table_of(table);
+  return t ? list_instances(*t, rows, cap) : IAMF_HIP_ERR_BAD_ARG;
+}
+
+int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int reset) {
+  const RouteTable *t = table_of(table);
+  return t ? tally_of(*t, launches_of(table), rows, cap, reset) : IAMF_HIP_ERR_BAD_ARG;
+}
 
 int iamf_hip_route_instances(iamf_hip_route_row *rows, int cap) { return list_instances(route_table(), rows, cap); }
 

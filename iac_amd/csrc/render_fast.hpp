@@ -209,11 +209,19 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       consumed by the projection, instead of all channels behind the projection.  Longer in flight: what a launch
 //       of few workgroups per CU waits for (512 streams: f32 +4 %, LPCM +8 %); a launch that fills every wave slot is
 //       bound by its instruction stream and loses to the per-channel issue (LPCM, 4096 streams: -6 %) — the host picks.
-template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true>
-__global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2)) void render_fast_kernel(const RenderParams p) {
+// LPB:  (LP) bytes per packet sample.  2: as above.  3: 24-bit little-endian samples (pcm/IAMF_pcm_decoder.c:71-76, 144-148:
+//       sample / 2^23), 12 bytes per lane and channel in ONE load, the four samples cut out of its three dwords where the
+//       channel is consumed; everything behind the projection is shared.
+//       Sixteen more dwords of input are live than in the 16-bit form: <16, 2> with the late prefetch (all sixteen channels
+//       requested at once) does not fit 128 registers without spilling and is built for three workgroups per CU instead.
+template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2>
+__global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2)))
+void render_fast_kernel(const RenderParams p) {
   static_assert(!(FIR && DOWN), "one renderer");
   static_assert(!(LP && (FIR || DOWN || IN2)) && (!LP || M <= 16), "the LPCM input feeds the plain matrix variant");
   static_assert(!(IN2 && (FIR || DOWN)), "the second element joins a matrix-rendered first one");
+  static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
+  constexpr bool LP3 = LP && LPB == 3;
   extern __shared__ float lds[];
   constexpr int R = kFRing;
   constexpr int NB = R / 16;
@@ -276,7 +284,8 @@ __global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((FIR || (M <=
       // LP: the LPCM decoder's "sample / 32768.f" (pcm/IAMF_pcm_decoder.c:64-83) is folded into the weight — (w * 2^-15) *
       // (float)s has the bits of w * (s * 2^-15): a power of two commutes with rounding in the normal range, which the host
       // has checked for this matrix (iamf_hip_batch::lp_scale_ok).  Two packed multiplies per channel and chunk less.
-      mat[t] = (f >= 0 ? p.matrix[f * M + m] : 0.f) * (LP ? 1.0f / 32768.0f : 1.0f);
+      // (LPB == 3: "/ 2^23", by the same argument — w * 2^-23 >= 2^-123 is normal for the weights the host lets through)
+      mat[t] = (f >= 0 ? p.matrix[f * M + m] : 0.f) * (LP ? (LPB == 3 ? 1.0f / 8388608.0f : 1.0f / 32768.0f) : 1.0f);
     }
     if (IN2 && p.in2 && t < OC * kFIn2) {
       const int c = t / kFIn2, m = t - c * kFIn2;
@@ -342,7 +351,12 @@ __global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((FIR || (M <=
   // LP: the prefetched packets' samples as they lie in memory (four 16-bit samples per channel), converted at the top of
   // the chunk that uses them: (float)sample * (1 / 32768), the expression of iamf_hip_lpcm_unpack and of the reference
   using lp_u2 = __attribute__((ext_vector_type(2))) unsigned;
-  lp_u2 xr[LP ? M : 1];
+  lp_u2 xr[(LP && !LP3) ? M : 1];
+  // LPB == 3: four 24-bit samples in three dwords — a[23:0], {b[15:0], a[31:24]}, {c[7:0], b[31:16]}, c[31:8]
+  struct lp_u3 {
+    unsigned a, b, c;
+  };
+  lp_u3 xr3[LP3 ? M : 1];
   const uint8_t *lp_s = LP ? p.lpcm + (int64_t)s * p.lpcm_stream_stride : nullptr;
   // The element's input goes through BUFFER loads: one resource per stream (base = the stream's region), the lane's byte
   // offset in one register for all channels, the channel's offset as the instruction's scalar offset — no address
@@ -368,7 +382,13 @@ __global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((FIR || (M <=
   const __amdgpu_buffer_rsrc_t rs_none = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void *>(LP ? static_cast<const void *>(lp_s) : static_cast<const void *>(in_s)), 0, 0, 0x00020000);
   auto load_lp_one = [&](int m, int f, int i, __amdgpu_buffer_rsrc_t rs) {
-    if constexpr (LP) {
+    if constexpr (LP3) {
+      // (dword-aligned: the stream's base, the frame stride and the run offsets are multiples of 4 — lpcm_form.hpp —
+      //  and 3 * i is one of 12)
+      const int vo = f * (int)p.lpcm_frame_stride + 3 * i;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, vo, p.lpcm_off[m], 2 /* nt */);
+      xr3[m] = lp_u3{v[0], v[1], v[2]};
+    } else if constexpr (LP) {
       const int vo = f * (int)p.lpcm_frame_stride + 2 * i;
       const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, p.lpcm_off[m], 2 /* nt */);
       xr[m] = lp_u2{v[0], v[1]};
@@ -408,7 +428,9 @@ __global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((FIR || (M <=
       load_x2(f, i);
     } else {
 #pragma unroll
-      for (int m = 0; m < (LP ? M : 0); ++m) xr[m] = lp_u2{0u, 0u};
+      for (int m = 0; m < ((LP && !LP3) ? M : 0); ++m) xr[m] = lp_u2{0u, 0u};
+#pragma unroll
+      for (int m = 0; m < (LP3 ? M : 0); ++m) xr3[m] = lp_u3{0u, 0u, 0u};
 #pragma unroll
       for (int m = 0; m < M; ++m) x[m] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -490,7 +512,21 @@ __global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((FIR || (M <=
             }
           }
         }
-        if constexpr (LP) {
+        if constexpr (LP3) {
+          // (the same ordering fence as the 16-bit form below, for the same reason)
+          if constexpr (OC == 2)
+            asm volatile("" : "+v"(xr3[m].a), "+v"(xr3[m].b), "+v"(xr3[m].c), "+v"(prj[0]), "+v"(prj[1]), "+v"(prj[2]), "+v"(prj[3]));
+          else
+            asm volatile("" : "+v"(xr3[m].a), "+v"(xr3[m].b), "+v"(xr3[m].c), "+v"(prj[0]), "+v"(prj[1]));
+          const unsigned a = xr3[m].a, b = xr3[m].b, c = xr3[m].c;   // (the scale 2^-23 sits in the weights)
+          // sign-extended from 24 bits: a bit-field extract of the dword (or of the two dwords' funnel) the sample lies in
+          const int s0 = (int)(a << 8) >> 8;
+          const int s1 = (int)(__builtin_amdgcn_alignbit(b, a, 24) << 8) >> 8;
+          const int s2 = (int)(__builtin_amdgcn_alignbit(c, b, 16) << 8) >> 8;
+          const int s3 = (int)c >> 8;
+          xa = f2{(float)s0, (float)s1};
+          xb = f2{(float)s2, (float)s3};
+        } else if constexpr (LP) {
           // (the packets of channel m are "produced" here, after channel m - 1 has been added up: left to itself the
           //  scheduler converts all sixteen channels first and spills what does not fit — 127 registers' worth)
           if constexpr (OC == 2)

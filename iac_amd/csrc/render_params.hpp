@@ -99,6 +99,9 @@ struct RenderParams {
   float *fir_hist_next;     // device, same shape: history after this call
   const void *fir_h16;      // device: split-f16 filter tables [M][ear][hi/lo][shift 8][304] (render_fir16.hpp) or nullptr
   float fir_inv_scale;      // 1 / (filter scale * input scale) of those tables
+  int32_t lpcm_bytes;       // (LPCM block below) bytes per packet sample: 0 or 2 = 16 bit, 3 = 24 bit.  Host only — the kernels
+                            // know it at compile time — and kept HERE, in what was padding in front of the next pointer:
+                            // the block keeps its size and every other field its offset, so no kernel's arguments move
   const float *fir_pq;      // device: spectra tables of the FFT stage [pairs][16][64] x 4 floats (render_fir_fft.hpp) or nullptr
   const float *fir_tw;      // device: its twiddles [16][64] + [16][4] complex
   const float *fir_zero;    // device: zero floats, M * frame size of them (what that stage loads for runs past the end of a
@@ -114,7 +117,8 @@ struct RenderParams {
   // ---- element 0 handed over as LPCM packets (render_fast_kernel<.., LP>, iamf_hip_batch_render_lpcm): 16-bit
   //      little-endian samples, one contiguous run per channel and frame.  Sample i of channel m, frame f, stream s:
   //      lpcm + s * lpcm_stream_stride + f * lpcm_frame_stride + lpcm_off[m] + 2 * i (bytes; every term a multiple of 8
-  //      for i a multiple of 4).  `in` is not read then ----
+  //      for i a multiple of 4).  `in` is not read then.  lpcm_bytes == 3 (above): 24-bit samples, 3 * i, every term a
+  //      multiple of 4 (lpcm_form.hpp) ----
   const uint8_t *lpcm;
   int64_t lpcm_stream_stride, lpcm_frame_stride;
   int32_t lpcm_off[16];

@@ -177,12 +177,34 @@ enum class Family {
   Fast,         // render_fast_kernel<M, OC>; variant 1: the mixing one (IN2)
   Wide,         // render_wide_kernel<M, MFMA>; variant 1: MFMA projection
   Generic,      // render_kernel<M>
+  Lpcm24,       // render_fast_kernel<.., LP, EARLY, LPB = 3> (iamf_render_lpcm24.hip); variant as Lpcm.  Table 2 of
+                // iamf_hip_route_table_instances: the base listing's row set is pinned
 };
 struct Route {
   Family family;
   int variant;
   int err;   // IAMF_HIP_OK unless family == Refused
 };
+
+// Which prefetch variant a launch of n_launch workgroups of the 24-bit LPCM form takes: the faster one per size as measured
+// (tools/lpcm24_rate.py, MI355X, 3rd-order element into stereo s16, 64 frames x 1024, profiles/r09_lpcm24_rate.json): the
+// early per-channel prefetch at every size — 512 / 2048 / 4096 streams: 0.370 / 1.346 / 2.688 ms against 0.417 / 1.400 /
+// 2.753 ms for the late one.  (Unlike the 16-bit form, whose late variant wins beyond 1024 workgroups: here <16, 2> with the
+// late prefetch is built for three workgroups per CU, render_fast.hpp.)  No cut, so the rule is the constant; the late
+// instances stay reachable by IAMF_HIP_LP_LATE=1.
+inline bool lpcm24_early(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+// Whether a range of n_launch streams takes the 24-bit form at all: a size at which it does not beat the unfused pair
+// (unpack, then the f32 kernel) by more than that pair's own run-to-run spread is not fused (render_prepare asks).  Same
+// run, same file: the unfused pair takes 4.26 / 4.66 / 4.61 times the fused call's time at 512 / 2048 / 4096 streams, its
+// spread against itself at most 0.0006 — every measured size wins, so every size is fused; this is where a size that stops
+// winning would be cut.
+inline bool lpcm24_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
 
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
@@ -198,6 +220,11 @@ inline Route pick_route(const RenderParams &p, int m) {
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
     if (!LpcmM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+    // 24-bit samples (lpcm_bytes: 0 or 2 = 16 bit): the same instances and refusals, the kernel's LPB = 3 form
+    // (IAMF_HIP_LP_EARLY=1 forces the early variant as IAMF_HIP_LP_LATE=1 forces the late one: tools/lpcm24_rate.py times both
+    //  at every size, and the tests run both whatever the cut)
+    if (p.lpcm_bytes == 3)
+      return take(Family::Lpcm24, !getenv("IAMF_HIP_LP_LATE") && (getenv("IAMF_HIP_LP_EARLY") || lpcm24_early(p.n_launch)));
     // up to four workgroups a CU: the early per-channel prefetch (latency bound); beyond: the plain one (issue bound).
     // Measured on MI355X, 512 / 4096 streams: 117 against 109 / 136 against 145 Gsamples/s (profiles/r04_ab_fast.txt)
     return take(Family::Lpcm, p.n_launch <= 1024 && !getenv("IAMF_HIP_LP_LATE"));
@@ -296,6 +323,13 @@ void for_each_render_instance_ext(F &&f) {
   for_each_int(FanLpM{}, [&](int m) { for_each_int(FanLpK{}, [&](int k) { f(IAMF_HIP_ROUTE_FANOUT_LPCM, 0, m, 0, k); }); });
 }
 
+// Table 2 (iamf_hip_route_table_instances): the 24-bit LPCM form, walking LpcmM x LpcmOC as its launcher does.
+template <class F>
+void for_each_render_instance_lpcm24(F &&f) {
+  for (int early = 0; early < 2; ++early)
+    for_each_int(LpcmM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM24, early, m, oc, 0); }); });
+}
+
 // the row of the kernel launch() runs for a route (a FirSplit call launches render_fast_kernel<2, 2> behind it as well:
 // launch() counts that row too)
 struct RouteKey {
@@ -317,6 +351,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::Fast: return {IAMF_HIP_ROUTE_FAST, r.variant, m, p.out_ch, 0};
     case Family::Wide: return {IAMF_HIP_ROUTE_WIDE, r.variant, m, 0, 0};
     case Family::Generic: return {IAMF_HIP_ROUTE_GENERIC, 0, m, 0, 0};
+    case Family::Lpcm24: return {IAMF_HIP_ROUTE_LPCM24, r.variant, m, p.out_ch, 0};   // a row of table 2
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

@@ -81,7 +81,7 @@ class RouteRow(C.Structure):   # iamf_hip_route_row
 
 # IAMF_HIP_ROUTE_*: the kernel families of iamf_hip_route_row::family
 ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, WIDE4_DEMIX=7, WIDE4_DOWN=8, WIDE4_MIX=9,
-             WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23)
+             WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, LPCM24=16, RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23)
 ROUTE_NAME = {v: k for k, v in ROUTE.items()}
 
 
@@ -216,6 +216,9 @@ def lib():
         L.iamf_hip_route_tally.argtypes = [C.POINTER(RouteRow), C.c_int, C.c_int]
         L.iamf_hip_route_instances_ext.argtypes = [C.POINTER(RouteRow), C.c_int]
         L.iamf_hip_route_tally_ext.argtypes = [C.POINTER(RouteRow), C.c_int, C.c_int]
+        L.iamf_hip_route_tables.argtypes = []
+        L.iamf_hip_route_table_instances.argtypes = [C.c_int, C.POINTER(RouteRow), C.c_int]
+        L.iamf_hip_route_table_tally.argtypes = [C.c_int, C.POINTER(RouteRow), C.c_int, C.c_int]
         L.iamf_hip_shard_split.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.iamf_hip_shard_create.argtypes = [C.POINTER(BatchConfig), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_shard_destroy.argtypes = [C.c_void_p]
@@ -323,6 +326,33 @@ def route_tally_ext(reset=True):
     cap = L.iamf_hip_route_instances_ext(None, 0) + 1
     rows = (RouteRow * cap)()
     n = L.iamf_hip_route_tally_ext(rows, cap, 1 if reset else 0)
+    return {(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k): r.launches for r in rows[:min(n, cap)]}
+
+
+def route_tables():
+    """iamf_hip_route_tables: how many tables the indexed form has (0 = the base listing, 1 = the extension, 2 = LPCM24)"""
+    return lib().iamf_hip_route_tables()
+
+
+def route_table_instances(t):
+    """iamf_hip_route_table_instances: the instances of table t, as route_instances lists table 0's; needs no GPU"""
+    L = lib()
+    n = L.iamf_hip_route_table_instances(t, None, 0)
+    if n < 0:
+        raise IamfHipError(n, "iamf_hip_route_table_instances")
+    rows = (RouteRow * max(n, 1))()
+    n = min(n, L.iamf_hip_route_table_instances(t, rows, n))
+    return [(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k) for r in rows[:n]]
+
+
+def route_table_tally(t, reset=False):
+    """iamf_hip_route_table_tally: {(family name, variant, m, c, k): launches} of table t since its last reset"""
+    L = lib()
+    cap = L.iamf_hip_route_table_instances(t, None, 0) + 1
+    if cap <= 0:
+        raise IamfHipError(cap - 1, "iamf_hip_route_table_tally")
+    rows = (RouteRow * cap)()
+    n = L.iamf_hip_route_table_tally(t, rows, cap, 1 if reset else 0)
     return {(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k): r.launches for r in rows[:min(n, cap)]}
 
 

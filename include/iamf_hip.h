@@ -625,12 +625,17 @@ int iamf_hip_lpcm_unpack(const iamf_hip_lpcm_layout *layout, const void *d_raw, 
  * (offsets relative to the frame's row; layout.channels = the element's channels, layout.frame_size = the batch's).
  * first_sample: with args->n_frames == 1 and args->n_samples > 0, the frame position of the first sample to render (a
  * trimmed start); else 0.  `args` as for iamf_hip_batch_render_ex with d_in == NULL (the in_* strides are not used).
- * Fused when: 16-bit little-endian, every channel a contiguous run (src_step == 2) at an offset that is a multiple of 8
- * bytes (with first_sample), strides multiples of 8, d_raw 16-byte aligned, and the batch is a plain matrix render of a
- * 1 / 4 / 9 / 16-channel element into one or two channels with the limiter on (no second element, ramps, demixer, down-mixer,
- * de-mapping, FIR or LFE generator).  Every other input — 24 / 32 bit, big-endian, coupled sub-streams, wide layouts —
- * takes iamf_hip_lpcm_unpack into a buffer of the batch and then the f32 kernels.  The PCM is the same bit for bit either
- * way (tests/test_gpu_lpcm.py); IAMF_HIP_LPCM_UNFUSED=1 in the environment forces the second way.
+ * Fused when: little-endian, every channel present and a contiguous run, d_raw 16-byte aligned, and
+ *   16 bit: src_step == 2, src_offset + 2 * first_sample a multiple of 8 bytes, both strides multiples of 8;
+ *   24 bit: src_step == 3, src_offset + 3 * first_sample a multiple of 4 bytes, both strides multiples of 4 (a lane's four
+ *           samples are one 12-byte load, which wants dword alignment; 48 + 4 bytes per sample-frame of a 3rd-order
+ *           element instead of the 180 of unpack + f32 kernel);
+ * and the batch is a plain matrix render of a 1 / 4 / 9 / 16-channel element into one or two channels with the limiter on
+ * (no second element, ramps, demixer, down-mixer, de-mapping, FIR or LFE generator; no weight outside 2^-100 .. 2^100).
+ * Every other input — 32 bit, big-endian, coupled sub-streams, wide layouts, runs off the grid — takes
+ * iamf_hip_lpcm_unpack into a buffer of the batch and then the f32 kernels.  The PCM and the stream state are the same bit
+ * for bit either way (tests/test_gpu_lpcm.py, test_gpu_lpcm24.py), so fused, unfused and f32 calls may follow one another
+ * on a batch; IAMF_HIP_LPCM_UNFUSED=1 in the environment forces the second way.
  * Returns what iamf_hip_batch_render_ex returns. */
 typedef struct iamf_hip_lpcm_input {
   const void *d_raw;
@@ -654,7 +659,8 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
  * fan-out and the single-batch calls may be mixed freely on the same batches.
  *
  * What runs is decided from what the call can observe, in this order:
- *   1. A member is packet-fusable when the packets have the form the single call fuses (see above), the member's single
+ *   1. A member is packet-fusable when the packets have the 16-bit form the single call fuses (see above; the single
+ *      call's 24-bit form is not one this entry fuses: such packets go by 3.), the member's single
  *      call would run the packet-fed kernel, the element has 4, 9 or 16 channels, and the member is one the f32 fan-out
  *      would fuse (no fixed PCM channel stride).  If at least two members are packet-fusable they share one launch that
  *      reads the packets once: 2 * M + sum of the members' output bytes per sample-frame instead of 2 * M per member.
@@ -710,6 +716,7 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *     WIDE                 variant 1 = MFMA projection, m
  *     WIDE4, WIDE4_MIX, WIDE4_LFE          variant 1 = MFMA projection, m, c
  *     LPCM                 variant 1 = early per-channel prefetch, 0 = late; m, c
+ *     LPCM24               the same for 24-bit samples (table 2 of iamf_hip_route_table_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -737,6 +744,7 @@ enum {
   IAMF_HIP_ROUTE_FIR_SPLIT = 13,
   IAMF_HIP_ROUTE_FIR_FUSED = 14,
   IAMF_HIP_ROUTE_FANOUT_LPCM = 15,   /* extension table only */
+  IAMF_HIP_ROUTE_LPCM24 = 16,        /* table 2 only */
   IAMF_HIP_ROUTE_RS_PLAIN = 20,
   IAMF_HIP_ROUTE_RS_TILE = 21,
   IAMF_HIP_ROUTE_RS_BLOCK = 22,
@@ -758,6 +766,14 @@ int iamf_hip_route_tally(iamf_hip_route_row *rows, int cap, int reset);
  * iamf_hip_route_tally_ext only, never as a NONE row of iamf_hip_route_tally. */
 int iamf_hip_route_instances_ext(iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_tally_ext(iamf_hip_route_row *rows, int cap, int reset);
+/* The indexed form of the two pairs above, for tables added since: both listings' row sets are pinned by their callers.
+ * iamf_hip_route_tables() tables; table 0 IS the base listing and table 1 the extension listing (the same rows and the
+ * same counters as the symbols above, which stay); table 2: LPCM24 rows (variant, m, c as LPCM), counters of its own — a
+ * launch of one of these instances shows in table 2 only, never as a NONE row of another tally.  Semantics per table as
+ * above; a table number outside 0 .. tables - 1: IAMF_HIP_ERR_BAD_ARG. */
+int iamf_hip_route_tables(void);
+int iamf_hip_route_table_instances(int table, iamf_hip_route_row *rows, int cap);
+int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int reset);
 
 /* ------------------------------------------------------------------------------------------
  * A group of decoder handles: callers of the reference API get the batch renderer's throughput.
