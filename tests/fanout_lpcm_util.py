@@ -77,13 +77,17 @@ class Drive:
     """K batches on one device buffer of packet rows.  Every step appends, per member and stream OF THE STEP'S RANGE, the
     bytes the step emitted; PCM rows outside the range must keep their fill."""
 
-    def __init__(self, matrices, specs, raw, L, row, x, fs):
+    def __init__(self, matrices, specs, raw, L, row, x, fs, packets=None, pcm_layout=None):
+        """packets: a packet layout of gpu_util (place_packets) or None: the rows as they are, dense, at the start of a fresh
+        allocation.  pcm_layout: the layout of every member's PCM rows (gpu_util.pcm_rows; None: DENSE)."""
         import torch
         import gpu_util as G
-        self.torch = torch
+        self.torch, self.G = torch, G
         self.S, self.F, _ = raw.shape
         self.m, self.fs, self.L, self.row = L.channels, fs, L, row
-        self.d_raw = torch.from_numpy(raw).cuda()
+        self.raw, self.packets, self.pcm_layout = raw, packets, pcm_layout or G.DENSE
+        self.d_raw = torch.from_numpy(raw).cuda() if packets is None else None
+        self.keep = None
         # the same samples as planar f32 frames (x None: a drive that makes no f32 call)
         self.xin = None if x is None else torch.from_numpy(G.to_frames(x, fs)).cuda()
         self.batches = [make_batch(mx, sp, self.S, fs) for mx, sp in zip(matrices, specs)]
@@ -94,19 +98,24 @@ class Drive:
         self.st = torch.cuda.current_stream().cuda_stream
 
     def bufs(self, n_samples):
+        """-> (the members' pcm_stream_stride_bytes, their PCM rows as torch tensors: S rows under the drive's PCM layout, every
+        byte the fill; .rows is the gpu_util.PcmRows, whose d_pcm is the call's pointer — the tensor's own under DENSE)"""
         caps = [(max(n_samples, 240) * b.oc * b.bps + 15) & ~15 for b in self.batches]
-        return caps, [self.torch.full((self.S, c), FILL, dtype=self.torch.uint8, device="cuda") for c in caps]
+        rows = self.G.pcm_rows_of_members(self.S, caps, self.pcm_layout, [b.bps for b in self.batches])
+        pcms = []
+        for r in rows:
+            t = r.tensor[0:]     # a tensor of its own on the same memory (far rows share an allocation)
+            t.rows = r
+            pcms.append(t)
+        return [r.stride for r in rows], pcms
 
     def _take(self, j, pcm, n, s0, cnt):
+        """the emitted runs of the range; every other byte of the allocation must still be the fill (rows_and_rest)"""
         self.torch.cuda.synchronize()
-        h = pcm.cpu().numpy()
         b = self.batches[j]
-        for s in range(self.S):
-            if s0 <= s < s0 + cnt:
-                self.out[j][s].append(h[s][:n * b.oc * b.bps].copy())
-                assert (h[s][n * b.oc * b.bps:] == FILL).all(), "member %d stream %d: bytes behind the emitted ones" % (j, s)
-            else:
-                assert (h[s] == FILL).all(), "member %d: PCM row %d outside the range [%d, %d) was written" % (j, s, s0, s0 + cnt)
+        h = self.G.rows_and_rest(pcm.rows, self.pcm_layout, n * b.oc * b.bps, only=(s0, cnt))
+        for s in range(s0, s0 + cnt):
+            self.out[j][s].append(h[s])
         self.emitted[j].append(n)
 
     def _range(self, s0, cnt):
@@ -116,9 +125,14 @@ class Drive:
 
     def lpcm_input(self, f0, first=0):
         inp = A.LpcmInput()
-        inp.d_raw = self.d_raw.data_ptr() + f0 * self.row
-        inp.raw_stream_stride = self.F * self.row
-        inp.raw_frame_stride = self.row
+        if self.packets is None:
+            inp.d_raw = self.d_raw.data_ptr() + f0 * self.row
+            inp.raw_stream_stride = self.F * self.row
+            inp.raw_frame_stride = self.row
+        else:
+            pl = self.G.place_packets(self.raw, self.L, self.packets, f0, keep=self.keep)
+            self.keep = pl.keep
+            inp.d_raw, inp.raw_stream_stride, inp.raw_frame_stride = pl.d_raw, pl.stream_stride, pl.frame_stride
         inp.first_sample = first
         inp.layout = self.L
         return inp
@@ -131,7 +145,7 @@ class Drive:
         """the call under test; returns its report (n_fused, input_fused, n_unpacks)"""
         cnt, f0 = self._range(s0, cnt)
         caps, pcms = self.bufs(n_samples or nf * self.fs)
-        ns, rep = A.render_fanout_lpcm(self.batches, self.lpcm_input(f0, first), nf, [p.data_ptr() for p in pcms], caps, self.st,
+        ns, rep = A.render_fanout_lpcm(self.batches, self.lpcm_input(f0, first), nf, [p.rows.d_pcm for p in pcms], caps, self.st,
                                        n_samples=n_samples, stream0=s0, n_streams=cnt)
         for j, n in enumerate(ns):
             self._take(j, pcms[j], n, s0, cnt)
@@ -146,7 +160,7 @@ class Drive:
         inp = self.lpcm_input(f0, first)
         for j, b in enumerate(self.batches):
             a = A.RenderArgs()
-            a.n_frames, a.n_samples, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, n_samples, pcms[j].data_ptr(), caps[j], self.st
+            a.n_frames, a.n_samples, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, n_samples, pcms[j].rows.d_pcm, caps[j], self.st
             self._take(j, pcms[j], b.render_lpcm_range(inp, a, s0, cnt), s0, cnt)
         self._advance(s0, cnt, nf)
 
@@ -158,7 +172,7 @@ class Drive:
         cnt, f0 = self._range(s0, cnt)
         caps, pcms = self.bufs(nf * self.fs)
         d_in, ss, fstr = self._f32(f0)
-        ns, fused = A.render_fanout_range(self.batches, d_in, ss, fstr, nf, [p.data_ptr() for p in pcms], caps, s0, cnt, self.st)
+        ns, fused = A.render_fanout_range(self.batches, d_in, ss, fstr, nf, [p.rows.d_pcm for p in pcms], caps, s0, cnt, self.st)
         for j, n in enumerate(ns):
             self._take(j, pcms[j], n, s0, cnt)
         self._advance(s0, cnt, nf)
@@ -172,7 +186,7 @@ class Drive:
         for j, b in enumerate(self.batches):
             a = A.RenderArgs()
             a.d_in, a.in_stream_stride, a.in_frame_stride = d_in, ss, fstr
-            a.n_frames, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, pcms[j].data_ptr(), caps[j], self.st
+            a.n_frames, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, pcms[j].rows.d_pcm, caps[j], self.st
             self._take(j, pcms[j], b.render_range(a, s0, cnt), s0, cnt)
         self._advance(s0, cnt, nf)
 
@@ -180,11 +194,12 @@ class Drive:
         cnt, _ = self._range(s0, cnt)
         caps, pcms = self.bufs(240)
         for j, b in enumerate(self.batches):
-            self._take(j, pcms[j], b.flush_range(pcms[j].data_ptr(), caps[j], self.st, s0, cnt), s0, cnt)
+            self._take(j, pcms[j], b.flush_range(pcms[j].rows.d_pcm, caps[j], self.st, s0, cnt), s0, cnt)
 
     def close(self):
         for b in self.batches:
             b.close()
+        self.d_raw = self.keep = self.xin = None     # the far layouts hold gigabytes
 
     def bytes_of(self, j, s):
         return np.concatenate(self.out[j][s])

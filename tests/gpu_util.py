@@ -41,6 +41,31 @@ def to_frames(x, frame_size):
 # far layouts both are placed as under PAD16.  Every float between the samples is a quiet NaN, so that a kernel that uses
 # one shows it in its output; every PCM byte starts as 0xA5 and rows_and_rest asserts that all but the emitted runs still are.
 
+# ------------------------------------------------------------------------------------------
+# packet layouts: where the LPCM packet rows of iamf_hip_batch_render_lpcm and the packet-fed fan-out lie
+# ------------------------------------------------------------------------------------------
+# Sample i of channel c, frame f, stream s is at d_raw + s * raw_stream_stride + f * raw_frame_stride + src_offset[c] +
+# src_step[c] * i (include/iamf_hip.h).  The fused kernels (render_fast_kernel<.., LP>, render_fanout_kernel<.., LP>) read
+# the rows as they lie if lpcm_form() (iac_amd/csrc/lpcm_form.hpp) admits them: d_raw 16-byte aligned, both strides on the
+# form's grid g (8 bytes for 16-bit samples, 4 for 24-bit), and if the call's frames fit 32-bit byte offsets
+# (fast_shape_ok: (frames + 2) * raw_frame_stride + 2^24 < 2^31); every other call is unpacked to f32 first.  `row` is the
+# packet row of lpcm_util.rows, a multiple of 16; B(n) = pk_bound(n) is the largest multiple of 16 that keeps the 32-bit
+# rule for a call of n frames (n = 3: the longest call of the tests):
+#
+#   name            d_raw - base  frame stride  stream stride        meant to
+#   PK_DENSE        0             row           F*row                what the runners always did
+#   PK_PAD16        16            row + 16      F*(row+16) + 48      nothing dense, everything 16-byte aligned: fused on every call
+#   PK_GRID         16            row + g       F*(row+g) + g        strides only on the form's grid: a call from an odd frame has d_raw off 16 bytes
+#   PK_OFF_BASE     8             row + 16      F*(row+16)           d_raw & 15 != 0: every call unfused
+#   PK_OFF_STRIDE   0             row + g/2     F*(row+g/2)          frame stride off the grid: every call unfused
+#   PK_FAR_STREAMS  16            row           2^31 + 16            stream 1 crosses the signed 32-bit byte offset, stream 2 the unsigned one
+#   PK_BOUND        0             B(n)          F*B(n)               the largest frame stride at which the call of n frames is still fused
+#   PK_BEYOND       0             B(n) + 16     F*(B(n)+16)          the call of n frames unfused (the unpacker at far frame strides), shorter ones fused
+#   PK_FRAME_MAJOR  16            S*(row+16)    row + 16             [F][S][row]: stream stride < frames * frame stride, which the ABI refuses
+#
+# base is 256-byte aligned.  Every byte that belongs to no channel's run is 0x7F at an even address and 0x80 at an odd
+# one: a load that strays yields a sample near full scale.
+
 Layout = namedtuple("Layout", "name")
 DENSE, PAD16, FRAME_MAJOR, OFF_IN, OFF_PCM, FAR_IN, FAR_PCM = [
     Layout(n) for n in ("DENSE", "PAD16", "FRAME_MAJOR", "OFF_IN", "OFF_PCM", "FAR_IN", "FAR_PCM")]
@@ -220,19 +245,26 @@ def place_ramp(ramp, layout, backend=TORCH):
 
 
 class PcmRows:
-    """an allocation of S PCM rows under a layout; .d_pcm and .stride are the call's arguments"""
+    """an allocation of S PCM rows under a layout; .d_pcm and .stride are the call's arguments.  room: bytes kept free
+    behind the last row; share / lead: no allocation of its own — the rows lie in the allocation of `share` (far rows of
+    the same layout, made with room for them), `lead` bytes behind its rows: the members of a fan-out under a far layout
+    then take one allocation between them, their guard zones apart"""
 
-    def __init__(self, S, need, layout, bps, backend):
+    def __init__(self, S, need, layout, bps, backend, room=0, share=None, lead=0):
         off, stride = pcm_geometry(layout, need, bps)
         head = 0 if layout == DENSE else PCM_HEAD
         self.S, self.need, self.layout, self.backend, self.stride = S, need, layout, backend, stride
-        self.first = head + off
-        self.size = self.first + (S - 1) * stride + need + head
+        self.first = head + off + lead
+        self.size = self.first + (S - 1) * stride + need + head + room
         self.far = self.size >= (1 << 28)
-        if not self.far:
+        if share is not None:
+            assert share.far and self.far and share.layout == layout and share.stride == stride and self.size <= share.size
+            self.tensor = share.tensor
+        elif not self.far:
             self.tensor = backend.upload(np.full(self.size, FILL, dtype=np.uint8))
         else:
             self.tensor = backend.empty(self.size, np.uint8)
+        if self.far:
             for lo, hi in self._zones():
                 backend.assign(self.tensor, lo, np.full(hi - lo, FILL, dtype=np.uint8))
         self.d_pcm = backend.ptr(self.tensor) + self.first
@@ -243,35 +275,173 @@ class PcmRows:
                  min(self.first + s * self.stride + self.need + FAR_GUARD, self.size)) for s in range(self.S)]
 
 
-def pcm_rows(S, need_bytes, layout, bps=2, backend=TORCH):
+def pcm_rows(S, need_bytes, layout, bps=2, backend=TORCH, **kw):
     """Returns (rows, d_pcm, pcm_stream_stride_bytes): S rows of need_bytes under `layout`, every byte of the allocation
-    0xA5 (under FAR_PCM: FAR_GUARD bytes on each side of every row; the rest is never looked at)."""
-    rows = PcmRows(S, need_bytes, layout, bps, backend)
+    0xA5 (under FAR_PCM: FAR_GUARD bytes on each side of every row; the rest is never looked at).  kw: PcmRows' room,
+    share and lead."""
+    rows = PcmRows(S, need_bytes, layout, bps, backend, **kw)
     return rows, rows.d_pcm, rows.stride
 
 
-def rows_and_rest(rows, layout, n_bytes):
+def pcm_rows_of_members(S, needs, layout, bpss, backend=TORCH):
+    """one PcmRows per member of a fan-out: allocations of their own, or, where the layout puts the rows far apart, one
+    allocation for all of them with every member's rows 2 * FAR_GUARD (and a little) behind the member's before"""
+    if pcm_geometry(layout, needs[0], bpss[0])[1] < (1 << 28):
+        return [PcmRows(S, n, layout, b, backend) for n, b in zip(needs, bpss)]
+    leads = [0]
+    for n in needs[:-1]:
+        leads.append(leads[-1] + r16(n) + 2 * FAR_GUARD + 256)
+    first = PcmRows(S, needs[0], layout, bpss[0], backend, room=leads[-1] + needs[-1])
+    return [first] + [PcmRows(S, n, layout, b, backend, share=first, lead=l) for n, b, l in zip(needs[1:], bpss[1:], leads[1:])]
+
+
+def rows_and_rest(rows, layout, n_bytes, only=None):
     """Per stream the first n_bytes of its row (numpy uint8), having asserted that every other byte of the allocation is
-    still 0xA5: the head, the rest of each row beyond the emitted run, the gaps between rows and the tail."""
+    still 0xA5: the head, the rest of each row beyond the emitted run, the gaps between rows and the tail.  only: (s0, cnt) —
+    a call over that range of streams: the rows outside it must be untouched and come back empty."""
     assert layout == rows.layout and 0 <= n_bytes <= rows.need
     zones = rows._zones() if rows.far else [(0, rows.size)]
     out = [None] * rows.S
+    want = [n_bytes if only is None or only[0] <= s < only[0] + only[1] else 0 for s in range(rows.S)]
     for lo, hi in zones:
         h = rows.backend.read(rows.tensor, lo, hi)
         for s in range(rows.S):
             a = rows.first + s * rows.stride
-            if lo <= a and a + n_bytes <= hi:
-                out[s] = h[a - lo:a - lo + n_bytes].copy()
-                h[a - lo:a - lo + n_bytes] = FILL
+            if lo <= a and a + want[s] <= hi:
+                out[s] = h[a - lo:a - lo + want[s]].copy()
+                h[a - lo:a - lo + want[s]] = FILL
         bad = np.flatnonzero(h != FILL)
         if bad.size:
             at = int(bad[0]) + lo - rows.first
             s = min(max(at // rows.stride, 0), rows.S - 1) if rows.stride else 0
             raise AssertionError("%s: %d bytes outside the emitted runs were written, the first at byte %d of row %d "
                                  "(%d bytes emitted, rows of %d, stride %d)"
-                                 % (layout.name, bad.size, at - s * rows.stride, s, n_bytes, rows.need, rows.stride))
+                                 % (layout.name, bad.size, at - s * rows.stride, s, want[s], rows.need, rows.stride))
     assert all(o is not None for o in out)
     return out
+
+
+# ---- the packet layouts (the second table at the top of the file) ----
+
+PK_DENSE, PK_PAD16, PK_GRID, PK_OFF_BASE, PK_OFF_STRIDE, PK_FAR_STREAMS, PK_BOUND, PK_BEYOND, PK_FRAME_MAJOR = [
+    Layout(n) for n in ("PK_DENSE", "PK_PAD16", "PK_GRID", "PK_OFF_BASE", "PK_OFF_STRIDE", "PK_FAR_STREAMS", "PK_BOUND", "PK_BEYOND",
+                        "PK_FRAME_MAJOR")]
+PK_SMALL = [PK_DENSE, PK_PAD16, PK_GRID, PK_OFF_BASE, PK_OFF_STRIDE]
+PK_FAR = [PK_FAR_STREAMS, PK_BOUND, PK_BEYOND]
+PK_LAYOUTS = PK_SMALL + PK_FAR
+PK_LONGEST = 3            # frames of the longest call of the tests: the n of B(n)
+
+
+def pk_grid(sample_bytes):
+    """the alignment grid of the fusable form with that many bytes per sample (lpcm_form.hpp)"""
+    return {2: 8, 3: 4}[sample_bytes]
+
+
+def pk_bound(n):
+    """B(n): the largest multiple of 16 with (n + 2) * B + 2^24 < 2^31"""
+    return ((2 ** 31 - 2 ** 24 - 1) // (n + 2)) & ~15
+
+
+def packet_geometry(layout, S, F, row, sample_bytes, longest=PK_LONGEST):
+    """-> (d_raw - base, raw_frame_stride, raw_stream_stride) in bytes, the table above"""
+    g = pk_grid(sample_bytes)
+    if layout == PK_DENSE:
+        return 0, row, F * row
+    if layout == PK_PAD16:
+        return 16, row + 16, F * (row + 16) + 48
+    if layout == PK_GRID:
+        return 16, row + g, F * (row + g) + g
+    if layout == PK_OFF_BASE:
+        return 8, row + 16, F * (row + 16)
+    if layout == PK_OFF_STRIDE:
+        return 0, row + g // 2, F * (row + g // 2)
+    if layout == PK_FAR_STREAMS:
+        return 16, row, 2 ** 31 + 16
+    if layout == PK_BOUND:
+        return 0, pk_bound(longest), F * pk_bound(longest)
+    if layout == PK_BEYOND:
+        return 0, pk_bound(longest) + 16, F * (pk_bound(longest) + 16)
+    if layout == PK_FRAME_MAJOR:
+        return 16, S * (row + 16), row + 16
+    raise ValueError(layout)
+
+
+def packet_fill(lo, hi):
+    """the bytes [lo, hi) of an allocation that holds no packets: 0x7F / 0x80 alternating by byte address"""
+    return np.where(np.arange(lo, hi) % 2 == 0, 0x7F, 0x80).astype(np.uint8)
+
+
+def packet_run_mask(L, row):
+    """[row] bool: the bytes of a packet row that belong to a channel's run"""
+    used = np.zeros(row, dtype=bool)
+    i = np.arange(L.frame_size)[:, None]
+    for c in range(L.channels):
+        if L.src_offset[c] >= 0:
+            used[(L.src_offset[c] + L.src_step[c] * i + np.arange(L.sample_bytes)[None, :]).reshape(-1)] = True
+    return used
+
+
+class _Packets:
+    """placed packet rows [S][F][row]: the allocation, the byte index of row [0][0] in it, and the zones that were written
+    ([(lo, hi)]: the whole allocation unless it is a far one)"""
+
+    def __init__(self, tensor, first, size, zones, backend):
+        self.tensor, self.first, self.size, self.zones, self.backend = tensor, first, size, zones, backend
+
+    def ptr(self, nbytes):
+        return self.backend.ptr(self.tensor) + self.first + nbytes
+
+
+def _place_packets(raw, L, off, fst, sst, dense, backend):
+    """raw [S][F][row] with row [s][f] at byte first + s*sst + f*fst of a fresh allocation, which covers every row plus a
+    row (rounded up to 256 bytes) in front and behind (dense: the rows and nothing else); the bytes of the rows that are
+    in no run, and every byte between the rows, are the fill.  Where that exceeds 2^28 bytes the allocation is left as it
+    comes and only the rows, with FAR_GUARD bytes of fill on either side, are written."""
+    S, F, row = raw.shape
+    used = packet_run_mask(L, row)
+    slack = 0 if dense else (row + 255) & ~255
+    first = slack + off
+    starts = sorted(first + s * sst + f * fst for s in range(S) for f in range(F))
+    assert all(b - a >= row for a, b in zip(starts, starts[1:])), "rows overlap"
+    n = starts[-1] + row + slack
+
+    def image(lo, hi):
+        host = packet_fill(lo, hi)
+        for s in range(S):
+            for f in range(F):
+                a = first + s * sst + f * fst
+                if lo <= a and a + row <= hi:
+                    host[a - lo:a - lo + row] = np.where(used, raw[s, f], host[a - lo:a - lo + row])
+        return host
+
+    if n < (1 << 28):
+        return _Packets(backend.upload(image(0, n)), first, n, [(0, n)], backend)
+    t = backend.empty(n, np.uint8)
+    zones = []
+    for a in starts:        # rows closer than the guards share a zone
+        lo, hi = max(a - FAR_GUARD, 0), min(a + row + FAR_GUARD, n)
+        if zones and lo <= zones[-1][1]:
+            zones[-1] = (zones[-1][0], hi)
+        else:
+            zones.append((lo, hi))
+    for lo, hi in zones:
+        backend.assign(t, lo, image(lo, hi))
+    return _Packets(t, first, n, zones, backend)
+
+
+PlacedPackets = namedtuple("PlacedPackets", "keep d_raw stream_stride frame_stride")
+
+
+def place_packets(raw, L, layout, f0=0, nf=None, backend=TORCH, keep=None, longest=PK_LONGEST):
+    """raw: numpy uint8 [S][F][row] and L, the rows and the layout of lpcm_util.rows.  Returns PlacedPackets(keep, d_raw,
+    raw_stream_stride, raw_frame_stride) for the call that starts at frame f0 and takes nf frames; keep is what holds the
+    device memory (pass it back for the next call of the same rows instead of placing them again)."""
+    S, F, row = raw.shape
+    assert row % 16 == 0 and 0 <= f0 and f0 + (nf or 0) <= F
+    off, fst, sst = packet_geometry(layout, S, F, row, L.sample_bytes, longest)
+    if keep is None:
+        keep = _place_packets(np.ascontiguousarray(raw, dtype=np.uint8), L, off, fst, sst, layout == PK_DENSE, backend)
+    return PlacedPackets(keep, keep.ptr(f0 * fst), sst, fst)
 
 
 def hip_render(matrix, out_ch, x, frame_size, fmt=A.FMT_S16, limiter=True, flush=True,

@@ -1,5 +1,5 @@
-"""LPCM packet rows for iamf_hip_batch_render_lpcm and the loop that renders them (shared by tests/test_gpu_lpcm.py and
-tests/route_cases.py)."""
+"""LPCM packet rows for iamf_hip_batch_render_lpcm and the loop that renders them (shared by tests/test_gpu_lpcm.py,
+tests/test_gpu_lpcm24.py, tests/test_gpu_packet_layouts.py and tests/route_cases.py)."""
 import numpy as np
 
 import gpu_util as G
@@ -51,45 +51,81 @@ def rows(ints, bps, le, widths, perm, head, pad, frame_size):
     return raw, L, row
 
 
-def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_samples=0, fmt=A.FMT_S16, layout=G.DENSE):
-    """layout: of the PCM rows only (gpu_util.pcm_rows); the packet rows have head, pad and perm"""
+def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_samples=0, fmt=A.FMT_S16, layout=G.DENSE,
+                packets=None, trims=None, emitted=None, refused=None):
+    """layout: of the PCM rows (gpu_util.pcm_rows).  packets: a packet layout of gpu_util (place_packets: the rows placed
+    under it, every byte outside the runs the 0x7F / 0x80 fill); None: the rows as they are, dense, at the start of a fresh
+    allocation.  trims: {call number: (first_sample, n_samples)} in place of first / n_samples for every call.  emitted:
+    a list that receives what every call and the flush said it emitted.  refused: (packet layout, error code, frames) —
+    before anything is rendered a call of that many frames is made under that packet layout and must be refused with that
+    code, leaving its PCM rows and (as the result shows) the batch untouched."""
     S, F, _ = raw.shape
     import torch
-    d_raw = torch.from_numpy(raw).cuda()
-    bps_out = {A.FMT_S16: 2, A.FMT_S24: 3, A.FMT_S32: 4}[fmt]
-    b = A.Batch(S, matrix, out_ch, frame_size=frame_size, out_format=fmt, limiter=True)
+    bps_out = {A.FMT_S16: 2, A.FMT_S24: 3, A.FMT_S32: 4, A.FMT_F32: 4}[fmt]
     st = torch.cuda.current_stream().cuda_stream
     outs = [[] for _ in range(S)]
-    f0 = 0
-    for nf in calls:
+    d_raw = keep = pcm = None
+    b = A.Batch(S, matrix, out_ch, frame_size=frame_size, out_format=fmt, limiter=True)
+
+    def packets_at(pk, f0, nf, keep):
+        """-> (iamf_hip_lpcm_input of the call, what holds its memory)"""
+        inp = A.LpcmInput()
+        if pk is None:
+            inp.d_raw, inp.raw_stream_stride, inp.raw_frame_stride = d_raw.data_ptr() + f0 * row, F * row, row
+        else:
+            pl = G.place_packets(raw, L, pk, f0, nf, keep=keep)
+            inp.d_raw, inp.raw_stream_stride, inp.raw_frame_stride, keep = pl.d_raw, pl.stream_stride, pl.frame_stride, pl.keep
+        inp.layout = L
+        return inp, keep
+
+    def call(inp, nf, trim):
         cap = max(nf * frame_size, 240) * out_ch * bps_out
         pcm, d_pcm, stride = G.pcm_rows(S, cap, layout, bps_out)
-        inp = A.LpcmInput()
-        inp.d_raw = d_raw.data_ptr() + f0 * row
-        inp.raw_stream_stride = F * row
-        inp.raw_frame_stride = row
-        inp.first_sample = first
-        inp.layout = L
+        inp.first_sample = trim[0]
         a = A.RenderArgs()
-        a.n_frames = nf
-        a.n_samples = n_samples
-        a.d_pcm = d_pcm
-        a.pcm_stream_stride_bytes = stride
-        a.stream = st
-        n = b.render_lpcm(inp, a)
+        a.n_frames, a.n_samples, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, trim[1], d_pcm, stride, st
+        return pcm, a
+
+    try:
+        if packets is None:
+            d_raw = torch.from_numpy(raw).cuda()
+        if refused:
+            r_pk, code, nf = refused
+            inp, r_keep = packets_at(r_pk, 0, nf, None)
+            pcm, a = call(inp, nf, (0, 0))
+            try:
+                b.render_lpcm(inp, a)
+                raise AssertionError("a call under %s was not refused" % r_pk.name)
+            except A.IamfHipError as e:
+                assert e.code == code, (r_pk.name, e.code, code)
+            torch.cuda.synchronize()
+            G.rows_and_rest(pcm, layout, 0)
+            pcm = r_keep = None
+        f0 = 0
+        for k, nf in enumerate(calls):
+            inp, keep = packets_at(packets, f0, nf, keep)
+            pcm, a = call(inp, nf, (trims or {}).get(k, (first, n_samples)))
+            n = b.render_lpcm(inp, a)
+            torch.cuda.synchronize()
+            h = G.rows_and_rest(pcm, layout, n * out_ch * bps_out)
+            pcm = None
+            for s in range(S):
+                outs[s].append(h[s])
+            if emitted is not None:
+                emitted.append(n)
+            f0 += nf
+        cap = 240 * out_ch * bps_out
+        pcm, d_pcm, stride = G.pcm_rows(S, cap, layout, bps_out)
+        n = b.flush(d_pcm, stride, st)
         torch.cuda.synchronize()
         h = G.rows_and_rest(pcm, layout, n * out_ch * bps_out)
         for s in range(S):
             outs[s].append(h[s])
-        f0 += nf
-    cap = 240 * out_ch * bps_out
-    pcm, d_pcm, stride = G.pcm_rows(S, cap, layout, bps_out)
-    n = b.flush(d_pcm, stride, st)
-    torch.cuda.synchronize()
-    h = G.rows_and_rest(pcm, layout, n * out_ch * bps_out)
-    for s in range(S):
-        outs[s].append(h[s])
-    b.close()
+        if emitted is not None:
+            emitted.append(n)
+    finally:
+        d_raw = keep = pcm = None     # the far layouts hold gigabytes
+        b.close()
     return [np.concatenate(o) for o in outs]
 
 

@@ -14,6 +14,7 @@
 namespace {
 #include "../../iac_amd/csrc/render_params.hpp"
 #include "../../iac_amd/csrc/render_route.hpp"
+#include "../../iac_amd/csrc/lpcm_form.hpp"
 
 const char *family_name(Family f) {
   static const char *const names[] = {"Refused", "Lpcm",      "FirSplit", "FirFused", "FastDown", "Wide4Lfe", "Wide4",
@@ -116,6 +117,72 @@ void list_checks() {
   printf("%-72s %s\n", "dispatch: the matching constant once, false outside the list", ok ? "ok" : "WRONG");
   ++g_cases;
   g_failed += ok ? 0 : 1;
+}
+
+// ---- the packet layouts of tests/gpu_util.py (the PK_ table there), 16-bit packets ----
+// tests/test_gpu_packet_layouts.py renders 3 streams of four 1024-sample frames in calls of 1 and 3 frames and expects, per
+// layout, the packet-fed kernel or the unpacker in front of the f32 kernel.  Each row is the geometry of one of those calls:
+// d_raw's residue, both strides, the frames; it asserts lpcm_form()'s answer and, where the form is admitted, pick_route()'s
+// family.  A call that is not fused is unpacked into dense f32 rows, which the aligned stereo block's route renders.
+void packet_layout_rows(const RenderParams &st) {
+  constexpr int kCh = 16, kF = 4, kG = 8;
+  constexpr int64_t kPkRow = 32912;   // lpcm_util.rows: 16 runs of 2048 bytes, head 8, pad 8, rounded up to 16
+  constexpr int64_t k31 = (int64_t)1 << 31;
+  constexpr int64_t kB3 = ((k31 - (1 << 24) - 1) / 5) & ~(int64_t)15;   // B(3): (3 + 2) * B + 2^24 < 2^31
+  static_assert(kB3 == 426141280 && 5 * kB3 + (1 << 24) < k31 && 5 * (kB3 + 16) + (1 << 24) >= k31 && 3 * (kB3 + 16) + (1 << 24) < k31,
+                "B(3)");
+  iamf_hip_lpcm_layout L;
+  memset(&L, 0, sizeof(L));
+  L.sample_bytes = 2;
+  L.little_endian = 1;
+  L.channels = kCh;
+  L.frame_size = 1024;
+  for (int c = 0; c < kCh; ++c) {   // reversed channel order: no offset ascends
+    L.src_offset[c] = 8 + (kCh - 1 - c) * (2048 + 8);
+    L.src_step[c] = 2;
+  }
+  struct Pk {
+    const char *name;
+    int64_t off, fst, sst;
+    bool fused[2];   // the call of 1 frame from frame 0, the call of 3 frames from frame 1
+  };
+  const Pk rows[] = {
+      {"PK_DENSE", 0, kPkRow, kF * kPkRow, {true, true}},
+      {"PK_PAD16", 16, kPkRow + 16, kF * (kPkRow + 16) + 48, {true, true}},
+      {"PK_GRID", 16, kPkRow + kG, kF * (kPkRow + kG) + kG, {true, false}},
+      {"PK_OFF_BASE", 8, kPkRow + 16, kF * (kPkRow + 16), {false, false}},
+      {"PK_OFF_STRIDE", 0, kPkRow + kG / 2, kF * (kPkRow + kG / 2), {false, false}},
+      {"PK_FAR_STREAMS", 16, kPkRow, k31 + 16, {true, true}},
+      {"PK_BOUND", 0, kB3, kF * kB3, {true, true}},
+      {"PK_BEYOND", 0, kB3 + 16, kF * (kB3 + 16), {true, false}},
+  };
+  const int f0s[2] = {0, 1}, nfs[2] = {1, 3};
+  for (const Pk &r : rows) {
+    for (int call = 0; call < 2; ++call) {
+      const uintptr_t raw = 0x50000 + (uintptr_t)((r.off + f0s[call] * r.fst) & 15);
+      const LpcmForm form = lpcm_form(L, kCh, r.sst, r.fst, raw, 0);
+      RenderParams p = st;
+      p.n_streams = p.n_launch = 3;
+      p.pos0 = (int64_t)f0s[call] * 1024;
+      p.total = nfs[call] * 1024;
+      const Route f32 = pick_route(p, kCh);   // the unpacked call: dense f32 rows of the batch's own buffer
+      p.lpcm = reinterpret_cast<const uint8_t *>(raw);
+      p.lpcm_frame_stride = r.fst;
+      p.lpcm_stream_stride = r.sst;
+      p.lpcm_bytes = lpcm_form_bytes(form);
+      const Route rt = form == LpcmForm::None ? Route{Family::Refused, 0, IAMF_HIP_ERR_INVALID_STATE} : pick_route(p, kCh);
+      const bool fused = form == LpcmForm::S16 && rt.family == Family::Lpcm && rt.variant == 1;
+      const bool form_ok = (form == LpcmForm::S16) == (r.fused[call] || !strcmp(r.name, "PK_BEYOND"));
+      const bool ok = form_ok && form != LpcmForm::S24 && fused == r.fused[call] &&
+                      (fused || rt.family == Family::Refused) && f32.family == Family::Fast && f32.variant == 0;
+      char what[96];
+      snprintf(what, sizeof(what), "%s, %d frame(s) from frame %d: %s", r.name, nfs[call], f0s[call],
+               r.fused[call] ? "Lpcm, early" : "unpack + Fast");
+      printf("%-72s form %d %s/%d/%d %s\n", what, (int)form, family_name(rt.family), rt.variant, rt.err, ok ? "ok" : "WRONG");
+      ++g_cases;
+      g_failed += ok ? 0 : 1;
+    }
+  }
 }
 
 // ---- the address rules: pointers, strides and the 32-bit bounds ----
@@ -322,6 +389,7 @@ int main() {
          IAMF_HIP_ERR_INVALID_STATE);
 
   address_rules(st, w, nl, f16, lp);
+  packet_layout_rows(st);
 
   printf("%d cases, %d wrong\n", g_cases, g_failed);
   if (!g_failed) printf("OK\n");

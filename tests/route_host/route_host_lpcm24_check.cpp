@@ -96,6 +96,74 @@ iamf_hip_lpcm_layout with_l(iamf_hip_lpcm_layout L, F f) {
   return L;
 }
 
+// ---- the packet layouts of tests/gpu_util.py (the PK_ table there), 24-bit packets ----
+// As packet_layout_rows() of route_host_check.cpp: one row per layout and call of tests/test_gpu_packet_layouts.py (3 streams,
+// four 1024-sample frames, a call of 1 frame from frame 0 and one of 3 frames from frame 1), lpcm_form()'s answer and
+// pick_route()'s family; a call that is not fused is unpacked into dense f32 rows for the f32 kernel.
+void packet_layout_rows() {
+  constexpr int kCh = 16, kF = 4, kG = 4;
+  constexpr int64_t kPkRow = 49232;   // lpcm_util.rows: 16 runs of 3072 bytes, head 4, pad 4, rounded up to 16
+  constexpr int64_t k31 = (int64_t)1 << 31;
+  constexpr int64_t kB3 = ((k31 - (1 << 24) - 1) / 5) & ~(int64_t)15;   // B(3): (3 + 2) * B + 2^24 < 2^31
+  static_assert(kB3 == 426141280 && 5 * kB3 + (1 << 24) < k31 && 5 * (kB3 + 16) + (1 << 24) >= k31 && 3 * (kB3 + 16) + (1 << 24) < k31,
+                "B(3)");
+  iamf_hip_lpcm_layout L = layout(kCh, 3, 4, 4);
+  for (int c = 0; c < kCh / 2; ++c) {   // reversed channel order: no offset ascends
+    const int32_t o = L.src_offset[c];
+    L.src_offset[c] = L.src_offset[kCh - 1 - c];
+    L.src_offset[kCh - 1 - c] = o;
+  }
+  struct Pk {
+    const char *name;
+    int64_t off, fst, sst;
+    bool fused[2];
+  };
+  const Pk rows[] = {
+      {"PK_DENSE", 0, kPkRow, kF * kPkRow, {true, true}},
+      {"PK_PAD16", 16, kPkRow + 16, kF * (kPkRow + 16) + 48, {true, true}},
+      {"PK_GRID", 16, kPkRow + kG, kF * (kPkRow + kG) + kG, {true, false}},
+      {"PK_OFF_BASE", 8, kPkRow + 16, kF * (kPkRow + 16), {false, false}},
+      {"PK_OFF_STRIDE", 0, kPkRow + kG / 2, kF * (kPkRow + kG / 2), {false, false}},
+      {"PK_FAR_STREAMS", 16, kPkRow, k31 + 16, {true, true}},
+      {"PK_BOUND", 0, kB3, kF * kB3, {true, true}},
+      {"PK_BEYOND", 0, kB3 + 16, kF * (kB3 + 16), {true, false}},
+  };
+  const int f0s[2] = {0, 1}, nfs[2] = {1, 3};
+  for (const Pk &r : rows) {
+    for (int c = 0; c < 2; ++c) {
+      const uintptr_t raw = kRaw + (uintptr_t)((r.off + f0s[c] * r.fst) & 15);
+      const LpcmForm form = lpcm_form(L, kCh, r.sst, r.fst, raw, 0);
+      RenderParams p = call(kCh, 2, lpcm_form_bytes(form));
+      p.n_streams = p.n_launch = 3;
+      p.pos0 = (int64_t)f0s[c] * 1024;
+      p.total = nfs[c] * 1024;
+      p.lpcm = reinterpret_cast<const uint8_t *>(raw);
+      p.lpcm_frame_stride = r.fst;
+      p.lpcm_stream_stride = r.sst;
+      RenderParams q = p;   // the unpacked call: dense f32 rows of the batch's own buffer
+      q.lpcm = nullptr;
+      q.lpcm_frame_stride = q.lpcm_stream_stride = 0;
+      q.lpcm_bytes = 0;
+      q.in_frame_stride = (int64_t)kCh * 1024;
+      q.in_stream_stride = nfs[c] * q.in_frame_stride;
+      const Route f32 = pick_route(q, kCh);
+      bool ok = f32.family == Family::Fast && f32.variant == 0 && form != LpcmForm::S16;
+      ok = ok && (form == LpcmForm::S24) == (r.fused[c] || !strcmp(r.name, "PK_BEYOND"));
+      for (int early = 0; early < 2; ++early) {   // under either switch, as the GPU test forces the variant
+        setenv(early ? "IAMF_HIP_LP_EARLY" : "IAMF_HIP_LP_LATE", "1", 1);
+        const Route rt = form == LpcmForm::None ? Route{Family::Refused, 0, IAMF_HIP_ERR_INVALID_STATE} : pick_route(p, kCh);
+        unsetenv(early ? "IAMF_HIP_LP_EARLY" : "IAMF_HIP_LP_LATE");
+        const bool fused = rt.family == Family::Lpcm24 && rt.variant == early;
+        ok = ok && fused == r.fused[c] && (fused || rt.family == Family::Refused);
+      }
+      char what[128];
+      snprintf(what, sizeof(what), "%s, %d frame(s) from frame %d: %s", r.name, nfs[c], f0s[c],
+               r.fused[c] ? "Lpcm24, the variant asked for" : "unpack + Fast");
+      row(what, ok);
+    }
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -205,6 +273,8 @@ int main() {
   row("  src_step == 4", form(with_l(L16, [](iamf_hip_lpcm_layout &L) { L.src_step[0] = 4; }), 16) == LpcmForm::None);
   row("  a missing channel", form(with_l(L16, [](iamf_hip_lpcm_layout &L) { L.src_offset[0] = -1; }), 16) == LpcmForm::None);
   row("  big-endian", form(with_l(L16, [](iamf_hip_lpcm_layout &L) { L.little_endian = 0; }), 16) == LpcmForm::None);
+
+  packet_layout_rows();
 
   printf("%d cases, %d wrong\n", g_cases, g_failed);
   if (!g_failed) printf("OK\n");

@@ -57,7 +57,7 @@ ROUTED = {
     "WIDE4_DOWN":  (GENERIC,  GENERIC),
     "WIDE4_MIX":   (GENERIC,  GENERIC),
     "WIDE4_LFE":   (GENERIC,  GENERIC),
-    "LPCM":        (SAME,     GENERIC),    # the packets keep their place; an offset PCM: unpacked, then the f32 path
+    "LPCM":        (SAME,     GENERIC),    # where the packets lie: tests/test_gpu_packet_layouts.py; an offset PCM: unpacked, then the f32 path
     "FANOUT":      (SINGLY,   SINGLY),     # no member is a call of the fast kernel: each is rendered on its own
     "FIR_SPLIT":   (REFUSED,  REFUSED),
     "FIR_FUSED":   (REFUSED,  REFUSED),

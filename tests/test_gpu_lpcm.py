@@ -159,6 +159,18 @@ def test_a_trimmed_frame(first, count):
         assert np.array_equal(got[s], np.concatenate(want[s])), "stream %d" % s
 
 
+@pytest.mark.parametrize("early", [1, 0])
+@pytest.mark.parametrize("first,n_samples", [(24, 1000), (0, 237), (0, 3)])
+def test_positions_off_the_16_sample_grid(first, n_samples, early, monkeypatch):
+    """a trimmed first frame leaves the streams off the grid of the limiter's 16-blocks: the packet-fed kernel takes whole
+    frames from there once the position has reached 240 (tests/test_gpu_lpcm24.py, check_off_grid: the same check on the
+    24-bit form)"""
+    import test_gpu_lpcm24 as T24
+    for k in T24.SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    T24.check_off_grid(2, first, n_samples, early)
+
+
 def test_bad_arguments_are_refused():
     mx = A.get_h2m_matrix(3, A.SS["BINAURAL"])
     b = A.Batch(2, mx, 2, frame_size=1024, out_format=A.FMT_S16, limiter=True)

@@ -53,18 +53,21 @@ def _reset(A):
     A.route_table_tally(2, reset=True)
 
 
-def _render(mx, oc, raw, L, row, fs, calls, first=0, n_samples=0, args_hook=None, batch_hook=None):
-    """lpcm_util.render_lpcm that also returns what every call (and the flush) said it emitted"""
+def _render(mx, oc, raw, L, row, fs, calls, first=0, n_samples=0, args_hook=None, batch_hook=None, fmt=None):
+    """lpcm_util.render_lpcm that also returns what every call (and the flush) said it emitted; fmt: the PCM format
+    (None: s16), the streams come back as gpu_util._view gives them"""
     import torch
     A, G, O = _mods()
     S, F, _ = raw.shape
     d_raw = torch.from_numpy(raw).cuda()
-    b = A.Batch(S, mx, oc, frame_size=fs, out_format=A.FMT_S16, limiter=True)
+    fmt = A.FMT_S16 if fmt is None else fmt
+    bps = {A.FMT_S16: 2, A.FMT_S24: 3, A.FMT_S32: 4, A.FMT_F32: 4}[fmt]
+    b = A.Batch(S, mx, oc, frame_size=fs, out_format=fmt, limiter=True)
     keep = batch_hook(b) if batch_hook else None
     st = torch.cuda.current_stream().cuda_stream
     outs, ns, f0 = [[] for _ in range(S)], [], 0
     for nf in calls:
-        cap = max(nf * fs, 240) * oc * 2
+        cap = max(nf * fs, 240) * oc * bps
         pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
         inp = A.LpcmInput()
         inp.d_raw, inp.raw_stream_stride, inp.raw_frame_stride = d_raw.data_ptr() + f0 * row, F * row, row
@@ -77,19 +80,19 @@ def _render(mx, oc, raw, L, row, fs, calls, first=0, n_samples=0, args_hook=None
         del held
         h = pcm.cpu().numpy()
         for s in range(S):
-            outs[s].append(h[s, :n * oc * 2].copy())
+            outs[s].append(h[s, :n * oc * bps].copy())
         ns.append(n)
         f0 += nf
-    pcm = torch.zeros((S, 240 * oc * 2), dtype=torch.uint8, device="cuda")
-    n = b.flush(pcm.data_ptr(), 240 * oc * 2, st)
+    pcm = torch.zeros((S, 240 * oc * bps), dtype=torch.uint8, device="cuda")
+    n = b.flush(pcm.data_ptr(), 240 * oc * bps, st)
     torch.cuda.synchronize()
     h = pcm.cpu().numpy()
     for s in range(S):
-        outs[s].append(h[s, :n * oc * 2].copy())
+        outs[s].append(h[s, :n * oc * bps].copy())
     ns.append(n)
     b.close()
     del keep
-    return [np.concatenate(o).view(np.int16).reshape(-1, oc) for o in outs], ns
+    return [G._view(np.concatenate(o), sum(ns), oc, fmt) for o in outs], ns
 
 
 def _fill_gaps(raw, L, fs, bps, m):
@@ -107,20 +110,26 @@ def _planar(ints, perm, bps=3):
     return np.ascontiguousarray(x.transpose(0, 2, 1, 3)).reshape(S, m, F * fs)
 
 
-def check_fused(mx, omx, oc, ints, fs, calls, early, head=16, pad=0, perm=None, first=0, n_samples=0, fill=False, what=""):
+def check_fused(mx, omx, oc, ints, fs, calls, early, head=16, pad=0, perm=None, first=0, n_samples=0, fill=False, what="", bd=16,
+                check=None):
+    """bd: the PCM format as tests/test_gpu_programmes.py names it (16 / 24 / 32, -32 = f32); check: the streams held against
+    the oracle and the twin (None: all); early None: no switch, the variant the host's rule picks (the early one)"""
+    import test_gpu_programmes as TP
     A, G, O = _mods()
+    fmt = {16: A.FMT_S16, 24: A.FMT_S24, 32: A.FMT_S32, -32: A.FMT_F32}[bd]
     S, F, m, _ = ints.shape
     perm = list(range(m)) if perm is None else perm
     raw, L, row = LP.rows(ints, 3, True, [1] * m, perm, head=head, pad=pad, frame_size=fs)
     if fill:
         raw = _fill_gaps(raw, L, fs, 3, m)
-    with R.environment(_variant(early)):
+    with R.environment({} if early is None else _variant(early)):
         _reset(A)
-        got, ns = _render(mx, oc, raw, L, row, fs, calls, first, n_samples)
+        got, ns = _render(mx, oc, raw, L, row, fs, calls, first, n_samples, fmt=fmt)
         t2, base, ext = A.route_table_tally(2, reset=True), A.route_tally(), A.route_tally_ext()
     with R.environment({"IAMF_HIP_LPCM_UNFUSED": "1"}):
-        twin, ns_twin = _render(mx, oc, raw, L, row, fs, calls, first, n_samples)
+        twin, ns_twin = _render(mx, oc, raw, L, row, fs, calls, first, n_samples, fmt=fmt)
         t2_twin, base_twin = A.route_table_tally(2, reset=True), A.route_tally()
+    early = 1 if early is None else early
     assert t2 == {("LPCM24", early, m, oc, 0): len(calls)}, (what, t2)
     assert base == {R.gen(m): 1} and ext == {}, (what, base, ext)
     assert t2_twin == {} and base_twin == {("FAST", 0, m, oc, 0): len(calls), R.gen(m): 1}, (what, t2_twin, base_twin)
@@ -130,10 +139,10 @@ def check_fused(mx, omx, oc, ints, fs, calls, early, head=16, pad=0, perm=None, 
         x, ofs = np.ascontiguousarray(x[:, :, first:first + n_samples]), n_samples
     else:
         ofs = fs
-    for s in range(S):
-        want = O.stream_run(omx, oc, x[s], ofs)
-        assert got[s].shape == want.shape and np.array_equal(got[s], want), (what, "stream %d against the oracle" % s)
-        assert np.array_equal(got[s], twin[s]), (what, "stream %d against the unfused twin" % s)
+    for s in (range(S) if check is None else check):
+        want = TP.oracle_stream(O, omx, oc, x[s], ofs, bd)
+        assert TP.mismatch(got[s], want) is None, (what, "stream %d against the oracle" % s, TP.mismatch(got[s], want))
+        assert TP.mismatch(got[s], twin[s]) is None, (what, "stream %d against the unfused twin" % s, TP.mismatch(got[s], twin[s]))
 
 
 @pytest.mark.parametrize("early", [1, 0])
@@ -206,6 +215,131 @@ def test_programmes(early):
     ints[2, 0, :, 100:340] = np.where(np.arange(240) % 2 == 0, FULL - 1, -FULL)[None, :]
     mx, omx = TP.selection(m, oc)
     check_fused(mx, omx, oc, ints, fs, [1, 2, 1], early, perm=[2, 0, 3, 1])
+
+
+@pytest.mark.parametrize("m,oc,early", [(16, 2, 1), (16, 2, 0), (9, 1, 1)])
+@pytest.mark.parametrize("bd", [24, 32, -32])
+def test_into_s24_s32_and_f32_pcm(m, oc, early, bd):
+    """the kernel's other pack stages behind the 24-bit loads: against the unfused twin and, in the formats
+    tests/test_gpu_programmes.py compares, the oracle"""
+    mx, omx = R.matrices(m, oc)
+    ints = LP.ints(np.random.default_rng(2500 + 10 * m + oc), 3, 3, m, 1024, 3)
+    perm = list(np.random.default_rng(50 + m).permutation(m))
+    check_fused(mx, omx, oc, ints, 1024, [2, 1], early, perm=perm, bd=bd, what="bd %d" % bd)
+
+
+def test_1025_streams():
+    """more workgroups than the 16-bit form's early variant takes (tests/route_cases.py, lpcm_m1_oc2_1025_streams): the first,
+    the 1024th and the 1025th stream, under the variant the host's rule picks"""
+    mx, omx = R.matrices(1, 2)
+    ints = LP.ints(np.random.default_rng(2520), 1025, 1, 1, 1024, 3)
+    check_fused(mx, omx, 2, ints, 1024, [1], None, check=[0, 1023, 1024])
+
+
+def check_off_grid(sb, first, n_samples, early):
+    """A first one-frame call trimmed to [first, first + n_samples), two calls of a whole frame, the flush.  The tally follows
+    fast_shape_ok (render_route.hpp): the trimmed call is no call of the vector kernels (its sample count is no multiple of
+    64), a whole frame from a position of at least 240 is fused whatever its residue mod 16, one from an off-grid position
+    below 240 is not.  PCM against the oracle over the kept samples and against the unfused twin.  (Shared with
+    tests/test_gpu_lpcm.py for the 16-bit form.)"""
+    A, G, O = _mods()
+    m, oc, fs, S, F = 16, 2, 1024, 3, 3
+    fam = "LPCM24" if sb == 3 else "LPCM"
+    assert n_samples % 64 and first + n_samples <= fs
+    mx, omx = R.matrices(m, oc)
+    ints = LP.ints(np.random.default_rng(2530 + 7 * sb + n_samples), S, F, m, fs, sb)
+    perm = list(np.random.default_rng(n_samples).permutation(m))
+    raw, L, row = LP.rows(ints, sb, True, [1] * m, perm, head=16, pad=0, frame_size=fs)
+    raw = _fill_gaps(raw, L, fs, sb, m)
+    calls, trims = [1, 1, 1], {0: (first, n_samples)}
+
+    def run(env):
+        emitted = []
+        with R.environment(env):
+            _reset(A)
+            got = LP.render_lpcm(mx, oc, raw, L, row, fs, calls, trims=trims, emitted=emitted)
+            return got, emitted, A.route_tally(), A.route_tally_ext(), A.route_table_tally(2, reset=True)
+
+    got, ns, base, ext, t2 = run(_variant(early))
+    twin, ns_twin, base_twin, ext_twin, t2_twin = run({"IAMF_HIP_LPCM_UNFUSED": "1"})
+    fused = [pos >= 240 or pos % 16 == 0 for pos in (n_samples, n_samples + fs)]     # where the whole-frame calls start
+    general = 1 + fused.count(False) + 1                                               # the trimmed call, ..., the flush
+    inst = {(fam, early, m, oc, 0): fused.count(True)}
+    if sb == 3:
+        assert t2 == inst and base == {R.gen(m): general}, (t2, base)
+    else:
+        assert t2 == {} and base == {**inst, R.gen(m): general}, (t2, base)
+    assert ext == ext_twin == t2_twin == {}
+    assert base_twin == {("FAST", 0, m, oc, 0): fused.count(True), R.gen(m): general}, base_twin
+    assert ns == ns_twin, (ns, ns_twin)
+    x = _planar(ints, perm, sb)
+    kept = np.ascontiguousarray(np.concatenate([x[:, :, first:first + n_samples], x[:, :, fs:]], axis=2))
+    for s in range(S):
+        want = O.stream_run(omx, oc, kept[s], fs)
+        g = got[s].view(np.int16).reshape(-1, oc)
+        assert g.shape == want.shape and np.array_equal(g, want), "stream %d against the oracle" % s
+        assert np.array_equal(got[s], twin[s]), "stream %d against the unfused twin" % s
+
+
+@pytest.mark.parametrize("early", [1, 0])
+@pytest.mark.parametrize("first,n_samples", [(24, 1000), (0, 237), (0, 3)])
+def test_positions_off_the_16_sample_grid(first, n_samples, early):
+    check_off_grid(3, first, n_samples, early)
+
+
+@pytest.mark.parametrize("early", [1, 0])
+def test_stream_ranges_advance_on_their_own(early):
+    """iamf_hip_batch_render_lpcm_range over [0, 2) and [2, 5) of a 5-stream batch: the ranges take different frame counts
+    per round and in one round only the first advances; per stream against the oracle, and the PCM rows outside a call's
+    range keep their fill"""
+    import torch
+    A, G, O = _mods()
+    m, oc, fs, S, F = 16, 2, 1024, 5, 4
+    mx, omx = R.matrices(m, oc)
+    ints = LP.ints(np.random.default_rng(2540), S, F, m, fs, 3)
+    perm = list(np.random.default_rng(2541).permutation(m))
+    raw, L, row = LP.rows(ints, 3, True, [1] * m, perm, head=16, pad=0, frame_size=fs)
+    d_raw = torch.from_numpy(_fill_gaps(raw, L, fs, 3, m)).cuda()
+    ranges = [(0, 2), (2, 3)]
+    rounds = [(1, 2), (2, 0), (1, 2)]          # frames per range and round: 1 + 2 + 1 and 2 + 0 + 2
+    st = torch.cuda.current_stream().cuda_stream
+    outs = [[] for _ in range(S)]
+    at = [0, 0]
+    with R.environment(_variant(early)):
+        _reset(A)
+        b = A.Batch(S, mx, oc, frame_size=fs, out_format=A.FMT_S16, limiter=True)
+        try:
+            def take(rows, n, s0, cnt):
+                torch.cuda.synchronize()
+                h = G.rows_and_rest(rows, G.DENSE, n * oc * 2, only=(s0, cnt))
+                for s in range(s0, s0 + cnt):
+                    outs[s].append(h[s])
+
+            for frames in rounds:
+                for r, (s0, cnt) in enumerate(ranges):
+                    nf = frames[r]
+                    if not nf:
+                        continue
+                    rows, d_pcm, stride = G.pcm_rows(S, nf * fs * oc * 2, G.DENSE, 2)
+                    inp = A.LpcmInput()
+                    inp.d_raw, inp.raw_stream_stride, inp.raw_frame_stride, inp.layout = d_raw.data_ptr() + at[r] * row, F * row, row, L
+                    a = A.RenderArgs()
+                    a.n_frames, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, d_pcm, stride, st
+                    take(rows, b.render_lpcm_range(inp, a, s0, cnt), s0, cnt)
+                    at[r] += nf
+            for s0, cnt in ranges:
+                rows, d_pcm, stride = G.pcm_rows(S, 240 * oc * 2, G.DENSE, 2)
+                take(rows, b.flush_range(d_pcm, stride, st, s0, cnt), s0, cnt)
+        finally:
+            b.close()
+        t2, base, ext = A.route_table_tally(2, reset=True), A.route_tally(), A.route_tally_ext()
+    assert at == [F, F]
+    assert t2 == {("LPCM24", early, m, oc, 0): 5} and base == {R.gen(m): 2} and ext == {}, (t2, base, ext)
+    x = _planar(ints, perm)
+    for s in range(S):
+        want = O.stream_run(omx, oc, x[s], fs)
+        got = np.concatenate(outs[s]).view(np.int16).reshape(-1, oc)
+        assert got.shape == want.shape and np.array_equal(got, want), "stream %d" % s
 
 
 def test_fused_f32_unfused_and_16_bit_calls_follow_one_another_on_one_batch():
