@@ -1139,6 +1139,10 @@ static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, i
                              int32_t n_streams, hipStream_t st, iamf_hip_render_args &a) {
   const iamf_hip_lpcm_layout &L = in->layout;
   const int fs = b->cfg.frame_size, ch = b->d_pre ? b->pre_l : b->m, ns = b->cfg.n_streams;
+  // as many frames per launch as the grid's third dimension takes; a range too wide for one frame is refused before
+  // anything is allocated or queued
+  const int fmax = 65535 / n_streams;
+  if (fmax == 0) return IAMF_HIP_ERR_UNIMPLEMENTED;
   const size_t need = (size_t)ns * nf * ch * fs;
   if (need > b->lp_in_floats) {   // grows with the largest call seen
     const int q = quiesce(b);     // a render queued earlier may still be reading the old buffer
@@ -1152,9 +1156,6 @@ static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, i
     HIPCHK(hipMemset(b->d_lp_in, 0, sizeof(float) * need));
     b->lp_in_floats = need;
   }
-  // as many frames per launch as the grid's third dimension takes
-  const int fmax = 65535 / n_streams > 0 ? 65535 / n_streams : 0;
-  if (fmax == 0) return IAMF_HIP_ERR_UNIMPLEMENTED;
   const int64_t lp_stream_stride = (int64_t)nf * ch * fs;
   for (int f = 0; f < nf; f += fmax) {
     const int r = iamf_hip_lpcm_unpack_frames(

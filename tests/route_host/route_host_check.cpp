@@ -292,6 +292,53 @@ void address_rules(const RenderParams &st, const RenderParams &w, const RenderPa
              Family::Refused, 0, IAMF_HIP_ERR_BAD_ARG);
 }
 
+// ---- long-lived streams: the rules that read the position (fast_shape_ok, pos16, pos_any) ----
+// A 48 kHz stream passes 2^31 samples after 12.4 hours and 2^32 after 24.9.  The rules look at pos0 & 15 and at
+// pos0 < kDelay only, so a call at a large position takes the route the same call takes at a small position of the same
+// residue: 2^31 as 4096, 2^31 + 16 as 4112, 2^32 + 8 as 4104, 2^40 + 237 as 4333.  A rule that narrowed pos0 to 32 bits
+// would see 0, 16, 8 and 237: below kDelay, where the off-grid positions go to the generic kernel.
+void long_positions(const RenderParams &st, const RenderParams &w, const RenderParams &nl, const RenderParams &lp) {
+  constexpr int64_t k31 = (int64_t)1 << 31, k32 = (int64_t)1 << 32, k40 = (int64_t)1 << 40;
+  const int64_t pairs[4][2] = {{k31, 4096}, {k31 + 16, 4112}, {k32 + 8, 4104}, {k40 + 237, 4333}};
+  struct Block {
+    const char *name;
+    RenderParams p;
+    int m;
+    Family grid, off;   // the family on the 16-sample grid and off it
+    int variant;
+  };
+  const Block blocks[] = {
+      {"stereo", st, 16, Family::Fast, Family::Fast, 0},
+      {"stereo + second element", with(st, second_element), 16, Family::Fast, Family::Fast, 1},
+      {"down-mixer 8 -> 2", with(aligned(8, 2), down_mixer), 8, Family::FastDown, Family::FastDown, 0},
+      {"LPCM", lp, 16, Family::Lpcm, Family::Lpcm, 1},
+      {"12 channels", w, 16, Family::Wide4, Family::Wide4, 0},
+      {"12 channels + second element", with(w, second_element), 16, Family::Wide4Mix, Family::Wide4Mix, 0},
+      {"down-mixer 12 -> 6", with(aligned(12, 6), down_mixer), 12, Family::Wide4Down, Family::Wide4Down, 0},
+      {"demixer 12 -> 12", with(aligned(12, 12), demixer), 12, Family::Wide4Demix, Family::Wide4Demix, 0},
+      {"LFE, 12 channels", with(w, lfe), 16, Family::Wide4Lfe, Family::Generic, 0},
+      {"12 channels, s24", aligned(16, 12, IAMF_HIP_FMT_S24), 16, Family::Wide, Family::Generic, 0},
+      {"11 channels", aligned(12, 11), 12, Family::Wide, Family::Generic, 0},
+      {"limiter off", nl, 16, Family::Nolim, Family::Nolim, 0},
+  };
+  for (const Block &b : blocks) {
+    for (const auto &pr : pairs) {
+      RenderParams big = b.p, small = b.p;
+      big.pos0 = pr[0];
+      small.pos0 = pr[1];
+      const Route rs = pick_route(small, b.m);
+      const Family want = (pr[1] & 15) ? b.off : b.grid;
+      // a family that differs between the grid and off it keeps its variant only on the grid
+      const int variant = want == Family::Generic ? 0 : b.variant;
+      char what[96];
+      snprintf(what, sizeof(what), "%s: pos0 = %lld as at %lld", b.name, (long long)pr[0], (long long)pr[1]);
+      expect(what, big, b.m, nullptr, rs.family, rs.variant, rs.err);
+      snprintf(what, sizeof(what), "%s: pos0 = %lld", b.name, (long long)pr[0]);
+      expect(what, big, b.m, nullptr, want, variant);
+    }
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -390,6 +437,7 @@ int main() {
 
   address_rules(st, w, nl, f16, lp);
   packet_layout_rows(st);
+  long_positions(st, w, nl, lp);
 
   printf("%d cases, %d wrong\n", g_cases, g_failed);
   if (!g_failed) printf("OK\n");

@@ -3,7 +3,9 @@ tests/route_host/route_host_check.cpp compiles it with the host compiler and che
 the expected kernel family, variant and return code (and the instance-list helper the launchers walk).  Every render
 kernel is exact, so a wrong routing decision is invisible to the parity tests and shows only as a slower rate; this
 is the test that sees it.  (That the routes are what gets launched: launch() in iamf_render.hip is a switch over them,
-and the GPU suites cover each family's results.)"""
+and the GPU suites cover each family's results.)  The table's last block holds the rules that read the stream position
+(fast_shape_ok, pos16, pos_any) at pos0 = 2^31, 2^31 + 16, 2^32 + 8 and 2^40 + 237: every such call must take the route
+the same call takes at 4096, 4112, 4104 and 4333."""
 import os
 import re
 import subprocess
@@ -22,5 +24,8 @@ def test_routing_table_on_the_host(tmp_path):
     assert p.returncode == 0, p.stdout + p.stderr
     out = p.stdout
     m = re.search(r"(\d+) cases, (\d+) wrong", out)
-    assert m and int(m.group(1)) >= 130 and int(m.group(2)) == 0, out
+    assert m and int(m.group(1)) >= 226 and int(m.group(2)) == 0, out
     assert "WRONG" not in out and out.strip().endswith("OK"), out
+    for pos, small in ((2 ** 31, 4096), (2 ** 31 + 16, 4112), (2 ** 32 + 8, 4104), (2 ** 40 + 237, 4333)):
+        for block in ("stereo", "12 channels", "12 channels, s24", "LFE, 12 channels", "LPCM", "limiter off"):
+            assert "%s: pos0 = %d as at %d" % (block, pos, small) in out, (block, pos)
