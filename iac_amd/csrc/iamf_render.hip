@@ -278,6 +278,9 @@ int reset_state(iamf_hip_batch *b) {
     HIPCHK(hipMemset(b->d_lfe_state, 0, sizeof(float) * 4 * (size_t)ns));
     HIPCHK(hipMemset(b->d_lfe_next, 0, sizeof(float) * 2 * (size_t)ns));
   }
+  // the copy and the memsets above went to the null stream: the caller's next render may run on a stream that does not
+  // wait for it, so the fresh state is in place before create / reset return
+  HIPCHK(hipStreamSynchronize(nullptr));
   b->spos.assign((size_t)ns, 0);
   b->sflushed.assign((size_t)ns, 0);
   b->any_rendered = false;
@@ -420,6 +423,8 @@ int lfe_prepass(iamf_hip_batch *b, const float *d_in, int64_t in_stream_stride, 
   const int ns = b->cfg.n_streams, nb = (ns + 63) / 64, t4 = (ltotal + 3) / 4;
   const size_t need_u = (size_t)nb * t4 * 64 * 4;
   if (need_u > b->lfe_u_floats) {  // grows with the largest call seen
+    const int q = quiesce(b);      // an earlier call on the batch may have used another stream
+    if (q != IAMF_HIP_OK) return q;
     HIPCHK(hipStreamSynchronize(st));
     (void)hipFree(b->d_lfe_u);
     b->d_lfe_u = nullptr;
@@ -598,6 +603,8 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       // the FFT stage's output of this call, [n_streams][2][total] (grows with the largest call seen)
       const size_t need = (size_t)b->cfg.n_streams * 2 * (size_t)total;
       if (need > b->fir_y_floats) {
+        const int q = quiesce(b);   // an earlier call on the batch may have used another stream
+        if (q != IAMF_HIP_OK) return q;
         HIPCHK(hipStreamSynchronize(static_cast<hipStream_t>(a.stream)));
         (void)hipFree(b->d_fir_y);
         b->d_fir_y = nullptr;
@@ -633,6 +640,8 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     const size_t per_stream = (size_t)(total > kDelay ? total : kDelay) * p.out_ch * bps;
     const size_t need = per_stream * (size_t)p.n_streams;
     if (need > b->nat_bytes) {
+      const int q = quiesce(b);   // an earlier call on the batch may have used another stream
+      if (q != IAMF_HIP_OK) return q;
       HIPCHK(hipStreamSynchronize(static_cast<hipStream_t>(a.stream)));
       (void)hipFree(b->d_nat);
       b->d_nat = nullptr;
@@ -1153,7 +1162,8 @@ static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, i
     b->lp_in_floats = 0;
     HIPCHK(hipMalloc(&b->d_lp_in, sizeof(float) * need));
     // rows of channels no sub-stream carries (src_offset < 0) are never written by the unpacker: keep them defined
-    HIPCHK(hipMemset(b->d_lp_in, 0, sizeof(float) * need));
+    // (on the call's stream, in front of the unpack kernel: a null-stream memset is not ordered with a non-blocking stream)
+    HIPCHK(hipMemsetAsync(b->d_lp_in, 0, sizeof(float) * need, st));
     b->lp_in_floats = need;
   }
   const int64_t lp_stream_stride = (int64_t)nf * ch * fs;

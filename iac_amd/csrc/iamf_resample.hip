@@ -740,7 +740,9 @@ int iamf_hip_resampler_create(int n_streams, int channels, int in_rate, int out_
       hipMemcpy(r->d_table, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice) != hipSuccess ||
       (!tab4.empty() && (hipMalloc(&r->d_table4, sizeof(float) * tab4.size()) != hipSuccess ||
                          hipMemcpy(r->d_table4, tab4.data(), sizeof(float) * tab4.size(), hipMemcpyHostToDevice) != hipSuccess)) ||
-      hipMemset(r->d_hist[0], 0, hist_bytes) != hipSuccess || hipMemset(r->d_hist[1], 0, hist_bytes) != hipSuccess) {
+      hipMemset(r->d_hist[0], 0, hist_bytes) != hipSuccess || hipMemset(r->d_hist[1], 0, hist_bytes) != hipSuccess ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {   // the null-stream work above is complete on return: the first
+                                                       // process call may use a stream that does not wait for it
     iamf_hip_resampler_destroy(r);
     return IAMF_HIP_ERR_DEVICE;
   }

@@ -11,7 +11,14 @@
  *
  * Pointers named d_* are DEVICE pointers owned by the caller (any allocator: hipMalloc, a
  * torch tensor's data_ptr ...).  `stream` is a hipStream_t passed as void* (NULL = default
- * stream).  Calls are asynchronous on that stream unless stated otherwise.
+ * stream).  Calls are asynchronous on that stream unless stated otherwise.  The stream may be one
+ * created with hipStreamNonBlocking: a call leaves no work on the null stream that its own stream
+ * could overtake (tests/test_gpu_streams.py).
+ * One exception holds for every render entry: scratch of the batch grows with the largest call seen
+ * (the LFE generator's pre-pass, the HRTF stage's output, the natural-layout rows of a fixed PCM
+ * channel stride, the f32 copy of unfused packets).  The call in which it grows waits, on the host,
+ * for the batch's last call (whatever stream that used) and for `stream`, then replaces the buffer.
+ * A call no larger than an earlier one on the same batch never waits.
  */
 #ifndef IAMF_HIP_H
 #define IAMF_HIP_H
@@ -142,12 +149,15 @@ typedef struct {
   int32_t reserved[2];
 } iamf_hip_batch_config;
 
-/* Creates device state for cfg->n_streams streams on the CURRENT HIP device.  Synchronous.
+/* Creates device state for cfg->n_streams streams on the CURRENT HIP device.  Synchronous: it waits
+ * for the null stream, and the state is in place on return, for a first render on any stream.
  * The batch remembers that device: every later call on it (setters, render, flush, reset) returns
  * IAMF_HIP_ERR_INVALID_STATE unless the same device is current; destroy switches to it and back.
  * Replaces, per stream: iamf_stream_renderer_open (IAMF_decoder.c:2480),
  * audio_effect_peak_limiter_create/_init (audio_effect_peak_limiter.c:50,73). */
 int iamf_hip_batch_create(const iamf_hip_batch_config *cfg, iamf_hip_batch **out);
+/* Synchronous: waits for the last call queued on the batch (the batch's own event, whatever stream
+ * that call used), then frees; the PCM of a render queued before it is complete when it returns. */
 void iamf_hip_batch_destroy(iamf_hip_batch *b);
 
 /* Per-stream linear gains (host arrays of n_streams floats, NULL = leave unchanged):
@@ -386,6 +396,9 @@ typedef struct iamf_hip_resampler iamf_hip_resampler;
  * iamf_stream_resampler_open calls them (IAMF_decoder.c:1892-1909); one state per stream */
 int iamf_hip_resampler_create(int n_streams, int channels, int in_rate, int out_rate,
                               iamf_hip_resampler **out);
+/* Create is synchronous: it waits for the null stream, and the tables and zeroed histories are in
+ * place on return, for a first call on any stream.  The resampler records no event: destroy frees
+ * at once, so the caller first waits for the calls it queued on it. */
 void iamf_hip_resampler_destroy(iamf_hip_resampler *r);
 /* sample-frames the output buffer must hold for ns input frames: ns * (out/in + 1), integer
  * division, as iamf_resample asks (IAMF_decoder.c:3225-3226) */
@@ -408,7 +421,8 @@ int iamf_hip_resampler_flush_range(iamf_hip_resampler *r, float *d_out, int64_t 
 int iamf_hip_resampler_same_state(const iamf_hip_resampler *r, int32_t stream_a, int32_t stream_b);
 
 /* Forgets all stream state (new IA sequence: limiter re-initialised as in
- * iamf_decoder_internal_configure, IAMF_decoder.c:3809-3815).  Synchronous. */
+ * iamf_decoder_internal_configure, IAMF_decoder.c:3809-3815).  Synchronous: waits for the whole
+ * device (every stream), and the fresh state is in place on return, for a next render on any stream. */
 int iamf_hip_batch_reset(iamf_hip_batch *b);
 
 /* ------------------------------------------------------------------------------------------
