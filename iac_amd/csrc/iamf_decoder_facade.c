@@ -262,6 +262,7 @@ struct IAMF_Decoder {
    * one mono-coded ambisonics element in 16-bit little-endian LPCM into one or two channels with the limiter on */
   uint8_t *h_raw;
   int lp_ok;
+  size_t lp_row_bytes; /* the raw row: every sub-stream of element 0 at its width */
   iamf_hip_lpcm_layout lp_layout;
   float gain_set[2]; /* element / output constant gains the batch holds (iamf_hip_batch_set_gains synchronises: only on change) */
   float *tmp; /* [MAX_SUBSTREAMS * 2][frame_size] unpack scratch */
@@ -301,6 +302,9 @@ static const int k_ss_layout[] = {IA_CHANNEL_LAYOUT_STEREO, IA_CHANNEL_LAYOUT_51
 static const int k_layout_channels[] = {1, 2, 6, 8, 10, 8, 10, 12, 6, 2};
 /* playback channel p of a layer layout is audio-layer channel k_al_of_pl[layout][p]
  * (IAMF_utils.c:117-133 vs :181-196) */
+/* sub-streams a channel-based element of `channels` channels couples when it couples every pair of its layout: all but C
+ * and LFE, which the layouts of six channels and more have */
+static int lp_canonical_coupled(int channels) { return channels >= 6 ? (channels - 2) / 2 : channels / 2; }
 static const int k_al_of_pl[9][12] = {
     {0}, {0, 1}, {0, 1, 4, 5, 2, 3}, {0, 1, 6, 7, 2, 3, 4, 5}, {0, 1, 8, 9, 2, 3, 4, 5, 6, 7},
     {0, 1, 6, 7, 2, 3, 4, 5}, {0, 1, 8, 9, 2, 3, 4, 5, 6, 7}, {0, 1, 10, 11, 2, 3, 4, 5, 6, 7, 8, 9},
@@ -1418,10 +1422,16 @@ static int setup_pipeline(struct IAMF_Decoder *d) {
      * fused kernel takes it and unpacks on the device otherwise; here: whether asking is worth it */
     const Element *e0 = d->sel_el[0];
     iamf_hip_lpcm_layout *L = &d->lp_layout;
-    d->lp_ok = p->nel == 1 && e0->type == AUDIO_ELEMENT_SCENE_BASED && !e0->amb_projection && !d->pre[0].use_dmx && !d->pre[0].use_demix &&
-               !resample && (d->sample_size == 16 || d->sample_size == 24) && d->little_endian && d->limiter_on && d->out_channels <= 2 &&
-               d->pcm_stride == d->out_channels && (d->frame_size & 63) == 0 && e0->nsub > 0 && e0->nsub <= MAX_SUBSTREAMS &&
-               (e0->channels == 1 || e0->channels == 4 || e0->channels == 9 || e0->channels == 16) && !getenv("IAMF_HIP_FACADE_UNPACK");
+    const int lp_common = p->nel == 1 && !d->pre[0].use_dmx && !d->pre[0].use_demix && !resample && d->little_endian && d->limiter_on &&
+                          d->out_channels <= 2 && d->pcm_stride == d->out_channels && (d->frame_size & 63) == 0 && e0->nsub > 0 &&
+                          e0->nsub <= MAX_SUBSTREAMS && !getenv("IAMF_HIP_FACADE_UNPACK");
+    /* a single-layer channel-based element, 16 bit, that couples every pair of its layout: the kernel's coupled form (a mono
+     * element: the mono-coded form, one channel) */
+    const int lp_chan = lp_common && e0->type == AUDIO_ELEMENT_CHANNEL_BASED && e0->nlayers == 1 && d->sample_size == 16 &&
+                        e0->nb_coupled == lp_canonical_coupled(e0->channels) && e0->nsub + e0->nb_coupled == e0->channels;
+    d->lp_ok = lp_chan || (lp_common && e0->type == AUDIO_ELEMENT_SCENE_BASED && !e0->amb_projection &&
+                           (d->sample_size == 16 || d->sample_size == 24) &&
+                           (e0->channels == 1 || e0->channels == 4 || e0->channels == 9 || e0->channels == 16));
     /* (16 or 24 bit: sub-stream s at s * frame_size * bytes, a multiple of 8 / of 4 with the frame size one of 64) */
     const int lp_bytes = d->sample_size == 24 ? 3 : 2;
     memset(L, 0, sizeof(*L));
@@ -1429,12 +1439,25 @@ static int setup_pipeline(struct IAMF_Decoder *d) {
     L->little_endian = 1;
     L->channels = e0->channels;
     L->frame_size = (int32_t)d->frame_size;
-    for (int c = 0; c < e0->channels && d->lp_ok; ++c) {
+    d->lp_row_bytes = (size_t)e0->nsub * d->frame_size * lp_bytes;
+    for (int c = 0; c < e0->channels && d->lp_ok && !lp_chan; ++c) {
       if (e0->amb_map[c] >= e0->nsub) d->lp_ok = 0; /* a channel no sub-stream carries: the f32 form zeroes it */
       L->src_offset[c] = (int32_t)(e0->amb_map[c] * d->frame_size * lp_bytes);
       L->src_step[c] = lp_bytes;
     }
-    if (d->lp_ok && hipHostMalloc((void **)&d->h_raw, (size_t)e0->nsub * d->frame_size * lp_bytes + 256, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
+    if (lp_chan) {
+      /* sub-streams at their width, one behind the other (coupled ones first: audio-layer channel a < 2 * nb_coupled is half
+       * a & 1 of sub-stream a >> 1); the renderer's order through k_al_of_pl as unpack_element.  Every offset a multiple of
+       * 8: the frame size is one of 64 */
+      const int nc = e0->nb_coupled;
+      d->lp_row_bytes = (size_t)e0->channels * d->frame_size * 2;
+      for (int c = 0; c < e0->channels; ++c) {
+        const int a = k_al_of_pl[e0->layout][c];
+        L->src_offset[c] = a < 2 * nc ? (int32_t)((a >> 1) * 4 * d->frame_size + (a & 1) * 2) : (int32_t)((nc * 4 + (a - 2 * nc) * 2) * d->frame_size);
+        L->src_step[c] = a < 2 * nc ? 4 : 2;
+      }
+    }
+    if (d->lp_ok && hipHostMalloc((void **)&d->h_raw, d->lp_row_bytes + 256, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   }
   d->pcm_cap = (size_t)4 * ((size_t)d->info.max_frame_size * d->pcm_stride + d->pcm_extra);
   if (hipHostMalloc(&d->h_pcm, d->pcm_cap, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
@@ -1635,18 +1658,22 @@ static int unpack_element(struct IAMF_Decoder *d, int ei) {
   return ns;
 }
 
-/* element 0's packets as they are -> the pinned raw row (sub-stream s at s * frame_size * sample bytes); unpack_element's
- * checks; returns samples per channel */
+/* element 0's packets as they are -> the pinned raw row (sub-streams one behind the other, each frame_size * sample bytes *
+ * its width: 2 for the coupled sub-streams of a channel-based element, which come first); unpack_element's checks; returns
+ * samples per channel */
 static int stage_lpcm_row(struct IAMF_Decoder *d) {
   const Element *e = d->sel_el[0];
   const int fs = (int)d->frame_size;
   const unsigned bps = (unsigned)d->lp_layout.sample_bytes;
   int ns = -1;
+  size_t off = 0;
   for (int s = 0; s < e->nsub; ++s) {
-    const int n = (int)(d->pkt_len[0][s] / bps);
+    const unsigned w = (e->type == AUDIO_ELEMENT_CHANNEL_BASED && s < e->nb_coupled) ? 2u : 1u;
+    const int n = (int)(d->pkt_len[0][s] / (w * bps));
     if (ns < 0) ns = n;
     if (n != ns || n > fs) return IAMF_ERR_INVALID_PACKET;
-    memcpy(d->h_raw + (size_t)s * fs * bps, d->pkt[0][s], (size_t)n * bps);
+    memcpy(d->h_raw + off, d->pkt[0][s], (size_t)n * w * bps);
+    off += (size_t)fs * w * bps;
   }
   return ns < 0 ? IAMF_ERR_INVALID_PACKET : ns;
 }
@@ -1857,7 +1884,7 @@ static int render_tu(struct IAMF_Decoder *d, void *pcm) {
     iamf_hip_lpcm_input in;
     memset(&in, 0, sizeof(in));
     in.d_raw = d->h_raw;
-    in.raw_stream_stride = in.raw_frame_stride = (int64_t)d->sel_el[0]->nsub * fs * d->lp_layout.sample_bytes;
+    in.raw_stream_stride = in.raw_frame_stride = (int64_t)d->lp_row_bytes;
     in.first_sample = s0;
     in.layout = d->lp_layout;
     a.d_pcm = d->h_pcm;

@@ -615,12 +615,20 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
   g->lp_ok = g->nel == 1 && !d0->pre[0].use_dmx && !d0->pre[0].use_demix && !d0->sel_el[0]->amb_projection &&
              (d0->sample_size == 16 || d0->sample_size == 24) &&
              d0->little_endian && d0->limiter_on && d0->out_channels <= 2 && d0->pcm_stride == d0->out_channels &&
-             d0->sel_el[0]->type == AUDIO_ELEMENT_SCENE_BASED && (g->fs & 63) == 0 && !d0->rs && !getenv("IAMF_HIP_GROUP_UNPACK");
-  /* (contiguous runs on the form's grid: 8 bytes for 16-bit samples, 4 for 24-bit ones) */
-  for (int c = 0; c < g->lay[0].channels && g->lp_ok; ++c)
-    if (g->lay[0].src_step[c] != g->lay[0].sample_bytes || g->lay[0].src_offset[c] < 0 ||
-        (g->lay[0].src_offset[c] & (g->lay[0].sample_bytes == 3 ? 3 : 7)))
-      g->lp_ok = 0;
+             (g->fs & 63) == 0 && !d0->rs && !getenv("IAMF_HIP_GROUP_UNPACK");
+  /* ... or one single-layer channel-based element, 16 bit, that couples every pair of its layout (the kernel's coupled
+   * form: group_build_layout has laid the pairs out as it wants them) or is mono */
+  const int lp_chan = d0->sel_el[0]->type == AUDIO_ELEMENT_CHANNEL_BASED && d0->sel_el[0]->nlayers == 1 && d0->sample_size == 16 &&
+                      d0->sel_el[0]->nb_coupled == lp_canonical_coupled(d0->sel_el[0]->channels) &&
+                      d0->sel_el[0]->nsub + d0->sel_el[0]->nb_coupled == d0->sel_el[0]->channels;
+  if (d0->sel_el[0]->type != AUDIO_ELEMENT_SCENE_BASED && !lp_chan) g->lp_ok = 0;
+  /* (contiguous runs on the form's grid: 8 bytes for 16-bit samples, 4 for 24-bit ones; a coupled pair's run: 8 bytes) */
+  for (int c = 0; c < g->lay[0].channels && g->lp_ok; ++c) {
+    const int step = g->lay[0].src_step[c], off = g->lay[0].src_offset[c];
+    if (off < 0) g->lp_ok = 0;
+    else if (lp_chan && step == 4) g->lp_ok = ((off - (off & 2)) & 7) == 0;
+    else if (step != g->lay[0].sample_bytes || (off & (g->lay[0].sample_bytes == 3 ? 3 : 7))) g->lp_ok = 0;
+  }
   for (int k = 0; k < 3; ++k) GCHK(!(g->cgain[k] = (float *)calloc((size_t)n, sizeof(float))));
   /* upload chunks: at most eight per round, at least eight handles each (an upload call costs ~4 us of host time) */
   g->chunk = (n + 7) / 8 < 8 ? 8 : (n + 7) / 8;

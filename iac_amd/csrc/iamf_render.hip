@@ -335,6 +335,7 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
     case Family::Refused: return r.err;
     case Family::Lpcm: launched = iamf_hip_fast_lpcm_launch(&p, m, r.variant, st); break;
     case Family::Lpcm24: launched = iamf_hip_fast_lpcm24_launch(&p, m, r.variant, st); break;
+    case Family::LpcmCoupled: launched = iamf_hip_fast_lpcm_coupled_launch(&p, m, r.variant, st); break;
     case Family::FirSplit: {
       // (1) the FFT stage for every hop of every stream -> y in HBM (overlap-save blocks are independent: one grid); (2)
       // gains, limiter, pack = the two-channel matrix kernel with the identity over y (one "frame" of `total` samples per
@@ -381,6 +382,7 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
   HIPCHK(hipGetLastError());
   const RouteKey k = route_key(r, p, m);   // the tally of iamf_hip_route_tally
   if (r.family == Family::Lpcm24) iamf_hip_route_count_table(2, k.family, k.variant, k.m, k.c, k.k);   // its own table
+  else if (r.family == Family::LpcmCoupled) iamf_hip_route_count_family(k.family, k.variant, k.m, k.c, k.k);   // no table's
   else iamf_hip_route_count(k.family, k.variant, k.m, k.c, k.k);
   if (r.family == Family::FirSplit) iamf_hip_route_count(IAMF_HIP_ROUTE_FAST, 0, 2, 2, 0);
   return IAMF_HIP_OK;
@@ -412,6 +414,7 @@ struct LpcmIn {
   int64_t stream_stride, frame_stride;
   int32_t off[16];
   int32_t bytes;   // per sample: 2 or 3 (lpcm_form.hpp)
+  int32_t coupled; // 1: LpcmForm::S16C, off[] of a pair's two channels 2 bytes apart
 };
 constexpr int kNotFused = INT32_MIN;
 
@@ -584,8 +587,11 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     p.lpcm_frame_stride = lp->frame_stride;
     for (int m = 0; m < 16; ++m) p.lpcm_off[m] = lp->off[m];
     p.lpcm_bytes = lp->bytes;
+    p.lpcm_coupled = lp->coupled;
     if (lp->bytes == 3 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
-    if (pick_route(p, m_eff).family != (lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm)) return kNotFused;
+    if (lp->coupled && !lpcm_coupled_fused(cnt)) return kNotFused;
+    if (pick_route(p, m_eff).family != (lp->coupled ? Family::LpcmCoupled : (lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm)))
+      return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -1097,7 +1103,8 @@ int iamf_hip_batch_render_range(iamf_hip_batch *b, const iamf_hip_render_args *a
 
 // Element 0 as LPCM packets.  Fused (render_fast_kernel<.., LP>: the packets' samples are converted where the render
 // kernel loads them) when the call is one of the headline kernel's and every channel is a contiguous run of little-endian
-// 16-bit or 24-bit samples on the form's grid (lpcm_form.hpp: 8 bytes / 4 bytes); in every other case exactly what the
+// 16-bit or 24-bit samples on the form's grid (lpcm_form.hpp: 8 bytes / 4 bytes), or the channels are the 16-bit coupled
+// pairs and mono runs of a loudspeaker layout (LpcmForm::S16C); in every other case exactly what the
 // caller would do itself: iamf_hip_lpcm_unpack into a buffer of the batch, then the f32 path.  Both give the same PCM
 // and leave the same stream state, bit for bit.
 int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args) {
@@ -1132,13 +1139,15 @@ static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *i
 }
 
 // packets of the fusable form as the fused kernels take them
-static void lpcm_in_of(const iamf_hip_lpcm_input *in, int ch, int first, LpcmIn &lp) {
+static void lpcm_in_of(const iamf_hip_lpcm_input *in, int ch, int first, LpcmForm form, LpcmIn &lp) {
   memset(&lp, 0, sizeof(lp));
   lp.raw = static_cast<const uint8_t *>(in->d_raw);
   lp.stream_stride = in->raw_stream_stride;
   lp.frame_stride = in->raw_frame_stride;
   lp.bytes = in->layout.sample_bytes;
-  for (int c = 0; c < ch; ++c) lp.off[c] = in->layout.src_offset[c] + lp.bytes * first;
+  lp.coupled = form == LpcmForm::S16C;
+  // (src_step: the sample bytes of a contiguous run, twice that for the halves of a coupled pair)
+  for (int c = 0; c < ch; ++c) lp.off[c] = in->layout.src_offset[c] + in->layout.src_step[c] * first;
 }
 
 // The RANGE's packets -> planar f32 in a buffer of the batch (rows indexed by the stream's number in the batch, as every
@@ -1195,7 +1204,7 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
   iamf_hip_render_args a = *args;
   if (form != LpcmForm::None) {
     LpcmIn lp;
-    lpcm_in_of(in, ch, first, lp);
+    lpcm_in_of(in, ch, first, form, lp);
     a.d_in = reinterpret_cast<const float *>(in->d_raw);   // not read by the fused kernel; non-null = "not a flush"
     a.in_stream_stride = a.in_frame_stride = 0;
     const int r = render_range_impl(b, &a, stream0, n_streams, &lp);
@@ -1459,7 +1468,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
   const int fc = lpcm_form_check(b0, in, n_frames, n_samples, &form, &first, &count);
   if (fc != IAMF_HIP_OK) return fc;
   // "the form the single call fuses" is the 16-bit one here: render_fanout_kernel<.., LP> reads no other, and 24-bit
-  // packets keep sharing one unpack pass and the f32 fan-out (include/iamf_hip.h)
+  // packets and coupled 16-bit ones (LpcmForm::S16C) keep sharing one unpack pass and the f32 fan-out (include/iamf_hip.h)
   const bool pk_form = form == LpcmForm::S16;
   iamf_hip_render_args args[IAMF_HIP_FANOUT_MAX];
   int64_t total = 0;
@@ -1491,7 +1500,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
     cls[j] = 0;
     if (pk_form) {
       LpcmIn lp;
-      lpcm_in_of(in, ch, first, lp);
+      lpcm_in_of(in, ch, first, form, lp);
       const int rc = render_prepare(b, args[j], (int)total, stream0, n_streams, &lp, pcs[j]);
       if (rc != kNotFused && rc != IAMF_HIP_OK) return rc;
       if (rc == IAMF_HIP_OK) {   // the member's single call takes Family::Lpcm (render_prepare has asked pick_route)

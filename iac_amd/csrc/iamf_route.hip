@@ -49,7 +49,9 @@ struct RouteTable {
       index[n] = n;
       ++n;
     };
-    if (table == 2) {
+    if (table == 3) {
+      for_each_render_instance_lpcm_coupled(add);
+    } else if (table == 2) {
       for_each_render_instance_lpcm24(add);
     } else if (table == 1) {
       for_each_render_instance_ext(add);
@@ -88,9 +90,16 @@ const RouteTable &route_table_lpcm24() {
   return t;
 }
 
+// behind the numbered tables: the coupled 16-bit LPCM form, listed per family only (iamf_hip_route_family_instances)
+const RouteTable &route_table_lpcm_coupled() {
+  static const RouteTable t(3);
+  return t;
+}
+
 std::atomic<int64_t> g_launches[kRouteCap + 1];
 std::atomic<int64_t> g_launches_ext[kRouteCap + 1];
 std::atomic<int64_t> g_launches_lpcm24[kRouteCap + 1];
+std::atomic<int64_t> g_launches_lpcm_coupled[kRouteCap + 1];
 
 // the indexed form: table 0 and 1 ARE the base and the extension listing (rows and counters), 2 onwards have their own
 constexpr int kRouteTables = 3;
@@ -100,6 +109,12 @@ const RouteTable *table_of(int table) {
 std::atomic<int64_t> *launches_of(int table) {
   return table == 0 ? g_launches : table == 1 ? g_launches_ext : table == 2 ? g_launches_lpcm24 : nullptr;
 }
+// The listing by family (iamf_hip_route_family_instances) walks every row set there is: the numbered tables, whose count is
+// pinned, and the sets added since, which have no number.  A family added to a set — or a set added here — is listed
+// without a new entry point.
+constexpr int kRouteSets = 4;
+const RouteTable *set_of(int set) { return set < kRouteTables ? table_of(set) : set == 3 ? &route_table_lpcm_coupled() : nullptr; }
+std::atomic<int64_t> *set_launches_of(int set) { return set < kRouteTables ? launches_of(set) : set == 3 ? g_launches_lpcm_coupled : nullptr; }
 
 int list_instances(const RouteTable &t, iamf_hip_route_row *rows, int cap) {
   for (int i = 0; rows && i < t.n && i < cap; ++i) rows[i] = t.rows[i];
@@ -122,7 +137,44 @@ int tally_of(const RouteTable &t, std::atomic<int64_t> *launches, iamf_hip_route
   return cnt;
 }
 
+// the rows of one family, in the order of their sets.  tally: only rows whose counter is not zero, with its value (reset:
+// and zeroed); else the listing.  -1: no set has a row of that family
+int family_rows(int family, bool tally, iamf_hip_route_row *rows, int cap, int reset) {
+  int cnt = 0;
+  bool known = false;
+  for (int set = 0; set < kRouteSets; ++set) {
+    const RouteTable &t = *set_of(set);
+    std::atomic<int64_t> *launches = set_launches_of(set);
+    for (int i = 0; i < t.n; ++i) {
+      if (t.rows[i].family != family) continue;
+      known = true;
+      int64_t v = 0;
+      if (tally) {
+        v = reset ? launches[i].exchange(0, std::memory_order_relaxed) : launches[i].load(std::memory_order_relaxed);
+        if (v == 0) continue;
+      }
+      if (rows && cnt < cap) {
+        rows[cnt] = t.rows[i];
+        rows[cnt].launches = v;
+      }
+      ++cnt;
+    }
+  }
+  return known ? cnt : -1;
+}
+
 }  // namespace
+
+void iamf_hip_route_count_family(int family, int variant, int m, int c, int k) {
+  const uint32_t key = pack_key(family, variant, m, c, k);
+  for (int set = 0; set < kRouteSets; ++set) {
+    const int i = set_of(set)->find(key);
+    if (i == kRouteCap) continue;
+    set_launches_of(set)[i].fetch_add(1, std::memory_order_relaxed);
+    return;
+  }
+  g_launches[kRouteCap].fetch_add(1, std::memory_order_relaxed);   // outside every set: the base tally's NONE row
+}
 
 void iamf_hip_route_count(int family, int variant, int m, int c, int k) {
   g_launches[route_table().find(pack_key(family, variant, m, c, k))].fetch_add(1, std::memory_order_relaxed);
@@ -149,6 +201,14 @@ int iamf_hip_route_table_instances(int table, iamf_hip_route_row *rows, int cap)
 int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int reset) {
   const RouteTable *t = table_of(table);
   return t ? tally_of(*t, launches_of(table), rows, cap, reset) : IAMF_HIP_ERR_BAD_ARG;
+}
+
+int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap) {
+  return family_rows(family, false, rows, cap, 0);
+}
+
+int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset) {
+  return family_rows(family, true, rows, cap, reset);
 }
 
 int iamf_hip_route_instances(iamf_hip_route_row *rows, int cap) { return list_instances(route_table(), rows, cap); }

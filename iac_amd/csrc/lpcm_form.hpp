@@ -1,19 +1,40 @@
 // lpcm_form.hpp — which packet form of an LPCM call the fused kernels read (render_fast_kernel<.., LP, .., LPB>,
-// render_fast.hpp).  Plain C++ like render_route.hpp (included inside the unit's namespace, behind <stdint.h> and
-// include/iamf_hip.h), so that tests/route_host can pin the rules without a GPU.  The caller has checked that the layout
-// is well-formed (iamf_render.hip, lpcm_form_check: every run inside its packet row); what is decided here is only whether
+// render_fast.hpp).  Plain C++ like render_route.hpp (included inside the unit's namespace, behind <stdint.h>,
+// include/iamf_hip.h and render_route.hpp, whose coupled pairing it asks), so that tests/route_host can pin the rules
+// without a GPU.  The caller has checked that the layout is well-formed (iamf_render.hip, lpcm_form_check: every run
+// inside its packet row); what is decided here is only whether
 // a kernel can LOAD the runs as they lie: a contiguous little-endian run per channel, aligned for the lane's one load of
-// four consecutive samples.
+// four consecutive samples — or, for the coupled form, a pair of channels interleaved sample by sample, aligned for the
+// lane's one load of four consecutive sample pairs.
 #pragma once
 
 enum class LpcmForm {
   None,   // not fusable: iamf_hip_lpcm_unpack, then the f32 kernels
   S16,    // 16-bit samples, 8-byte loads
   S24,    // 24-bit samples, 12-byte loads (dword-aligned)
+  S16C,   // 16-bit samples, the loudspeaker layouts' canonical coupling: pairs interleaved sample by sample (16-byte loads,
+          // 8-byte aligned), C and LFE mono runs as S16
 };
 
 // sample bytes of a fusable form (RenderParams::lpcm_bytes), 0 for None
-inline int lpcm_form_bytes(LpcmForm f) { return f == LpcmForm::S16 ? 2 : (f == LpcmForm::S24 ? 3 : 0); }
+inline int lpcm_form_bytes(LpcmForm f) { return (f == LpcmForm::S16 || f == LpcmForm::S16C) ? 2 : (f == LpcmForm::S24 ? 3 : 0); }
+
+// S16C: every pair of lpcm_coupled_paired() (render_route.hpp) is ONE run of interleaved samples (step 4, the partner 2 bytes on) whose
+// lane quads — 16 bytes — start on the 8-byte grid; channels 2 and 3 are mono runs under the S16 rule.
+inline bool lpcm_form_coupled(const iamf_hip_lpcm_layout &L, int ch, int first) {
+  if (!lpcm_coupled_m(ch)) return false;
+  for (int c = 0; c < ch; ++c) {
+    if (L.src_offset[c] < 0) return false;              // a channel no sub-stream carries
+    if (!lpcm_coupled_paired(ch, c)) {
+      if (L.src_step[c] != 2 || ((L.src_offset[c] + 2 * first) & 7)) return false;
+    } else if (!(c & 1)) {
+      if (L.src_step[c] != 4 || L.src_step[c + 1] != 4) return false;
+      if (L.src_offset[c + 1] != L.src_offset[c] + 2) return false;
+      if ((L.src_offset[c] + 4 * first) & 7) return false;
+    }
+  }
+  return true;
+}
 
 // L: the call's layout of `ch` channels; strides in bytes; raw_bits: the packet buffer's address (its low bits are looked
 // at); first: iamf_hip_lpcm_input::first_sample (the kernels start at sample `first` of every run).
@@ -26,9 +47,12 @@ inline LpcmForm lpcm_form(const iamf_hip_lpcm_layout &L, int ch, int64_t raw_str
   // size a multiple of 4, sb * 4 * k keeps the grid; the buffer, the strides and the runs' starts have to be on it.
   const int grid = sb == 2 ? 7 : 3;
   if ((raw_stream_stride & grid) || (raw_frame_stride & grid)) return LpcmForm::None;
+  // 16-bit packets of a loudspeaker layout's channel count: the coupled form or none (no kernel is built for such an element
+  // coded as mono sub-streams or paired otherwise: it is unpacked)
+  if (sb == 2 && lpcm_coupled_m(ch)) return lpcm_form_coupled(L, ch, first) ? LpcmForm::S16C : LpcmForm::None;
   for (int c = 0; c < ch; ++c) {
     if (L.src_offset[c] < 0) return LpcmForm::None;     // a channel no sub-stream carries
-    if (L.src_step[c] != sb) return LpcmForm::None;     // coupled sub-streams: samples interleaved
+    if (L.src_step[c] != sb) return LpcmForm::None;     // coupled sub-streams other than S16C's: samples interleaved
     if ((L.src_offset[c] + sb * first) & grid) return LpcmForm::None;
   }
   return sb == 2 ? LpcmForm::S16 : LpcmForm::S24;

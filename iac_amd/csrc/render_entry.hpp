@@ -21,6 +21,9 @@ IAMF_INTERNAL int iamf_hip_fanout_lp_launch(const void *params, int m, int k, hi
 IAMF_INTERNAL int iamf_hip_fast_lpcm_launch(const void *params, int m, int early, hipStream_t st);
 // iamf_render_lpcm24.hip: the same for 24-bit samples (params->lpcm_bytes == 3); early: Route::variant of Family::Lpcm24
 IAMF_INTERNAL int iamf_hip_fast_lpcm24_launch(const void *params, int m, int early, hipStream_t st);
+// iamf_render_lpcm_coupled.hip: the same for the coupled 16-bit form (params->lpcm_coupled); early: Route::variant of
+// Family::LpcmCoupled
+IAMF_INTERNAL int iamf_hip_fast_lpcm_coupled_launch(const void *params, int m, int early, hipStream_t st);
 // iamf_render_fir_m2b.hip: render_fast_kernel<M, 2, stage> / the FFT stage alone (fir_fft_kernel)
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch(const void *params, int m, int stage, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch_fft(const void *params, int m, hipStream_t st);
@@ -36,3 +39,5 @@ IAMF_INTERNAL void iamf_hip_route_count(int family, int variant, int m, int c, i
 IAMF_INTERNAL void iamf_hip_route_count_ext(int family, int variant, int m, int c, int k);
 // ... of an instance of table `table` of iamf_hip_route_table_instances (0 and 1: the two above)
 IAMF_INTERNAL void iamf_hip_route_count_table(int table, int family, int variant, int m, int c, int k);
+// ... of an instance listed by family only (iamf_hip_route_family_instances): whichever row set holds it
+IAMF_INTERNAL void iamf_hip_route_count_family(int family, int variant, int m, int c, int k);

@@ -214,13 +214,20 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       channel is consumed; everything behind the projection is shared.
 //       Sixteen more dwords of input are live than in the 16-bit form: <16, 2> with the late prefetch (all sixteen channels
 //       requested at once) does not fit 128 registers without spilling and is built for three workgroups per CU instead.
-template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2>
+// LPC:  (LP, LPB == 2) the coupled form: the channel pairs of a loudspeaker layout — lpcm_coupled_paired(M, m), lpcm_form.hpp:
+//       (0,1) and, from six channels on, (4,5) .. (M-2, M-1) — are coupled sub-streams, the two channels interleaved sample
+//       by sample.  A lane's four sample-frames of a pair are 16 contiguous bytes L0 R0 L1 R1 L2 R2 L3 R3, ONE load on the
+//       8-byte grid into the four dwords the two channels' packets would have held; L is cut out of the low halves where
+//       channel m is consumed, R out of the sign-extended high halves where m + 1 is.  Channels 2 and 3 (C, LFE) are mono
+//       runs as above.  The pairing is a compile-time function of M: no run-time branch per channel.
+template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2, bool LPC = false>
 __global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2)))
 void render_fast_kernel(const RenderParams p) {
   static_assert(!(FIR && DOWN), "one renderer");
   static_assert(!(LP && (FIR || DOWN || IN2)) && (!LP || M <= 16), "the LPCM input feeds the plain matrix variant");
   static_assert(!(IN2 && (FIR || DOWN)), "the second element joins a matrix-rendered first one");
   static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
+  static_assert(!LPC || (LP && LPB == 2 && lpcm_coupled_m(M)), "coupled pairs: 16-bit packets of a loudspeaker layout");
   constexpr bool LP3 = LP && LPB == 3;
   extern __shared__ float lds[];
   constexpr int R = kFRing;
@@ -388,6 +395,22 @@ void render_fast_kernel(const RenderParams p) {
       const int vo = f * (int)p.lpcm_frame_stride + 3 * i;
       const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, vo, p.lpcm_off[m], 2 /* nt */);
       xr3[m] = lp_u3{v[0], v[1], v[2]};
+    } else if constexpr (LPC) {
+      // a pair is loaded once, when its first channel is named: 16 bytes on the 8-byte grid (the stream's base is 16-byte
+      // aligned, the frame stride and the pair's run offset multiples of 8 — lpcm_form.hpp — and 4 * i one of 16); the
+      // dwords {L0:R0} .. {L3:R3} lie in xr[m], xr[m + 1]
+      if (lpcm_coupled_paired(M, m)) {
+        if (!(m & 1)) {
+          const int vo = f * (int)p.lpcm_frame_stride + 4 * i;
+          const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, p.lpcm_off[m], 2 /* nt */);
+          xr[m] = lp_u2{v[0], v[1]};
+          xr[m + 1 < M ? m + 1 : m] = lp_u2{v[2], v[3]};
+        }
+      } else {
+        const int vo = f * (int)p.lpcm_frame_stride + 2 * i;
+        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, p.lpcm_off[m], 2 /* nt */);
+        xr[m] = lp_u2{v[0], v[1]};
+      }
     } else if constexpr (LP) {
       const int vo = f * (int)p.lpcm_frame_stride + 2 * i;
       const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, p.lpcm_off[m], 2 /* nt */);
@@ -526,6 +549,32 @@ void render_fast_kernel(const RenderParams p) {
           const int s3 = (int)c >> 8;
           xa = f2{(float)s0, (float)s1};
           xb = f2{(float)s2, (float)s3};
+        } else if constexpr (LPC) {
+          if (lpcm_coupled_paired(M, m)) {   // (m is a constant of the unrolled loop)
+            // half m & 1 of the pair whose four dwords lie in xr[m & ~1], xr[m | 1] (the same ordering fence as the 16-bit form
+            // below, on all four: the partner's half is still to be, or has just been, cut out of them)
+            const int m0 = m & ~1, m1 = (m | 1) < M ? (m | 1) : m;
+            if constexpr (OC == 2)
+              asm volatile("" : "+v"(xr[m0].x), "+v"(xr[m0].y), "+v"(xr[m1].x), "+v"(xr[m1].y), "+v"(prj[0]), "+v"(prj[1]), "+v"(prj[2]), "+v"(prj[3]));
+            else
+              asm volatile("" : "+v"(xr[m0].x), "+v"(xr[m0].y), "+v"(xr[m1].x), "+v"(xr[m1].y), "+v"(prj[0]), "+v"(prj[1]));
+            const unsigned a = xr[m0].x, b = xr[m0].y, c = xr[m1].x, d = xr[m1].y;   // (the scale 2^-15 sits in the weights)
+            if ((m & 1) == 0) {
+              xa = f2{(float)(int)(short)(a & 0xffffu), (float)(int)(short)(b & 0xffffu)};
+              xb = f2{(float)(int)(short)(c & 0xffffu), (float)(int)(short)(d & 0xffffu)};
+            } else {
+              xa = f2{(float)((int)a >> 16), (float)((int)b >> 16)};
+              xb = f2{(float)((int)c >> 16), (float)((int)d >> 16)};
+            }
+          } else {   // C, LFE: a mono run, the 16-bit form's conversion below
+            if constexpr (OC == 2)
+              asm volatile("" : "+v"(xr[m].x), "+v"(xr[m].y), "+v"(prj[0]), "+v"(prj[1]), "+v"(prj[2]), "+v"(prj[3]));
+            else
+              asm volatile("" : "+v"(xr[m].x), "+v"(xr[m].y), "+v"(prj[0]), "+v"(prj[1]));
+            const unsigned a = xr[m].x, b = xr[m].y;
+            xa = f2{(float)(int)(short)(a & 0xffffu), (float)((int)a >> 16)};
+            xb = f2{(float)(int)(short)(b & 0xffffu), (float)((int)b >> 16)};
+          }
         } else if constexpr (LP) {
           // (the packets of channel m are "produced" here, after channel m - 1 has been added up: left to itself the
           //  scheduler converts all sixteen channels first and spills what does not fit — 127 registers' worth)
@@ -555,8 +604,12 @@ void render_fast_kernel(const RenderParams p) {
         }
         // channel m's registers are free: its samples of the NEXT chunk are requested now (kEarly), in flight under the
         // rest of the projection and everything behind it
+        // (LPC: a pair's, once its SECOND channel has been consumed)
         if constexpr (kEarly) {
-          if constexpr (LP) load_lp_one(m, pf_f, pf_i, rs_pf);
+          if constexpr (LPC) {
+            if (!lpcm_coupled_paired(M, m)) load_lp_one(m, pf_f, pf_i, rs_pf);
+            else if (m & 1) load_lp_one(m - 1, pf_f, pf_i, rs_pf);
+          } else if constexpr (LP) load_lp_one(m, pf_f, pf_i, rs_pf);
           else load_f32_one(m, pf_f, pf_i, rs_pf);
         }
       }

@@ -44,6 +44,14 @@ using FanK = Ints<2, 3, 4>;
 // render_fast_kernel<M, OC, .., LP>: mono-coded ambisonics elements as LPCM packets
 using LpcmM = Ints<1, 4, 9, 16>;
 using LpcmOC = Ints<1, 2>;
+// render_fast_kernel<.., LP, EARLY, 2, LPC>: channel-based elements whose pairs are coupled sub-streams (lpcm_form.hpp,
+// S16C) — stereo, 5.1, 5.1.2 / 7.1, 5.1.4 / 7.1.2, 7.1.4 — into LpcmOC
+using LpcmCoupledM = Ints<2, 6, 8, 10, 12>;
+// The coupled form's pairing, a function of the channel count alone.  In the renderer's (playback) order every loudspeaker
+// layout of LpcmCoupledM reads L R [C LFE, then pairs]: channels (0,1) are a coupled pair, 2 and 3 mono sub-streams,
+// (4,5) .. (M-2, M-1) pairs again.  The form rule (lpcm_form.hpp) and the kernel (render_fast.hpp, LPC) both build on it.
+IAMF_HD constexpr bool lpcm_coupled_m(int m_total) { return LpcmCoupledM::has(m_total); }
+IAMF_HD constexpr bool lpcm_coupled_paired(int m_total, int m) { return m_total == 2 || m < 2 || m >= 4; }
 // render_fanout_kernel<M, K, LP>: the fan-out fed with LPCM packets.  M: what LpcmM and FanM share (mono-coded ambisonics
 // elements are the only ones whose channels are contiguous 16-bit runs), K within FanK
 using FanLpM = Ints<4, 9, 16>;
@@ -179,6 +187,8 @@ enum class Family {
   Generic,      // render_kernel<M>
   Lpcm24,       // render_fast_kernel<.., LP, EARLY, LPB = 3> (iamf_render_lpcm24.hip); variant as Lpcm.  Table 2 of
                 // iamf_hip_route_table_instances: the base listing's row set is pinned
+  LpcmCoupled,  // render_fast_kernel<.., LP, EARLY, 2, LPC> (iamf_render_lpcm_coupled.hip); variant as Lpcm.  Listed by
+                // iamf_hip_route_family_instances only: the three tables' row sets are pinned
 };
 struct Route {
   Family family;
@@ -206,6 +216,29 @@ inline bool lpcm24_fused(int n_launch) {
   return true;
 }
 
+// Which prefetch variant a launch of n_launch workgroups of the coupled 16-bit form (RenderParams::lpcm_coupled) takes: the
+// faster one per size as measured (tools/lpcm_coupled_rate.py, MI355X, stereo / 5.1 / 7.1.4 element into stereo s16, 64
+// frames x 1024, profiles/r10_lpcm_coupled_rate.json): the early per-pair prefetch at every size and for every element —
+// 7.1.4, 512 / 2048 / 4096 streams: 0.694 / 1.477 / 2.838 ms against 0.750 / 1.573 / 3.066 ms for the late one; stereo:
+// 0.296 / 0.632 / 1.225 against 0.322 / 0.674 / 1.311 — by 5 to 9 %, the baseline's run-to-run spread being at most 0.3 %.
+// (Unlike the mono-coded 16-bit form, whose late variant wins beyond 1024 workgroups: a pair is ONE request for two
+// channels, so the early form issues half as many per chunk.)  No cut, so the rule is the constant; the late instances stay
+// reachable by IAMF_HIP_LP_LATE=1, and IAMF_HIP_LP_EARLY=1 forces the early one (pick_route).
+inline bool lpcm_coupled_early(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+// Whether a range of n_launch streams takes the coupled form at all (render_prepare asks): a size at which it does not
+// beat what the call ran before — unpack, then the f32 kernel, timed from a build of the parent commit in the same process —
+// by more than that pair's own run-to-run spread is not fused.  Same run, same file: the pair takes 1.45 / 1.89 / 1.93
+// (stereo), 1.78 / 2.57 / 2.63 (5.1) and 2.18 / 3.34 / 3.46 (7.1.4) times the fused call's time at 512 / 2048 / 4096 streams,
+// its spread against itself at most 0.0027 — every measured size wins, so every size is fused; this is where a size that
+// stops winning would be cut.
+inline bool lpcm_coupled_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
 // rules.  The environment switches are read at every call (the tests set and unset them within one process).
@@ -219,6 +252,12 @@ inline Route pick_route(const RenderParams &p, int m) {
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
+    // the coupled 16-bit form: its own instances (the pairing is a function of m: lpcm_form.hpp), the same refusals
+    if (p.lpcm_coupled) {
+      if (!LpcmCoupledM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on || p.lpcm_bytes == 3)
+        return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      return take(Family::LpcmCoupled, !getenv("IAMF_HIP_LP_LATE") && (getenv("IAMF_HIP_LP_EARLY") || lpcm_coupled_early(p.n_launch)));
+    }
     if (!LpcmM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on) return refuse(IAMF_HIP_ERR_INVALID_STATE);
     // 24-bit samples (lpcm_bytes: 0 or 2 = 16 bit): the same instances and refusals, the kernel's LPB = 3 form
     // (IAMF_HIP_LP_EARLY=1 forces the early variant as IAMF_HIP_LP_LATE=1 forces the late one: tools/lpcm24_rate.py times both
@@ -330,6 +369,13 @@ void for_each_render_instance_lpcm24(F &&f) {
     for_each_int(LpcmM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM24, early, m, oc, 0); }); });
 }
 
+// The coupled 16-bit LPCM form (iamf_hip_route_family_instances), walking LpcmCoupledM x LpcmOC as its launcher does.
+template <class F>
+void for_each_render_instance_lpcm_coupled(F &&f) {
+  for (int early = 0; early < 2; ++early)
+    for_each_int(LpcmCoupledM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM_COUPLED, early, m, oc, 0); }); });
+}
+
 // the row of the kernel launch() runs for a route (a FirSplit call launches render_fast_kernel<2, 2> behind it as well:
 // launch() counts that row too)
 struct RouteKey {
@@ -352,6 +398,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::Wide: return {IAMF_HIP_ROUTE_WIDE, r.variant, m, 0, 0};
     case Family::Generic: return {IAMF_HIP_ROUTE_GENERIC, 0, m, 0, 0};
     case Family::Lpcm24: return {IAMF_HIP_ROUTE_LPCM24, r.variant, m, p.out_ch, 0};   // a row of table 2
+    case Family::LpcmCoupled: return {IAMF_HIP_ROUTE_LPCM_COUPLED, r.variant, m, p.out_ch, 0};   // a family listing's row
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

@@ -81,7 +81,8 @@ class RouteRow(C.Structure):   # iamf_hip_route_row
 
 # IAMF_HIP_ROUTE_*: the kernel families of iamf_hip_route_row::family
 ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, WIDE4_DEMIX=7, WIDE4_DOWN=8, WIDE4_MIX=9,
-             WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, LPCM24=16, RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23)
+             WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, LPCM24=16, LPCM_COUPLED=17,
+             RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23)
 ROUTE_NAME = {v: k for k, v in ROUTE.items()}
 
 
@@ -219,6 +220,8 @@ def lib():
         L.iamf_hip_route_tables.argtypes = []
         L.iamf_hip_route_table_instances.argtypes = [C.c_int, C.POINTER(RouteRow), C.c_int]
         L.iamf_hip_route_table_tally.argtypes = [C.c_int, C.POINTER(RouteRow), C.c_int, C.c_int]
+        L.iamf_hip_route_family_instances.argtypes = [C.c_int, C.POINTER(RouteRow), C.c_int]
+        L.iamf_hip_route_family_tally.argtypes = [C.c_int, C.POINTER(RouteRow), C.c_int, C.c_int]
         L.iamf_hip_shard_split.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.iamf_hip_shard_create.argtypes = [C.POINTER(BatchConfig), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_shard_destroy.argtypes = [C.c_void_p]
@@ -353,6 +356,36 @@ def route_table_tally(t, reset=False):
         raise IamfHipError(cap - 1, "iamf_hip_route_table_tally")
     rows = (RouteRow * cap)()
     n = L.iamf_hip_route_table_tally(t, rows, cap, 1 if reset else 0)
+    return {(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k): r.launches for r in rows[:min(n, cap)]}
+
+
+def _family_id(family):
+    return ROUTE[family] if isinstance(family, str) else int(family)
+
+
+def route_family_instances(family):
+    """iamf_hip_route_family_instances: the instances of one kernel family (a ROUTE name or id), whichever table lists them
+    or none does (LPCM_COUPLED); needs no GPU.  A family no instance belongs to raises IamfHipError(-1)."""
+    L = lib()
+    fam = _family_id(family)
+    n = L.iamf_hip_route_family_instances(fam, None, 0)
+    if n < 0:
+        raise IamfHipError(n, "iamf_hip_route_family_instances")
+    rows = (RouteRow * max(n, 1))()
+    n = min(n, L.iamf_hip_route_family_instances(fam, rows, n))
+    return [(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k) for r in rows[:n]]
+
+
+def route_family_tally(family, reset=False):
+    """iamf_hip_route_family_tally: {(family name, variant, m, c, k): launches} of one family since its rows' last reset
+    (for a family of tables 0 .. 2: the counters of that table)"""
+    L = lib()
+    fam = _family_id(family)
+    cap = L.iamf_hip_route_family_instances(fam, None, 0)
+    if cap < 0:
+        raise IamfHipError(cap, "iamf_hip_route_family_tally")
+    rows = (RouteRow * max(cap, 1))()
+    n = L.iamf_hip_route_family_tally(fam, rows, cap, 1 if reset else 0)
     return {(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k): r.launches for r in rows[:min(n, cap)]}
 
 

@@ -646,10 +646,16 @@ int iamf_hip_lpcm_unpack(const iamf_hip_lpcm_layout *layout, const void *d_raw, 
  *           element instead of the 180 of unpack + f32 kernel);
  * and the batch is a plain matrix render of a 1 / 4 / 9 / 16-channel element into one or two channels with the limiter on
  * (no second element, ramps, demixer, down-mixer, de-mapping, FIR or LFE generator; no weight outside 2^-100 .. 2^100).
- * Every other input — 32 bit, big-endian, coupled sub-streams, wide layouts, runs off the grid — takes
- * iamf_hip_lpcm_unpack into a buffer of the batch and then the f32 kernels.  The PCM and the stream state are the same bit
- * for bit either way (tests/test_gpu_lpcm.py, test_gpu_lpcm24.py), so fused, unfused and f32 calls may follow one another
- * on a batch; IAMF_HIP_LPCM_UNFUSED=1 in the environment forces the second way.
+ * Also fused, 16 bit only: the coupled form of a channel-based element of 2 / 6 / 8 / 10 / 12 channels in playback order
+ * (L R [C LFE, then pairs]) under the same batch conditions.  Channels (0,1) and, from six channels on, (4,5) ..
+ * (channels-2, channels-1) are coupled sub-streams — src_step == 4 on both, the second's src_offset 2 bytes behind the
+ * first's, the first's src_offset + 4 * first_sample a multiple of 8 bytes (a lane's four sample pairs are one 16-byte
+ * load) — and channels 2 and 3 mono runs by the 16-bit rule above; strides multiples of 8.  2 * channels + 4 bytes per
+ * sample-frame into s16 stereo instead of the 10 * channels + 4 of unpack + f32 kernel.
+ * Every other input — 32 bit, big-endian, any other pairing of coupled sub-streams (24-bit pairs included), wide layouts,
+ * runs off the grid — takes iamf_hip_lpcm_unpack into a buffer of the batch and then the f32 kernels.  The PCM and the
+ * stream state are the same bit for bit either way (tests/test_gpu_lpcm.py, test_gpu_lpcm24.py, test_gpu_lpcm_coupled.py),
+ * so fused, unfused and f32 calls may follow one another on a batch; IAMF_HIP_LPCM_UNFUSED=1 in the environment forces the second way.
  * Returns what iamf_hip_batch_render_ex returns. */
 typedef struct iamf_hip_lpcm_input {
   const void *d_raw;
@@ -674,7 +680,7 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
  *
  * What runs is decided from what the call can observe, in this order:
  *   1. A member is packet-fusable when the packets have the 16-bit form the single call fuses (see above; the single
- *      call's 24-bit form is not one this entry fuses: such packets go by 3.), the member's single
+ *      call's 24-bit form and its coupled 16-bit form are not ones this entry fuses: such packets go by 3.), the member's single
  *      call would run the packet-fed kernel, the element has 4, 9 or 16 channels, and the member is one the f32 fan-out
  *      would fuse (no fixed PCM channel stride).  If at least two members are packet-fusable they share one launch that
  *      reads the packets once: 2 * M + sum of the members' output bytes per sample-frame instead of 2 * M per member.
@@ -731,6 +737,7 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *     WIDE4, WIDE4_MIX, WIDE4_LFE          variant 1 = MFMA projection, m, c
  *     LPCM                 variant 1 = early per-channel prefetch, 0 = late; m, c
  *     LPCM24               the same for 24-bit samples (table 2 of iamf_hip_route_table_instances only)
+ *     LPCM_COUPLED         the same for the coupled 16-bit form (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -759,6 +766,7 @@ enum {
   IAMF_HIP_ROUTE_FIR_FUSED = 14,
   IAMF_HIP_ROUTE_FANOUT_LPCM = 15,   /* extension table only */
   IAMF_HIP_ROUTE_LPCM24 = 16,        /* table 2 only */
+  IAMF_HIP_ROUTE_LPCM_COUPLED = 17,  /* no table: iamf_hip_route_family_instances / _family_tally */
   IAMF_HIP_ROUTE_RS_PLAIN = 20,
   IAMF_HIP_ROUTE_RS_TILE = 21,
   IAMF_HIP_ROUTE_RS_BLOCK = 22,
@@ -788,6 +796,14 @@ int iamf_hip_route_tally_ext(iamf_hip_route_row *rows, int cap, int reset);
 int iamf_hip_route_tables(void);
 int iamf_hip_route_table_instances(int table, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int reset);
+/* The listing by kernel family, open-ended: a family added later needs no new entry and no new table (the three tables'
+ * row sets are pinned by their callers).  family: IAMF_HIP_ROUTE_*.  For a family of tables 0 .. 2 these give that family's
+ * rows of its table — the SAME counters, so a reset here resets them there; for LPCM_COUPLED its rows (variant, m, c as
+ * LPCM), which no table lists and whose launches show in no table's tally.  _instances: every row of the family;
+ * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
+ * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed. */
+int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
+int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
 /* ------------------------------------------------------------------------------------------
  * A group of decoder handles: callers of the reference API get the batch renderer's throughput.
