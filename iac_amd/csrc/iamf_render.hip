@@ -187,6 +187,7 @@ struct iamf_hip_batch {
   std::vector<uint8_t> sflushed;    // per stream: the limiter's tail has been emitted
   bool any_rendered = false;        // the setters that must precede the first render check this
   bool lp_scale_ok = false;         // every non-zero weight w has w * 2^-15 exact and w * 2^-15 * sample normal (fused LPCM form)
+  bool lp2_scale_ok = false;        // the same for the second element's matrix (iamf_hip_batch_set_second_element)
   float *d_matrix = nullptr, *d_gains = nullptr, *d_ctab = nullptr, *d_ring_y = nullptr,
         *d_ring_pm = nullptr;
   LimState *d_lim = nullptr;
@@ -221,6 +222,9 @@ struct iamf_hip_batch {
   // iamf_hip_batch_render_lpcm, calls the fused kernel does not take: the unpacked element and the unpacker's {first, count}
   float *d_lp_in = nullptr;
   size_t lp_in_floats = 0;
+  // iamf_hip_batch_render_lpcm_mix, unfused: the unpacked second element
+  float *d_lp_in2 = nullptr;
+  size_t lp_in2_floats = 0;
   float *d_fir_id = nullptr;                        // 2 x 2 identity + slot map for the limiter / pack kernel behind it
   int32_t *d_fir_id_feed = nullptr;
   float fir_inv_scale = 1.f;
@@ -327,7 +331,8 @@ void launch_wide_m(const RenderParams &p, dim3 grid, hipStream_t st) {
 
 // Runs the kernel pick_route (render_route.hpp) names.  `launched` is false only if a launcher's instance list and the
 // one the route was picked by disagree, which sharing the lists rules out.
-int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
+// (p: the block every kernel takes and, behind it, what Family::LpcmMix alone reads)
+int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
   const Route r = pick_route(p, m);
   const dim3 grid((unsigned)p.n_launch);
   bool launched = false;
@@ -336,6 +341,9 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
     case Family::Lpcm: launched = iamf_hip_fast_lpcm_launch(&p, m, r.variant, st); break;
     case Family::Lpcm24: launched = iamf_hip_fast_lpcm24_launch(&p, m, r.variant, st); break;
     case Family::LpcmCoupled: launched = iamf_hip_fast_lpcm_coupled_launch(&p, m, r.variant, st); break;
+    case Family::LpcmMix:
+      launched = p.lpcm_coupled ? iamf_hip_fast_lpcm_mix_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_lpcm_mix_launch(&p, m, r.variant, st);
+      break;
     case Family::FirSplit: {
       // (1) the FFT stage for every hop of every stream -> y in HBM (overlap-save blocks are independent: one grid); (2)
       // gains, limiter, pack = the two-channel matrix kernel with the identity over y (one "frame" of `total` samples per
@@ -382,7 +390,7 @@ int launch(const RenderParams &p, int m, size_t lds_bytes, hipStream_t st) {
   HIPCHK(hipGetLastError());
   const RouteKey k = route_key(r, p, m);   // the tally of iamf_hip_route_tally
   if (r.family == Family::Lpcm24) iamf_hip_route_count_table(2, k.family, k.variant, k.m, k.c, k.k);   // its own table
-  else if (r.family == Family::LpcmCoupled) iamf_hip_route_count_family(k.family, k.variant, k.m, k.c, k.k);   // no table's
+  else if (r.family == Family::LpcmCoupled || r.family == Family::LpcmMix) iamf_hip_route_count_family(k.family, k.variant, k.m, k.c, k.k);   // no table's
   else iamf_hip_route_count(k.family, k.variant, k.m, k.c, k.k);
   if (r.family == Family::FirSplit) iamf_hip_route_count(IAMF_HIP_ROUTE_FAST, 0, 2, 2, 0);
   return IAMF_HIP_OK;
@@ -465,7 +473,7 @@ int lfe_prepass(iamf_hip_batch *b, const float *d_in, int64_t in_stream_stride, 
 // stride, the `done` event, the emitted count) — so that iamf_hip_batch_render_fanout can prepare every member, launch
 // once, and commit each, and restates none of it.
 struct PreparedCall {
-  RenderParams p;
+  RenderMixParams p;   // (the part behind RenderParams: set for Family::LpcmMix only)
   iamf_hip_render_args a;
   int m_eff;
   size_t lds;
@@ -475,10 +483,16 @@ struct PreparedCall {
   int total, s0, cnt;
 };
 
-int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc) {
+// lp2 (with lp, iamf_hip_batch_render_lpcm_mix): the second element as packets too; a.d_in2 is then a non-null placeholder.
+int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc,
+                   const LpcmIn *lp2 = nullptr) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
-  if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || b->has2 || a.d_element_ramp || a.d_element2_ramp ||
-             a.d_output_ramp || !b->lp_scale_ok || getenv("IAMF_HIP_LPCM_UNFUSED")))
+  if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || !b->lp_scale_ok || getenv("IAMF_HIP_LPCM_UNFUSED")))
+    return kNotFused;
+  // a second element or ramps: the two-element packet form only, which also keeps away from a fixed PCM channel stride
+  if (lp && !lp2 && (b->has2 || a.d_element_ramp || a.d_element2_ramp || a.d_output_ramp)) return kNotFused;
+  if (lp2 && (!lp || !b->has2 || !b->lp2_scale_ok ||
+              (b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels)))
     return kNotFused;
   if (s0 < 0 || cnt <= 0 || s0 + cnt > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
   if (a.lfe_pre_samples < 0 || a.lfe_post_samples < 0 ||
@@ -492,8 +506,8 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   // per-batch (not per-stream) state: the FIR history ping-pong.  (The LFE generator's pre-pass takes the range: streams
   // outside it keep their filter state, round 4.)
   if (!whole && b->fir) return IAMF_HIP_ERR_UNIMPLEMENTED;
+  memset(&pc.p, 0, sizeof(pc.p));
   RenderParams &p = pc.p;
-  memset(&p, 0, sizeof(p));
   p.stream0 = s0;
   p.n_launch = cnt;
   p.in = a.d_in;
@@ -589,8 +603,20 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     p.lpcm_bytes = lp->bytes;
     p.lpcm_coupled = lp->coupled;
     if (lp->bytes == 3 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
-    if (lp->coupled && !lpcm_coupled_fused(cnt)) return kNotFused;
-    if (pick_route(p, m_eff).family != (lp->coupled ? Family::LpcmCoupled : (lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm)))
+    if (lp->coupled && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
+    if (lp2) {   // the kernel reads RenderMixParams; pick_route the packets' place in the in2 fields (strides in bytes)
+      p.lpcm_mix = lp2->coupled ? 2 : 1;
+      p.in2 = reinterpret_cast<const float *>(lp2->raw);
+      p.in2_stream_stride = lp2->stream_stride;
+      p.in2_frame_stride = lp2->frame_stride;
+      pc.p.lpcm2 = lp2->raw;
+      pc.p.lpcm2_stream_stride = lp2->stream_stride;
+      pc.p.lpcm2_frame_stride = lp2->frame_stride;
+      for (int m = 0; m < 4; ++m) pc.p.lpcm2_off[m] = lp2->off[m];
+      if (!lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
+    }
+    if (pick_route(p, m_eff).family !=
+        (lp2 ? Family::LpcmMix : (lp->coupled ? Family::LpcmCoupled : (lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm))))
       return kNotFused;
   }
   if (b->fir) {
@@ -1028,6 +1054,7 @@ void iamf_hip_batch_destroy(iamf_hip_batch *b) {
   (void)hipFree(b->d_fir_pre[1]);
   (void)hipFree(b->d_fir_y);
   (void)hipFree(b->d_lp_in);
+  (void)hipFree(b->d_lp_in2);
   (void)hipFree(b->d_fir_id);
   (void)hipFree(b->d_fir_id_feed);
   if (!b->lfe_shared) {
@@ -1116,10 +1143,11 @@ int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in,
 // still indexed by the stream's number in the batch)
 // The packet-form checks of an LPCM call of nf frames (n_samples as iamf_hip_render_args::n_samples): an error, or
 // IAMF_HIP_OK with the trim {first, count} and whether the packets have the form the fused kernels read
-static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int n_samples, LpcmForm *form_out,
-                           int *first_out, int *count_out) {
+// (ch: the channels of the element the packets hold — element 0's, or the second element's for iamf_hip_batch_render_lpcm_mix)
+static int lpcm_form_check_ch(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int ch, int nf, int n_samples, LpcmForm *form_out,
+                              int *first_out, int *count_out) {
   const iamf_hip_lpcm_layout &L = in->layout;
-  const int fs = b->cfg.frame_size, ch = b->d_pre ? b->pre_l : b->m;
+  const int fs = b->cfg.frame_size;
   if (L.sample_bytes < 2 || L.sample_bytes > 4 || L.channels != ch || ch > IAMF_HIP_LPCM_MAX_CHANNELS || L.frame_size != fs ||
       (fs & 3) || in->raw_frame_stride <= 0 || in->raw_stream_stride < (int64_t)nf * in->raw_frame_stride)
     return IAMF_HIP_ERR_BAD_ARG;
@@ -1138,6 +1166,11 @@ static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *i
   return IAMF_HIP_OK;
 }
 
+static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int n_samples, LpcmForm *form_out,
+                           int *first_out, int *count_out) {
+  return lpcm_form_check_ch(b, in, b->d_pre ? b->pre_l : b->m, nf, n_samples, form_out, first_out, count_out);
+}
+
 // packets of the fusable form as the fused kernels take them
 static void lpcm_in_of(const iamf_hip_lpcm_input *in, int ch, int first, LpcmForm form, LpcmIn &lp) {
   memset(&lp, 0, sizeof(lp));
@@ -1153,40 +1186,49 @@ static void lpcm_in_of(const iamf_hip_lpcm_input *in, int ch, int first, LpcmFor
 // The RANGE's packets -> planar f32 in a buffer of the batch (rows indexed by the stream's number in the batch, as every
 // buffer of a range call); a's input fields then name that buffer.  {first, count} travel in the unpacker's kernel arguments
 // (a device word updated by a blocking copy cost K host synchronisations per round of a group with K divergent runs).
+// (second: the SECOND element's packets, into the batch's second buffer and a's in2 fields — iamf_hip_batch_render_lpcm_mix)
 static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int first, int count, int32_t stream0,
-                             int32_t n_streams, hipStream_t st, iamf_hip_render_args &a) {
+                             int32_t n_streams, hipStream_t st, iamf_hip_render_args &a, bool second = false) {
   const iamf_hip_lpcm_layout &L = in->layout;
-  const int fs = b->cfg.frame_size, ch = b->d_pre ? b->pre_l : b->m, ns = b->cfg.n_streams;
+  const int fs = b->cfg.frame_size, ch = second ? b->m2 : (b->d_pre ? b->pre_l : b->m), ns = b->cfg.n_streams;
+  float *&d_buf = second ? b->d_lp_in2 : b->d_lp_in;
+  size_t &buf_floats = second ? b->lp_in2_floats : b->lp_in_floats;
   // as many frames per launch as the grid's third dimension takes; a range too wide for one frame is refused before
   // anything is allocated or queued
   const int fmax = 65535 / n_streams;
   if (fmax == 0) return IAMF_HIP_ERR_UNIMPLEMENTED;
   const size_t need = (size_t)ns * nf * ch * fs;
-  if (need > b->lp_in_floats) {   // grows with the largest call seen
+  if (need > buf_floats) {   // grows with the largest call seen
     const int q = quiesce(b);     // a render queued earlier may still be reading the old buffer
     if (q != IAMF_HIP_OK) return q;
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(b->d_lp_in);
-    b->d_lp_in = nullptr;
-    b->lp_in_floats = 0;
-    HIPCHK(hipMalloc(&b->d_lp_in, sizeof(float) * need));
+    (void)hipFree(d_buf);
+    d_buf = nullptr;
+    buf_floats = 0;
+    HIPCHK(hipMalloc(&d_buf, sizeof(float) * need));
     // rows of channels no sub-stream carries (src_offset < 0) are never written by the unpacker: keep them defined
     // (on the call's stream, in front of the unpack kernel: a null-stream memset is not ordered with a non-blocking stream)
-    HIPCHK(hipMemsetAsync(b->d_lp_in, 0, sizeof(float) * need, st));
-    b->lp_in_floats = need;
+    HIPCHK(hipMemsetAsync(d_buf, 0, sizeof(float) * need, st));
+    buf_floats = need;
   }
   const int64_t lp_stream_stride = (int64_t)nf * ch * fs;
   for (int f = 0; f < nf; f += fmax) {
     const int r = iamf_hip_lpcm_unpack_frames(
         &L, static_cast<const uint8_t *>(in->d_raw) + (int64_t)stream0 * in->raw_stream_stride + (int64_t)f * in->raw_frame_stride,
         in->raw_stream_stride, in->raw_frame_stride, nf - f < fmax ? nf - f : fmax, nullptr, 0,
-        b->d_lp_in + (int64_t)stream0 * lp_stream_stride + (size_t)f * ch * fs, lp_stream_stride, (int64_t)ch * fs, n_streams, st, first,
+        d_buf + (int64_t)stream0 * lp_stream_stride + (size_t)f * ch * fs, lp_stream_stride, (int64_t)ch * fs, n_streams, st, first,
         count);
     if (r != IAMF_HIP_OK) return r;
   }
-  a.d_in = b->d_lp_in;
-  a.in_stream_stride = lp_stream_stride;
-  a.in_frame_stride = (int64_t)ch * fs;
+  if (second) {
+    a.d_in2 = d_buf;
+    a.in2_stream_stride = lp_stream_stride;
+    a.in2_frame_stride = (int64_t)ch * fs;
+  } else {
+    a.d_in = d_buf;
+    a.in_stream_stride = lp_stream_stride;
+    a.in_frame_stride = (int64_t)ch * fs;
+  }
   return IAMF_HIP_OK;
 }
 
@@ -1219,6 +1261,60 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
     if (rc != IAMF_HIP_OK || total == 0) return rc;
   }
   const int ur = lpcm_unpack_range(b, in, nf, first, count, stream0, n_streams, static_cast<hipStream_t>(args->stream), a);
+  if (ur != IAMF_HIP_OK) return ur;
+  return render_range_impl(b, &a, stream0, n_streams, nullptr);
+}
+
+// Both elements of a mix as LPCM packets (include/iamf_hip.h).  Fused (render_fast_kernel<.., LP2>: Family::LpcmMix) when
+// each element's packets have a form its side of the kernel reads — element 0: S16 with LpcmM channels or S16C; element 1:
+// S16 with 1 or 4 channels or S16C with 2 (lpcm_form() on each element's own layout) — and pick_route takes the call; in
+// every other case both elements are unpacked, each into a buffer of the batch, and the f32 path renders them.  Both ways
+// give the same PCM and leave the same stream state, bit for bit.  Every refusal comes before the first launch.
+int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call) return IAMF_HIP_ERR_BAD_ARG;
+  const iamf_hip_lpcm_input *in0 = &call->in[0], *in1 = &call->in[1];
+  const iamf_hip_render_args *args = &call->args;
+  if (!b->has2 || args->d_in || args->d_in2 || !in0->d_raw || !in1->d_raw || in0->first_sample != in1->first_sample ||
+      !args->d_pcm || args->n_frames < 0)
+    return IAMF_HIP_ERR_BAD_ARG;
+  if (stream0 < 0 || n_streams <= 0 || stream0 + n_streams > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
+  if (args->n_frames == 0) return 0;
+  const int ch = b->d_pre ? b->pre_l : b->m, nf = args->n_frames;
+  LpcmForm form0 = LpcmForm::None, form1 = LpcmForm::None;
+  int first = 0, count = 0, first1 = 0, count1 = 0;
+  int fc = lpcm_form_check_ch(b, in0, ch, nf, args->n_samples, &form0, &first, &count);
+  if (fc != IAMF_HIP_OK) return fc;
+  fc = lpcm_form_check_ch(b, in1, b->m2, nf, args->n_samples, &form1, &first1, &count1);
+  if (fc != IAMF_HIP_OK) return fc;
+  // Everything the render call would refuse is refused here, in front of the fused attempt and of the first unpack launch
+  // (the two packet buffers stand in for d_in / d_in2: "not a flush", "a second element is given")
+  iamf_hip_render_args a = *args;
+  a.d_in = reinterpret_cast<const float *>(in0->d_raw);
+  a.d_in2 = reinterpret_cast<const float *>(in1->d_raw);
+  a.in_stream_stride = a.in_frame_stride = a.in2_stream_stride = a.in2_frame_stride = 0;
+  int64_t total = 0;
+  const int rc = range_args_check(b, &a, stream0, n_streams, &total);
+  if (rc != IAMF_HIP_OK || total == 0) return rc;
+  const bool form0_ok = (form0 == LpcmForm::S16 && LpcmM::has(ch)) || form0 == LpcmForm::S16C;
+  const bool form1_ok = (form1 == LpcmForm::S16 || form1 == LpcmForm::S16C) &&
+                        lpcm_mix_m2_ok(form1 == LpcmForm::S16C ? 2 : 1, b->m2);
+  if (form0_ok && form1_ok) {
+    LpcmIn lp0, lp1;
+    lpcm_in_of(in0, ch, first, form0, lp0);
+    lpcm_in_of(in1, b->m2, first, form1, lp1);
+    PreparedCall pc;
+    int r = render_prepare(b, a, (int)total, stream0, n_streams, &lp0, pc, &lp1);
+    if (r == IAMF_HIP_OK) {
+      r = render_launch(pc);
+      return r != IAMF_HIP_OK ? r : render_commit(b, pc);
+    }
+    if (r != kNotFused) return r;
+  }
+  const hipStream_t st = static_cast<hipStream_t>(args->stream);
+  int ur = lpcm_unpack_range(b, in0, nf, first, count, stream0, n_streams, st, a);
+  if (ur != IAMF_HIP_OK) return ur;
+  ur = lpcm_unpack_range(b, in1, nf, first, count, stream0, n_streams, st, a, true);
   if (ur != IAMF_HIP_OK) return ur;
   return render_range_impl(b, &a, stream0, n_streams, nullptr);
 }
@@ -1644,6 +1740,10 @@ int iamf_hip_batch_set_second_element(iamf_hip_batch *b, const iamf_hip_matrix *
   HIPCHK(hipMemcpy(b->d_src_feed2, feed, sizeof(feed), hipMemcpyHostToDevice));
   b->m2 = mx->m;
   b->has2 = true;
+  // the two-element packet form folds the decoder's 2^-15 into these weights as well (see lp_scale_ok)
+  b->lp2_scale_ok = true;
+  for (float w : fm)
+    if (w != 0.f && !(fabsf(w) >= 0x1p-100f && fabsf(w) <= 0x1p100f)) b->lp2_scale_ok = false;
   return IAMF_HIP_OK;
 }
 

@@ -24,6 +24,10 @@ IAMF_INTERNAL int iamf_hip_fast_lpcm24_launch(const void *params, int m, int ear
 // iamf_render_lpcm_coupled.hip: the same for the coupled 16-bit form (params->lpcm_coupled); early: Route::variant of
 // Family::LpcmCoupled
 IAMF_INTERNAL int iamf_hip_fast_lpcm_coupled_launch(const void *params, int m, int early, hipStream_t st);
+// iamf_render_lpcm_mix.hip, iamf_render_lpcm_mix_coupled.hip: both elements as 16-bit packets, element 0 mono-coded / coupled
+// (params->lpcm_coupled); params: a RenderMixParams; lp2: Route::variant of Family::LpcmMix
+IAMF_INTERNAL int iamf_hip_fast_lpcm_mix_launch(const void *params, int m, int lp2, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_fast_lpcm_mix_coupled_launch(const void *params, int m, int lp2, hipStream_t st);
 // iamf_render_fir_m2b.hip: render_fast_kernel<M, 2, stage> / the FFT stage alone (fir_fft_kernel)
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch(const void *params, int m, int stage, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch_fft(const void *params, int m, hipStream_t st);

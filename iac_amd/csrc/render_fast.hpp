@@ -220,11 +220,19 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       8-byte grid into the four dwords the two channels' packets would have held; L is cut out of the low halves where
 //       channel m is consumed, R out of the sign-extended high halves where m + 1 is.  Channels 2 and 3 (C, LFE) are mono
 //       runs as above.  The pairing is a compile-time function of M: no run-time branch per channel.
-template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2, bool LPC = false>
-__global__ __launch_bounds__(FIR == 1 ? 512 : 256, FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2)))
-void render_fast_kernel(const RenderParams p) {
+// LP2:  (LP, LPB == 2, IN2, EARLY) the second element arrives as 16-bit packets too (RenderMixParams::lpcm2, iamf_hip_batch_render_lpcm_mix):
+//       1: mono-coded runs, m2 = 1 or 4 at run time, one 8-byte load per channel and lane; 2: ONE coupled stereo pair
+//       (m2 == 2), one 16-byte load per lane, L out of the low halves and R out of the sign-extended high halves as LPC does.
+//       Through a buffer resource of its own; converted where the mixing stage consumes it, "/ 32768" folded into the staged
+//       mat2 weights as it is into mat.  Everything behind the two projections is the IN2 body.  Element 0's next chunk is
+//       requested channel by channel under the projection (kEarly); element 1's and the ramps' behind the mixing stage.
+template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2, bool LPC = false,
+          int LP2 = 0>
+__global__ __launch_bounds__(FIR == 1 ? 512 : 256, LP2 ? lpcm_mix_wgs(M, OC, LP2) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
+void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, RenderParams> p) {
   static_assert(!(FIR && DOWN), "one renderer");
-  static_assert(!(LP && (FIR || DOWN || IN2)) && (!LP || M <= 16), "the LPCM input feeds the plain matrix variant");
+  static_assert(!(LP && (FIR || DOWN || (IN2 && !LP2))) && (!LP || M <= 16), "the LPCM input feeds the plain matrix variant");
+  static_assert(LP2 == 0 || ((LP2 == 1 || LP2 == 2) && LP && IN2 && EARLY && LPB == 2), "a packet-fed second element joins a 16-bit packet-fed first one");
   static_assert(!(IN2 && (FIR || DOWN)), "the second element joins a matrix-rendered first one");
   static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
   static_assert(!LPC || (LP && LPB == 2 && lpcm_coupled_m(M)), "coupled pairs: 16-bit packets of a loudspeaker layout");
@@ -245,7 +253,7 @@ void render_fast_kernel(const RenderParams p) {
   constexpr bool kTab = FIR == 0 || FIR == 3;   // the limiter-table window and head are staged in LDS
   // the matrix variant reads its weights four input channels at a time (one 16-byte LDS read per output slot and group)
   constexpr bool kWG = !FIR && !DOWN && (M % 4) == 0;
-  constexpr bool kEarly = EARLY && !FIR && !DOWN && !IN2;
+  constexpr bool kEarly = EARLY && !FIR && !DOWN && (!IN2 || LP2 != 0);
   float *mat = win + (kTab ? 2 * kFWin : 0);  // [OC*M]  feed-major matrix rows of the OC slots
   float *misc = mat + ((OC * M + 15) & ~15);  // [16]
   float *mat2 = misc + 16;              // [OC][kFIn2]  second element's matrix rows (IN2 only; aliases fir)
@@ -298,6 +306,8 @@ void render_fast_kernel(const RenderParams p) {
       const int c = t / kFIn2, m = t - c * kFIn2;
       const int f = p.src_feed2[c];
       mat2[t] = (f >= 0 && m < p.m2) ? p.matrix2[f * p.m2 + m] : 0.f;
+      // LP2: the decoder's "/ 32768" of element 1 folded into its weights, as into mat above (iamf_hip_batch::lp2_scale_ok)
+      if constexpr (LP2 != 0) mat2[t] *= 1.0f / 32768.0f;
     }
     chain_wave_publish(misc + 12);
   }
@@ -327,9 +337,37 @@ void render_fast_kernel(const RenderParams p) {
 #pragma unroll
   for (int m = 0; m < (IN2 ? kFIn2 : 1); ++m) x2[m] = make_float4(0.f, 0.f, 0.f, 0.f);
   float4 rmp[IN2 ? 3 : 1];  // per-sample gains of element 0, element 1 and the output, where given
+  // LP2: element 1's packets as they lie in memory — 1: channel m's four samples in x2r[m]; 2: the pair's {L0:R0} .. {L3:R3}
+  // in x2r[0], x2r[1] — converted where the mixing stage consumes them
+  using lp2_u2 = __attribute__((ext_vector_type(2))) unsigned;
+  lp2_u2 x2r[LP2 == 1 ? kFIn2 : (LP2 == 2 ? 2 : 1)];
+  const auto lp2_rsrc = [&]() {
+    if constexpr (LP2 != 0)
+      return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.lpcm2 + (int64_t)s * p.lpcm2_stream_stride), 0, 0x7fffffff, 0x00020000);
+    else
+      return 0;
+  };
+  const auto rs_in2 = lp2_rsrc();   // (32-bit offsets inside a stream's region of one call: pick_route bounds them)
+  (void)rs_in2;
   auto load_x2 = [&](int f, int i) {  // the lane's 4 samples of the second element's channels (frame f, position i)
+    if constexpr (LP2 == 1) {
+      const int vo = f * (int)p.lpcm2_frame_stride + 2 * i;
+#pragma unroll
+      for (int m = 0; m < kFIn2; ++m) {
+        x2r[m] = lp2_u2{0u, 0u};
+        if (m < p.m2) {
+          const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs_in2, vo, p.lpcm2_off[m], 2 /* nt */);
+          x2r[m] = lp2_u2{v[0], v[1]};
+        }
+      }
+    } else if constexpr (LP2 == 2) {
+      const int vo = f * (int)p.lpcm2_frame_stride + 4 * i;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_in2, vo, p.lpcm2_off[0], 2 /* nt */);
+      x2r[0] = lp2_u2{v[0], v[1]};
+      x2r[1] = lp2_u2{v[2], v[3]};
+    }
     if constexpr (IN2) {
-      if (p.in2) {
+      if (LP2 == 0 && p.in2) {
         const float *src = in2_s + (int64_t)f * p.in2_frame_stride + i;
 #pragma unroll
         for (int m = 0; m < kFIn2; ++m)
@@ -458,6 +496,8 @@ void render_fast_kernel(const RenderParams p) {
       for (int m = 0; m < M; ++m) x[m] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int m = 0; m < (IN2 ? kFIn2 : 0); ++m) x2[m] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int m = 0; m < (LP2 == 1 ? kFIn2 : (LP2 == 2 ? 2 : 0)); ++m) x2r[m] = lp2_u2{0u, 0u};
     }
     load_drec(k / fs);
   }
@@ -632,6 +672,17 @@ void render_fast_kernel(const RenderParams p) {
       downmix_factors(drec, k - (k / fs) * fs, cf);
       downmix4<M, OC>(x, yd, cf, p.dmx_in_layout, p.dmx_out_layout);
     }
+    if constexpr (LP2 == 1) {   // (the scale 2^-15 sits in the mat2 weights; channels at or beyond m2 hold zeros)
+#pragma unroll
+      for (int m = 0; m < kFIn2; ++m) {
+        const unsigned a = x2r[m].x, b = x2r[m].y;
+        x2[m] = make_float4((float)(int)(short)(a & 0xffffu), (float)((int)a >> 16), (float)(int)(short)(b & 0xffffu), (float)((int)b >> 16));
+      }
+    } else if constexpr (LP2 == 2) {
+      const unsigned a = x2r[0].x, b = x2r[0].y, c = x2r[1].x, d = x2r[1].y;
+      x2[0] = make_float4((float)(int)(short)(a & 0xffffu), (float)(int)(short)(b & 0xffffu), (float)(int)(short)(c & 0xffffu), (float)(int)(short)(d & 0xffffu));
+      x2[1] = make_float4((float)((int)a >> 16), (float)((int)b >> 16), (float)((int)c >> 16), (float)((int)d >> 16));
+    }
     if (act)
 #pragma unroll
     for (int c = 0; c < OC; ++c) {
@@ -707,6 +758,11 @@ void render_fast_kernel(const RenderParams p) {
 #pragma unroll
       for (int r = 0; r < 5; ++r)
         if (t + 256 * r < kFWin) win[t + 256 * r] = wv[r];
+    }
+    if constexpr (kEarly && LP2 != 0) {
+      // element 1 and the ramps of the NEXT chunk, now that the mixing stage has consumed this chunk's (element 0's are in
+      // flight since the projection); a lane past the end of the call keeps what it holds: never used
+      if (k + kFChunk < p.total) load_x2(pf_f, pf_i);
     }
     if constexpr (!FIR && !kEarly) {
 #pragma unroll

@@ -76,6 +76,11 @@ struct RenderParams {
   int32_t demix_steps;      // bit 0 S1to2, 1 S2to3, 2 S3to5, 3 S5to7, 4 TF2toT2, 5 T2toT4
   int32_t demix_skip;       // samples at the start of every frame that use the previous mode
   int32_t demix_i0;         // frame position of the call's first sample (trimmed single-frame calls)
+  int32_t lpcm_mix;         // (RenderMixParams below) 0, or the form of a second element handed over as LPCM packets: 1 mono-coded
+                            // runs, 2 one coupled pair (render_fast_kernel's LP2).  `in2` then holds the packets' address and
+                            // in2_stream_stride / in2_frame_stride their strides in BYTES, for pick_route; the kernel reads
+                            // RenderMixParams.  Host only, and kept HERE, in what was padding in front of the next pointer,
+                            // like lpcm_bytes: no kernel's arguments move
   const int32_t *demix_tab; // device: [0..12) chs_in, [12..24) chs_out, [24] n_gain, [25..37) gain_ch,
                             //         [40..64) decoded position of an IAChannel (0 if it is not decoded)
   const float *demix_ftab;  // device: [0..12) gains, start_window[frame_size], stop_window[frame_size],
@@ -126,6 +131,16 @@ struct RenderParams {
   const uint8_t *lpcm;
   int64_t lpcm_stream_stride, lpcm_frame_stride;
   int32_t lpcm_off[16];
+};
+
+// render_fast_kernel<.., LP2> (iamf_hip_batch_render_lpcm_mix): the block above and, behind it, the SECOND element as 16-bit
+// little-endian LPCM packets.  Sample i of its channel m, frame f, stream s: lpcm2 + s * lpcm2_stream_stride + f *
+// lpcm2_frame_stride + lpcm2_off[m] + 2 * i (mono-coded runs), or lpcm2_off[0] + 4 * i and 2 bytes on for the L and R of one
+// coupled pair; every term a multiple of 8.  A type of its own: the block above keeps its size for every other kernel.
+struct RenderMixParams : RenderParams {
+  const uint8_t *lpcm2;
+  int64_t lpcm2_stream_stride, lpcm2_frame_stride;
+  int32_t lpcm2_off[4];
 };
 
 // IAChannel ids (reference IAMF_types.h:61-90; L5/R5 alias L7/R7)

@@ -52,6 +52,18 @@ using LpcmCoupledM = Ints<2, 6, 8, 10, 12>;
 // (4,5) .. (M-2, M-1) pairs again.  The form rule (lpcm_form.hpp) and the kernel (render_fast.hpp, LPC) both build on it.
 IAMF_HD constexpr bool lpcm_coupled_m(int m_total) { return LpcmCoupledM::has(m_total); }
 IAMF_HD constexpr bool lpcm_coupled_paired(int m_total, int m) { return m_total == 2 || m < 2 || m >= 4; }
+// render_fast_kernel<.., LP2>: BOTH elements of a mix as 16-bit packets (iamf_hip_batch_render_lpcm_mix).  Element 0: LpcmM
+// (mono-coded) or LpcmCoupledM (coupled); outputs LpcmOC; element 1: LP2 = 1 mono-coded runs (m2 = 1 or 4 at run time), 2 one
+// coupled stereo pair (m2 == 2).
+using LpcmMixK = Ints<1, 2>;
+IAMF_HD constexpr bool lpcm_mix_m2_ok(int lp2, int m2) { return lp2 == 1 ? (m2 == 1 || m2 == 4) : (lp2 == 2 && m2 == 2); }
+// Workgroups per CU the instance <M, OC, LP2> is built for: the highest of 4 / 3 / 2 at which the compiler reports no scratch
+// and no vector spill.  Every one of the 36 instances fits four (at most 127 vector registers: <16, 2, 1>; DESIGN.md 4.1e has
+// the table), where the f32 mixing variant is built for two; an instance that stops fitting gets its own answer here.
+IAMF_HD constexpr int lpcm_mix_wgs(int m, int oc, int lp2) {
+  (void)m, (void)oc, (void)lp2;
+  return 4;
+}
 // render_fanout_kernel<M, K, LP>: the fan-out fed with LPCM packets.  M: what LpcmM and FanM share (mono-coded ambisonics
 // elements are the only ones whose channels are contiguous 16-bit runs), K within FanK
 using FanLpM = Ints<4, 9, 16>;
@@ -189,6 +201,9 @@ enum class Family {
                 // iamf_hip_route_table_instances: the base listing's row set is pinned
   LpcmCoupled,  // render_fast_kernel<.., LP, EARLY, 2, LPC> (iamf_render_lpcm_coupled.hip); variant as Lpcm.  Listed by
                 // iamf_hip_route_family_instances only: the three tables' row sets are pinned
+  LpcmMix,      // render_fast_kernel<.., LP, true, 2, LPC, LP2> (iamf_render_lpcm_mix.hip, iamf_render_lpcm_mix_coupled.hip): both
+                // elements of a mix as 16-bit packets; variant = LP2 (1 mono-coded second element, 2 a coupled pair).  Listed
+                // by iamf_hip_route_family_instances only
 };
 struct Route {
   Family family;
@@ -239,6 +254,19 @@ inline bool lpcm_coupled_fused(int n_launch) {
   return true;
 }
 
+// Whether a range of n_launch streams takes the two-element packet form at all (render_prepare asks), under the rule of
+// lpcm_coupled_fused(): a (shape, size) at which it does not beat what a caller ran before — iamf_hip_lpcm_unpack of the
+// second element, then iamf_hip_batch_render_lpcm with d_in2, timed from a build of the parent commit in the same process —
+// by more than that baseline's own run-to-run spread is not fused.  Measured (tools/lpcm_mix_rate.py, MI355X, into stereo
+// s16, 64 frames x 1024, profiles/r11_lpcm_mix_rate.json): the baseline takes 3.93 / 5.19 / 5.62 (3rd-order bed + coupled
+// stereo), 1.85 / 2.59 / 2.67 (5.1 + mono) and 2.36 / 3.87 / 3.96 (7.1.4 + coupled stereo) times the fused call's time at
+// 512 / 2048 / 4096 streams, its spread against itself at most 0.0026 — every measured (shape, size) wins, so every size
+// is fused; this is where one that stops winning would be cut.
+inline bool lpcm_mix_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
 // rules.  The environment switches are read at every call (the tests set and unset them within one process).
@@ -252,6 +280,20 @@ inline Route pick_route(const RenderParams &p, int m) {
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
+    // both elements as 16-bit packets (RenderParams::lpcm_mix, zero unless iamf_hip_batch_render_lpcm_mix set it): the
+    // refusals of the single-element forms, element 1's packets on the same grid and inside the same 32-bit offset bound as
+    // element 0's (fast_shape_ok), ramps under fast_shape_ok's rules
+    if (p.lpcm_mix) {
+      if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m)) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on ||
+          p.lpcm_bytes == 3)
+        return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if (!p.in2 || !LpcmMixK::has(p.lpcm_mix) || !lpcm_mix_m2_ok(p.lpcm_mix, p.m2)) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if ((reinterpret_cast<uintptr_t>(p.in2) & 15) || (p.in2_stream_stride & 7) || (p.in2_frame_stride & 7))
+        return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if (((int64_t)p.total / p.frame_size + 2) * p.in2_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31)
+        return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      return take(Family::LpcmMix, p.lpcm_mix);
+    }
     // the coupled 16-bit form: its own instances (the pairing is a function of m: lpcm_form.hpp), the same refusals
     if (p.lpcm_coupled) {
       if (!LpcmCoupledM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on || p.lpcm_bytes == 3)
@@ -376,6 +418,17 @@ void for_each_render_instance_lpcm_coupled(F &&f) {
     for_each_int(LpcmCoupledM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM_COUPLED, early, m, oc, 0); }); });
 }
 
+// The two-element packet form (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x LpcmOC x LpcmMixK as its
+// two launchers do; k = LP2.
+template <class F>
+void for_each_render_instance_lpcm_mix(F &&f) {
+  const auto rows = [&](int m) {
+    for_each_int(LpcmOC{}, [&](int oc) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_LPCM_MIX, 0, m, oc, k); }); });
+  };
+  for_each_int(LpcmM{}, rows);
+  for_each_int(LpcmCoupledM{}, rows);
+}
+
 // the row of the kernel launch() runs for a route (a FirSplit call launches render_fast_kernel<2, 2> behind it as well:
 // launch() counts that row too)
 struct RouteKey {
@@ -399,6 +452,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::Generic: return {IAMF_HIP_ROUTE_GENERIC, 0, m, 0, 0};
     case Family::Lpcm24: return {IAMF_HIP_ROUTE_LPCM24, r.variant, m, p.out_ch, 0};   // a row of table 2
     case Family::LpcmCoupled: return {IAMF_HIP_ROUTE_LPCM_COUPLED, r.variant, m, p.out_ch, 0};   // a family listing's row
+    case Family::LpcmMix: return {IAMF_HIP_ROUTE_LPCM_MIX, 0, m, p.out_ch, r.variant};   // a family listing's row, k = LP2
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

@@ -70,6 +70,10 @@ class LpcmInput(C.Structure):   # iamf_hip_lpcm_input
                 ("first_sample", C.c_int32), ("layout", LpcmLayout)]
 
 
+class LpcmMixCall(C.Structure):   # iamf_hip_lpcm_mix_call
+    _fields_ = [("in_", LpcmInput * 2), ("args", RenderArgs)]
+
+
 class FanoutReport(C.Structure):   # iamf_hip_fanout_report
     _fields_ = [("n_fused", C.c_int32), ("input_fused", C.c_int32), ("n_unpacks", C.c_int32), ("reserved", C.c_int32)]
 
@@ -82,7 +86,7 @@ class RouteRow(C.Structure):   # iamf_hip_route_row
 # IAMF_HIP_ROUTE_*: the kernel families of iamf_hip_route_row::family
 ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, WIDE4_DEMIX=7, WIDE4_DOWN=8, WIDE4_MIX=9,
              WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, LPCM24=16, LPCM_COUPLED=17,
-             RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23)
+             RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23, LPCM_MIX=25)
 ROUTE_NAME = {v: k for k, v in ROUTE.items()}
 
 
@@ -178,6 +182,7 @@ def lib():
         L.iamf_hip_batch_render_ex.argtypes = [C.c_void_p, C.POINTER(RenderArgs)]
         L.iamf_hip_batch_render_lpcm.argtypes = [C.c_void_p, C.POINTER(LpcmInput), C.POINTER(RenderArgs)]
         L.iamf_hip_batch_render_lpcm_range.argtypes = [C.c_void_p, C.POINTER(LpcmInput), C.POINTER(RenderArgs), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_lpcm_mix.argtypes = [C.c_void_p, C.POINTER(LpcmMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_resampler_destroy.argtypes = [C.c_void_p]
@@ -546,6 +551,18 @@ class Batch:
         r = lib().iamf_hip_batch_render_lpcm_range(self.h, C.byref(lpcm_input), C.byref(args), stream0, n_streams)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_lpcm_range")
+        return r
+
+    def render_lpcm_mix(self, in0, in1, args, stream0=None, n_streams=None):
+        """iamf_hip_batch_render_lpcm_mix: element 0 and the second element as LPCM packets (two LpcmInput), `args` a
+        RenderArgs with d_in = d_in2 = None; the whole batch unless a range is named"""
+        call = LpcmMixCall()
+        call.in_[0], call.in_[1], call.args = in0, in1, args
+        s0 = 0 if stream0 is None else stream0
+        n = self.cfg.n_streams - s0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_lpcm_mix(self.h, C.byref(call), s0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_lpcm_mix")
         return r
 
     def render_range(self, args, stream0, n_streams):

@@ -668,6 +668,35 @@ int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in,
 int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
                                      int32_t stream0, int32_t n_streams);
 
+/* BOTH elements of a two-element mix handed over as LPCM packets: a bed plus a small second element (dialogue, commentary),
+ * the one multi-element shape of the base profile (the reference allows two elements per mix presentation).  For a batch
+ * with a second element (iamf_hip_batch_set_second_element) the call leaves the batch, d_pcm and its return value exactly as
+ *   iamf_hip_lpcm_unpack of in[0] and of in[1] into planar f32, then iamf_hip_batch_render_range with d_in / d_in2 on them
+ * would: PCM, the sample-frames emitted and the persisted stream state are the same bit for bit, for every packet layout
+ * iamf_hip_lpcm_unpack accepts, every output layout and PCM format, and every combination of ramps — so this call, the
+ * single-element packet call and the f32 calls may follow one another on a batch.
+ *   in[0], in[1]  element 0 and element 1, each with its own buffer, strides and layout as for iamf_hip_batch_render_lpcm
+ *                 (in[1].layout.channels = the second element's channels); both first_sample must be equal.
+ *   args          as for iamf_hip_batch_render_lpcm; d_in AND d_in2 must be NULL (the in_* / in2_* strides are not used).
+ * One KERNEL when: the batch conditions of iamf_hip_batch_render_lpcm hold except that the second element and ramps are
+ * welcome (ramps 16-byte aligned, ramp_stream_stride a multiple of 4); no fixed PCM channel stride; element 0 has the 16-bit
+ * form that call fuses (mono-coded runs of 1 / 4 / 9 / 16 channels, or the coupled form of 2 / 6 / 8 / 10 / 12); element 1 is
+ * 16-bit little-endian on the same grid (d_raw 16-byte aligned, strides multiples of 8) and is either mono-coded runs of 1 or
+ * 4 channels or ONE coupled stereo pair; and no weight of either matrix lies outside 2^-100 .. 2^100.  Then the render kernel
+ * reads both elements' packets itself: 2 * (channels + channels2) + 4 bytes per sample-frame into s16 stereo instead of the
+ * 10 * (channels + channels2) + 4 of two unpack passes and the f32 mixing kernel.  Every other input — 24-bit or big-endian
+ * packets on either side, a stereo second element coded as two mono runs, wide layouts, limiter off, ... — is unpacked into
+ * two buffers of the batch and takes the f32 kernels; IAMF_HIP_LPCM_UNFUSED=1 forces that.
+ * Returns the sample-frames emitted per stream, as iamf_hip_batch_render_lpcm_range.  IAMF_HIP_ERR_BAD_ARG, before anything
+ * is queued, allocated or changed: a batch without a second element, non-NULL args.d_in or args.d_in2, a NULL d_raw in
+ * either input, different first_sample in the two inputs, a bad range; and, with its own code, whatever
+ * iamf_hip_batch_render_range refuses. */
+typedef struct {
+  iamf_hip_lpcm_input in[2];
+  iamf_hip_render_args args;
+} iamf_hip_lpcm_mix_call;
+int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_call *call, int32_t stream0, int32_t n_streams);
+
 /* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
  * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
  *
@@ -738,6 +767,9 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *     LPCM                 variant 1 = early per-channel prefetch, 0 = late; m, c
  *     LPCM24               the same for 24-bit samples (table 2 of iamf_hip_route_table_instances only)
  *     LPCM_COUPLED         the same for the coupled 16-bit form (iamf_hip_route_family_instances only)
+ *     LPCM_MIX             both elements of a mix as 16-bit packets (iamf_hip_batch_render_lpcm_mix): m, c of element 0 as LPCM /
+ *                          LPCM_COUPLED, k = form of element 1 (1 mono-coded runs, 2 a coupled pair); variant 0
+ *                          (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -770,7 +802,8 @@ enum {
   IAMF_HIP_ROUTE_RS_PLAIN = 20,
   IAMF_HIP_ROUTE_RS_TILE = 21,
   IAMF_HIP_ROUTE_RS_BLOCK = 22,
-  IAMF_HIP_ROUTE_RS_DIRECT = 23
+  IAMF_HIP_ROUTE_RS_DIRECT = 23,
+  IAMF_HIP_ROUTE_LPCM_MIX = 25       /* no table: iamf_hip_route_family_instances / _family_tally (18, 19, 24: unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -801,7 +834,8 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * rows of its table — the SAME counters, so a reset here resets them there; for LPCM_COUPLED its rows (variant, m, c as
  * LPCM), which no table lists and whose launches show in no table's tally.  _instances: every row of the family;
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
- * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed. */
+ * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
+ * the same way: rows and counters of its own, in no table. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
