@@ -344,6 +344,7 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
     case Family::LpcmMix:
       launched = p.lpcm_coupled ? iamf_hip_fast_lpcm_mix_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_lpcm_mix_launch(&p, m, r.variant, st);
       break;
+    case Family::FastInterleaved: launched = iamf_hip_fast_interleaved_launch(&p, m, st); break;
     case Family::FirSplit: {
       // (1) the FFT stage for every hop of every stream -> y in HBM (overlap-save blocks are independent: one grid); (2)
       // gains, limiter, pack = the two-channel matrix kernel with the identity over y (one "frame" of `total` samples per
@@ -390,7 +391,7 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
   HIPCHK(hipGetLastError());
   const RouteKey k = route_key(r, p, m);   // the tally of iamf_hip_route_tally
   if (r.family == Family::Lpcm24) iamf_hip_route_count_table(2, k.family, k.variant, k.m, k.c, k.k);   // its own table
-  else if (r.family == Family::LpcmCoupled || r.family == Family::LpcmMix) iamf_hip_route_count_family(k.family, k.variant, k.m, k.c, k.k);   // no table's
+  else if (r.family == Family::LpcmCoupled || r.family == Family::LpcmMix || r.family == Family::FastInterleaved) iamf_hip_route_count_family(k.family, k.variant, k.m, k.c, k.k);   // no table's
   else iamf_hip_route_count(k.family, k.variant, k.m, k.c, k.k);
   if (r.family == Family::FirSplit) iamf_hip_route_count(IAMF_HIP_ROUTE_FAST, 0, 2, 2, 0);
   return IAMF_HIP_OK;
@@ -484,8 +485,9 @@ struct PreparedCall {
 };
 
 // lp2 (with lp, iamf_hip_batch_render_lpcm_mix): the second element as packets too; a.d_in2 is then a non-null placeholder.
+// il (iamf_hip_batch_render_interleaved): the call may take the interleaved form of the fast kernel; everything else as without.
 int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc,
-                   const LpcmIn *lp2 = nullptr) {
+                   const LpcmIn *lp2 = nullptr, bool il = false) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
   if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || !b->lp_scale_ok || getenv("IAMF_HIP_LPCM_UNFUSED")))
     return kNotFused;
@@ -684,6 +686,8 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     p.pcm = b->d_nat;
     p.pcm_stream_stride = (int64_t)per_stream;
   }
+  // the interleaved form packs into the caller's buffer itself and knows no LFE slot; pick_route has the call's other rules
+  p.interleaved = (il && !restride && !b->lfe && interleaved_fused(cnt)) ? 1 : 0;
   pc.a = a;
   pc.m_eff = m_eff;
   pc.lds = lds;
@@ -1317,6 +1321,22 @@ int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_ca
   ur = lpcm_unpack_range(b, in1, nf, first, count, stream0, n_streams, st, a, true);
   if (ur != IAMF_HIP_OK) return ur;
   return render_range_impl(b, &a, stream0, n_streams, nullptr);
+}
+
+// Interleaved f32 of any call length (include/iamf_hip.h): iamf_hip_batch_render_range with leave to take
+// render_fast_kernel<.., IL, RAG> (Family::FastInterleaved) where pick_route's rules hold.  The same checks in the same
+// order, the same internal route (render_prepare, render_launch, render_commit) for everything else.
+int iamf_hip_batch_render_interleaved(iamf_hip_batch *b, const iamf_hip_interleaved_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  if (b->cfg.frame_size != 1) return IAMF_HIP_ERR_BAD_ARG;
+  int64_t total = 0;
+  const int rc = range_args_check(b, &call->args, stream0, n_streams, &total);
+  if (rc != IAMF_HIP_OK || total == 0) return rc;
+  PreparedCall pc;
+  int r = render_prepare(b, call->args, (int)total, stream0, n_streams, nullptr, pc, nullptr, true);
+  if (r != IAMF_HIP_OK) return r;
+  r = render_launch(pc);
+  return r != IAMF_HIP_OK ? r : render_commit(b, pc);
 }
 
 int iamf_hip_batch_render_ex(iamf_hip_batch *b, const iamf_hip_render_args *a) {

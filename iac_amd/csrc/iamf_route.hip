@@ -49,7 +49,9 @@ struct RouteTable {
       index[n] = n;
       ++n;
     };
-    if (table == 4) {
+    if (table == 5) {
+      for_each_render_instance_interleaved(add);
+    } else if (table == 4) {
       for_each_render_instance_lpcm_mix(add);
     } else if (table == 3) {
       for_each_render_instance_lpcm_coupled(add);
@@ -104,11 +106,18 @@ const RouteTable &route_table_lpcm_mix() {
   return t;
 }
 
+// ... and the interleaved f32 form (FAST_INTERLEAVED)
+const RouteTable &route_table_interleaved() {
+  static const RouteTable t(5);
+  return t;
+}
+
 std::atomic<int64_t> g_launches[kRouteCap + 1];
 std::atomic<int64_t> g_launches_ext[kRouteCap + 1];
 std::atomic<int64_t> g_launches_lpcm24[kRouteCap + 1];
 std::atomic<int64_t> g_launches_lpcm_coupled[kRouteCap + 1];
 std::atomic<int64_t> g_launches_lpcm_mix[kRouteCap + 1];
+std::atomic<int64_t> g_launches_interleaved[kRouteCap + 1];
 
 // the indexed form: table 0 and 1 ARE the base and the extension listing (rows and counters), 2 onwards have their own
 constexpr int kRouteTables = 3;
@@ -121,12 +130,20 @@ std::atomic<int64_t> *launches_of(int table) {
 // The listing by family (iamf_hip_route_family_instances) walks every row set there is: the numbered tables, whose count is
 // pinned, and the sets added since, which have no number.  A family added to a set — or a set added here — is listed
 // without a new entry point.
-constexpr int kRouteSets = 5;
+constexpr int kRouteSets = 6;
 const RouteTable *set_of(int set) {
-  return set < kRouteTables ? table_of(set) : set == 3 ? &route_table_lpcm_coupled() : set == 4 ? &route_table_lpcm_mix() : nullptr;
+  return set < kRouteTables ? table_of(set)
+         : set == 3 ? &route_table_lpcm_coupled()
+         : set == 4 ? &route_table_lpcm_mix()
+         : set == 5 ? &route_table_interleaved()
+                    : nullptr;
 }
 std::atomic<int64_t> *set_launches_of(int set) {
-  return set < kRouteTables ? launches_of(set) : set == 3 ? g_launches_lpcm_coupled : set == 4 ? g_launches_lpcm_mix : nullptr;
+  return set < kRouteTables ? launches_of(set)
+         : set == 3 ? g_launches_lpcm_coupled
+         : set == 4 ? g_launches_lpcm_mix
+         : set == 5 ? g_launches_interleaved
+                    : nullptr;
 }
 
 int list_instances(const RouteTable &t, iamf_hip_route_row *rows, int cap) {

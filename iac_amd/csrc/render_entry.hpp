@@ -28,6 +28,8 @@ IAMF_INTERNAL int iamf_hip_fast_lpcm_coupled_launch(const void *params, int m, i
 // (params->lpcm_coupled); params: a RenderMixParams; lp2: Route::variant of Family::LpcmMix
 IAMF_INTERNAL int iamf_hip_fast_lpcm_mix_launch(const void *params, int m, int lp2, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fast_lpcm_mix_coupled_launch(const void *params, int m, int lp2, hipStream_t st);
+// iamf_render_interleaved.hip: render_fast_kernel<M, OC, .., IL, RAG>, interleaved f32 of any call length (params->interleaved)
+IAMF_INTERNAL int iamf_hip_fast_interleaved_launch(const void *params, int m, hipStream_t st);
 // iamf_render_fir_m2b.hip: render_fast_kernel<M, 2, stage> / the FFT stage alone (fir_fft_kernel)
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch(const void *params, int m, int stage, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch_fft(const void *params, int m, hipStream_t st);

@@ -53,12 +53,17 @@ __device__ __forceinline__ float readlane_f(float v, int lane) {
 // With stop_clean the walk ends behind the first block after b0 in which nothing triggered (the caller
 // then re-evaluates the rest of the chunk in parallel from the state reached); the return value is
 // the first block NOT processed.
-template <typename Lookup>
+// RAG: the chunk holds `cnt` samples, any number >= 1, and nblk counts its partial last block.  That block has L < 64 real
+// lanes: the lanes behind them see a peak of 0 (they never trigger, and they end a run of triggers), every count of settled
+// lanes is taken up to L instead of 64, and the walk ends behind lane L - 1 — (n, gs, ge) and g_last are then the state after
+// the chunk's last REAL sample.
+template <bool RAG = false, typename Lookup>
 __device__ __forceinline__ int limiter_wave(const float *arr_p, float *arr_g,
                                             Lookup ctab, int b0, int nblk, int &n, float &gs,
                                             float &ge, float &g_last, float thr, int n_atk, int n_end,
-                                            bool stop_clean = false) {
+                                            bool stop_clean = false, int cnt = 0) {
   const int lane = threadIdx.x & 63;
+  int last_lane = 63;   // (RAG) the last real lane of the last block walked
   // A dependent chain: whenever this wave has an instruction ready it should go first, ahead of the
   // co-resident workgroup's wave on the same SIMD (which has a whole chunk of independent work).
   __builtin_amdgcn_s_setprio(3);
@@ -66,7 +71,13 @@ __device__ __forceinline__ int limiter_wave(const float *arr_p, float *arr_g,
   float gacc = 1.0f;
   int b = b0;
   for (; b < nblk; ++b) {
-    const float pk = arr_p[b * 64 + lane];
+    float pk = arr_p[b * 64 + lane];
+    int L = 64;   // real lanes of this block
+    if constexpr (RAG) {
+      L = cnt - 64 * b < 64 ? cnt - 64 * b : 64;
+      pk = lane < L ? pk : 0.f;
+      last_lane = L - 1;
+    }
     const float e = thr / pk;  // targetEndGain if this sample triggers (IEEE division, as the reference)
     int l0 = 0;
     bool clean = true;
@@ -82,7 +93,7 @@ __device__ __forceinline__ int limiter_wave(const float *arr_p, float *arr_g,
       const unsigned long long mask = __ballot(tr);
       if (mask == 0ull) {
         if (lane >= l0) gacc = g;
-        n = n + (64 - l0) < n_end ? n + (64 - l0) : n_end;
+        n = n + (L - l0) < n_end ? n + (L - l0) : n_end;
         break;
       }
       clean = false;
@@ -92,7 +103,7 @@ __device__ __forceinline__ int limiter_wave(const float *arr_p, float *arr_g,
       ge = readlane_f(e, f);
       n = 0;
       l0 = f + 1;
-      if (l0 >= 64) break;
+      if (l0 >= L) break;
 
       // A trigger is usually followed by a run of triggers.  Assume every later lane's
       // predecessor triggered: g[l] = g[l-1] - a1*(g[l-1] - e[l-1]).  Jacobi sweeps with a
@@ -133,9 +144,13 @@ __device__ __forceinline__ int limiter_wave(const float *arr_p, float *arr_g,
       if (lane > f && lane <= m) gacc = G;
       gs = readlane_f(G, m - 1);
       ge = readlane_f(e, m - 1);
+      if (RAG && m >= L) {  // the run reaches the chunk's last real sample (lane m is the first absent one)
+        n = 0;
+        break;
+      }
       n = 1;  // lane m stepped once from the trigger at m-1 and did not re-trigger
       l0 = m + 1;
-      if (l0 >= 64) break;
+      if (l0 >= L) break;
     }
     arr_g[b * 64 + lane] = gacc;
     if (stop_clean && clean && b > b0) {
@@ -143,7 +158,7 @@ __device__ __forceinline__ int limiter_wave(const float *arr_p, float *arr_g,
       break;
     }
   }
-  g_last = readlane_f(gacc, 63);
+  g_last = readlane_f(gacc, RAG ? last_lane : 63);
   __builtin_amdgcn_s_setprio(0);
   return b;
 }
@@ -226,8 +241,17 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       Through a buffer resource of its own; converted where the mixing stage consumes it, "/ 32768" folded into the staged
 //       mat2 weights as it is into mat.  Everything behind the two projections is the IN2 body.  Element 0's next chunk is
 //       requested channel by channel under the projection (kEarly); element 1's and the ramps' behind the mixing stage.
+// IL:   (plain matrix variant, frame size 1: iamf_hip_batch_render_interleaved) the element arrives as ordinary interleaved
+//       f32, [sample-frame][channel] with the sample-frames dense.  A lane's four sample-frames are 16 * M contiguous bytes
+//       of the stream's buffer resource: one 16-byte load for M = 1, two for M = 2, transposed in registers into the x[m]
+//       quads the projection consumes.  The resource ends with the call (total * M * 4 bytes), so lanes and components past
+//       its end read zeros; the next chunk is requested once the last channel of this one has been consumed.
+// RAG:  the call may have any length >= 1: the last chunk's `cnt` need not be a multiple of 64 or of 4.  Absent samples
+//       enter the ring as zeros (behind everything that is persisted), never count as a hit, and the limiter's recurrence,
+//       the step count and the PCM stores end with sample cnt - 1; the ring position behind the call is then no multiple of
+//       16, which only the persisting code sees (the next call places its own ring).
 template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2, bool LPC = false,
-          int LP2 = 0>
+          int LP2 = 0, bool IL = false, bool RAG = false>
 __global__ __launch_bounds__(FIR == 1 ? 512 : 256, LP2 ? lpcm_mix_wgs(M, OC, LP2) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
 void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, RenderParams> p) {
   static_assert(!(FIR && DOWN), "one renderer");
@@ -236,6 +260,8 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   static_assert(!(IN2 && (FIR || DOWN)), "the second element joins a matrix-rendered first one");
   static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
   static_assert(!LPC || (LP && LPB == 2 && lpcm_coupled_m(M)), "coupled pairs: 16-bit packets of a loudspeaker layout");
+  static_assert(!IL || (!FIR && !DOWN && !IN2 && !LP && EARLY && M <= 2), "interleaved f32 feeds the plain matrix variant, one or two channels");
+  static_assert(!RAG || IL, "ragged calls: the interleaved form");
   constexpr bool LP3 = LP && LPB == 3;
   extern __shared__ float lds[];
   constexpr int R = kFRing;
@@ -408,13 +434,16 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   // arithmetic per load (a 64-bit pointer per channel cost an add each and, for the packets' sixteen run offsets, sixteen
   // scalar register pairs that did not fit).  Offsets are 32-bit: the host sends longer calls elsewhere (fast_shape_ok).
   const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void *>(LP ? static_cast<const void *>(lp_s) : static_cast<const void *>(in_s)), 0, 0x7fffffff, 0x00020000);
+      const_cast<void *>(LP ? static_cast<const void *>(lp_s) : static_cast<const void *>(in_s)), 0, IL ? p.total * M * 4 : 0x7fffffff, 0x00020000);
   // Frames that are whole chunks (frame size a multiple of 1024 — the usual 1024): a chunk lies in ONE frame, its frame
   // number and position are workgroup-uniform counters; otherwise each lane divides.
   const bool fr_uni = (fs & (kFChunk - 1)) == 0;
   int fu = 0, iu = 0;   // frame / position of the first sample of the chunk the next prefetch fetches (fr_uni)
   auto frame_pos = [&](int kq, int &f, int &i) {
-    if (fr_uni) {
+    if constexpr (IL) {   // frame size 1
+      f = kq;
+      i = 0;
+    } else if (fr_uni) {
       f = fu;
       i = iu + 4 * t;
     } else {
@@ -466,9 +495,28 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
 #pragma unroll
     for (int m = 0; m < (LP ? M : 0); ++m) load_lp_one(m, f, i, rs_in);
   };
+  // IL: the lane's four sample-frames from sample-frame k of the call on (k a multiple of 4: 16 * M bytes on their own grid,
+  // the stream's base and stride being multiples of 16 bytes — pick_route), transposed into x[m]
+  auto load_il = [&](int k, __amdgpu_buffer_rsrc_t rs) {
+    if constexpr (IL) {
+      const int vo = 4 * M * k;
+      const auto a = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 0, 2 /* nt */);
+      if constexpr (M == 1) {
+        x[0] = make_float4(__uint_as_float(a[0]), __uint_as_float(a[1]), __uint_as_float(a[2]), __uint_as_float(a[3]));
+      } else {
+        const auto b = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, 16, 2 /* nt */);
+        x[0] = make_float4(__uint_as_float(a[0]), __uint_as_float(a[2]), __uint_as_float(b[0]), __uint_as_float(b[2]));
+        x[M - 1] = make_float4(__uint_as_float(a[1]), __uint_as_float(a[3]), __uint_as_float(b[1]), __uint_as_float(b[3]));
+      }
+    }
+  };
   auto load_f32 = [&](int f, int i) {
+    if constexpr (IL) {
+      load_il(f, rs_in);   // (frame size 1: the frame number is the sample-frame's)
+    } else {
 #pragma unroll
-    for (int m = 0; m < ((!LP && !FIR) ? M : 0); ++m) load_f32_one(m, f, i, rs_in);
+      for (int m = 0; m < ((!LP && !FIR) ? M : 0); ++m) load_f32_one(m, f, i, rs_in);
+    }
   };
   float drec[DOWN ? 11 : 1];  // DOWN: the frame record of the lane's samples, fetched with them
   const int dmx_nfr = DOWN ? (p.total + fs - 1) / fs : 0;
@@ -524,7 +572,7 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   if constexpr (!FIR) fetch_window(n_st);
 
   for (int c0 = 0; c0 < p.total; c0 += kFChunk) {
-    const int cnt = p.total - c0 < kFChunk ? p.total - c0 : kFChunk;  // multiple of 64
+    const int cnt = p.total - c0 < kFChunk ? p.total - c0 : kFChunk;  // multiple of 64 (RAG: any number >= 1)
     const int k = c0 + 4 * t;
     const bool valid = act && 4 * t < cnt;
     const int64_t gk = p.pos0 + k;
@@ -650,7 +698,9 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
             if (!lpcm_coupled_paired(M, m)) load_lp_one(m, pf_f, pf_i, rs_pf);
             else if (m & 1) load_lp_one(m - 1, pf_f, pf_i, rs_pf);
           } else if constexpr (LP) load_lp_one(m, pf_f, pf_i, rs_pf);
-          else load_f32_one(m, pf_f, pf_i, rs_pf);
+          else if constexpr (IL) {   // (the sample-frames hold every channel: once the last one has been consumed)
+            if (m == M - 1) load_il(pf_f, rs_pf);
+          } else load_f32_one(m, pf_f, pf_i, rs_pf);
         }
       }
     }
@@ -743,6 +793,15 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
         v.y = ((v.y * m_eg) * m_og) * m_lg;
         v.z = ((v.z * m_eg) * m_og) * m_lg;
         v.w = ((v.w * m_eg) * m_og) * m_lg;
+      }
+      if constexpr (RAG) {
+        if (cnt < kFChunk) {   // (workgroup-uniform) the ragged last chunk: samples behind its end are zeros, whatever was loaded
+          const int nr = cnt - 4 * t;
+          v.x = nr > 0 ? v.x : 0.f;
+          v.y = nr > 1 ? v.y : 0.f;
+          v.z = nr > 2 ? v.z : 0.f;
+          v.w = nr > 3 ? v.w : 0.f;
+        }
       }
       y[c] = v;
       pm.x = fmaxf(pm.x, fabsf(v.x));
@@ -843,7 +902,7 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
         return (d >= 0 && d < kFWin) ? win[d] : head[ci < kFWin ? ci : kFWin - 1];
       }
     };
-    const int nblk = cnt >> 6;
+    const int nblk = RAG ? (cnt + 63) >> 6 : cnt >> 6;   // (RAG: the partial block counts)
     int bs = 0;
     while (true) {
       if (act) {
@@ -890,7 +949,14 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
           }
           g = make_float4(gh[0], gh[1], gh[2], gh[3]);
           // the first sample that contradicts the hypothesis: sought only in a wave that has one
-          const float px = pk4.x * g.x, py = pk4.y * g.y, pz = pk4.z * g.z, pw = pk4.w * g.w;
+          float px = pk4.x * g.x, py = pk4.y * g.y, pz = pk4.z * g.z, pw = pk4.w * g.w;
+          if constexpr (RAG) {   // absent samples never contradict the hypothesis (their windows hold real peaks)
+            const int nr = cnt - 4 * t;
+            px = nr > 0 ? px : 0.f;
+            py = nr > 1 ? py : 0.f;
+            pz = nr > 2 ? pz : 0.f;
+            pw = nr > 3 ? pw : 0.f;
+          }
           const bool hit = valid && fmaxf(fmaxf(px, py), fmaxf(pz, pw)) > thr;
           if (__ballot(hit) != 0ull && hit) {
             if (pw > thr) kfirst = 4 * t + 3;
@@ -898,7 +964,10 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
             if (py > thr) kfirst = 4 * t + 1;
             if (px > thr) kfirst = 4 * t + 0;
           }
-          if (4 * t + 4 == cnt) misc[8] = g.w;  // gain of the chunk's last sample under the hypothesis
+          if constexpr (RAG) {   // sample cnt - 1 is any of the lane's four
+            const int jl = cnt - 1 - 4 * t;
+            if (jl >= 0 && jl < 4) misc[8] = jl == 0 ? g.x : (jl == 1 ? g.y : (jl == 2 ? g.z : g.w));
+          } else if (4 * t + 4 == cnt) misc[8] = g.w;  // gain of the chunk's last sample under the hypothesis
         }
         const unsigned long long any = __ballot(kfirst != kBig);
         if (lane == 0) misc[wave] = __int_as_float(any ? __builtin_amdgcn_readlane(kfirst, __builtin_ctzll(any)) : kBig);
@@ -917,7 +986,7 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
       if (act && wave == cw) {
         int ln = n_st + 64 * (b0 - bs) < n_end ? n_st + 64 * (b0 - bs) : n_end;
         float lgs = gs, lge = ge, lgl = g_cur;
-        const int be = limiter_wave(arr_p, arr_g, look, b0, nblk, ln, lgs, lge, lgl, thr, n_atk, n_end, true);
+        const int be = limiter_wave<RAG>(arr_p, arr_g, look, b0, nblk, ln, lgs, lge, lgl, thr, n_atk, n_end, true, cnt);
         if (lane == 0) {
           misc[4] = lgl;
           misc[5] = lgs;
@@ -950,6 +1019,8 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
         o[c] = make_float4(d.x * g.x, d.y * g.y, d.z * g.z, d.w * g.w);
       }
       uint8_t *dst = pcm + (j0 - out_base) * (int64_t)OC * bytes;
+      // RAG: the chunk's last quad writes its nr real sample-frames only, piece by piece; whole quads keep their stores
+      const int nr = RAG ? (cnt - 4 * t < 4 ? cnt - 4 * t : 4) : 4;
       if (p.out_format == IAMF_HIP_FMT_S16) {
         int v[OC][4];
 #pragma unroll
@@ -965,7 +1036,19 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
           w.y = (uint32_t)(v[0][1] & 0xffff) | ((uint32_t)v[OC - 1][1] << 16);
           w.z = (uint32_t)(v[0][2] & 0xffff) | ((uint32_t)v[OC - 1][2] << 16);
           w.w = (uint32_t)(v[0][3] & 0xffff) | ((uint32_t)v[OC - 1][3] << 16);
-          *reinterpret_cast<uint4 *>(dst) = w;
+          if (RAG && nr < 4) {
+            uint32_t *d2 = reinterpret_cast<uint32_t *>(dst);
+            d2[0] = w.x;
+            if (nr > 1) d2[1] = w.y;
+            if (nr > 2) d2[2] = w.z;
+          } else {
+            *reinterpret_cast<uint4 *>(dst) = w;
+          }
+        } else if (RAG && nr < 4) {
+          uint16_t *d1 = reinterpret_cast<uint16_t *>(dst);
+          d1[0] = (uint16_t)(v[0][0] & 0xffff);
+          if (nr > 1) d1[1] = (uint16_t)(v[0][1] & 0xffff);
+          if (nr > 2) d1[2] = (uint16_t)(v[0][2] & 0xffff);
         } else {
           uint2 w;
           w.x = (uint32_t)(v[0][0] & 0xffff) | ((uint32_t)v[0][1] << 16);
@@ -978,6 +1061,7 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
           const float ov[4] = {o[c].x, o[c].y, o[c].z, o[c].w};
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
+            if (RAG && j >= nr) continue;
             const int vv = (int)to_scaled(ov[j], 8388608.f, -8388608.f, 8388607.f);
             uint8_t *d3 = dst + (j * OC + c) * 3;
             d3[0] = (uint8_t)(vv & 0xff);
@@ -992,16 +1076,16 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
           const float ov[4] = {o[c].x, o[c].y, o[c].z, o[c].w};
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            d32[j * OC + c] = (int32_t)(long long)to_scaled(ov[j], 2147483648.f, -2147483648.f, 2147483647.f);
+            if (!RAG || j < nr) d32[j * OC + c] = (int32_t)(long long)to_scaled(ov[j], 2147483648.f, -2147483648.f, 2147483647.f);
         }
       } else {
         float *df = reinterpret_cast<float *>(dst);
 #pragma unroll
         for (int c = 0; c < OC; ++c) {
           df[0 * OC + c] = o[c].x;
-          df[1 * OC + c] = o[c].y;
-          df[2 * OC + c] = o[c].z;
-          df[3 * OC + c] = o[c].w;
+          if (!RAG || nr > 1) df[1 * OC + c] = o[c].y;
+          if (!RAG || nr > 2) df[2 * OC + c] = o[c].z;
+          if (!RAG || nr > 3) df[3 * OC + c] = o[c].w;
         }
       }
     }

@@ -89,6 +89,10 @@ struct RenderParams {
   int32_t demix_layout;     // IAChannelLayoutType of the target layout (render_wide4_kernel<.., DMX>)
   int32_t demix_gmask;      // bit m: decoded channel m takes the output gain demix_ftab[12 + 2*frame_size + m]
   int32_t demix_w4;         // 1 if the in-register demixer of render_wide4.hpp covers this configuration
+  int32_t interleaved;      // 1: the call came through iamf_hip_batch_render_interleaved (frame size 1: `in` is ordinary interleaved
+                            // f32) and may take render_fast_kernel<.., IL, RAG> (pick_route: Family::FastInterleaved); 0: every
+                            // rule as it stood.  Host only, and kept HERE, in what was padding in front of the next pointer,
+                            // like lpcm_bytes: the block keeps its size and every other field its offset
   // ---- render_wide4.hpp: where lanes that have nothing to emit send their 16-byte store, so that every
   //      chunk issues the same vector-memory instructions and the compiler can COUNT them (s_waitcnt vmcnt(N)
   //      instead of vmcnt(0) at the top of the chunk loop); device [n_streams][256 lanes][16 B] ----

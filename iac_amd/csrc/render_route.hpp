@@ -64,6 +64,10 @@ IAMF_HD constexpr int lpcm_mix_wgs(int m, int oc, int lp2) {
   (void)m, (void)oc, (void)lp2;
   return 4;
 }
+// render_fast_kernel<.., IL, RAG>: ordinary interleaved f32 of any call length (iamf_hip_batch_render_interleaved): the stage
+// behind the resampler, mono or stereo in and out
+using InterleavedM = Ints<1, 2>;
+using InterleavedOC = Ints<1, 2>;
 // render_fanout_kernel<M, K, LP>: the fan-out fed with LPCM packets.  M: what LpcmM and FanM share (mono-coded ambisonics
 // elements are the only ones whose channels are contiguous 16-bit runs), K within FanK
 using FanLpM = Ints<4, 9, 16>;
@@ -147,6 +151,25 @@ inline bool fast_shape_ok(const RenderParams &p, bool force_generic) {
   return true;
 }
 
+// What the interleaved, ragged form of the fast kernel (render_fast.hpp, IL and RAG) needs of a call that came through
+// iamf_hip_batch_render_interleaved: one matrix-rendered element of one or two channels with constant gains into one or two
+// channels with the limiter on, dense sample-frames on the 16-byte grid, any length.  The position as fast_shape_ok wants
+// it: a multiple of 16, or 240 samples on (the ring is placed per call).  IAMF_HIP_INTERLEAVED_UNFUSED=1 sends every such
+// call down the rules below, as does a zero `interleaved`.
+inline bool interleaved_shape_ok(const RenderParams &p, int m, bool force_generic) {
+  if (!p.interleaved || force_generic || getenv("IAMF_HIP_INTERLEAVED_UNFUSED")) return false;
+  if (!p.limiter_on || !p.in || !InterleavedOC::has(p.out_ch) || !InterleavedM::has(m) || p.og_ch < p.out_ch || p.n_end < kFWin) return false;
+  if (p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe || p.lpcm)
+    return false;
+  if (p.frame_size != 1 || p.in_frame_stride != m) return false;   // dense: sample-frame k of the call at float k * m
+  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  if ((p.pos0 & 15) && p.pos0 < kDelay) return false;
+  // the kernel addresses a stream's input of one call with 32-bit byte offsets, and its buffer resource ends with the call
+  if (p.total < 1 || (int64_t)p.total * m * 4 + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
+  return true;
+}
+
 // What the wide kernels (render_wide.hpp, render_wide4.hpp) share: 3..24 output channels, limiter on, aligned calls.
 // (Not looked at here: the stream position and the stages in front — demixer, down-mixer, mixer — which differ
 // between the two: pick_route.)
@@ -204,6 +227,8 @@ enum class Family {
   LpcmMix,      // render_fast_kernel<.., LP, true, 2, LPC, LP2> (iamf_render_lpcm_mix.hip, iamf_render_lpcm_mix_coupled.hip): both
                 // elements of a mix as 16-bit packets; variant = LP2 (1 mono-coded second element, 2 a coupled pair).  Listed
                 // by iamf_hip_route_family_instances only
+  FastInterleaved,  // render_fast_kernel<M, OC, .., IL, RAG> (iamf_render_interleaved.hip): interleaved f32 of any call length,
+                // RenderParams::interleaved.  Listed by iamf_hip_route_family_instances only
 };
 struct Route {
   Family family;
@@ -267,6 +292,20 @@ inline bool lpcm_mix_fused(int n_launch) {
   return true;
 }
 
+// Whether a range of n_launch streams that came through iamf_hip_batch_render_interleaved takes the interleaved form at all
+// (render_prepare asks), under the rule of lpcm_coupled_fused(): a size at which it does not beat what the call ran before —
+// iamf_hip_batch_render_range on a twin batch in the same process, the general kernel — by more than that baseline's own
+// run-to-run spread is not fused.  Measured (tools/interleaved_rate.py, MI355X, mono and stereo through the identity into
+// s16, 64 x 1115 or 64 x 1024 sample-frames per stream and step, profiles/r12_interleaved_rate.json): the baseline takes
+// 1.88 / 1.85 / 1.54 (mono) and 1.85 / 1.69 / 1.50 (stereo) times the new entry's time in calls of 1115 sample-frames at
+// 512 / 2048 / 4096 streams, 1.66 / 1.70 / 1.46 and 1.66 / 1.65 / 1.36 in calls of 1024, 3.66 / 3.88 / 3.44 and 3.59 / 3.61 /
+// 3.13 in one call of 64 x 1115; its spread against itself at most 0.0078 — every measured (shape, size) wins, so every
+// size is fused; this is where one that stops winning would be cut.
+inline bool interleaved_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
 // rules.  The environment switches are read at every call (the tests set and unset them within one process).
@@ -277,6 +316,10 @@ inline Route pick_route(const RenderParams &p, int m) {
   const bool mixing = p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp;
   const bool staged = p.demix_on || p.dmx_on || mixing;   // a stage in front of or beside the projection
   const bool fast_shape = fast_shape_ok(p, force_generic);
+
+  // interleaved f32 of any call length (RenderParams::interleaved, zero unless iamf_hip_batch_render_interleaved set it): the
+  // form's own kernel where its rules hold, else whatever the rules below give the call
+  if (interleaved_shape_ok(p, m, force_generic)) return take(Family::FastInterleaved);
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
@@ -429,6 +472,12 @@ void for_each_render_instance_lpcm_mix(F &&f) {
   for_each_int(LpcmCoupledM{}, rows);
 }
 
+// The interleaved form (iamf_hip_route_family_instances), walking InterleavedM x InterleavedOC as its launcher does.
+template <class F>
+void for_each_render_instance_interleaved(F &&f) {
+  for_each_int(InterleavedM{}, [&](int m) { for_each_int(InterleavedOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, oc, 0); }); });
+}
+
 // the row of the kernel launch() runs for a route (a FirSplit call launches render_fast_kernel<2, 2> behind it as well:
 // launch() counts that row too)
 struct RouteKey {
@@ -453,6 +502,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::Lpcm24: return {IAMF_HIP_ROUTE_LPCM24, r.variant, m, p.out_ch, 0};   // a row of table 2
     case Family::LpcmCoupled: return {IAMF_HIP_ROUTE_LPCM_COUPLED, r.variant, m, p.out_ch, 0};   // a family listing's row
     case Family::LpcmMix: return {IAMF_HIP_ROUTE_LPCM_MIX, 0, m, p.out_ch, r.variant};   // a family listing's row, k = LP2
+    case Family::FastInterleaved: return {IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, p.out_ch, 0};   // a family listing's row
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

@@ -74,6 +74,10 @@ class LpcmMixCall(C.Structure):   # iamf_hip_lpcm_mix_call
     _fields_ = [("in_", LpcmInput * 2), ("args", RenderArgs)]
 
 
+class InterleavedCall(C.Structure):   # iamf_hip_interleaved_call
+    _fields_ = [("args", RenderArgs), ("reserved", C.c_int32 * 4)]
+
+
 class FanoutReport(C.Structure):   # iamf_hip_fanout_report
     _fields_ = [("n_fused", C.c_int32), ("input_fused", C.c_int32), ("n_unpacks", C.c_int32), ("reserved", C.c_int32)]
 
@@ -86,7 +90,7 @@ class RouteRow(C.Structure):   # iamf_hip_route_row
 # IAMF_HIP_ROUTE_*: the kernel families of iamf_hip_route_row::family
 ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, WIDE4_DEMIX=7, WIDE4_DOWN=8, WIDE4_MIX=9,
              WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, LPCM24=16, LPCM_COUPLED=17,
-             RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23, LPCM_MIX=25)
+             RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23, LPCM_MIX=25, FAST_INTERLEAVED=27)
 ROUTE_NAME = {v: k for k, v in ROUTE.items()}
 
 
@@ -183,6 +187,7 @@ def lib():
         L.iamf_hip_batch_render_lpcm.argtypes = [C.c_void_p, C.POINTER(LpcmInput), C.POINTER(RenderArgs)]
         L.iamf_hip_batch_render_lpcm_range.argtypes = [C.c_void_p, C.POINTER(LpcmInput), C.POINTER(RenderArgs), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_lpcm_mix.argtypes = [C.c_void_p, C.POINTER(LpcmMixCall), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_interleaved.argtypes = [C.c_void_p, C.POINTER(InterleavedCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_resampler_destroy.argtypes = [C.c_void_p]
@@ -563,6 +568,18 @@ class Batch:
         r = lib().iamf_hip_batch_render_lpcm_mix(self.h, C.byref(call), s0, n)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_lpcm_mix")
+        return r
+
+    def render_interleaved(self, args, stream0=None, n_streams=None):
+        """iamf_hip_batch_render_interleaved on a frame_size == 1 batch: `args` a RenderArgs whose d_in is interleaved f32,
+        n_frames sample-frames of any number; the whole batch unless a range is named"""
+        call = InterleavedCall()
+        call.args = args
+        s0 = 0 if stream0 is None else stream0
+        n = self.cfg.n_streams - s0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_interleaved(self.h, C.byref(call), s0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_interleaved")
         return r
 
     def render_range(self, args, stream0, n_streams):

@@ -697,6 +697,31 @@ typedef struct {
 } iamf_hip_lpcm_mix_call;
 int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_call *call, int32_t stream0, int32_t n_streams);
 
+/* Ordinary interleaved f32 PCM of ANY call length: the limiter stage behind a rate converter (iamf_hip_resampler_process
+ * hands out 1114 or 1115 sample-frames for 1024 at 44.1 -> 48 kHz), or any caller that holds interleaved float PCM.  On a
+ * batch created with frame_size == 1 the call leaves the batch, d_pcm and its return value exactly as
+ *   iamf_hip_batch_render_range(b, &call->args, stream0, n_streams)
+ * does, bit for bit, persisted stream state included — so calls of either entry, flushes, restarts, exports and imports may
+ * follow one another on one batch.
+ *   args      as for iamf_hip_batch_render_range with frame_size == 1: d_in is [stream][sample-frame][channel] f32,
+ *             in_frame_stride the floats from one sample-frame to the next, n_frames the sample-frames of the call (any
+ *             number >= 1; 0 does nothing).
+ *   reserved  0.
+ * One pass of the FOUR-samples-per-lane kernel (IAMF_HIP_ROUTE_FAST_INTERLEAVED) when: limiter on; one or two input channels
+ * into one or two output channels; no second element, ramps, down-mixer, demixer, projection, HRTF stage, LFE generator,
+ * reduced out_gain_channels or fixed PCM channel stride; dense sample-frames (in_frame_stride == channels); d_in 16-byte
+ * aligned and in_stream_stride a multiple of 4 floats; d_pcm and pcm_stream_stride_bytes multiples of 16; the streams'
+ * position a multiple of 16 or at least 240; the call shorter than 2^29 / channels sample-frames.  Every other call takes
+ * exactly the path of iamf_hip_batch_render_range (the one-sample-per-lane kernel); IAMF_HIP_INTERLEAVED_UNFUSED=1 forces that.
+ * Returns the sample-frames emitted per stream.  IAMF_HIP_ERR_BAD_ARG, before anything is queued, allocated or changed: a NULL
+ * batch or call, non-zero reserved, a batch whose frame_size is not 1; and, with its own code, whatever
+ * iamf_hip_batch_render_range refuses. */
+typedef struct {
+  iamf_hip_render_args args;
+  int32_t reserved[4];
+} iamf_hip_interleaved_call;
+int iamf_hip_batch_render_interleaved(iamf_hip_batch *b, const iamf_hip_interleaved_call *call, int32_t stream0, int32_t n_streams);
+
 /* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
  * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
  *
@@ -770,6 +795,8 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *     LPCM_MIX             both elements of a mix as 16-bit packets (iamf_hip_batch_render_lpcm_mix): m, c of element 0 as LPCM /
  *                          LPCM_COUPLED, k = form of element 1 (1 mono-coded runs, 2 a coupled pair); variant 0
  *                          (iamf_hip_route_family_instances only)
+ *     FAST_INTERLEAVED     interleaved f32 of any call length (iamf_hip_batch_render_interleaved): m, c; variant 0
+ *                          (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -803,7 +830,8 @@ enum {
   IAMF_HIP_ROUTE_RS_TILE = 21,
   IAMF_HIP_ROUTE_RS_BLOCK = 22,
   IAMF_HIP_ROUTE_RS_DIRECT = 23,
-  IAMF_HIP_ROUTE_LPCM_MIX = 25       /* no table: iamf_hip_route_family_instances / _family_tally (18, 19, 24: unused) */
+  IAMF_HIP_ROUTE_LPCM_MIX = 25,      /* no table: iamf_hip_route_family_instances / _family_tally (18, 19, 24: unused) */
+  IAMF_HIP_ROUTE_FAST_INTERLEAVED = 27   /* no table either (26: unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -835,7 +863,7 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * LPCM), which no table lists and whose launches show in no table's tally.  _instances: every row of the family;
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
- * the same way: rows and counters of its own, in no table. */
+ * the same way: rows and counters of its own, in no table; so is FAST_INTERLEAVED. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
