@@ -33,8 +33,11 @@ def call_sizes(n, call):
     return [call] * (n // call) + ([n % call] if n % call else [])
 
 
+PLATEAU_DB = (0, -6)     # the plateau pair's other thresholds: 0 dB is 1.0f exactly
+
+
 def limiter_cases():
-    """(key, programme name, extra arguments, rate, n, samples per call)"""
+    """(key, programme name, extra arguments, rate, n, samples per call[, threshold in dB])"""
     out = []
     for f in P.LIMITER:
         if f is P.release_to_idle:
@@ -48,6 +51,17 @@ def limiter_cases():
     for k in range(P.SWEEP):
         for call in (1024, 960):
             out.append(("limiter/retrigger_sweep/k%d/c%d" % (k, call), "retrigger_sweep", {"k": k}, 48000, 12288, call))
+    # the other rates of tests/test_gpu_rates.py: the full release and the eight re-trigger positions at frames(rate) frames
+    for rate in P.SWEEP_RATES:
+        n = 1024 * P.frames(rate)
+        out.append(("limiter/release_to_idle/%d/f%d/c1024" % (rate, P.frames(rate)), "release_to_idle", {}, rate, n, 1024))
+        for k in range(P.SWEEP):
+            out.append(("limiter/retrigger_sweep/%d/k%d/c1024" % (rate, k), "retrigger_sweep", {"k": k}, rate, n, 1024))
+    for rate in (48000,) + P.SWEEP_RATES:      # chunks that start inside the attack
+        out.append(("limiter/attack_across_chunks/%d/c1024" % rate, "attack_across_chunks", {}, rate, 1024 * max(P.frames(rate), 4), 1024))
+    for db in PLATEAU_DB:
+        for name in ("dc_at_threshold", "dc_one_ulp_above"):
+            out.append(("limiter/%s/%ddB/c1024" % (name, db), name, {"db": float(db)}, 48000, 6144, 1024, float(db)))
     return out
 
 
@@ -58,11 +72,11 @@ def digest(a):
 def main():
     pins = {"_note": NOTE}
     with np.errstate(all="ignore"):
-        for key, name, args, rate, n, call in limiter_cases():
+        for key, name, args, rate, n, call, *thr_db in limiter_cases():
             x = getattr(P, name)(2, n, rate, **args)
-            y, _ = GG.ref_limiter(x, call_sizes(n, call), rate=rate)
+            y, _ = GG.ref_limiter(x, call_sizes(n, call), rate=rate, **({"thr_db": thr_db[0]} if thr_db else {}))
             pins[key] = dict(programme=name, args=args, ch=2, rate=rate, n=n, call=call, out_len=int(y.shape[1]),
-                             sha256=digest(y))
+                             sha256=digest(y), **({"thr_db": thr_db[0]} if thr_db else {}))
         c = P.demix_case(1024)
         for f in P.DEMIXER:
             y = D.drive_demixer(GG.ref, "demixer_", c, P.demix_input(f, c))

@@ -12,8 +12,8 @@ ORDER = {"foa": 1, "soa": 2, "toa": 3}
 CHANNELS = {"foa": 4, "soa": 9, "toa": 16}
 
 
-def member(layout, fmt=A.FMT_S16, eg=1.0, og=1.0, lg=None, thr_db=-1.0, limiter=True):
-    return dict(layout=layout, fmt=fmt, eg=eg, og=og, lg=lg, thr_db=thr_db, limiter=limiter)
+def member(layout, fmt=A.FMT_S16, eg=1.0, og=1.0, lg=None, thr_db=-1.0, limiter=True, rate=48000):
+    return dict(layout=layout, fmt=fmt, eg=eg, og=og, lg=lg, thr_db=thr_db, limiter=limiter, rate=rate)
 
 
 # Clipped 16-bit input cannot drive a mono rendition of an ambisonics element above 0.7071 of full scale: the mono members'
@@ -35,7 +35,7 @@ def gain_product(sp):
 
 def make_batch(mx, sp, S, fs):
     oc = A.layout_channels(A.SS[sp["layout"]])
-    b = A.Batch(S, mx, oc, frame_size=fs, out_format=sp["fmt"], limiter=sp["limiter"], threshold_db=sp["thr_db"],
+    b = A.Batch(S, mx, oc, frame_size=fs, out_format=sp["fmt"], limiter=sp["limiter"], threshold_db=sp["thr_db"], sample_rate=sp.get("rate", 48000),
                 loudness=sp["lg"] is not None, projection=A.PROJ_EXACT if oc > 2 else A.PROJ_AUTO)
     b.set_gains(element=[sp["eg"]] * S, output=[sp["og"]] * S, loudness=None if sp["lg"] is None else [sp["lg"]] * S)
     b.oc, b.bps = oc, BPS[sp["fmt"]]

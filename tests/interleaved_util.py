@@ -47,7 +47,7 @@ def hot(m, total, streams=S, seed=3100):
     return np.stack([synth.hot(seed + 11 * s, m, total, sigma=0.2, burst_phase=90 + 173 * s, burst_period=700) for s in range(streams)])
 
 
-def want(omx, oc, x, sizes, bd=16, eg=1.0, og=1.0, flush=True):
+def want(omx, oc, x, sizes, bd=16, eg=1.0, og=1.0, flush=True, sample_rate=48000, threshold_db=-1.0):
     """the oracle of one stream: x [m][total] rendered, the constant gains, the mixer's 0 + y, the limiter over calls of
     `sizes` (and its flush), packed -> (PCM [n][oc] (s24: [n][oc][3]), the limiter's input [oc][total])"""
     import oracle_lib as O
@@ -57,7 +57,8 @@ def want(omx, oc, x, sizes, bd=16, eg=1.0, og=1.0, flush=True):
     z = np.ascontiguousarray(np.zeros_like(y) + y, dtype=np.float32)
     O.lib().orc_frame_gain_const(O.fp(z), oc, n, float(og))
     pre = z.copy()
-    z, _ = O.limiter_run(z, sizes, flush=flush)
+    with np.errstate(all="ignore"):
+        z, _ = O.limiter_run(z, sizes, flush=flush, rate=sample_rate, thr_db=threshold_db)
     return (np.ascontiguousarray(z.T) if bd == -32 else O.pack(z, bd)), pre
 
 
@@ -107,10 +108,10 @@ def seam_retrigger():
 
 
 def drive(amx, m, oc, x, steps, bd=16, streams=None, eg=EG, og=OG, pad=0, off_floats=0, rng=None, out_stream=None,
-          before_call=None, second=None, out_ramp=False, frame_size=1, export=True):
+          before_call=None, second=None, out_ramp=False, frame_size=1, export=True, sample_rate=48000, threshold_db=-1.0):
     """x [S][m][total].  pad: floats between sample-frames (in_frame_stride = m + pad); off_floats: d_in that many floats
     behind a 256-byte aligned base; rng: (s0, cnt) — every step over that range only; second: (matrix, x2 [S][m2][total]) —
-    a second element on the batch; out_ramp: an all-0.5 output ramp on every call."""
+    a second element on the batch; out_ramp: an all-0.5 output ramp on every call; sample_rate, threshold_db: the batch's."""
     import torch
     import iac_amd as A
     import gpu_util as G
@@ -119,7 +120,8 @@ def drive(amx, m, oc, x, steps, bd=16, streams=None, eg=EG, og=OG, pad=0, off_fl
     bps = {16: 2, 24: 3, 32: 4, -32: 4}[bd]
     st = out_stream if out_stream is not None else torch.cuda.current_stream().cuda_stream
     s0, cnt = rng or (0, Sx)
-    b = A.Batch(Sx, amx, oc, frame_size=frame_size, out_format=fmt, projection=A.PROJ_EXACT)
+    b = A.Batch(Sx, amx, oc, frame_size=frame_size, out_format=fmt, projection=A.PROJ_EXACT, sample_rate=sample_rate,
+                threshold_db=threshold_db)
     recs, pos = [], 0
     try:
         b.set_gains(element=[eg[s % len(eg)] for s in range(Sx)], output=[og[s % len(og)] for s in range(Sx)])
@@ -238,7 +240,8 @@ def check(m, oc, x, lengths, bd=16, mats=None, fused=None, what="", eg=EG, og=OG
     import test_gpu_programmes as TP
     s0, cnt = kw.get("rng") or (0, x.shape[0])
     for s in range(s0, s0 + cnt):
-        w, pre = want(omx, oc, x[s][:, :sum(lengths)], list(lengths), bd, eg[s % len(eg)], og[s % len(og)])
+        w, pre = want(omx, oc, x[s][:, :sum(lengths)], list(lengths), bd, eg[s % len(eg)], og[s % len(og)],
+                      sample_rate=kw.get("sample_rate", 48000), threshold_db=kw.get("threshold_db", -1.0))
         g = stream_pcm(got, s, oc, bd)
         assert TP.mismatch(g, w) is None, (what, "stream %d against the oracle" % s, TP.mismatch(g, w))
     return got, ref

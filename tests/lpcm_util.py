@@ -52,8 +52,8 @@ def rows(ints, bps, le, widths, perm, head, pad, frame_size):
 
 
 def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_samples=0, fmt=A.FMT_S16, layout=G.DENSE,
-                packets=None, trims=None, emitted=None, refused=None):
-    """layout: of the PCM rows (gpu_util.pcm_rows).  packets: a packet layout of gpu_util (place_packets: the rows placed
+                packets=None, trims=None, emitted=None, refused=None, sample_rate=48000, threshold_db=-1.0):
+    """sample_rate, threshold_db: the batch's (the limiter's step counts and threshold).  layout: of the PCM rows (gpu_util.pcm_rows).  packets: a packet layout of gpu_util (place_packets: the rows placed
     under it, every byte outside the runs the 0x7F / 0x80 fill); None: the rows as they are, dense, at the start of a fresh
     allocation.  trims: {call number: (first_sample, n_samples)} in place of first / n_samples for every call.  emitted:
     a list that receives what every call and the flush said it emitted.  refused: (packet layout, error code, frames) —
@@ -65,7 +65,8 @@ def render_lpcm(matrix, out_ch, raw, L, row, frame_size, calls, first=0, n_sampl
     st = torch.cuda.current_stream().cuda_stream
     outs = [[] for _ in range(S)]
     d_raw = keep = pcm = None
-    b = A.Batch(S, matrix, out_ch, frame_size=frame_size, out_format=fmt, limiter=True)
+    b = A.Batch(S, matrix, out_ch, frame_size=frame_size, out_format=fmt, limiter=True, sample_rate=sample_rate,
+                threshold_db=threshold_db)
 
     def packets_at(pk, f0, nf, keep):
         """-> (iamf_hip_lpcm_input of the call, what holds its memory)"""

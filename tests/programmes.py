@@ -17,6 +17,20 @@ RELEASE_FRAMES = {48000: 12, 44100: 11, 16000: 5, 96000: 21}
 # 240 samples behind), recorded from the oracle's trace and asserted in tests/test_programmes_cpu.py
 RELEASE_LAST_STEP = {48000: 10204, 44100: 9387, 16000: 3792, 96000: 19849}
 BURST_AT, BURST_LEN = 100, 240
+# the rates the limiter kernels are run at beside 48 kHz (tests/test_gpu_rates.py), with (n_atk, n_end) as limiter_steps
+# gives them; tests/test_programmes_cpu.py asserts the table.  5408 Hz: n_end is the staged window of the fast, wide4 and
+# fan-out kernels exactly (1088 words); 8000: a release shorter than two chunks; 22050 / 44100: n_atk % 4 = 3 / 1; 96000
+# and up: an attack longer than one, three and four 64-sample blocks (384 kHz: than the 240-sample look-ahead).
+RATE_STEPS = {5408: (6, 1088), 8000: (8, 1608), 22050: (23, 4433), 44100: (45, 8864), 96000: (97, 19298),
+              192000: (193, 38574), 384000: (385, 77114)}
+SWEEP_RATES = tuple(RATE_STEPS)
+# both sides of the two window bounds: the last rate a kernel must refuse and the first it takes (kWWin = 320 of
+# render_wide.hpp, kFWin = 1088 of the other vector kernels)
+WINDOW_RATES = {1587: (2, 319), 1588: (2, 320), 5407: (6, 1087), 5408: (6, 1088)}
+# release_to_idle at frames(rate) frames of 1024: the last release step, from the oracle's trace like RELEASE_LAST_STEP
+# (the noise of channel 1 depends on the length, so 96 kHz has one entry per length)
+RELEASE_LAST_STEP_AT = {(5408, 4): 1667, (8000, 4): 2187, (22050, 7): 4984, (44100, 11): 9387, (96000, 22): 19732,
+                        (192000, 41): 39100, (384000, 78): 77693}
 
 
 def _noise(seed, channels, n, sigma):
@@ -42,6 +56,53 @@ def limiter_steps(rate):
     return n_atk, k
 
 
+def frames(rate):
+    """frames of 1024 that hold the re-trigger sweep at `rate` (its last impulse enters at LAST_TRIGGER + n_end + 2) and one
+    more whole chunk, plus one: release_to_idle then ends at least one idle chunk before the end as well"""
+    n_end = limiter_steps(rate)[1]
+    return -(-(LAST_TRIGGER + n_end + 2 + 1024) // 1024) + 1
+
+
+def release_frames(rate):
+    """frames of release_to_idle: RELEASE_FRAMES where it has the rate, else frames(rate)"""
+    return RELEASE_FRAMES.get(rate, frames(rate))
+
+
+def release_last_step(rate, n_frames=None):
+    """the last release step of release_to_idle(2, 1024 * n_frames, rate) as recorded from the oracle's trace"""
+    n_frames = release_frames(rate) if n_frames is None else n_frames
+    if RELEASE_FRAMES.get(rate) == n_frames:
+        return RELEASE_LAST_STEP[rate]
+    return RELEASE_LAST_STEP_AT[(rate, n_frames)]
+
+
+_FIRST_CALLS = [1, 3, 2, 5, 1]
+_CALLS_BY_FRAMES = {11: [1, 3, 2, 4, 1], 5: [1, 3, 1]}     # what the tests at 44.1 and 16 kHz have always used
+
+
+def cut_calls(n_frames):
+    """n_frames cut into calls: 1, 3, 2, 5, 1 as far as they fit, then the rest in one call, or in two of unequal length
+    from ten frames on, so that chunk, call and release boundaries fall in different places"""
+    if n_frames in _CALLS_BY_FRAMES:
+        return list(_CALLS_BY_FRAMES[n_frames])
+    out = []
+    for c in _FIRST_CALLS:
+        if sum(out) + c > n_frames:
+            break
+        out.append(c)
+    rest = n_frames - sum(out)
+    if rest >= 10:
+        out += [rest // 3, rest - rest // 3]
+    elif rest:
+        out.append(rest)
+    return out
+
+
+def thr(db=-1.0):
+    """the limiter's threshold as the library derives it: (float)pow(10, (float)db / 20), the quotient in f32"""
+    return F32(10.0 ** float(F32(db) / F32(20.0)))
+
+
 # ---- limiter programmes ----
 
 def silence(channels, n, rate=48000):
@@ -63,14 +124,14 @@ def loud_then_silence(channels, n, rate=48000):
     return x
 
 
-def dc_at_threshold(channels, n, rate=48000):
+def dc_at_threshold(channels, n, rate=48000, db=-1.0):
     """DC exactly at the threshold: peak * 1.0 > thr is false, no trigger ever"""
-    return _const(channels, n, THR)
+    return _const(channels, n, thr(db))
 
 
-def dc_one_ulp_above(channels, n, rate=48000):
+def dc_one_ulp_above(channels, n, rate=48000, db=-1.0):
     """DC one ulp above the threshold: a trigger on every step the window holds it at gain 1"""
-    return _const(channels, n, np.nextafter(THR, F32(2)))
+    return _const(channels, n, np.nextafter(thr(db), F32(2)))
 
 
 def _square(channels, n, amp):
@@ -138,10 +199,62 @@ def retrigger_sweep(channels, n, rate=48000, k=0, last_trigger=None):
     return x
 
 
+def attack_tails(n):
+    """[(chunk c, j)] of attack_across_chunks: chunks 1 .. 4 as far as n holds one more chunk behind them, j = c"""
+    return [(c, c) for c in range(1, 5) if 1024 * (c + 1) <= n]
+
+
+def attack_across_chunks(channels, n, rate=48000):
+    """impulses of 1.5 * 2^(c-1) at 1024 c - 240 - c over noise of sigma 0.05, c = 1 .. 4: each triggers on every step it is in
+    the window, the last one c steps before the 1024-chunk c; that chunk starts c steps into the attack, so its first
+    hypothesis (no trigger in the chunk) changes from the attack to the release formula n_atk - c samples in: in another lane
+    of a quad for every c, whatever n_atk % 4 is.  At the low rates the gain has all but settled by then (gs within an ulp or
+    so of ge), and the two formulas differ by less than a 16-bit step: f32 output shows them apart."""
+    x = _noise(4600, channels, n, 0.05)
+    for c, j in attack_tails(n):
+        x[:, 1024 * c - 240 - j] = 1.5 * 2.0 ** (c - 1)
+    return x
+
+
 # the step (= index of the input sample that enters at it) of the last trigger the lone 1.5 impulse at 100 causes: the
 # gain approaches thr / 1.5 from above, so every step that has the impulse in its window triggers.  From the oracle's
 # trace; tests/test_programmes_cpu.py asserts it.
 LAST_TRIGGER = BURST_AT + 240
+
+
+# ---- the packet grid: what an LPCM-fed kernel can be given ----
+# Packets cannot carry samples beyond full scale, so a packet-fed family gets a programme divided by 4 and rounded to the
+# packet's integers, and renders it through a selection matrix of weight 4.0: a power of two, so every product is exact and
+# the rendered signal is from_packet_grid(to_packet_grid(x)).  tests/test_programmes_cpu.py proves from the oracle's trace
+# that the sweep still hits its four boundaries on that grid.
+PACKET_WEIGHT = 4.0
+PACKET = ["release_to_idle", "onset_after_silence", "loud_then_silence", "silence"]     # and the eight sweep streams
+
+
+def to_packet_grid(x, bits=16):
+    """[..] float32 -> int64 packet samples of x / PACKET_WEIGHT"""
+    full = 2 ** (bits - 1)
+    q = np.rint(np.asarray(x, dtype=np.float64) * (full / PACKET_WEIGHT))
+    return np.clip(q, -full, full - 1).astype(np.int64)
+
+
+def from_packet_grid(ints, bits=16):
+    """the signal a weight of PACKET_WEIGHT renders from those packet samples, exact in f32"""
+    return ((np.asarray(ints).astype(np.float64) / 2 ** (bits - 1)).astype(F32) * F32(PACKET_WEIGHT)).astype(F32)
+
+
+def on_packet_grid(x, bits=16):
+    return from_packet_grid(to_packet_grid(x, bits), bits)
+
+
+def boundary_set(m, n, rate=48000, packet_bits=0):
+    """[(name, x [m][n])]: the eight sweep streams, release_to_idle, onset_after_silence, loud_then_silence and silence
+    (tests/test_gpu_rates.py, every family but the five limiter copies); packet_bits: on that packet grid"""
+    out = [("retrigger_sweep_k%d" % k, retrigger_sweep(m, n, rate, k=k)) for k in range(SWEEP)]
+    out += [(nm, globals()[nm](m, n, rate)) for nm in PACKET]
+    if packet_bits:
+        out = [(nm, on_packet_grid(x, packet_bits)) for nm, x in out]
+    return out
 
 
 def pack_edge_values():
@@ -188,12 +301,13 @@ def loud(channels, n, rate=48000):
 
 def nonfinite(channels, n, rate=48000):
     """noise of sigma 0.3 with one NaN, one +inf and one -inf in different channels and chunks, and one stretch of
-    alternating +-3e38 whose matrix sums overflow"""
+    alternating +-3e38 whose matrix sums overflow; n >= 4096"""
     x = _noise(4400, channels, n, 0.3)
     x[0, 700] = np.nan
     x[1 % channels, 1024 + 333] = np.inf
     x[2 % channels, 3 * 1024 + 1] = -np.inf
-    t = np.arange(4 * 1024 + 500, 4 * 1024 + 564)
+    t0 = min(4 * 1024 + 500, n - 564)         # (four frames, the shortest programmes: the stretch ends the fourth chunk)
+    t = np.arange(t0, t0 + 64)
     x[:, t] = (F32(3e38) * np.where(t % 2 == 0, 1.0, -1.0)).astype(F32)
     return x
 

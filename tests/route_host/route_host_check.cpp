@@ -339,6 +339,69 @@ void long_positions(const RenderParams &st, const RenderParams &w, const RenderP
   }
 }
 
+// ---- the staged limiter-table windows: n_end against kFWin (render_fast.hpp, render_wide4.hpp, render_fanout.hpp) and
+// kWWin (render_wide.hpp) ----
+// iamf_hip_batch_create derives (n_atk, n_end) from the sample rate: (6, 1087) at 5407 Hz, (6, 1088) at 5408 Hz, (2, 319) at
+// 1587 Hz and (2, 320) at 1588 Hz (tests/test_programmes_cpu.py asserts these from the same accumulation).  A vector kernel
+// stages a window of its table as long as the constant and must not get a table that ends inside it; one step on it must.
+// A member of a fan-out is fused where its own call routes to Fast/0 (iamf_hip_render_fanout), so the stereo rows are its
+// rows too.  tests/test_gpu_rates.py runs both sides of each bound on the GPU.
+void window_rules(const RenderParams &st, const RenderParams &w, const RenderParams &lp, const RenderParams &f16) {
+  static_assert(kFWin == 1088 && kWWin == 320, "the rates of tests/programmes.py (WINDOW_RATES) sit on these two");
+  const int UNIMPL = IAMF_HIP_ERR_UNIMPLEMENTED;
+  const auto below = [](RenderParams &p) { p.n_atk = 6; p.n_end = kFWin - 1; };
+  const auto at = [](RenderParams &p) { p.n_atk = 6; p.n_end = kFWin; };
+  const auto wbelow = [](RenderParams &p) { p.n_atk = 2; p.n_end = kWWin - 1; };
+  const auto wat = [](RenderParams &p) { p.n_atk = 2; p.n_end = kWWin; };
+  struct Row {
+    const char *name;
+    RenderParams p;
+    int m;
+    Family taken;       // n_end == kFWin
+    int variant;
+    Family refused;     // n_end == kFWin - 1: what the call falls to
+    int err;
+  };
+  const Row rows[] = {
+      {"stereo (and a fan-out's member)", st, 16, Family::Fast, 0, Family::Generic, IAMF_HIP_OK},
+      {"mono", aligned(16, 1), 16, Family::Fast, 0, Family::Generic, IAMF_HIP_OK},
+      {"stereo + second element", with(st, second_element), 16, Family::Fast, 1, Family::Generic, IAMF_HIP_OK},
+      {"down-mixer 6 -> 2", with(aligned(6, 2), down_mixer), 6, Family::FastDown, 0, Family::Generic, IAMF_HIP_OK},
+      {"LPCM", lp, 16, Family::Lpcm, 1, Family::Refused, IAMF_HIP_ERR_INVALID_STATE},
+      {"FIR", f16, 16, Family::FirSplit, 0, Family::Refused, UNIMPL},
+      // the wide4 family: at 1087 the plain call lands on the 256-sample kernel, whose window is 320; the staged variants,
+      // which that kernel does not have, on the general one
+      {"12 channels", w, 16, Family::Wide4, 0, Family::Wide, IAMF_HIP_OK},
+      {"6 -> 6", aligned(6, 6), 6, Family::Wide4, 0, Family::Wide, IAMF_HIP_OK},
+      {"12 channels, MFMA", with(w, [](RenderParams &p) { p.use_mfma = 1; }), 16, Family::Wide4, 1, Family::Wide, IAMF_HIP_OK},
+      {"12 channels + second element", with(w, second_element), 16, Family::Wide4Mix, 0, Family::Generic, IAMF_HIP_OK},
+      {"down-mixer 12 -> 6", with(aligned(12, 6), down_mixer), 12, Family::Wide4Down, 0, Family::Generic, IAMF_HIP_OK},
+      {"demixer 12 -> 12", with(aligned(12, 12), demixer), 12, Family::Wide4Demix, 0, Family::Generic, IAMF_HIP_OK},
+      {"LFE, 12 channels", with(w, lfe), 16, Family::Wide4Lfe, 0, Family::Generic, IAMF_HIP_OK},
+  };
+  for (const Row &r : rows) {
+    char what[96];
+    snprintf(what, sizeof(what), "%s: n_end = kFWin", r.name);
+    expect(what, with(r.p, at), r.m, nullptr, r.taken, r.variant);
+    snprintf(what, sizeof(what), "%s: n_end = kFWin - 1", r.name);
+    // (the MFMA row keeps its variant on the 256-sample kernel, every other refused side is variant 0)
+    expect(what, with(r.p, below), r.m, nullptr, r.refused, r.refused == Family::Wide ? r.variant : 0, r.err);
+  }
+  // where wide4 refuses for another reason as well, 1087 or 1088 makes no difference
+  expect("12 channels, IAMF_HIP_NO_WIDE4: n_end = kFWin - 1", with(w, below), 16, "IAMF_HIP_NO_WIDE4", Family::Wide, 0);
+  // render_wide.hpp's own window
+  const RenderParams e11 = aligned(12, 11), w24 = aligned(16, 12, IAMF_HIP_FMT_S24);
+  expect("12 -> 11: n_end = kWWin", with(e11, wat), 12, nullptr, Family::Wide, 0);
+  expect("12 -> 11: n_end = kWWin - 1", with(e11, wbelow), 12, nullptr, Family::Generic, 0);
+  expect("12 -> 11, MFMA: n_end = kWWin", with(e11, [&](RenderParams &p) { wat(p); p.use_mfma = 1; }), 12, nullptr, Family::Wide, 1);
+  expect("12 -> 11, MFMA: n_end = kWWin - 1", with(e11, [&](RenderParams &p) { wbelow(p); p.use_mfma = 1; }), 12, nullptr, Family::Generic, 0);
+  expect("12 channels, s24: n_end = kWWin", with(w24, wat), 16, nullptr, Family::Wide, 0);
+  expect("12 channels, s24: n_end = kWWin - 1", with(w24, wbelow), 16, nullptr, Family::Generic, 0);
+  expect("12 channels, s16: n_end = kWWin (wide4 refuses, the 256-sample kernel takes it)", with(w, wat), 16, nullptr, Family::Wide, 0);
+  expect("12 channels, s16: n_end = kWWin - 1", with(w, wbelow), 16, nullptr, Family::Generic, 0);
+  expect("stereo: n_end = kWWin", with(st, wat), 16, nullptr, Family::Generic, 0);
+}
+
 }  // namespace
 
 int main() {
@@ -438,6 +501,7 @@ int main() {
   address_rules(st, w, nl, f16, lp);
   packet_layout_rows(st);
   long_positions(st, w, nl, lp);
+  window_rules(st, w, lp, f16);
 
   printf("%d cases, %d wrong\n", g_cases, g_failed);
   if (!g_failed) printf("OK\n");

@@ -217,6 +217,10 @@ int main() {
   expect("  m = 6: no instance", call(6, 2, 3), 6, nullptr, Family::Refused, 0, STATE);
   expect("  6 output channels: no instance", call(16, 6, 3), 16, nullptr, Family::Refused, 0, STATE);
   expect("  pos0 = 8: not a call of the fast kernel", with(p24, [](RenderParams &p) { p.pos0 = 8; }), 16, nullptr, Family::Refused, 0, STATE);
+  // the staged limiter-table window (kFWin, render_fast.hpp): (n_atk, n_end) = (6, 1087) at 5407 Hz and (6, 1088) at 5408 Hz
+  expect("  n_end = kFWin - 1: a table that ends inside the staged window", with(p24, [](RenderParams &p) { p.n_atk = 6; p.n_end = kFWin - 1; }), 16,
+         nullptr, Family::Refused, 0, STATE);
+  expect("  n_end = kFWin", with(p24, [](RenderParams &p) { p.n_atk = 6; p.n_end = kFWin; }), 16, nullptr, Family::Lpcm24, 1);
   expect("  total % 64 != 0", with(p24, [](RenderParams &p) { p.total = 4096 + 32; }), 16, nullptr, Family::Refused, 0, STATE);
   expect("  limiter off", with(p24, [](RenderParams &p) { p.limiter_on = 0; }), 16, nullptr, Family::Refused, 0, STATE);
   expect("  down-mixer", with(call(4, 2, 3), [](RenderParams &p) { p.dmx_on = 1; }), 4, nullptr, Family::Refused, 0, STATE);

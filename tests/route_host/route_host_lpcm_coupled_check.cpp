@@ -257,6 +257,10 @@ int main() {
   expect("  6 output channels: no instance", call(12, 6, 1), 12, nullptr, Family::Refused, 0, STATE);
   expect("  limiter off", with(pc, [](RenderParams &p) { p.limiter_on = 0; }), 12, nullptr, Family::Refused, 0, STATE);
   expect("  pos0 = 8: not a call of the fast kernel", with(pc, [](RenderParams &p) { p.pos0 = 8; }), 12, nullptr, Family::Refused, 0, STATE);
+  // the staged limiter-table window (kFWin, render_fast.hpp): (n_atk, n_end) = (6, 1087) at 5407 Hz and (6, 1088) at 5408 Hz
+  expect("  n_end = kFWin - 1: a table that ends inside the staged window", with(pc, [](RenderParams &p) { p.n_atk = 6; p.n_end = kFWin - 1; }), 12,
+         nullptr, Family::Refused, 0, STATE);
+  expect("  n_end = kFWin", with(pc, [](RenderParams &p) { p.n_atk = 6; p.n_end = kFWin; }), 12, nullptr, Family::LpcmCoupled, 1);
   expect("  pos0 = 250: off the 16-sample grid, past the look-ahead", with(pc, [](RenderParams &p) { p.pos0 = 250; }), 12, nullptr,
          Family::LpcmCoupled, 1);
   expect("  total % 64 != 0", with(pc, [](RenderParams &p) { p.total = 4096 + 32; }), 12, nullptr, Family::Refused, 0, STATE);

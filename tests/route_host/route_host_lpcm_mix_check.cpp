@@ -182,6 +182,10 @@ int main() {
   expect("  6 output channels: no instance", call(12, 6, 1, 2, 2), 12, nullptr, Family::Refused, 0, STATE);
   expect("  limiter off", with(pm, [](RenderParams &p) { p.limiter_on = 0; }), 16, nullptr, Family::Refused, 0, STATE);
   expect("  pos0 = 8: not a call of the fast kernel", with(pm, [](RenderParams &p) { p.pos0 = 8; }), 16, nullptr, Family::Refused, 0, STATE);
+  // the staged limiter-table window (kFWin, render_fast.hpp): (n_atk, n_end) = (6, 1087) at 5407 Hz and (6, 1088) at 5408 Hz
+  expect("  n_end = kFWin - 1: a table that ends inside the staged window", with(pm, [](RenderParams &p) { p.n_atk = 6; p.n_end = kFWin - 1; }), 16,
+         nullptr, Family::Refused, 0, STATE);
+  expect("  n_end = kFWin", with(pm, [](RenderParams &p) { p.n_atk = 6; p.n_end = kFWin; }), 16, nullptr, Family::LpcmMix, 2);
   expect("  pos0 = 250: off the 16-sample grid, past the look-ahead", with(pm, [](RenderParams &p) { p.pos0 = 250; }), 16, nullptr, Family::LpcmMix, 2);
   expect("  total % 64 != 0", with(pm, [](RenderParams &p) { p.total = 4096 + 32; }), 16, nullptr, Family::Refused, 0, STATE);
   expect("  down-mixer", with(pc, [](RenderParams &p) { p.dmx_on = 1; }), 12, nullptr, Family::Refused, 0, STATE);

@@ -46,8 +46,9 @@ def _mods():
     return A, G, O
 
 
-def selection(m, oc, kind=None, channels=None, lfe1=-1):
-    """(product matrix, oracle matrix): output o copies input o % m"""
+def selection(m, oc, kind=None, channels=None, lfe1=-1, weight=1.0):
+    """(product matrix, oracle matrix): output o copies input o % m (weight: times that, programmes.PACKET_WEIGHT for the
+    packet-fed kernels)"""
     A, G, O = _mods()
     if kind == A.KIND_H2M:                  # rows = the feeds (the LFE slot is no feed)
         n = channels - 1
@@ -55,7 +56,7 @@ def selection(m, oc, kind=None, channels=None, lfe1=-1):
         w[np.arange(n), np.arange(n) % m] = 1.0
         return R._custom(A, O, A.KIND_H2M, m, n, w, channels, lfe1)
     w = np.zeros((m, oc), dtype=np.float32)
-    w[np.arange(oc) % m, np.arange(oc)] = 1.0
+    w[np.arange(oc) % m, np.arange(oc)] = weight
     return R._custom(A, O, A.KIND_M2M, m, oc, w, oc)
 
 
@@ -162,26 +163,33 @@ def test_fast_table_matrix():
     run_family(("FAST", 0, 2, 2, 0), 2, 2, some(2, ["silence", "release_to_idle", "loud"]), table=True)
 
 
-def run_second(inst, m, oc):
+def second_pairs(m, n=N, rate=48000):
     """a one-channel second element mixed in: silent beside a release, a release beside silence, a release beside an onset"""
+    return [("release_to_idle + silence", P.release_to_idle(m, n, rate), P.silence(1, n, rate)),
+            ("silence + release_to_idle", P.silence(m, n, rate), P.release_to_idle(1, n, rate)),
+            ("onset_after_silence + release_to_idle", P.onset_after_silence(m, n, rate), P.release_to_idle(1, n, rate))]
+
+
+def run_second(inst, m, oc, pairs=None, calls=CALLS, rate=48000):
+    """pairs [(name, x [m][n], x2 [1][n])]: the second element mixed in, one pair per stream (default: second_pairs)"""
     import torch
     A, G, O = _mods()
-    pairs = [("release_to_idle + silence", P.release_to_idle(m, N), P.silence(1, N)),
-             ("silence + release_to_idle", P.silence(m, N), P.release_to_idle(1, N)),
-             ("onset_after_silence + release_to_idle", P.onset_after_silence(m, N), P.release_to_idle(1, N))]
+    pairs = pairs or second_pairs(m)
+    N = pairs[0][1].shape[1]
+    assert N == FS * sum(calls)
     (mx, omx), (mx2, omx2) = selection(m, oc), selection(1, oc)
     x, x2 = np.stack([p[1] for p in pairs]), np.stack([p[2] for p in pairs])
     A.route_reset()
-    b = A.Batch(len(pairs), mx, oc, frame_size=FS, out_format=A.FMT_S16, projection=A.PROJ_EXACT)
+    b = A.Batch(len(pairs), mx, oc, frame_size=FS, out_format=A.FMT_S16, projection=A.PROJ_EXACT, sample_rate=rate)
     b.set_second_element(mx2, [1.0] * len(pairs))
-    got = G.run_ex(A, G, torch, b, len(pairs), m, x, FS, oc, A.FMT_S16, x2=x2, m2=1, calls=CALLS)
+    got = G.run_ex(A, G, torch, b, len(pairs), m, x, FS, oc, A.FMT_S16, x2=x2, m2=1, calls=list(calls))
     b.close()
-    R.check_tally(A.route_tally(), expected_tally(inst, m, len(CALLS)))
+    R.check_tally(A.route_tally(), expected_tally(inst, m, len(calls)))
     bad = []
     for s, (name, xs, xs2) in enumerate(pairs):
         y0, y1 = O.render(omx, xs, oc), O.render(omx2, xs2, oc)
         z = ((np.zeros_like(y0) + y0) + y1).astype(np.float32)
-        z, _ = O.limiter_run(z, [FS] * (N // FS))
+        z, _ = O.limiter_run(z, [FS] * (N // FS), rate=rate)
         d = mismatch(got[s], O.pack(z, 16))
         if d:
             bad.append("%s: %s" % (name, d))
@@ -192,16 +200,20 @@ def test_fast_second_element():
     run_second(("FAST", 1, 2, 2, 0), 2, 2)
 
 
-def run_down(inst, m, oc, names):
-    """the parametric down-mixer in front of the limiter (route_cases.run_down's schedule of modes and offsets)"""
+def run_down(inst, m, oc, names, N=N, calls=CALLS, rate=48000):
+    """the parametric down-mixer in front of the limiter (route_cases.run_down's schedule of modes and offsets); names: the
+    programmes (or (name, x [m][N]) pairs), one per stream"""
     import torch
     A, G, O = _mods()
+    progs = [(nm, getattr(P, nm)(m, N, rate)) if isinstance(nm, str) else nm for nm in names]
+    names = [p[0] for p in progs]
+    assert N == FS * sum(calls)
     L = A.lib()
     il, ol = R._DOWN_PAIR[(m, oc)]
     assert L.iamf_hip_dmx_valid(il, ol) == 1
     F, S = N // FS, len(names)
     sched = [((-1, 1, 2, 4, 5, 6, 0, 2)[f % 8], (0, 0, 37, 128, 0, FS - 3, 4, 0)[f % 8]) for f in range(F)]
-    x = np.stack([np.ascontiguousarray(getattr(P, nm)(m, N).reshape(m, F, FS).transpose(1, 0, 2)) for nm in names])
+    x = np.stack([np.ascontiguousarray(xs.reshape(m, F, FS).transpose(1, 0, 2)) for _, xs in progs])
     frames = (A.DmxFrame * (S * F))()
     stt = A.DmxState()
     for s in range(S):
@@ -222,15 +234,15 @@ def run_down(inst, m, oc, names):
         return d
 
     A.route_reset()
-    b = A.Batch(S, A.dmx_matrix(il, ol), oc, frame_size=FS, out_format=A.FMT_S16, limiter=True)
-    got = R._ex_loop(A, b, x, extra, list(CALLS), oc)
+    b = A.Batch(S, A.dmx_matrix(il, ol), oc, frame_size=FS, out_format=A.FMT_S16, limiter=True, sample_rate=rate)
+    got = R._ex_loop(A, b, x, extra, list(calls), oc)
     b.close()
-    R.check_tally(A.route_tally(), expected_tally(inst, m, len(CALLS)))
+    R.check_tally(A.route_tally(), expected_tally(inst, m, len(calls)))
     bad = []
     for s, nm in enumerate(names):
         with np.errstate(all="ignore"):
             y = O.downmix_run(il, ol, x[s], sched, 1, 3)
-            z, _ = O.limiter_run(np.ascontiguousarray(y.transpose(1, 0, 2).reshape(oc, N)), [FS] * F)
+            z, _ = O.limiter_run(np.ascontiguousarray(y.transpose(1, 0, 2).reshape(oc, N)), [FS] * F, rate=rate)
         d = mismatch(got[s], O.pack(z, 16))
         if d:
             bad.append("%s: %s" % (nm, d))
@@ -278,17 +290,25 @@ def test_lpcm_packets(early):
 
 def test_fanout_limiter_programmes():
     """one element into a stereo and a mono batch in one launch; each member against its own oracle run"""
+    run_fanout(4, [2, 1], limiter_set(4))
+
+
+def run_fanout(m, ocs, progs, calls=CALLS, rate=48000, thr=-1.0, fused=True):
+    """progs [(name, x [m][n])], one per stream, into len(ocs) members of ocs[j] channels in one launch per call; fused: whether
+    the members' calls are expected in the shared kernel (else each is rendered singly, by the general kernel)"""
     import torch
     A, G, O = _mods()
-    m, ocs = 4, [2, 1]
-    progs = limiter_set(m)
+    K = len(ocs)
+    N = progs[0][1].shape[1]
+    assert N == FS * sum(calls)
     S, F = len(progs), N // FS
     mxs = [selection(m, oc) for oc in ocs]
     x = np.stack([p[1] for p in progs])
     xin = torch.from_numpy(G.to_frames(x, FS)).cuda()
     st = torch.cuda.current_stream().cuda_stream
-    batches = [A.Batch(S, mxs[j][0], ocs[j], frame_size=FS, projection=A.PROJ_EXACT) for j in range(2)]
-    outs = [[[] for _ in range(S)] for _ in range(2)]
+    batches = [A.Batch(S, mxs[j][0], ocs[j], frame_size=FS, projection=A.PROJ_EXACT, sample_rate=rate, threshold_db=thr)
+               for j in range(K)]
+    outs = [[[] for _ in range(S)] for _ in range(K)]
 
     def take(j, pcm, n):
         torch.cuda.synchronize()
@@ -298,13 +318,13 @@ def test_fanout_limiter_programmes():
 
     A.route_reset()
     f0 = 0
-    for nf in CALLS:
+    for nf in calls:
         caps = [(nf * FS * oc * 2 + 15) & ~15 for oc in ocs]
         pcms = [torch.zeros((S, cap), dtype=torch.uint8, device="cuda") for cap in caps]
-        n_emitted, fused = A.render_fanout(batches, xin.data_ptr() + 4 * f0 * m * FS, F * m * FS, m * FS, nf,
-                                           [p.data_ptr() for p in pcms], caps, st)
-        assert fused == 2, fused
-        for j in range(2):
+        n_emitted, n_fused = A.render_fanout(batches, xin.data_ptr() + 4 * f0 * m * FS, F * m * FS, m * FS, nf,
+                                             [p.data_ptr() for p in pcms], caps, st)
+        assert n_fused == (K if fused else 0), n_fused
+        for j in range(K):
             take(j, pcms[j], n_emitted[j])
         f0 += nf
     for j, b in enumerate(batches):
@@ -312,11 +332,14 @@ def test_fanout_limiter_programmes():
         pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
         take(j, pcm, b.flush(pcm.data_ptr(), cap, st))
         b.close()
-    R.check_tally(A.route_tally(), expected_tally(("FANOUT", 0, m, 0, 2), m, len(CALLS), flushes=2))
+    if fused:
+        R.check_tally(A.route_tally(), expected_tally(("FANOUT", 0, m, 0, K), m, len(calls), flushes=K))
+    else:
+        R.check_tally(A.route_tally(), {R.gen(m): K * (len(calls) + 1)})
     bad = []
-    for j in range(2):
+    for j in range(K):
         for s, (name, xs) in enumerate(progs):
-            d = mismatch(np.concatenate(outs[j][s]), oracle_stream(O, mxs[j][1], ocs[j], xs, FS, 16))
+            d = mismatch(np.concatenate(outs[j][s]), oracle_stream(O, mxs[j][1], ocs[j], xs, FS, 16, thr=thr, rate=rate))
             if d:
                 bad.append("member %d (%d ch), %s: %s" % (j, ocs[j], name, d))
     assert not bad, "\n".join(bad)

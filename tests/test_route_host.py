@@ -24,7 +24,13 @@ def test_routing_table_on_the_host(tmp_path):
     assert p.returncode == 0, p.stdout + p.stderr
     out = p.stdout
     m = re.search(r"(\d+) cases, (\d+) wrong", out)
-    assert m and int(m.group(1)) >= 226 and int(m.group(2)) == 0, out
+    assert m and int(m.group(1)) >= 262 and int(m.group(2)) == 0, out
+    # both sides of the staged limiter-table windows (kFWin, kWWin), every family that stages one
+    for block in ("stereo (and a fan-out's member)", "stereo + second element", "down-mixer 6 -> 2", "LPCM", "12 channels",
+                  "12 channels + second element", "down-mixer 12 -> 6", "demixer 12 -> 12", "LFE, 12 channels"):
+        for side in ("kFWin", "kFWin - 1"):
+            assert re.search(r"^%s: n_end = %s\s" % (re.escape(block), re.escape(side)), out, re.M), (block, side)
+    assert "12 -> 11: n_end = kWWin - 1" in out and re.search(r"^12 -> 11: n_end = kWWin\s", out, re.M)
     assert "WRONG" not in out and out.strip().endswith("OK"), out
     for pos, small in ((2 ** 31, 4096), (2 ** 31 + 16, 4112), (2 ** 32 + 8, 4104), (2 ** 40 + 237, 4333)):
         for block in ("stereo", "12 channels", "12 channels, s24", "LFE, 12 channels", "LPCM", "limiter off"):

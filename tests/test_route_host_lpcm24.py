@@ -20,5 +20,5 @@ def test_lpcm24_form_and_routing_on_the_host(tmp_path):
     assert p.returncode == 0, p.stdout + p.stderr
     out = p.stdout
     m = re.search(r"(\d+) cases, (\d+) wrong", out)
-    assert m and int(m.group(1)) >= 76 and int(m.group(2)) == 0, out
+    assert m and int(m.group(1)) >= 80 and int(m.group(2)) == 0, out
     assert "WRONG" not in out and out.strip().endswith("OK"), out
