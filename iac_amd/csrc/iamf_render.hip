@@ -218,13 +218,13 @@ struct iamf_hip_batch {
   float *d_fir_pre[2] = {nullptr, nullptr};         // the history at the input's channel stride (RenderParams::fir_pre), or null
   size_t fir_pre_bytes = 0;
   float *d_fir_y = nullptr;                         // [n_streams][2][total] f32: its output when it runs as its own kernel
-  size_t fir_y_floats = 0;
+  size_t fir_y_bytes = 0;
   // iamf_hip_batch_render_lpcm, calls the fused kernel does not take: the unpacked element and the unpacker's {first, count}
   float *d_lp_in = nullptr;
-  size_t lp_in_floats = 0;
+  size_t lp_in_bytes = 0;
   // iamf_hip_batch_render_lpcm_mix, unfused: the unpacked second element
   float *d_lp_in2 = nullptr;
-  size_t lp_in2_floats = 0;
+  size_t lp_in2_bytes = 0;
   float *d_fir_id = nullptr;                        // 2 x 2 identity + slot map for the limiter / pack kernel behind it
   int32_t *d_fir_id_feed = nullptr;
   float fir_inv_scale = 1.f;
@@ -235,7 +235,7 @@ struct iamf_hip_batch {
   double lfe_div = 0.0;
   float *d_lfe_state = nullptr, *d_lfe_next = nullptr, *d_lfe_u = nullptr;
   bool lfe_shared = false;   // d_lfe_state / d_lfe_next belong to another batch (iamf_hip_batch_share_lfe_state)
-  size_t lfe_u_floats = 0;
+  size_t lfe_u_bytes = 0;
   // fixed PCM channel stride (cfg.pcm_stride_channels): the kernels pack into d_nat, restride_kernel re-lays
   uint8_t *d_nat = nullptr;
   size_t nat_bytes = 0;
@@ -255,6 +255,34 @@ bool on_batch_device(const iamf_hip_batch *b) {
 // event behind the last render (not for the stream handle, which the caller may have destroyed since)
 int quiesce(iamf_hip_batch *b) {
   if (b->rendered) HIPCHK(hipEventSynchronize(b->done));
+  return IAMF_HIP_OK;
+}
+
+// the channels of element 0 as the caller hands them over: in front of the projection's de-mapping where there is one
+int element_channels(const iamf_hip_batch *b) { return b->d_pre ? b->pre_l : b->m; }
+
+// streams [s0, s0 + cnt) lie in the batch
+bool range_ok(const iamf_hip_batch *b, int32_t s0, int32_t cnt) {
+  return s0 >= 0 && cnt > 0 && (int64_t)s0 + cnt <= b->cfg.n_streams;
+}
+
+// A scratch buffer of the batch that grows with the largest call seen: *ptr with *have bytes, of which the call on `st` needs
+// need_bytes.  The old buffer may still be read by a render queued earlier, on another stream perhaps: wait for the batch's
+// event and for the call's stream, then free it.  *ptr and *have are valid after every failure (null and 0 once the old
+// buffer is gone).  zero: a new buffer is cleared on the call's stream (a null-stream memset is not ordered with a
+// non-blocking stream).
+template <class T>
+int grow_scratch(iamf_hip_batch *b, hipStream_t st, T **ptr, size_t *have, size_t need_bytes, bool zero = false) {
+  if (need_bytes <= *have) return IAMF_HIP_OK;
+  const int q = quiesce(b);
+  if (q != IAMF_HIP_OK) return q;
+  HIPCHK(hipStreamSynchronize(st));
+  (void)hipFree(*ptr);
+  *ptr = nullptr;
+  *have = 0;
+  HIPCHK(hipMalloc(ptr, need_bytes));
+  if (zero) HIPCHK(hipMemsetAsync(*ptr, 0, need_bytes, st));
+  *have = need_bytes;
   return IAMF_HIP_OK;
 }
 
@@ -329,6 +357,31 @@ void launch_wide_m(const RenderParams &p, dim3 grid, hipStream_t st) {
   else launch_big_lds<&render_wide_kernel<M, false>, 80 * 1024>(grid, dim3(256), lds, st, p);
 }
 
+// Family::FirSplit: (1) the FFT stage for every hop of every stream -> y in HBM (overlap-save blocks are independent: one
+// grid); (2) gains, limiter, pack = the two-channel matrix kernel with the identity over y (one "frame" of `total` samples
+// per stream).  1024 streams x 64 frames: 1.5 ms (vector ALU) + 0.6 ms (the limiter's chain, four workgroups a CU).
+// Tried and dropped, both bit-exact: slices of STREAMS with the limiter kernel of one slice beside the stage of the next on
+// a second stream (23.8 against 33.2 Gsamples/s: the limiter kernel takes 0.6 ms for 256 streams as for 1024), and slices of
+// TIME the same way (31.1: four resident limiter workgroups and two stage workgroups each want all 512 VGPRs of a SIMD
+// lane, so the two kernels take turns instead of overlapping).
+int launch_fir_split(const RenderParams &p, int m, dim3 grid, hipStream_t st) {
+  if (!dispatch(FirHomeM{}, m, [&](auto M) { launch_fft_m<M.value>(p, st); }) && !iamf_hip_fir_m2b_launch_fft(&p, m, st))
+    return IAMF_HIP_ERR_INTERNAL;
+  HIPCHK(hipGetLastError());
+  RenderParams q = p;
+  q.in = p.fir_y;                               // planar [2][total]: channel stride = "frame size" = total
+  q.in_stream_stride = 2 * (int64_t)p.total;
+  q.in_frame_stride = 2 * (int64_t)p.total;
+  q.frame_size = p.total;
+  q.matrix = p.fir_id_matrix;
+  q.src_feed = p.fir_id_feed;
+  q.n_feeds = 2;
+  q.fir_taps = 0;
+  q.fir_hist = q.fir_hist_next = nullptr;
+  launch_fast_m<2>(q, false, grid, st);
+  return IAMF_HIP_OK;
+}
+
 // Runs the kernel pick_route (render_route.hpp) names.  `launched` is false only if a launcher's instance list and the
 // one the route was picked by disagree, which sharing the lists rules out.
 // (p: the block every kernel takes and, behind it, what Family::LpcmMix alone reads)
@@ -346,27 +399,8 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
       break;
     case Family::FastInterleaved: launched = iamf_hip_fast_interleaved_launch(&p, m, st); break;
     case Family::FirSplit: {
-      // (1) the FFT stage for every hop of every stream -> y in HBM (overlap-save blocks are independent: one grid); (2)
-      // gains, limiter, pack = the two-channel matrix kernel with the identity over y (one "frame" of `total` samples per
-      // stream).  1024 streams x 64 frames: 1.5 ms (vector ALU) + 0.6 ms (the limiter's chain, four workgroups a CU).
-      // Tried and dropped, both bit-exact: slices of STREAMS with the limiter kernel of one slice beside the stage of the
-      // next on a second stream (23.8 against 33.2 Gsamples/s: the limiter kernel takes 0.6 ms for 256 streams as for
-      // 1024), and slices of TIME the same way (31.1: four resident limiter workgroups and two stage workgroups each want
-      // all 512 VGPRs of a SIMD lane, so the two kernels take turns instead of overlapping).
-      if (!dispatch(FirHomeM{}, m, [&](auto M) { launch_fft_m<M.value>(p, st); }) && !iamf_hip_fir_m2b_launch_fft(&p, m, st))
-        return IAMF_HIP_ERR_INTERNAL;
-      HIPCHK(hipGetLastError());
-      RenderParams q = p;
-      q.in = p.fir_y;                               // planar [2][total]: channel stride = "frame size" = total
-      q.in_stream_stride = 2 * (int64_t)p.total;
-      q.in_frame_stride = 2 * (int64_t)p.total;
-      q.frame_size = p.total;
-      q.matrix = p.fir_id_matrix;
-      q.src_feed = p.fir_id_feed;
-      q.n_feeds = 2;
-      q.fir_taps = 0;
-      q.fir_hist = q.fir_hist_next = nullptr;
-      launch_fast_m<2>(q, false, grid, st);
+      const int e = launch_fir_split(p, m, grid, st);
+      if (e != IAMF_HIP_OK) return e;
       launched = true;
       break;
     }
@@ -390,10 +424,8 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
   if (!launched) return IAMF_HIP_ERR_INTERNAL;
   HIPCHK(hipGetLastError());
   const RouteKey k = route_key(r, p, m);   // the tally of iamf_hip_route_tally
-  if (r.family == Family::Lpcm24) iamf_hip_route_count_table(2, k.family, k.variant, k.m, k.c, k.k);   // its own table
-  else if (r.family == Family::LpcmCoupled || r.family == Family::LpcmMix || r.family == Family::FastInterleaved) iamf_hip_route_count_family(k.family, k.variant, k.m, k.c, k.k);   // no table's
-  else iamf_hip_route_count(k.family, k.variant, k.m, k.c, k.k);
-  if (r.family == Family::FirSplit) iamf_hip_route_count(IAMF_HIP_ROUTE_FAST, 0, 2, 2, 0);
+  iamf_hip_route_count(k.set, k.family, k.variant, k.m, k.c, k.k);
+  if (r.family == Family::FirSplit) iamf_hip_route_count(0, IAMF_HIP_ROUTE_FAST, 0, 2, 2, 0);
   return IAMF_HIP_OK;
 }
 
@@ -426,6 +458,12 @@ struct LpcmIn {
   int32_t coupled; // 1: LpcmForm::S16C, off[] of a pair's two channels 2 bytes apart
 };
 constexpr int kNotFused = INT32_MIN;
+// the family a packet call must route to for a fused kernel to read its packets (lp2: the second element's, or null)
+Family lpcm_family(const LpcmIn *lp, const LpcmIn *lp2) {
+  if (lp2) return Family::LpcmMix;
+  if (lp->coupled) return Family::LpcmCoupled;
+  return lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm;
+}
 
 // HOA LFE generator over `ltotal` samples of the element rows at d_in: feed-forward part in parallel, the recurrence one lane
 // per stream, both on the caller's stream (render_lfe.hpp); the output lies in b->d_lfe_u (t4 quads per stream), the filter
@@ -433,17 +471,8 @@ constexpr int kNotFused = INT32_MIN;
 int lfe_prepass(iamf_hip_batch *b, const float *d_in, int64_t in_stream_stride, int64_t in_frame_stride, int ltotal,
                 hipStream_t st, int s0, int cnt, int *t4_out) {
   const int ns = b->cfg.n_streams, nb = (ns + 63) / 64, t4 = (ltotal + 3) / 4;
-  const size_t need_u = (size_t)nb * t4 * 64 * 4;
-  if (need_u > b->lfe_u_floats) {  // grows with the largest call seen
-    const int q = quiesce(b);      // an earlier call on the batch may have used another stream
-    if (q != IAMF_HIP_OK) return q;
-    HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(b->d_lfe_u);
-    b->d_lfe_u = nullptr;
-    b->lfe_u_floats = 0;
-    HIPCHK(hipMalloc(&b->d_lfe_u, sizeof(float) * need_u));
-    b->lfe_u_floats = need_u;
-  }
+  const int gr = grow_scratch(b, st, &b->d_lfe_u, &b->lfe_u_bytes, sizeof(float) * (size_t)nb * t4 * 64 * 4);
+  if (gr != IAMF_HIP_OK) return gr;
   LfeParams lp;
   memset(&lp, 0, sizeof(lp));
   lp.in = d_in;
@@ -496,7 +525,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   if (lp2 && (!lp || !b->has2 || !b->lp2_scale_ok ||
               (b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels)))
     return kNotFused;
-  if (s0 < 0 || cnt <= 0 || s0 + cnt > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  if (!range_ok(b, s0, cnt)) return IAMF_HIP_ERR_BAD_ARG;
   if (a.lfe_pre_samples < 0 || a.lfe_post_samples < 0 ||
       ((a.lfe_pre_samples || a.lfe_post_samples) &&
        (a.n_frames != 1 || (int64_t)a.lfe_pre_samples + total + a.lfe_post_samples > b->cfg.frame_size)))
@@ -617,9 +646,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       for (int m = 0; m < 4; ++m) pc.p.lpcm2_off[m] = lp2->off[m];
       if (!lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     }
-    if (pick_route(p, m_eff).family !=
-        (lp2 ? Family::LpcmMix : (lp->coupled ? Family::LpcmCoupled : (lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm))))
-      return kNotFused;
+    if (pick_route(p, m_eff).family != lpcm_family(lp, lp2)) return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -634,18 +661,10 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     p.fir_pre_next = b->d_fir_pre[b->fir_cur ^ 1];
     if (a.d_in && b->d_fir_pq && (b->cfg.frame_size & 63) == 0 && !getenv("IAMF_HIP_FIR_FUSED") && !getenv("IAMF_HIP_FIR_F16") &&
         !getenv("IAMF_HIP_FIR_F32")) {
-      // the FFT stage's output of this call, [n_streams][2][total] (grows with the largest call seen)
-      const size_t need = (size_t)b->cfg.n_streams * 2 * (size_t)total;
-      if (need > b->fir_y_floats) {
-        const int q = quiesce(b);   // an earlier call on the batch may have used another stream
-        if (q != IAMF_HIP_OK) return q;
-        HIPCHK(hipStreamSynchronize(static_cast<hipStream_t>(a.stream)));
-        (void)hipFree(b->d_fir_y);
-        b->d_fir_y = nullptr;
-        b->fir_y_floats = 0;
-        HIPCHK(hipMalloc(&b->d_fir_y, sizeof(float) * need));
-        b->fir_y_floats = need;
-      }
+      // the FFT stage's output of this call, [n_streams][2][total]
+      const int gr = grow_scratch(b, static_cast<hipStream_t>(a.stream), &b->d_fir_y, &b->fir_y_bytes,
+                                  sizeof(float) * (size_t)b->cfg.n_streams * 2 * (size_t)total);
+      if (gr != IAMF_HIP_OK) return gr;
       p.fir_y = b->d_fir_y;
       p.fir_id_matrix = b->d_fir_id;
       p.fir_id_feed = b->d_fir_id_feed;
@@ -672,17 +691,8 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   const int bps = iamf_hip_format_bytes(p.out_format);
   if (restride) {  // pack naturally into scratch, then re-lay with the fixed channel stride
     const size_t per_stream = (size_t)(total > kDelay ? total : kDelay) * p.out_ch * bps;
-    const size_t need = per_stream * (size_t)p.n_streams;
-    if (need > b->nat_bytes) {
-      const int q = quiesce(b);   // an earlier call on the batch may have used another stream
-      if (q != IAMF_HIP_OK) return q;
-      HIPCHK(hipStreamSynchronize(static_cast<hipStream_t>(a.stream)));
-      (void)hipFree(b->d_nat);
-      b->d_nat = nullptr;
-      b->nat_bytes = 0;
-      HIPCHK(hipMalloc(&b->d_nat, need));
-      b->nat_bytes = need;
-    }
+    const int gr = grow_scratch(b, static_cast<hipStream_t>(a.stream), &b->d_nat, &b->nat_bytes, per_stream * (size_t)p.n_streams);
+    if (gr != IAMF_HIP_OK) return gr;
     p.pcm = b->d_nat;
     p.pcm_stream_stride = (int64_t)per_stream;
   }
@@ -730,13 +740,18 @@ int render_commit(iamf_hip_batch *b, const PreparedCall &pc) {
   return n_emit;
 }
 
-int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr) {
+// a prepared call: launch, then commit.  The sample-frames emitted per stream, or the launch's error
+int render_finish(iamf_hip_batch *b, const PreparedCall &pc) {
+  const int r = render_launch(pc);
+  return r != IAMF_HIP_OK ? r : render_commit(b, pc);
+}
+
+// the whole call (lp, lp2, il: as render_prepare, whose kNotFused comes back before anything is changed or launched)
+int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr,
+                const LpcmIn *lp2 = nullptr, bool il = false) {
   PreparedCall pc;
-  int r = render_prepare(b, a, total, s0, cnt, lp, pc);
-  if (r != IAMF_HIP_OK) return r;
-  r = render_launch(pc);
-  if (r != IAMF_HIP_OK) return r;
-  return render_commit(b, pc);
+  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il);
+  return r != IAMF_HIP_OK ? r : render_finish(b, pc);
 }
 
 // feed-major copy of a renderer matrix and its output-slot map (h2m_rdr.c:1114-1150 keeps the
@@ -1097,7 +1112,7 @@ int iamf_hip_batch_set_gains(iamf_hip_batch *b, const float *eg, const float *og
 static int range_args_check(const iamf_hip_batch *b, const iamf_hip_render_args *a, int32_t stream0, int32_t n_streams, int64_t *total_out) {
   *total_out = 0;
   if (!b || !a || !a->d_in || !a->d_pcm || a->n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
-  if (stream0 < 0 || n_streams <= 0 || stream0 + n_streams > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  if (!range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
   if (a->n_frames == 0) return IAMF_HIP_OK;
   if (b->has2 && !a->d_in2) return IAMF_HIP_ERR_BAD_ARG;
   if (b->dmx && !a->d_dmx_frames) return IAMF_HIP_ERR_BAD_ARG;
@@ -1172,7 +1187,7 @@ static int lpcm_form_check_ch(const iamf_hip_batch *b, const iamf_hip_lpcm_input
 
 static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int n_samples, LpcmForm *form_out,
                            int *first_out, int *count_out) {
-  return lpcm_form_check_ch(b, in, b->d_pre ? b->pre_l : b->m, nf, n_samples, form_out, first_out, count_out);
+  return lpcm_form_check_ch(b, in, element_channels(b), nf, n_samples, form_out, first_out, count_out);
 }
 
 // packets of the fusable form as the fused kernels take them
@@ -1194,27 +1209,15 @@ static void lpcm_in_of(const iamf_hip_lpcm_input *in, int ch, int first, LpcmFor
 static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int first, int count, int32_t stream0,
                              int32_t n_streams, hipStream_t st, iamf_hip_render_args &a, bool second = false) {
   const iamf_hip_lpcm_layout &L = in->layout;
-  const int fs = b->cfg.frame_size, ch = second ? b->m2 : (b->d_pre ? b->pre_l : b->m), ns = b->cfg.n_streams;
+  const int fs = b->cfg.frame_size, ch = second ? b->m2 : element_channels(b), ns = b->cfg.n_streams;
   float *&d_buf = second ? b->d_lp_in2 : b->d_lp_in;
-  size_t &buf_floats = second ? b->lp_in2_floats : b->lp_in_floats;
   // as many frames per launch as the grid's third dimension takes; a range too wide for one frame is refused before
   // anything is allocated or queued
   const int fmax = 65535 / n_streams;
   if (fmax == 0) return IAMF_HIP_ERR_UNIMPLEMENTED;
-  const size_t need = (size_t)ns * nf * ch * fs;
-  if (need > buf_floats) {   // grows with the largest call seen
-    const int q = quiesce(b);     // a render queued earlier may still be reading the old buffer
-    if (q != IAMF_HIP_OK) return q;
-    HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(d_buf);
-    d_buf = nullptr;
-    buf_floats = 0;
-    HIPCHK(hipMalloc(&d_buf, sizeof(float) * need));
-    // rows of channels no sub-stream carries (src_offset < 0) are never written by the unpacker: keep them defined
-    // (on the call's stream, in front of the unpack kernel: a null-stream memset is not ordered with a non-blocking stream)
-    HIPCHK(hipMemsetAsync(d_buf, 0, sizeof(float) * need, st));
-    buf_floats = need;
-  }
+  // zeroed when it grows: rows of channels no sub-stream carries (src_offset < 0) are never written by the unpacker
+  const int gr = grow_scratch(b, st, &d_buf, second ? &b->lp_in2_bytes : &b->lp_in_bytes, sizeof(float) * (size_t)ns * nf * ch * fs, true);
+  if (gr != IAMF_HIP_OK) return gr;
   const int64_t lp_stream_stride = (int64_t)nf * ch * fs;
   for (int f = 0; f < nf; f += fmax) {
     const int r = iamf_hip_lpcm_unpack_frames(
@@ -1239,10 +1242,10 @@ static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, i
 int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
                                      int32_t stream0, int32_t n_streams) {
   if (!b || !in || !args || !in->d_raw || args->d_in || !args->d_pcm || args->n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
-  if (stream0 < 0 || n_streams <= 0 || stream0 + n_streams > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  if (!range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
   if (args->n_frames == 0) return 0;
-  const int ch = b->d_pre ? b->pre_l : b->m, nf = args->n_frames;
+  const int ch = element_channels(b), nf = args->n_frames;
   LpcmForm form = LpcmForm::None;
   int first = 0, count = 0;
   const int fc = lpcm_form_check(b, in, nf, args->n_samples, &form, &first, &count);
@@ -1281,10 +1284,10 @@ int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_ca
   if (!b->has2 || args->d_in || args->d_in2 || !in0->d_raw || !in1->d_raw || in0->first_sample != in1->first_sample ||
       !args->d_pcm || args->n_frames < 0)
     return IAMF_HIP_ERR_BAD_ARG;
-  if (stream0 < 0 || n_streams <= 0 || stream0 + n_streams > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  if (!range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
   if (args->n_frames == 0) return 0;
-  const int ch = b->d_pre ? b->pre_l : b->m, nf = args->n_frames;
+  const int ch = element_channels(b), nf = args->n_frames;
   LpcmForm form0 = LpcmForm::None, form1 = LpcmForm::None;
   int first = 0, count = 0, first1 = 0, count1 = 0;
   int fc = lpcm_form_check_ch(b, in0, ch, nf, args->n_samples, &form0, &first, &count);
@@ -1307,12 +1310,7 @@ int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_ca
     LpcmIn lp0, lp1;
     lpcm_in_of(in0, ch, first, form0, lp0);
     lpcm_in_of(in1, b->m2, first, form1, lp1);
-    PreparedCall pc;
-    int r = render_prepare(b, a, (int)total, stream0, n_streams, &lp0, pc, &lp1);
-    if (r == IAMF_HIP_OK) {
-      r = render_launch(pc);
-      return r != IAMF_HIP_OK ? r : render_commit(b, pc);
-    }
+    const int r = render_call(b, a, (int)total, stream0, n_streams, &lp0, &lp1);
     if (r != kNotFused) return r;
   }
   const hipStream_t st = static_cast<hipStream_t>(args->stream);
@@ -1325,18 +1323,14 @@ int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_ca
 
 // Interleaved f32 of any call length (include/iamf_hip.h): iamf_hip_batch_render_range with leave to take
 // render_fast_kernel<.., IL, RAG> (Family::FastInterleaved) where pick_route's rules hold.  The same checks in the same
-// order, the same internal route (render_prepare, render_launch, render_commit) for everything else.
+// order, the same internal route (render_call) for everything else.
 int iamf_hip_batch_render_interleaved(iamf_hip_batch *b, const iamf_hip_interleaved_call *call, int32_t stream0, int32_t n_streams) {
   if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
   if (b->cfg.frame_size != 1) return IAMF_HIP_ERR_BAD_ARG;
   int64_t total = 0;
   const int rc = range_args_check(b, &call->args, stream0, n_streams, &total);
   if (rc != IAMF_HIP_OK || total == 0) return rc;
-  PreparedCall pc;
-  int r = render_prepare(b, call->args, (int)total, stream0, n_streams, nullptr, pc, nullptr, true);
-  if (r != IAMF_HIP_OK) return r;
-  r = render_launch(pc);
-  return r != IAMF_HIP_OK ? r : render_commit(b, pc);
+  return render_call(b, call->args, (int)total, stream0, n_streams, nullptr, nullptr, true);
 }
 
 int iamf_hip_batch_render_ex(iamf_hip_batch *b, const iamf_hip_render_args *a) {
@@ -1385,7 +1379,7 @@ static bool fan_members_distinct(iamf_hip_batch *const *batches, void *const *d_
 // iamf_hip_batch_render_ex
 static bool fan_member_like(const iamf_hip_batch *b, const iamf_hip_batch *b0) {
   return b->cfg.n_streams == b0->cfg.n_streams && b->cfg.frame_size == b0->cfg.frame_size && b->m == b0->m &&
-         (b->d_pre ? b->pre_l : b->m) == (b0->d_pre ? b0->pre_l : b0->m) && !(b->has2 || b->dmx || b->demix);
+         element_channels(b) == element_channels(b0) && !(b->has2 || b->dmx || b->demix);
 }
 
 // state: the range at one position in every member, unflushed; the HRTF stage's history is per batch, not per stream, so
@@ -1512,7 +1506,7 @@ static int fanout_range_impl(iamf_hip_batch *const *batches, int32_t n_batches, 
     }
     if (!iamf_hip_fanout_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
     HIPCHK(hipGetLastError());
-    iamf_hip_route_count(IAMF_HIP_ROUTE_FANOUT, 0, b0->m, 0, k);
+    iamf_hip_route_count(0, IAMF_HIP_ROUTE_FANOUT, 0, b0->m, 0, k);
     for (int j = 0; j < n_batches; ++j) {
       if (!fuse[j]) continue;
       const int r = render_commit(batches[j], pcs[j]);
@@ -1565,7 +1559,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
   if (!fan_members_distinct(batches, d_pcm, n_batches)) return IAMF_HIP_ERR_BAD_ARG;
   // ---- the members against each other and the range (as the f32 entry), the device (as the single LPCM call) ----
   iamf_hip_batch *b0 = batches[0];
-  const int ch = b0->d_pre ? b0->pre_l : b0->m;
+  const int ch = element_channels(b0);
   for (int j = 0; j < n_batches; ++j)
     if (!fan_member_like(batches[j], b0)) return IAMF_HIP_ERR_BAD_ARG;
   if (stream0 + n_streams > b0->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
@@ -1659,7 +1653,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
     }
     if (!iamf_hip_fanout_lp_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
     HIPCHK(hipGetLastError());
-    iamf_hip_route_count_ext(IAMF_HIP_ROUTE_FANOUT_LPCM, 0, b0->m, 0, k);
+    iamf_hip_route_count(1, IAMF_HIP_ROUTE_FANOUT_LPCM, 0, b0->m, 0, k);   // the extension table
     for (int j = 0; j < n_batches; ++j) {
       if (cls[j] != 2) continue;
       const int r = render_commit(batches[j], pcs[j]);
@@ -1672,9 +1666,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
   // ---- 2. the members whose single call reads the packets itself, in member order ----
   for (int j = 0; j < n_batches; ++j) {
     if (cls[j] != 1) continue;
-    int r = render_launch(pcs[j]);
-    if (r != IAMF_HIP_OK) return r;
-    r = render_commit(batches[j], pcs[j]);
+    const int r = render_finish(batches[j], pcs[j]);
     if (r < 0) return r;
     emitted[j] = r;
   }
@@ -1715,7 +1707,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
 int iamf_hip_batch_flush_range(iamf_hip_batch *b, void *d_pcm, int64_t pcm_stream_stride_bytes, void *stream,
                                int32_t stream0, int32_t n_streams) {
   if (!b || !d_pcm) return IAMF_HIP_ERR_BAD_ARG;
-  if (stream0 < 0 || n_streams <= 0 || stream0 + n_streams > b->cfg.n_streams) return IAMF_HIP_ERR_BAD_ARG;
+  if (!range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
   for (int i = stream0; i < stream0 + n_streams; ++i)
     if (b->sflushed[(size_t)i]) return IAMF_HIP_ERR_INVALID_STATE;
   if (!b->cfg.limiter_enable) return 0;
@@ -2109,10 +2101,6 @@ uint32_t batch_signature(const iamf_hip_batch *b) {
                         b->cfg.limiter_enable ? 1u : 0u, thr_bits, (uint32_t)b->n_end, (uint32_t)b->n_atk,
                         (uint32_t)b->cfg.sample_rate, (b->lfe && !b->lfe_shared) ? 1u : 0u, b->has2 ? 1u : 0u};
   return state_hash(w, (int)(sizeof(w) / sizeof(w[0])));
-}
-
-bool range_ok(const iamf_hip_batch *b, int32_t s0, int32_t cnt) {
-  return s0 >= 0 && cnt > 0 && (int64_t)s0 + cnt <= b->cfg.n_streams;
 }
 
 // `st` behind everything queued on the batch so far, whatever stream that used

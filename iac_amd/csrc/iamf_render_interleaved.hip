@@ -10,43 +10,11 @@
 // sample-frames emitted and the persisted stream state are bit-identical to the general kernel's (tests/test_gpu_interleaved.py).
 // Entry: iamf_hip_batch_render_interleaved (iamf_render.hip), which takes the path of iamf_hip_batch_render_range for every
 // call this kernel does not take.
-#include <hip/hip_runtime.h>
-
-#include <stdint.h>
-#include <atomic>
-#include <stdlib.h>
-#include <string.h>
-
-#include <type_traits>
-
-#include "../../include/iamf_hip.h"
-#include "render_entry.hpp"
-
-namespace {
-
-#include "render_common.hpp"
-#include "render_downmix.hpp"
-#include "render_fir.hpp"
-#include "render_fir16.hpp"
-#include "render_fir_fft.hpp"
-#include "render_fast.hpp"
-
-template <int M, int OC>
-void launch_il_mc(const RenderParams &p, hipStream_t st) {
-  constexpr size_t lds = sizeof(float) * (size_t)fast_lds_floats(OC, M);
-  // built for the four workgroups per CU of the planar f32 form <M, OC> (render_fast_kernel's launch bounds)
-  static_assert(lds * 4 <= 160 * 1024, "the workgroups the instance is built for fit a CU's LDS");
-  launch_big_lds<&render_fast_kernel<M, OC, 0, false, false, false, true, 2, false, 0, true, true>, 80 * 1024>(dim3((unsigned)p.n_launch), dim3(256), lds,
-                                                                                                                st, p);
-}
-
-}  // namespace
+#include "render_fast_unit.hpp"
 
 int iamf_hip_fast_interleaved_launch(const void *params, int m, hipStream_t st) {
   RenderParams p;
   memcpy(&p, params, sizeof(p));
   if (!p.interleaved || !p.in || p.frame_size != 1 || p.in_frame_stride != m) return 0;
-  return dispatch(InterleavedM{}, m, [&](auto M) {
-    return dispatch(InterleavedOC{}, p.out_ch, [&](auto OC) { launch_il_mc<M.value, OC.value>(p, st); });
-  });
+  return launch_fast_interleaved<InterleavedM, InterleavedOC>(p, m, st);
 }

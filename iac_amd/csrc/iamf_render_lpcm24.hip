@@ -8,43 +8,11 @@
 // expression (pcm/IAMF_pcm_decoder.c:71-76, 144-148: sample / 2^23, the power of two folded into the staged weights):
 // results are bit-identical to the unfused pair (tests/test_gpu_lpcm24.py).  Entry: iamf_hip_batch_render_lpcm
 // (iamf_render.hip), which falls back to exactly that pair for every input this kernel does not take.
-#include <hip/hip_runtime.h>
-
-#include <stdint.h>
-#include <atomic>
-#include <stdlib.h>
-#include <string.h>
-
-#include <type_traits>
-
-#include "../../include/iamf_hip.h"
-#include "render_entry.hpp"
-
-namespace {
-
-#include "render_common.hpp"
-#include "render_downmix.hpp"
-#include "render_fir.hpp"
-#include "render_fir16.hpp"
-#include "render_fir_fft.hpp"
-#include "render_fast.hpp"
-
-template <int M, int OC>
-void launch_lp24_mc(const RenderParams &p, bool early, hipStream_t st) {
-  const size_t lds = sizeof(float) * (size_t)fast_lds_floats(OC, M);
-  const dim3 grid((unsigned)p.n_launch);
-  // early: the per-channel prefetch (pick_route says when)
-  if (early) launch_big_lds<&render_fast_kernel<M, OC, 0, false, false, true, true, 3>, 80 * 1024>(grid, dim3(256), lds, st, p);
-  else launch_big_lds<&render_fast_kernel<M, OC, 0, false, false, true, false, 3>, 80 * 1024>(grid, dim3(256), lds, st, p);
-}
-
-}  // namespace
+#include "render_fast_unit.hpp"
 
 int iamf_hip_fast_lpcm24_launch(const void *params, int m, int early, hipStream_t st) {
   RenderParams p;
   memcpy(&p, params, sizeof(p));
   if (!p.lpcm || p.lpcm_bytes != 3) return 0;
-  return dispatch(LpcmM{}, m, [&](auto M) {
-    return dispatch(LpcmOC{}, p.out_ch, [&](auto OC) { launch_lp24_mc<M.value, OC.value>(p, early != 0, st); });
-  });
+  return launch_fast_lp<LpcmM, LpcmOC, 3, false>(p, m, early != 0, st);
 }

@@ -14,43 +14,11 @@
 // are bit-identical to the unfused sequence (tests/test_gpu_lpcm_mix.py).
 // Entry: iamf_hip_batch_render_lpcm_mix (iamf_render.hip), which falls back to exactly that sequence for every input this
 // kernel does not take.
-#include <hip/hip_runtime.h>
-
-#include <stdint.h>
-#include <atomic>
-#include <stdlib.h>
-#include <string.h>
-
-#include <type_traits>
-
-#include "../../include/iamf_hip.h"
-#include "render_entry.hpp"
-
-namespace {
-
-#include "render_common.hpp"
-#include "render_downmix.hpp"
-#include "render_fir.hpp"
-#include "render_fir16.hpp"
-#include "render_fir_fft.hpp"
-#include "render_fast.hpp"
-
-template <int M, int OC, int LP2>
-void launch_lpmix_mck(const RenderMixParams &p, hipStream_t st) {
-  constexpr size_t lds = sizeof(float) * (size_t)fast_lds_floats(OC, M);   // (the second element's matrix rows are in it)
-  static_assert(lds * lpcm_mix_wgs(M, OC, LP2) <= 160 * 1024, "the workgroups the instance is built for fit a CU's LDS");
-  launch_big_lds<&render_fast_kernel<M, OC, 0, false, true, true, true, 2, false, LP2>, 80 * 1024>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
-}
-
-}  // namespace
+#include "render_fast_unit.hpp"
 
 int iamf_hip_fast_lpcm_mix_launch(const void *params, int m, int lp2, hipStream_t st) {
   RenderMixParams p;
   memcpy(&p, params, sizeof(p));
   if (!p.lpcm || !p.lpcm2 || p.lpcm_coupled || p.lpcm_bytes == 3 || p.lpcm_mix != lp2) return 0;
-  return dispatch(LpcmM{}, m, [&](auto M) {
-    return dispatch(LpcmOC{}, p.out_ch, [&](auto OC) {
-      return dispatch(LpcmMixK{}, lp2, [&](auto K) { launch_lpmix_mck<M.value, OC.value, K.value>(p, st); });
-    });
-  });
+  return launch_fast_lp_mix<LpcmM, LpcmOC, false, LpcmMixK>(p, m, lp2, st);
 }

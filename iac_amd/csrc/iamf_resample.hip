@@ -664,7 +664,7 @@ int rs_run(iamf_hip_resampler *r, const float *d_in, int64_t in_stride, int ns, 
     hipLaunchKernelGGL(resample_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
   }
   RS_HIPCHK(hipGetLastError());
-  iamf_hip_route_count(ran.family, ran.variant, ran.m, ran.c, ran.k);
+  iamf_hip_route_count(0, ran.family, ran.variant, ran.m, ran.c, ran.k);
   for (int i = s0; i < s0 + cnt; ++i) {
     r->last_sample[(size_t)i] = ls - consumed;
     r->frac[(size_t)i] = fr;

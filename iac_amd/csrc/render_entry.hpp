@@ -3,7 +3,9 @@
 // declaration does not compile.  Kernel and parameter types live in each unit's anonymous namespace (the kernels' symbol
 // names depend on it), hence `const void *params`: the caller's RenderParams / FanParams, the same definition on both
 // sides (render_params.hpp, render_fanout.hpp).  Each returns 1 if it launched, 0 if (m, the block's channel counts) is
-// not in the instance list the caller has already consulted (render_route.hpp).
+// not in the instance list the caller has already consulted (render_route.hpp).  The units that feed render_fast_kernel
+// another input form (the six iamf_hip_fast_*_launch entries) share their launchers: render_fast_unit.hpp.  Behind the
+// launch entries: the unpacker's, and the one entry through which every launcher counts what it ran (iamf_route.hip).
 #pragma once
 
 #define IAMF_INTERNAL extern "C" __attribute__((visibility("hidden")))
@@ -39,11 +41,7 @@ IAMF_INTERNAL int iamf_hip_lpcm_unpack_frames(const iamf_hip_lpcm_layout *lay, c
                                               int64_t first_count_stride, float *d_out, int64_t out_stream_stride,
                                               int64_t out_frame_stride, int32_t n_streams, void *stream, int32_t uniform_first,
                                               int32_t uniform_count);
-// iamf_route.hip: one launch of the instance (family, variant, m, c, k) of iamf_hip_route_row succeeded
-IAMF_INTERNAL void iamf_hip_route_count(int family, int variant, int m, int c, int k);
-// ... of an instance of the extension table (iamf_hip_route_instances_ext)
-IAMF_INTERNAL void iamf_hip_route_count_ext(int family, int variant, int m, int c, int k);
-// ... of an instance of table `table` of iamf_hip_route_table_instances (0 and 1: the two above)
-IAMF_INTERNAL void iamf_hip_route_count_table(int table, int family, int variant, int m, int c, int k);
-// ... of an instance listed by family only (iamf_hip_route_family_instances): whichever row set holds it
-IAMF_INTERNAL void iamf_hip_route_count_family(int family, int variant, int m, int c, int k);
+// iamf_route.hip: one launch of the instance (family, variant, m, c, k) of iamf_hip_route_row succeeded; set: the row set
+// that lists it (RouteKey::set of render_route.hpp; 0: the base table, 1: the extension table).  The one counting entry:
+// launch() and the two fan-out entries of iamf_render.hip and the resampler call it
+IAMF_INTERNAL void iamf_hip_route_count(int set, int family, int variant, int m, int c, int k);

@@ -15,6 +15,7 @@
 // ------------------------------------------------------------------------------------------
 
 #include "instance_lists.hpp"
+#include "resample_route.hpp"   // the resampler's instances are rows of the base table (for_each_instance_of_set)
 
 // inputs of render_kernel (render_generic.hpp) and render_nolim_kernel.  11 inputs: no element of the reference has them,
 // but the stage behind the resampler takes the OUTPUT layout's channels through the identity, and Sound System E has 11
@@ -220,15 +221,17 @@ enum class Family {
   Fast,         // render_fast_kernel<M, OC>; variant 1: the mixing one (IN2)
   Wide,         // render_wide_kernel<M, MFMA>; variant 1: MFMA projection
   Generic,      // render_kernel<M>
-  Lpcm24,       // render_fast_kernel<.., LP, EARLY, LPB = 3> (iamf_render_lpcm24.hip); variant as Lpcm.  Table 2 of
-                // iamf_hip_route_table_instances: the base listing's row set is pinned
-  LpcmCoupled,  // render_fast_kernel<.., LP, EARLY, 2, LPC> (iamf_render_lpcm_coupled.hip); variant as Lpcm.  Listed by
-                // iamf_hip_route_family_instances only: the three tables' row sets are pinned
+  // The families below are listed in row sets of their own (for_each_instance_of_set, RouteKey::set): the base table's row
+  // set is pinned, and so are those of the numbered tables, of which there stay three.
+  Lpcm24,       // render_fast_kernel<.., LP, EARLY, LPB = 3> (iamf_render_lpcm24.hip); variant as Lpcm.  Set 2, which is table 2
+                // of iamf_hip_route_table_instances
+  LpcmCoupled,  // render_fast_kernel<.., LP, EARLY, 2, LPC> (iamf_render_lpcm_coupled.hip); variant as Lpcm.  Set 3: behind the
+                // numbered tables, listed by iamf_hip_route_family_instances only
   LpcmMix,      // render_fast_kernel<.., LP, true, 2, LPC, LP2> (iamf_render_lpcm_mix.hip, iamf_render_lpcm_mix_coupled.hip): both
-                // elements of a mix as 16-bit packets; variant = LP2 (1 mono-coded second element, 2 a coupled pair).  Listed
-                // by iamf_hip_route_family_instances only
+                // elements of a mix as 16-bit packets; variant = LP2 (1 mono-coded second element, 2 a coupled pair).  Set 4,
+                // listed by family only
   FastInterleaved,  // render_fast_kernel<M, OC, .., IL, RAG> (iamf_render_interleaved.hip): interleaved f32 of any call length,
-                // RenderParams::interleaved.  Listed by iamf_hip_route_family_instances only
+                // RenderParams::interleaved.  Set 5, listed by family only
 };
 struct Route {
   Family family;
@@ -478,10 +481,29 @@ void for_each_render_instance_interleaved(F &&f) {
   for_each_int(InterleavedM{}, [&](int m) { for_each_int(InterleavedOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, oc, 0); }); });
 }
 
-// the row of the kernel launch() runs for a route (a FirSplit call launches render_fast_kernel<2, 2> behind it as well:
-// launch() counts that row too)
+// The row sets behind the listing, by number: f as above for every instance of set `set`.  Sets 0 .. kRouteTables - 1 are
+// the numbered tables of iamf_hip_route_table_instances — their count and the rows of each are pinned — and the sets behind
+// them are listed by family only (iamf_hip_route_family_instances), in this order.  The only place that maps a set number
+// to a walker: iamf_route.hip builds and counts by it, and every key is in exactly one set (tests/route_host).
+constexpr int kRouteTables = 3;
+constexpr int kRouteSets = 6;
+template <class F>
+void for_each_instance_of_set(int set, F &&f) {
+  switch (set) {
+    case 0: for_each_render_instance(f); for_each_resample_instance(f); break;   // the base table: the resampler's kernels too
+    case 1: for_each_render_instance_ext(f); break;
+    case 2: for_each_render_instance_lpcm24(f); break;
+    case 3: for_each_render_instance_lpcm_coupled(f); break;
+    case 4: for_each_render_instance_lpcm_mix(f); break;
+    case 5: for_each_render_instance_interleaved(f); break;
+  }
+}
+
+// the row of the kernel launch() runs for a route, and the set that lists it: what iamf_hip_route_count takes (a FirSplit
+// call launches render_fast_kernel<2, 2> behind it as well: launch() counts that row too)
 struct RouteKey {
   int family, variant, m, c, k;
+  int set = 0;   // the base table, unless route_key says otherwise
 };
 inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
   switch (r.family) {
@@ -499,10 +521,10 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::Fast: return {IAMF_HIP_ROUTE_FAST, r.variant, m, p.out_ch, 0};
     case Family::Wide: return {IAMF_HIP_ROUTE_WIDE, r.variant, m, 0, 0};
     case Family::Generic: return {IAMF_HIP_ROUTE_GENERIC, 0, m, 0, 0};
-    case Family::Lpcm24: return {IAMF_HIP_ROUTE_LPCM24, r.variant, m, p.out_ch, 0};   // a row of table 2
-    case Family::LpcmCoupled: return {IAMF_HIP_ROUTE_LPCM_COUPLED, r.variant, m, p.out_ch, 0};   // a family listing's row
-    case Family::LpcmMix: return {IAMF_HIP_ROUTE_LPCM_MIX, 0, m, p.out_ch, r.variant};   // a family listing's row, k = LP2
-    case Family::FastInterleaved: return {IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, p.out_ch, 0};   // a family listing's row
+    case Family::Lpcm24: return {IAMF_HIP_ROUTE_LPCM24, r.variant, m, p.out_ch, 0, 2};   // a row of table 2
+    case Family::LpcmCoupled: return {IAMF_HIP_ROUTE_LPCM_COUPLED, r.variant, m, p.out_ch, 0, 3};   // a family listing's row
+    case Family::LpcmMix: return {IAMF_HIP_ROUTE_LPCM_MIX, 0, m, p.out_ch, r.variant, 4};   // a family listing's row, k = LP2
+    case Family::FastInterleaved: return {IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, p.out_ch, 0, 5};   // a family listing's row
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

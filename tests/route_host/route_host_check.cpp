@@ -77,6 +77,55 @@ void lpcm(RenderParams &p) {
 
 int g_failed = 0, g_cases = 0;
 
+// ---- the row sets behind the tally (for_each_instance_of_set; iamf_route.hip builds its tables from them) ----
+// iamf_hip_route_count(set, ..) goes straight to the set it is given and searches no other, so every key (family, variant,
+// m, c, k) must be in exactly one set and once within it, and route_key() must name that set (expect() asks for every route
+// of the table below).  The per-form checks beside this file assert it for their own form against the others only.
+struct ListedRow {
+  int set, family, variant, m, c, k;
+};
+constexpr int kListedCap = 4096;
+ListedRow g_listed[kListedCap];
+int g_n_listed = -1;
+int listed_rows() {
+  if (g_n_listed >= 0) return g_n_listed;
+  g_n_listed = 0;
+  for (int s = 0; s < kRouteSets; ++s)
+    for_each_instance_of_set(s, [&](int f, int v, int m, int c, int k) {
+      if (g_n_listed < kListedCap) g_listed[g_n_listed] = ListedRow{s, f, v, m, c, k};
+      ++g_n_listed;
+    });
+  return g_n_listed;
+}
+bool same_key(const ListedRow &a, int f, int v, int m, int c, int k) {
+  return a.family == f && a.variant == v && a.m == m && a.c == c && a.k == k;
+}
+// the set that lists the key; -1: none, -2: more than one row
+int set_listing(int f, int v, int m, int c, int k) {
+  int set = -1;
+  for (int i = 0; i < listed_rows() && i < kListedCap; ++i)
+    if (same_key(g_listed[i], f, v, m, c, k)) set = set == -1 ? g_listed[i].set : -2;
+  return set;
+}
+void set_checks() {
+  const int n = listed_rows();
+  int per_set[kRouteSets] = {0}, repeated = 0, outside = 0;
+  for (int i = 0; i < n && i < kListedCap; ++i) {
+    const ListedRow &r = g_listed[i];
+    ++per_set[r.set];
+    if (set_listing(r.family, r.variant, r.m, r.c, r.k) != r.set) ++repeated;
+  }
+  bool none_empty = true;
+  for (int s = 0; s < kRouteSets; ++s) none_empty = none_empty && per_set[s] > 0;
+  const int no_set[2] = {-1, kRouteSets};
+  for (int s : no_set) for_each_instance_of_set(s, [&](int, int, int, int, int) { ++outside; });
+  static_assert(kRouteTables == 3 && kRouteSets >= kRouteTables, "iamf_hip_route_tables() is pinned at three");
+  const bool ok = n > 0 && n <= kListedCap && none_empty && repeated == 0 && outside == 0;
+  printf("%-72s %d rows, %d repeated %s\n", "row sets: every key in exactly one set, once", n, repeated, ok ? "ok" : "WRONG");
+  ++g_cases;
+  g_failed += ok ? 0 : 1;
+}
+
 // env: one switch set to "1" for this case, or null
 void expect(const char *what, RenderParams p, int m, const char *env, Family family, int variant, int err = IAMF_HIP_OK) {
   if (env) setenv(env, "1", 1);
@@ -88,7 +137,9 @@ void expect(const char *what, RenderParams p, int m, const char *env, Family fam
   for_each_render_instance([&](int f, int v, int km, int kc, int kk) {
     listed = listed || (f == k.family && v == k.variant && km == k.m && kc == k.c && kk == k.k);
   });
-  const bool ok = r.family == family && r.variant == variant && r.err == err && listed;
+  // ... and counts in the set that lists it (iamf_hip_route_count goes by RouteKey::set alone)
+  const bool own_set = r.family == Family::Refused || set_listing(k.family, k.variant, k.m, k.c, k.k) == k.set;
+  const bool ok = r.family == family && r.variant == variant && r.err == err && listed && own_set;
   printf("%-72s %s/%d/%d %s\n", what, family_name(r.family), r.variant, r.err, ok ? "ok" : "WRONG");
   if (!ok) printf("    expected %s/%d/%d\n", family_name(family), variant, err);
   ++g_cases;
@@ -409,6 +460,7 @@ int main() {
                                   "IAMF_HIP_FIR_FUSED", "IAMF_HIP_LP_LATE"};
   for (const char *e : switches) unsetenv(e);
   list_checks();
+  set_checks();
   const int UNIMPL = IAMF_HIP_ERR_UNIMPLEMENTED;
 
   // ---- stereo ----
