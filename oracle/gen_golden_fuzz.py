@@ -5,7 +5,8 @@ container.  Every stream is decoded in a process of its own: a combination the r
 ("crash") and left out of the comparison instead of ending the run.
 
     python oracle/gen_golden_fuzz.py            # all seeds
-    python oracle/gen_golden_fuzz.py --one 17   # (internal) one stream -> a JSON line on stdout"""
+    python oracle/gen_golden_fuzz.py --one 17   # (internal) one stream -> a JSON line on stdout
+    python oracle/gen_golden_fuzz.py --stacks   # only tests/golden/fuzz_stacks.json: every layer stack (e2e_fuzz.stack_streams)"""
 import ctypes as C
 import json
 import os
@@ -78,7 +79,47 @@ def one_gmix(seed):
     return dict(handles=out)
 
 
+def one_stack(k):
+    ref = C.CDLL(os.path.join(HERE, *REF["default"]))
+    stream, c = F.build_stack(k)
+    try:
+        pcm, rets = decode_stream(ref, stream, c["layout"], **F.decode_kwargs(c))
+    except AssertionError as e:
+        return dict(error=str(e))
+    if not all(pcm[:, ch].any() for ch in range(pcm.shape[1])):   # a layer that did not reach its channels
+        return dict(error="silent output channel")
+    return dict(sha256=F.digest(pcm), shape=list(pcm.shape), rets=[int(r) for r in rets])
+
+
+def stacks():
+    """the 476 streams of e2e_fuzz.stack_streams(), each decoded in a process of its own; the reference must decode every
+    one of them (a stack it refused or died on would be a stack left out: nothing is written then)"""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def run(k):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--stack-one", str(k)], capture_output=True, text=True)
+        return dict(crash=r.returncode) if r.returncode else json.loads(r.stdout.strip().splitlines()[-1])
+    with ThreadPoolExecutor(8) as pool:
+        res = list(pool.map(run, range(F.N_STACK_STREAMS)))
+    out = {}
+    for k, (r, (i, li)) in enumerate(zip(res, F.stack_streams())):
+        c = F.stack_stream_case(k)
+        print("  fuzz stack %3d %-20s -> %-10s %s" % (k, c["scalable_layers1"], c["layout"], r.get("shape") or r))
+        out[str(k)] = r
+    bad = {k: v for k, v in out.items() if "sha256" not in v}
+    assert not bad, bad
+    with open(os.path.join(ROOT, "tests", "golden", "fuzz_stacks.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+    print("fuzz goldens (stacks) written:", len(out), "decoded, 0 refused, 0 crashed")
+
+
 def main():
+    if sys.argv[1:] == ["--stacks"]:
+        stacks()
+        return
+    if len(sys.argv) >= 3 and sys.argv[1] == "--stack-one":
+        print(json.dumps(one_stack(int(sys.argv[2]))))
+        return
     if len(sys.argv) >= 3 and sys.argv[1] == "--gmix":
         print(json.dumps(one_gmix(int(sys.argv[2]))))
         return

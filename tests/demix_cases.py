@@ -11,6 +11,7 @@ The table logic below restates, for TEST purposes, the reference's helpers:
   recon-gain flags -> channel order  IAMF_decoder.c:371-448
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -150,9 +151,11 @@ def recon_order(layout, flags):
 
 # ---- stage-level cases: what demixer_* of the reference is driven with ----
 # schedule entries: (mode or -1 = keep, recon gains (one per recon channel, k/255) or None = keep)
-def _sched(n_rec, seed):
+def _sched(n_rec, seed, rot=0):
+    """rot: the mode list rotated left by that many frames (the recon gains stay with their frames)"""
     rng = np.random.default_rng(seed)
     modes = [-1, 1, 2, 2, 4, 5, 6, 0, 0, 1]
+    modes = modes[rot % len(modes):] + modes[:rot % len(modes)]
     out = []
     for f, m in enumerate(modes):
         rg = None
@@ -162,14 +165,14 @@ def _sched(n_rec, seed):
     return out
 
 
-def make_case(layers, layer_gains=None, default=(1, 3), offset=0, fs=256, seed=700):
+def make_case(layers, layer_gains=None, default=(1, 3), offset=0, fs=256, seed=700, rot=0):
     layout = layers[-1]
     order, per_layer = channels_order(layers)
     flags = recon_flags(layers[0], layout) if len(layers) > 1 else 0
     rec = recon_order(layout, flags)
     return dict(layers=layers, layout=layout, order=order, per_layer=per_layer, flags=flags, recon=rec,
                 gains=output_gain_list(layers, layer_gains or {}), default=default, offset=offset, fs=fs,
-                seed=seed, schedule=_sched(len(rec), seed))
+                seed=seed, schedule=_sched(len(rec), seed, rot))
 
 
 STAGE_CASES = {
@@ -181,6 +184,158 @@ STAGE_CASES = {
     "312_512_712": make_case([8, 3, 6], {0: (0b110011, 1.1885022)}, default=(6, 2), offset=37, seed=750),
     "714_single": make_case([7], seed=760),
 }
+
+
+# ---- every layer stack the format allows ----
+# The nine layouts under  a < b  <=>  surround(a) <= surround(b), top(a) <= top(b), a != b ; a stack of layers is a
+# chain of that order (IAMF_decoder.c:450-531 derives each layer's new channels from exactly these two counts).
+_STACK_COUNTS = [9, 31, 54, 51, 25, 5]
+
+
+@functools.lru_cache(maxsize=None)
+def _all_stacks():
+    below = lambda a, b: a != b and SURROUND[a] <= SURROUND[b] and TOP[a] <= TOP[b]
+    chains, grow = [], [[a] for a in range(9)]
+    while grow:
+        chains += grow
+        grow = [c + [b] for c in grow for b in range(9) if below(c[-1], b)]
+    chains.sort(key=lambda c: (len(c), c))   # shortest first, each length in lexicographic order of the layout numbers
+    assert [sum(len(c) == n for c in chains) for n in range(1, 7)] == _STACK_COUNTS and len(chains) == 175
+    return tuple(tuple(c) for c in chains)
+
+
+def all_stacks():
+    """the 175 chains, shortest first, each length in lexicographic order of the layout numbers"""
+    return [list(c) for c in _all_stacks()]
+
+
+def step_mask(layout, order):
+    """which of the six de-mix steps reconstruct the target layout from the decoded channels `order`: bit 0 S1to2, 1 S2to3,
+    2 S3to5, 3 S5to7, 4 TF2toT2, 5 T2toT4 (demixer.c:126-424: a step runs when the channel it produces is asked for and
+    is not there yet, and asks for its own inputs in turn).  Restates the planner of iamf_hip_batch_set_demixer."""
+    have, steps = set(order), [0]
+
+    def need(*names):
+        assert all(CH[n] in have for n in names), (layout, order, names)
+
+    def step(bit, *made):
+        steps[0] |= bit
+        have.update(CH[n] for n in made)
+
+    def s2():
+        need("L2")
+        if CH["R2"] not in have:
+            need("MONO"), step(1, "R2")
+
+    def s3():
+        if CH["R3"] not in have:
+            s2(), need("C"), step(2, "L3", "R3")
+
+    def s5():
+        if CH["SR5"] not in have:
+            s3(), need("L5", "R5"), step(4, "SL5", "SR5")
+
+    def s7():
+        if CH["BR7"] not in have:
+            s5(), need("SL7", "SR7"), step(8, "BL7", "BR7")
+
+    def h2():
+        if CH["HR"] not in have:
+            need("TL", "TR"), s5(), step(16, "HL", "HR")
+
+    def h4():
+        if CH["HBR"] not in have:
+            h2(), need("HFL", "HFR"), step(32, "HBL", "HBR")
+
+    by_channel = {CH["R2"]: s2, CH["L3"]: s3, CH["R3"]: s3, CH["SL5"]: s5, CH["SR5"]: s5, CH["BL7"]: s7, CH["BR7"]: s7,
+                  CH["HL"]: h2, CH["HR"]: h2, CH["HBL"]: h4, CH["HBR"]: h4}
+    for ch in PLAYBACK[layout]:
+        if ch not in have:
+            by_channel[ch]()
+        assert ch in have, (layout, order, ch)
+    return steps[0]
+
+
+# at fs 256 the cross-fade is 16 long: 240 and 250 leave no room for it; aligned and unaligned offsets take turns
+STACK_OFFSETS = [0, 37, 4, 240, 8, 250]
+STACK_MODES = [0, 1, 2, 4, 5, 6]
+STACK_GAINS_Q78 = [-768, 768, -1536, 384, -512, 256, -256, 1152]   # dB in Q7.8, as an output-gain field carries them
+
+
+def q78_linear(q):
+    """db2lin of a Q7.8 gain the way the decoder computes it (IAMF_utils.c: powf(10, dB / 20) in float)"""
+    return float(np.float32(10.0) ** (np.float32(q / 256.0) / np.float32(20.0)))
+
+
+def _gained_channels(layers, layer_gains, order):
+    return [ch for ch, _ in output_gain_list(layers, layer_gains) if ch in order]
+
+
+def stack_gains(i, layers=None):
+    """{layer: (flag mask, Q7.8 gain)} of stack i: one gained layer, two for stacks of three layers or more; layers, masks
+    and gains rotate with i.  A layer is taken from those with a flag that names a decoded channel not gained yet (any
+    layer if there is none: 7.1 on its own has no such flag), and its mask is stepped on from a start that rotates with i
+    until no DECODED channel is gained twice and, where possible, one more is gained.  Six flags a layer: at most 12
+    entries in the gain list."""
+    layers = layers or all_stacks()[i]
+    order, _ = channels_order(layers)
+    out = {}
+
+    def masks(li, q):
+        """(masks of layer li that gain no decoded channel twice, those of them that gain one more)"""
+        have = len(_gained_channels(layers, out, order))
+        ok, more = [], []
+        for step in range(63):
+            mask = (11 * i + 29 * len(out) + step) % 63 + 1
+            got = _gained_channels(layers, {**out, li: (mask, q)}, order)
+            if len(got) == len(set(got)):
+                ok.append(mask)
+                if len(got) > have:
+                    more.append(mask)
+        return ok, more
+
+    for k in range(1 if len(layers) < 3 else 2):
+        q = STACK_GAINS_Q78[(i + 3 * k) % len(STACK_GAINS_Q78)]
+        free = [li for li in range(len(layers)) if li not in out]
+        pool = [li for li in free if masks(li, q)[1]] or free
+        li = pool[(i // (k + 1)) % len(pool)]
+        ok, more = masks(li, q)
+        out[li] = ((more or ok)[0], q)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _stack_classes():
+    """{(target layout, step mask): [stack ids]}"""
+    out = {}
+    for i, st in enumerate(all_stacks()):
+        out.setdefault((st[-1], step_mask(st[-1], channels_order(st)[0])), []).append(i)
+    return out
+
+
+def stack_case(i, fs=256, offset=None):
+    """make_case of stack i of all_stacks() (fs, offset: another frame geometry); everything else rotates with i: the
+    default demixing mode (i % 6) and weight (i % 11), the mode schedule (rotated left by i), the output gains
+    (stack_gains) and the frame offset, which steps through STACK_OFFSETS along the stacks of one (target layout, step
+    mask) class, so that every class meets offset 0 and, where it has the members, the others in turn."""
+    layers = all_stacks()[i]
+    cls = next(v for v in _stack_classes().values() if i in v)
+    gains = stack_gains(i, layers)
+    c = make_case(layers, {li: (m, q78_linear(q)) for li, (m, q) in gains.items()},
+                  default=(STACK_MODES[i % 6], i % 11), offset=STACK_OFFSETS[cls.index(i) % 6] if offset is None else offset,
+                  fs=fs, seed=2000 + i, rot=i)
+    c["layer_gains_q78"] = gains
+    c["steps"] = step_mask(c["layout"], c["order"])
+    gained = [ch for ch, _ in c["gains"] if ch in c["order"]]
+    assert len(c["gains"]) <= 12, (i, c["gains"])                      # the reference's gain arrays hold 12
+    assert len(gained) == len(set(gained)), (i, c["gains"])            # no decoded channel gained twice
+    return c
+
+
+def stack_tables(c):
+    """the tables a stack case derives from its layers, as tests/golden/demix_stacks.json stores them"""
+    return dict(layers=list(c["layers"]), order=list(c["order"]), recon=list(c["recon"]), flags=c["flags"],
+                gains=[[ch, g] for ch, g in c["gains"]], default=list(c["default"]), offset=c["offset"])
 
 
 def case_input(c):

@@ -386,6 +386,52 @@ def build(seed, variant="default"):
         del E.CASES[name]
 
 
+# Every layer stack the format allows (demix_cases.all_stacks: 175) as a scalable element of its own, decoded into the
+# layout of its top layer (175 streams), of its first layer (stacks of two layers or more) and of its middle layer (three or
+# more): 476 streams between them.  The facade restates the reference's layer tables (new channels of a layer, output-gain
+# channels, recon-gain flags and order, the choice of the layer to decode up to): this is every row of them.
+STACK_LAYOUTS = {0: ("ss", 12), 1: ("ss", 0), 2: ("ss", 1), 3: ("ss", 2), 4: ("ss", 3), 5: ("ss", 8), 6: ("ss", 10), 7: ("ss", 9),
+                 8: ("ss", 11)}   # IAChannelLayoutType -> the sound system with its channels
+
+
+def stack_streams():
+    """[(stack id, index of the layer whose layout is asked for)]: top layers first, then first layers, then middle ones"""
+    import demix_cases as D
+    st = D.all_stacks()
+    out = [(i, len(s) - 1) for i, s in enumerate(st)]
+    out += [(i, 0) for i, s in enumerate(st) if len(s) >= 2]
+    out += [(i, len(s) // 2) for i, s in enumerate(st) if len(s) >= 3]
+    assert len(out) == 476 and len(st) == 175
+    return out
+
+
+N_STACK_STREAMS = 476
+
+
+def stack_stream_case(k):
+    """stream k of stack_streams(): 4 frames of 1024, 16 bit; output gains, demixing default and the per-frame modes rotate
+    with the stack as in demix_cases.stack_case"""
+    import demix_cases as D
+    i, li = stack_streams()[k]
+    layers = D.all_stacks()[i]
+    modes = [1, 1, 2, 4, 5, 6, 0, 2]
+    c = dict(layout=STACK_LAYOUTS[layers[li]], bit_depth=16, frames=4, fs=1024, seed=930000 + 7 * i, sample_size=16,
+             pair=("scalable",), scalable_layers1=layers, scalable_gains1=D.stack_gains(i, layers),
+             dmx_default1=(D.STACK_MODES[i % 6], i % 11), scalable_modes1=[modes[(i + f) % 8] for f in range(4)],
+             stack=i, stack_layer=li)
+    assert not reference_gain_list_overflows(c), (k, c)
+    return c
+
+
+def build_stack(k):
+    name = "fuzz_stack_%d" % k
+    E.CASES[name] = stack_stream_case(k)
+    try:
+        return E.build(name)[0], E.CASES[name]
+    finally:
+        del E.CASES[name]
+
+
 def reference_h_slot_23_is_stale(c, layouts):
     """slot 23 of Sound System H from a scene-based element behind a resampler is stale frame-buffer content in the reference
     (render_H2M never writes it for H; see case()): case() keeps that combination out of the sets, a run-time layout SWITCH to

@@ -417,6 +417,69 @@ def demix_frames(A, c, ns):
     return frames
 
 
+def demix_render(A, c, mx, out_ch, x, calls):
+    """x [S][F][ch][fs] decoded channels -> demixer -> mx -> limiter -> s16; one render_ex per entry of `calls`, then
+    the flush.  Returns [S][n][out_ch].  An entry of `calls` is
+      nf               that many whole frames;
+      (s0, n)          ONE frame whose first s0 samples were trimmed away before the call and of which n are rendered, given
+                       the way the decoder facade's render_tu gives it (include/iamf_hip.h, iamf_hip_render_args): every
+                       channel row starts at the first KEPT sample (rows stay frame_size apart; what lies behind the n
+                       samples is NaN here, nothing may read it), the record is the frame's own, n_frames = 1,
+                       demix_sample0 = s0, n_samples = n (0 for a whole frame);
+      ("refuse", s0, n)  the same call on the next frame, which must be refused with IAMF_HIP_ERR_BAD_ARG: it consumes no
+                       frame and emits nothing."""
+    import torch
+    S, F, ch, fs = x.shape
+    b = A.Batch(S, mx, out_ch, frame_size=fs, out_format=A.FMT_S16, limiter=True)
+    b.set_demixer(c["layout"], c["order"], c["gains"], c["offset"])
+    frames = demix_frames(A, c, S)
+    xin = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+    outs = [[] for _ in range(S)]
+    f0 = 0
+    for call in list(calls) + [0]:
+        refuse = isinstance(call, tuple) and call[0] == "refuse"
+        s0, n = (call[-2], call[-1]) if isinstance(call, tuple) else (0, 0)
+        nf = 1 if isinstance(call, tuple) else call
+        cap = max(nf * fs, 240) * out_ch * 2
+        pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
+        if nf:
+            # the records of this call's frames, [S][nf]
+            raw = np.frombuffer(bytes(frames), dtype=np.uint8).reshape(S, F, -1)[:, f0:f0 + nf].copy()
+            d_fr = torch.from_numpy(raw).cuda()
+            a = A.RenderArgs()
+            a.d_in, a.in_stream_stride, a.in_frame_stride = xin.data_ptr() + 4 * f0 * ch * fs, F * ch * fs, ch * fs
+            if isinstance(call, tuple):
+                cut = np.full((S, ch, fs), np.nan, dtype=np.float32)
+                keep = x[:, f0, :, max(s0, 0):max(s0, 0) + n]
+                cut[:, :, :keep.shape[2]] = keep
+                d_cut = torch.from_numpy(cut).cuda()
+                a.d_in, a.in_stream_stride = d_cut.data_ptr(), ch * fs
+                a.demix_sample0, a.n_samples = s0, (n if n < fs else 0)
+            a.n_frames, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, pcm.data_ptr(), cap, st
+            a.d_demix_frames = d_fr.data_ptr()
+            if refuse:
+                try:
+                    b.render_ex(a)
+                except A.IamfHipError as e:
+                    assert e.code == -1, e   # IAMF_HIP_ERR_BAD_ARG
+                else:
+                    raise AssertionError("demix_sample0 %d with %d samples of %d was not refused" % (s0, n, fs))
+                torch.cuda.synchronize()
+                assert not pcm.cpu().numpy().any()
+                continue
+            n = b.render_ex(a)
+        else:
+            n = b.flush(pcm.data_ptr(), cap, st)
+        torch.cuda.synchronize()
+        h = pcm.cpu().numpy()
+        for s in range(S):
+            outs[s].append(h[s][:n * out_ch * 2].view(np.int16).reshape(n, out_ch).copy())
+        f0 += nf
+    b.close()
+    return [np.concatenate(o, axis=0) for o in outs]
+
+
 def run_demix(c):
     """scalable channel audio: the demixer in front of the projection (render_wide4_kernel<.., DMX>); kw: m, oc, calls, layout"""
     import torch

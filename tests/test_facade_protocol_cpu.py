@@ -136,3 +136,38 @@ def test_every_e2e_stream_configures_and_returns_the_reference_counts_without_a_
                               limiter=case.get("limiter", True), threshold=case.get("threshold", -1.0))
     assert list(rets) == list(golden.npz("e2e")[name + "_rets"]), name
     assert pcm.shape == golden.npz("e2e")[name].shape
+
+
+def test_the_stack_goldens_hold_a_decode_of_every_stream():
+    import json
+    import e2e_fuzz as F
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "fuzz_stacks.json")))
+    assert sorted(gold, key=int) == [str(k) for k in range(476)] and F.N_STACK_STREAMS == 476 == len(F.stack_streams())
+    assert all(set(v) == {"sha256", "shape", "rets"} for v in gold.values())   # no "error", no "crash": nothing left out
+    import demix_cases as D
+    tops = sum(li == len(D.all_stacks()[i]) - 1 for i, li in F.stack_streams())
+    assert (tops, len(F.stack_streams()) - tops) == (175, 301)   # every stack into its top layout; first and middle layers
+    # the GPU test runs them in nine groups, by output layout: every stream is in one
+    per_out = [sum(F.stack_stream_case(k)["layout"] == F.STACK_LAYOUTS[o] for k in range(476)) for o in range(9)]
+    assert per_out == [88, 52, 41, 58, 39, 27, 51, 88, 32] and sum(per_out) == 476
+
+
+@pytest.fixture(scope="module")
+def stack_gold():
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "fuzz_stacks.json")))
+
+
+@pytest.mark.parametrize("k", range(476))
+def test_every_layer_stack_configures_and_returns_the_reference_counts_without_a_gpu(stub_lib, stack_gold, k):
+    """the 476 streams of e2e_fuzz.stack_streams() — every layer stack into the layout of its top, first and middle layer —
+    through the facade's host side with the device replaced by stand-ins: IAMF_decoder_configure accepts each (layer tables,
+    the layer to decode up to, the demixer's plan of that layer's channels) and every decode call returns the count the
+    reference returned (tests/golden/fuzz_stacks.json)"""
+    import e2e_fuzz as F
+    from decoder_driver import decode_stream
+    stream, c = F.build_stack(k)
+    pcm, rets = decode_stream(stub_lib, stream, c["layout"], **F.decode_kwargs(c))
+    want = stack_gold[str(k)]
+    assert [int(r) for r in rets] == want["rets"], (k, c["scalable_layers1"], c["layout"])
+    assert list(pcm.shape) == want["shape"], (k, c["scalable_layers1"], c["layout"])

@@ -190,7 +190,8 @@ def test_random_demixer_configuration_matches_oracle(hip, seed):
     partitions: decoded layers -> demixer -> layout matrix -> limiter -> s16 (wide4 demixer variant
     where it applies, else the generic kernel) against the oracle demixer + renderer chain"""
     import demix_cases as D
-    from test_gpu_wide4 import _demix_render, _LAYOUT_SS
+    from route_cases import demix_render as _demix_render
+    from test_gpu_wide4 import _LAYOUT_SS
     A, G = hip
     rng = np.random.default_rng(5000 + seed)
     layers = _DEMIX_STACKS[int(rng.integers(len(_DEMIX_STACKS)))]

@@ -48,6 +48,34 @@ def test_random_stream_through_a_group_of_handles(lib, seed):
         assert F.digest(pcm) == want["sha256"], (seed, i)
 
 
+GOLD_ST = json.load(open(os.path.join(_G, "fuzz_stacks.json")))
+
+
+_STACK_OUT = ["mono", "stereo", "5.1", "5.1.2", "5.1.4", "7.1", "7.1.2", "7.1.4", "3.1.2"]   # IAChannelLayoutType 0..8
+
+
+@pytest.mark.parametrize("out", range(9), ids=lambda t: _STACK_OUT[t])
+def test_every_layer_stack_matches_the_reference_decoder(lib, out):
+    """every layer stack the format allows (the 175 chains of the nine loudspeaker layouts, e2e_fuzz.stack_streams) as a
+    scalable element, decoded into the layout of its top layer, of its first layer and of its middle layer — 476 streams,
+    the facade's layer tables row by row (new channels of a layer, output-gain channels, recon-gain flags and order, the
+    layer to decode up to): PCM digest and per-call return values are the reference's (tests/golden/fuzz_stacks.json, which
+    holds a decode of every one of them: the reference refused none).  One test per OUTPUT layout (88 + 52 + 41 + 58 + 39
+    + 27 + 51 + 88 + 32 streams; a stream takes some 10 ms); the failure message names every stream of the group that differs."""
+    ks = [k for k in range(F.N_STACK_STREAMS) if F.stack_stream_case(k)["layout"] == F.STACK_LAYOUTS[out]]
+    failed = []
+    for k in ks:
+        want = GOLD_ST[str(k)]
+        assert "sha256" in want, want
+        stream, c = F.build_stack(k)
+        pcm, rets = decode_stream(lib, stream, c["layout"], **F.decode_kwargs(c))
+        got = dict(rets=[int(r) for r in rets], shape=list(pcm.shape), sha256=F.digest(pcm))
+        bad = [f for f in ("rets", "shape", "sha256") if got[f] != want[f]]
+        if bad:
+            failed.append((k, c["scalable_layers1"], c["scalable_gains1"], c["dmx_default1"], bad))
+    assert ks and not failed, "%d of %d streams differ: %s" % (len(failed), len(ks), failed)
+
+
 class _Variant:
     """the decoder library with every handle it opens switched to one of the reference's other builds"""
 

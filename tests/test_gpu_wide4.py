@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import route_cases as R
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -117,61 +118,6 @@ def test_wide4_short_last_chunk(hip, fs, calls):
 
 
 # ---- scalable channel audio: the demixer in front of the projection (render_wide4_kernel<.., DMX>) ----
-def _demix_frames(A, c, S):
-    import ctypes as C
-    F = len(c["schedule"])
-    frames = (A.DemixFrame * (S * F))()
-    st = A.DemixState()
-    rec = (C.c_int32 * 12)(*c["recon"])
-    for s in range(S):
-        A.lib().iamf_hip_demix_state_init(C.byref(st))
-        A.lib().iamf_hip_demix_set_info(C.byref(st), c["default"][0], c["default"][1])
-        cur = [1.0] * len(c["recon"])
-        for f, (mode, rg) in enumerate(c["schedule"]):
-            if rg is not None:
-                cur = rg
-            if mode > -1:
-                A.lib().iamf_hip_demix_set_info(C.byref(st), mode, -1)
-            A.lib().iamf_hip_demix_frame_fill(C.byref(st), len(cur), rec, (C.c_float * 12)(*cur),
-                                              C.byref(frames[s * F + f]))
-    return frames
-
-
-def _demix_render(A, c, mx, out_ch, x, calls):
-    """x [S][F][ch][fs] decoded channels -> demixer -> mx -> limiter -> s16; one render_ex per entry of
-    `calls` (frames), then the flush.  Returns [S][n][out_ch]."""
-    import torch
-    S, F, ch, fs = x.shape
-    b = A.Batch(S, mx, out_ch, frame_size=fs, out_format=A.FMT_S16, limiter=True)
-    b.set_demixer(c["layout"], c["order"], c["gains"], c["offset"])
-    frames = _demix_frames(A, c, S)
-    xin = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    st = torch.cuda.current_stream().cuda_stream
-    outs = [[] for _ in range(S)]
-    f0 = 0
-    for nf in calls + [0]:
-        cap = max(nf * fs, 240) * out_ch * 2
-        pcm = torch.zeros((S, cap), dtype=torch.uint8, device="cuda")
-        if nf:
-            # the records of this call's frames, [S][nf]
-            raw = np.frombuffer(bytes(frames), dtype=np.uint8).reshape(S, F, -1)[:, f0:f0 + nf].copy()
-            d_fr = torch.from_numpy(raw).cuda()
-            a = A.RenderArgs()
-            a.d_in, a.in_stream_stride, a.in_frame_stride = xin.data_ptr() + 4 * f0 * ch * fs, F * ch * fs, ch * fs
-            a.n_frames, a.d_pcm, a.pcm_stream_stride_bytes, a.stream = nf, pcm.data_ptr(), cap, st
-            a.d_demix_frames = d_fr.data_ptr()
-            n = b.render_ex(a)
-        else:
-            n = b.flush(pcm.data_ptr(), cap, st)
-        torch.cuda.synchronize()
-        h = pcm.cpu().numpy()
-        for s in range(S):
-            outs[s].append(h[s][:n * out_ch * 2].view(np.int16).reshape(n, out_ch).copy())
-        f0 += nf
-    b.close()
-    return [np.concatenate(o, axis=0) for o in outs]
-
-
 def _demix_cases():
     import demix_cases as D
     cases = dict(D.STAGE_CASES)  # 256-sample frames: four frame records per 1024-sample chunk
@@ -210,9 +156,9 @@ def test_wide4_demixer_exact(hip, name, monkeypatch):
             except KeyError:
                 continue
             och = A.layout_channels(A.SS[out])
-        got = _demix_render(A, c, mx, och, x, calls)
+        got = R.demix_render(A, c, mx, och, x, calls)
         monkeypatch.setenv("IAMF_HIP_NO_WIDE4", "1")
-        ref = _demix_render(A, c, mx, och, x, calls)
+        ref = R.demix_render(A, c, mx, och, x, calls)
         monkeypatch.delenv("IAMF_HIP_NO_WIDE4")
         for s in range(S):
             xd = np.ascontiguousarray(dem[s].transpose(1, 0, 2).reshape(ch, F * fs))

@@ -107,6 +107,37 @@ def test_demixer_bit_exact(golden):
         assert np.array_equal(got.view(np.uint32), gold[name].view(np.uint32)), name
 
 
+def test_demixer_every_stack_bit_exact():
+    """every layer stack the format allows — the 175 chains of the nine layouts under (surround, top) <=, 46 classes of
+    (target layout, de-mix step mask) — with gains, defaults, offsets and schedules that rotate with the stack
+    (demix_cases.stack_case): the oracle's output has the digest the real demixer_* left in tests/golden/demix_stacks.json
+    (oracle/gen_golden_extra.py --demix-stacks), and the case's derived tables are the ones it was driven with"""
+    import hashlib
+    import json
+    import os
+
+    import demix_cases as D
+    gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "demix_stacks.json")))
+    stacks = D.all_stacks()
+    assert len(stacks) == 175 and sorted(gold, key=int) == [str(i) for i in range(175)]
+    assert [sum(len(s) == n for s in stacks) for n in range(1, 7)] == [9, 31, 54, 51, 25, 5]
+    cases = [D.stack_case(i) for i in range(175)]
+    assert len({(c["layout"], c["steps"]) for c in cases}) == 46
+    # what the 175 cases cover between them
+    assert {c["default"][0] for c in cases} == {0, 1, 2, 4, 5, 6} and {c["default"][1] for c in cases} == set(range(11))
+    assert {c["offset"] for c in cases} == {0, 4, 8, 37, 240, 250}
+    assert all(len(c["layer_gains_q78"]) == (2 if len(c["layers"]) >= 3 else 1) for c in cases)
+    bad = []
+    for i, c in enumerate(cases):
+        want = dict(gold[str(i)])
+        sha = want.pop("sha256")
+        assert D.stack_tables(c) == want, (i, c["layers"])
+        got = D.drive_demixer(O.lib(), "orc_demixer_", c, D.case_input(c))
+        if hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest() != sha:
+            bad.append((i, c["layers"]))
+    assert not bad, bad
+
+
 def test_downmix_invalid_pairs_refused(golden):
     for a, b in golden.manifest["dmx/_invalid"]:
         assert not O.Downmixer(a, b).ok(), (a, b)
