@@ -398,6 +398,7 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
       launched = p.lpcm_coupled ? iamf_hip_fast_lpcm_mix_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_lpcm_mix_launch(&p, m, r.variant, st);
       break;
     case Family::FastInterleaved: launched = iamf_hip_fast_interleaved_launch(&p, m, st); break;
+    case Family::FastRagged: launched = iamf_hip_fast_ragged_launch(&p, m, st); break;
     case Family::FirSplit: {
       const int e = launch_fir_split(p, m, grid, st);
       if (e != IAMF_HIP_OK) return e;
@@ -515,8 +516,9 @@ struct PreparedCall {
 
 // lp2 (with lp, iamf_hip_batch_render_lpcm_mix): the second element as packets too; a.d_in2 is then a non-null placeholder.
 // il (iamf_hip_batch_render_interleaved): the call may take the interleaved form of the fast kernel; everything else as without.
+// rag (iamf_hip_batch_render_ragged): the call may take the planar ragged form; everything else as without.
 int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc,
-                   const LpcmIn *lp2 = nullptr, bool il = false) {
+                   const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
   if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || !b->lp_scale_ok || getenv("IAMF_HIP_LPCM_UNFUSED")))
     return kNotFused;
@@ -698,6 +700,8 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   }
   // the interleaved form packs into the caller's buffer itself and knows no LFE slot; pick_route has the call's other rules
   p.interleaved = (il && !restride && !b->lfe && interleaved_fused(cnt)) ? 1 : 0;
+  // so does the planar ragged form (an LFE slot: pick_route sees p.lfe)
+  p.ragged = (rag && !restride && ragged_fused(cnt)) ? 1 : 0;
   pc.a = a;
   pc.m_eff = m_eff;
   pc.lds = lds;
@@ -746,11 +750,11 @@ int render_finish(iamf_hip_batch *b, const PreparedCall &pc) {
   return r != IAMF_HIP_OK ? r : render_commit(b, pc);
 }
 
-// the whole call (lp, lp2, il: as render_prepare, whose kNotFused comes back before anything is changed or launched)
+// the whole call (lp, lp2, il, rag: as render_prepare, whose kNotFused comes back before anything is changed or launched)
 int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr,
-                const LpcmIn *lp2 = nullptr, bool il = false) {
+                const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false) {
   PreparedCall pc;
-  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il);
+  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il, rag);
   return r != IAMF_HIP_OK ? r : render_finish(b, pc);
 }
 
@@ -1331,6 +1335,17 @@ int iamf_hip_batch_render_interleaved(iamf_hip_batch *b, const iamf_hip_interlea
   const int rc = range_args_check(b, &call->args, stream0, n_streams, &total);
   if (rc != IAMF_HIP_OK || total == 0) return rc;
   return render_call(b, call->args, (int)total, stream0, n_streams, nullptr, nullptr, true);
+}
+
+// Planar f32 of any call length (include/iamf_hip.h): iamf_hip_batch_render_range with leave to take
+// render_fast_kernel<.., IL = false, RAG> (Family::FastRagged) where pick_route's rules hold.  The same checks in the same
+// order, the same internal route (render_call) for everything else.
+int iamf_hip_batch_render_ragged(iamf_hip_batch *b, const iamf_hip_ragged_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  int64_t total = 0;
+  const int rc = range_args_check(b, &call->args, stream0, n_streams, &total);
+  if (rc != IAMF_HIP_OK || total == 0) return rc;
+  return render_call(b, call->args, (int)total, stream0, n_streams, nullptr, nullptr, false, true);
 }
 
 int iamf_hip_batch_render_ex(iamf_hip_batch *b, const iamf_hip_render_args *a) {

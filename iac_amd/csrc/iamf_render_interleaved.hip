@@ -16,5 +16,5 @@ int iamf_hip_fast_interleaved_launch(const void *params, int m, hipStream_t st) 
   RenderParams p;
   memcpy(&p, params, sizeof(p));
   if (!p.interleaved || !p.in || p.frame_size != 1 || p.in_frame_stride != m) return 0;
-  return launch_fast_interleaved<InterleavedM, InterleavedOC>(p, m, st);
+  return launch_fast_rag<InterleavedM, InterleavedOC, true>(p, m, st);
 }

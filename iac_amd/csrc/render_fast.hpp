@@ -250,6 +250,12 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       enter the ring as zeros (behind everything that is persisted), never count as a hit, and the limiter's recurrence,
 //       the step count and the PCM stores end with sample cnt - 1; the ring position behind the call is then no multiple of
 //       16, which only the persisting code sees (the next call places its own ring).
+//       Without IL (iamf_hip_batch_render_ragged, iamf_render_ragged.hip): the plain planar f32 form.  Nothing ends the
+//       buffer resource with the call there, so the last quad of a call with total & 3 != 0 loads the floats that lie behind
+//       n_samples in the frame's row — whatever the decoder left, NaN and Inf included — and the lanes behind it the stream's
+//       first samples.  Both are replaced by zeros by a SELECT on the rendered quad, in front of the maxima: nothing loaded
+//       for an absent sample reaches a reduction over lanes, the ring, the vote or the PCM.  The loads themselves stay inside
+//       the frames' rows: the host only sends calls whose frame size is a multiple of 4 (pick_route, ragged_shape_ok).
 template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2, bool LPC = false,
           int LP2 = 0, bool IL = false, bool RAG = false>
 __global__ __launch_bounds__(FIR == 1 ? 512 : 256, LP2 ? lpcm_mix_wgs(M, OC, LP2) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
@@ -261,7 +267,7 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
   static_assert(!LPC || (LP && LPB == 2 && lpcm_coupled_m(M)), "coupled pairs: 16-bit packets of a loudspeaker layout");
   static_assert(!IL || (!FIR && !DOWN && !IN2 && !LP && EARLY && M <= 2), "interleaved f32 feeds the plain matrix variant, one or two channels");
-  static_assert(!RAG || IL, "ragged calls: the interleaved form");
+  static_assert(!RAG || IL || (!FIR && !DOWN && !IN2 && !LP && EARLY), "ragged calls: the interleaved form, or the plain planar f32 one");
   constexpr bool LP3 = LP && LPB == 3;
   extern __shared__ float lds[];
   constexpr int R = kFRing;

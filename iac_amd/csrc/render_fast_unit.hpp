@@ -1,5 +1,6 @@
 // render_fast_unit.hpp — what the translation units that feed render_fast_kernel (render_fast.hpp) another input form share:
-// iamf_render_lpcm.hip, _lpcm24.hip, _lpcm_coupled.hip, _lpcm_mix.hip, _lpcm_mix_coupled.hip and iamf_render_interleaved.hip.
+// iamf_render_lpcm.hip, _lpcm24.hip, _lpcm_coupled.hip, _lpcm_mix.hip, _lpcm_mix_coupled.hip, iamf_render_interleaved.hip and
+// iamf_render_ragged.hip.
 // The units stay separate, so that they compile side by side; each includes this header at file scope and nothing else, and
 // holds its head comment and its entry of render_entry.hpp: the parameter sanity test and one call of a launcher below, in
 // which the form's template arguments are written once.  A launcher dispatches over the lists it is given, which are the
@@ -58,16 +59,17 @@ bool launch_fast_lp_mix(const RenderMixParams &p, int m, int lp2, hipStream_t st
   });
 }
 
-// Interleaved f32 of any call length: render_fast_kernel<M, OC, 0, false, false, false, true, 2, false, 0, IL = true, RAG = true>
-template <class MList, class OCList>
-bool launch_fast_interleaved(const RenderParams &p, int m, hipStream_t st) {
+// f32 of any call length: render_fast_kernel<M, OC, 0, false, false, false, true, 2, false, 0, IL, RAG = true>.  IL: ordinary
+// interleaved sample-frames (iamf_render_interleaved.hip); else planar rows (iamf_render_ragged.hip)
+template <class MList, class OCList, bool IL>
+bool launch_fast_rag(const RenderParams &p, int m, hipStream_t st) {
   return dispatch(MList{}, m, [&](auto M) {
     return dispatch(OCList{}, p.out_ch, [&](auto OC) {
       constexpr int m_ = decltype(M)::value, oc_ = decltype(OC)::value;
       constexpr size_t lds = sizeof(float) * (size_t)fast_lds_floats(oc_, m_);
       // built for the four workgroups per CU of the planar f32 form <M, OC> (render_fast_kernel's launch bounds)
       static_assert(lds * 4 <= 160 * 1024, "the workgroups the instance is built for fit a CU's LDS");
-      launch_big_lds<&render_fast_kernel<m_, oc_, 0, false, false, false, true, 2, false, 0, true, true>, 80 * 1024>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
+      launch_big_lds<&render_fast_kernel<m_, oc_, 0, false, false, false, true, 2, false, 0, IL, true>, 80 * 1024>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
     });
   });
 }

@@ -103,6 +103,10 @@ struct RenderParams {
   int32_t og_ch;            // output channels the OUTPUT gain multiplies (iamf_hip_batch_config::out_gain_channels; = out_ch: all)
   int32_t lfe_k0;           // the generator's output of the call's first sample sits at index lfe_k0 (trimmed frames: the
                             // filter also ran over the lfe_k0 samples cut off in front, iamf_hip_render_args)
+  int32_t ragged;           // 1: the call came through iamf_hip_batch_render_ragged and, where it is no whole number of 64-sample
+                            // blocks, may take render_fast_kernel<.., IL = false, RAG = true> (pick_route: Family::FastRagged); 0:
+                            // every rule as it stood.  Host only, and kept HERE, in the 4 bytes of padding in front of the
+                            // double, like lpcm_bytes: the block keeps its size and every other field its offset
   double lfe_div;           // sqrt(n) of h2m_rdr.c:1162; 0 = the `* 0.5` form (n <= 2)
   int32_t lfe_mask;         // bit c: output slot c is an LFE slot (src_feed[c] == -2), for render_wide4.hpp
   // ---- HRTF FIR renderer (render_fast_kernel<M, 2, true>): matrix = h[2][M][fir_taps] ----

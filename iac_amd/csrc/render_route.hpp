@@ -69,6 +69,10 @@ IAMF_HD constexpr int lpcm_mix_wgs(int m, int oc, int lp2) {
 // behind the resampler, mono or stereo in and out
 using InterleavedM = Ints<1, 2>;
 using InterleavedOC = Ints<1, 2>;
+// render_fast_kernel<.., IL = false, RAG = true>: planar f32 of any call length (iamf_hip_batch_render_ragged) — the element
+// shapes LPCM streams take, LpcmM and LpcmCoupledM together (a live service renders what it decodes, frame by frame)
+using RaggedM = Ints<1, 2, 4, 6, 8, 9, 10, 12, 16>;
+using RaggedOC = Ints<1, 2>;
 // render_fanout_kernel<M, K, LP>: the fan-out fed with LPCM packets.  M: what LpcmM and FanM share (mono-coded ambisonics
 // elements are the only ones whose channels are contiguous 16-bit runs), K within FanK
 using FanLpM = Ints<4, 9, 16>;
@@ -171,6 +175,29 @@ inline bool interleaved_shape_ok(const RenderParams &p, int m, bool force_generi
   return true;
 }
 
+// What the planar ragged form of the fast kernel (render_fast.hpp, RAG without IL) needs of a call that came through
+// iamf_hip_batch_render_ragged: fast_shape_ok's rule for the plain matrix variant — one matrix-rendered element with constant
+// gains into one or two channels, limiter on, planar rows on the 16-byte grid — with "whole 64-sample blocks" replaced by
+// "any length >= 1 that is NOT a whole number of blocks".  A call of whole blocks is left to the rules below (Family::Fast
+// and so on), as is every call with a zero `ragged`.  What keeps the kernel's loads inside the frames' rows: frame_size is a
+// multiple of 4 and a call's total is n_frames * frame_size or an n_samples <= frame_size, so a lane's quad that starts
+// below `total` ends inside its row (iamf_render_ragged.hip).  IAMF_HIP_RAGGED_UNFUSED=1 sends every such call down the
+// rules below.
+inline bool ragged_shape_ok(const RenderParams &p, int m, bool force_generic) {
+  if (!p.ragged || force_generic || getenv("IAMF_HIP_RAGGED_UNFUSED")) return false;
+  if (!p.limiter_on || !p.in || !RaggedOC::has(p.out_ch) || !RaggedM::has(m) || p.og_ch < p.out_ch || p.n_end < kFWin) return false;
+  if (p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe || p.lpcm)
+    return false;
+  if (p.total < 1 || !(p.total & 63) || (p.frame_size & 3)) return false;
+  if ((p.pos0 & 15) && p.pos0 < kDelay) return false;
+  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  // the kernel addresses a stream's input of one call with 32-bit byte offsets: fast_shape_ok's bound
+  const int64_t frames = (int64_t)p.total / p.frame_size + 2;
+  if (frames * p.in_frame_stride * 4 + 100 * (int64_t)p.frame_size >= (int64_t)1 << 31) return false;
+  return true;
+}
+
 // What the wide kernels (render_wide.hpp, render_wide4.hpp) share: 3..24 output channels, limiter on, aligned calls.
 // (Not looked at here: the stream position and the stages in front — demixer, down-mixer, mixer — which differ
 // between the two: pick_route.)
@@ -232,6 +259,8 @@ enum class Family {
                 // listed by family only
   FastInterleaved,  // render_fast_kernel<M, OC, .., IL, RAG> (iamf_render_interleaved.hip): interleaved f32 of any call length,
                 // RenderParams::interleaved.  Set 5, listed by family only
+  FastRagged,   // render_fast_kernel<M, OC, .., IL = false, RAG = true> (iamf_render_ragged.hip): planar f32 of any call length that
+                // is no whole number of 64-sample blocks, RenderParams::ragged.  Set 6, listed by family only
 };
 struct Route {
   Family family;
@@ -309,6 +338,20 @@ inline bool interleaved_fused(int n_launch) {
   return true;
 }
 
+// Whether a range of n_launch streams that came through iamf_hip_batch_render_ragged takes the planar ragged form at all
+// (render_prepare asks), under the rule of lpcm_coupled_fused(): a size at which it does not beat what the call ran before —
+// iamf_hip_batch_render_range on a twin batch in the same process, the general kernel — by more than that baseline's own
+// run-to-run spread is not fused.  Measured (tools/ragged_rate.py, MI355X, a 3rd-order and a stereo element into stereo s16,
+// 64 calls of one frame per stream and step, profiles/r13_ragged_rate.json): the baseline takes 1.88 / 1.55 / 1.49 (3rd
+// order) and 1.97 / 1.87 / 1.59 (stereo) times the new entry's time in calls of 1000 samples at 512 / 2048 / 4096 streams,
+// 1.60 / 1.44 / 1.28 and 1.61 / 1.56 / 1.28 in calls of 480; its spread against itself at most 0.0027 — every measured
+// (shape, size) wins, so every size is fused; this is where one that stops winning would be cut.  (One call of 64 frames
+// of 1000 is 1000 whole blocks: both entries run Family::Fast there, 0.99 to 1.01 of each other.)
+inline bool ragged_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
 // rules.  The environment switches are read at every call (the tests set and unset them within one process).
@@ -323,6 +366,9 @@ inline Route pick_route(const RenderParams &p, int m) {
   // interleaved f32 of any call length (RenderParams::interleaved, zero unless iamf_hip_batch_render_interleaved set it): the
   // form's own kernel where its rules hold, else whatever the rules below give the call
   if (interleaved_shape_ok(p, m, force_generic)) return take(Family::FastInterleaved);
+  // planar f32 that is no whole number of 64-sample blocks (RenderParams::ragged, zero unless iamf_hip_batch_render_ragged set
+  // it): the same way
+  if (ragged_shape_ok(p, m, force_generic)) return take(Family::FastRagged);
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
@@ -481,12 +527,18 @@ void for_each_render_instance_interleaved(F &&f) {
   for_each_int(InterleavedM{}, [&](int m) { for_each_int(InterleavedOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, oc, 0); }); });
 }
 
+// The planar ragged form (iamf_hip_route_family_instances), walking RaggedM x RaggedOC as its launcher does.
+template <class F>
+void for_each_render_instance_ragged(F &&f) {
+  for_each_int(RaggedM{}, [&](int m) { for_each_int(RaggedOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_FAST_RAGGED, 0, m, oc, 0); }); });
+}
+
 // The row sets behind the listing, by number: f as above for every instance of set `set`.  Sets 0 .. kRouteTables - 1 are
 // the numbered tables of iamf_hip_route_table_instances — their count and the rows of each are pinned — and the sets behind
 // them are listed by family only (iamf_hip_route_family_instances), in this order.  The only place that maps a set number
 // to a walker: iamf_route.hip builds and counts by it, and every key is in exactly one set (tests/route_host).
 constexpr int kRouteTables = 3;
-constexpr int kRouteSets = 6;
+constexpr int kRouteSets = 7;
 template <class F>
 void for_each_instance_of_set(int set, F &&f) {
   switch (set) {
@@ -496,6 +548,7 @@ void for_each_instance_of_set(int set, F &&f) {
     case 3: for_each_render_instance_lpcm_coupled(f); break;
     case 4: for_each_render_instance_lpcm_mix(f); break;
     case 5: for_each_render_instance_interleaved(f); break;
+    case 6: for_each_render_instance_ragged(f); break;
   }
 }
 
@@ -525,6 +578,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::LpcmCoupled: return {IAMF_HIP_ROUTE_LPCM_COUPLED, r.variant, m, p.out_ch, 0, 3};   // a family listing's row
     case Family::LpcmMix: return {IAMF_HIP_ROUTE_LPCM_MIX, 0, m, p.out_ch, r.variant, 4};   // a family listing's row, k = LP2
     case Family::FastInterleaved: return {IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, p.out_ch, 0, 5};   // a family listing's row
+    case Family::FastRagged: return {IAMF_HIP_ROUTE_FAST_RAGGED, 0, m, p.out_ch, 0, 6};   // a family listing's row
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

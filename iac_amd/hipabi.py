@@ -78,6 +78,10 @@ class InterleavedCall(C.Structure):   # iamf_hip_interleaved_call
     _fields_ = [("args", RenderArgs), ("reserved", C.c_int32 * 4)]
 
 
+class RaggedCall(C.Structure):   # iamf_hip_ragged_call
+    _fields_ = [("args", RenderArgs), ("reserved", C.c_int32 * 4)]
+
+
 class FanoutReport(C.Structure):   # iamf_hip_fanout_report
     _fields_ = [("n_fused", C.c_int32), ("input_fused", C.c_int32), ("n_unpacks", C.c_int32), ("reserved", C.c_int32)]
 
@@ -90,7 +94,7 @@ class RouteRow(C.Structure):   # iamf_hip_route_row
 # IAMF_HIP_ROUTE_*: the kernel families of iamf_hip_route_row::family
 ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, WIDE4_DEMIX=7, WIDE4_DOWN=8, WIDE4_MIX=9,
              WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, LPCM24=16, LPCM_COUPLED=17,
-             RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23, LPCM_MIX=25, FAST_INTERLEAVED=27)
+             RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23, LPCM_MIX=25, FAST_INTERLEAVED=27, FAST_RAGGED=29)
 ROUTE_NAME = {v: k for k, v in ROUTE.items()}
 
 
@@ -188,6 +192,7 @@ def lib():
         L.iamf_hip_batch_render_lpcm_range.argtypes = [C.c_void_p, C.POINTER(LpcmInput), C.POINTER(RenderArgs), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_lpcm_mix.argtypes = [C.c_void_p, C.POINTER(LpcmMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_interleaved.argtypes = [C.c_void_p, C.POINTER(InterleavedCall), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_ragged.argtypes = [C.c_void_p, C.POINTER(RaggedCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_resampler_destroy.argtypes = [C.c_void_p]
@@ -580,6 +585,18 @@ class Batch:
         r = lib().iamf_hip_batch_render_interleaved(self.h, C.byref(call), s0, n)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_interleaved")
+        return r
+
+    def render_ragged(self, args, stream0=None, n_streams=None):
+        """iamf_hip_batch_render_ragged: `args` a RenderArgs as for render_range, a call of any length; the whole batch unless
+        a range is named"""
+        call = RaggedCall()
+        call.args = args
+        s0 = 0 if stream0 is None else stream0
+        n = self.cfg.n_streams - s0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_ragged(self.h, C.byref(call), s0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_ragged")
         return r
 
     def render_range(self, args, stream0, n_streams):

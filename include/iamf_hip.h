@@ -722,6 +722,33 @@ typedef struct {
 } iamf_hip_interleaved_call;
 int iamf_hip_batch_render_interleaved(iamf_hip_batch *b, const iamf_hip_interleaved_call *call, int32_t stream0, int32_t n_streams);
 
+/* Planar f32 PCM of ANY call length: a live service that renders one frame of 1000, 480 or 120 samples per call, or the
+ * first or last frame of a stream, which arrives trimmed (n_frames == 1, n_samples set).  On any batch the call leaves the
+ * batch, d_pcm and its return value exactly as
+ *   iamf_hip_batch_render_range(b, &call->args, stream0, n_streams)
+ * does, bit for bit, persisted stream state included — so calls of either entry, flushes, restarts, gain changes, exports and
+ * imports may follow one another on one batch.
+ *   args      as for iamf_hip_batch_render_range.
+ *   reserved  0.
+ * One pass of the FOUR-samples-per-lane kernel (IAMF_HIP_ROUTE_FAST_RAGGED) when the call's samples per stream (n_frames *
+ * frame_size, or n_samples) are at least 1 and NO multiple of 64, and: limiter on; an element of 1, 2, 4, 6, 8, 9, 10, 12 or 16
+ * channels into one or two output channels; no second element, ramps, down-mixer, demixer, projection, pre-matrix, HRTF
+ * stage, LFE generator, reduced out_gain_channels or fixed PCM channel stride; frame_size a multiple of 4; d_in 16-byte
+ * aligned, in_stream_stride and in_frame_stride multiples of 4 floats; d_pcm and pcm_stream_stride_bytes multiples of 16; the
+ * streams' position a multiple of 16 or at least 240; (n_frames + 2) * in_frame_stride * 4 + 100 * frame_size below 2^31.
+ * The kernel loads whole quads of four floats: for a frame trimmed to n_samples it loads up to 3 floats BEHIND n_samples in
+ * every channel's row, which must therefore be readable — every channel row of a frame is frame_size floats from d_in on, as
+ * the layout of iamf_hip_render_args has it, trimmed or not.  It reads no float outside those rows [0, frame_size) of the
+ * call's frames, and what lies behind n_samples — NaN and Inf included — changes nothing.  Every other call, a call of whole 64-sample blocks included,
+ * takes exactly the path of iamf_hip_batch_render_range; IAMF_HIP_RAGGED_UNFUSED=1 forces that.
+ * Returns the sample-frames emitted per stream.  IAMF_HIP_ERR_BAD_ARG, before anything is queued, allocated or changed: a NULL
+ * batch or call, non-zero reserved; and, with its own code, whatever iamf_hip_batch_render_range refuses. */
+typedef struct {
+  iamf_hip_render_args args;
+  int32_t reserved[4];
+} iamf_hip_ragged_call;
+int iamf_hip_batch_render_ragged(iamf_hip_batch *b, const iamf_hip_ragged_call *call, int32_t stream0, int32_t n_streams);
+
 /* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
  * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
  *
@@ -797,6 +824,8 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *                          (iamf_hip_route_family_instances only)
  *     FAST_INTERLEAVED     interleaved f32 of any call length (iamf_hip_batch_render_interleaved): m, c; variant 0
  *                          (iamf_hip_route_family_instances only)
+ *     FAST_RAGGED          planar f32 of any call length (iamf_hip_batch_render_ragged): m, c; variant 0
+ *                          (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -831,7 +860,8 @@ enum {
   IAMF_HIP_ROUTE_RS_BLOCK = 22,
   IAMF_HIP_ROUTE_RS_DIRECT = 23,
   IAMF_HIP_ROUTE_LPCM_MIX = 25,      /* no table: iamf_hip_route_family_instances / _family_tally (18, 19, 24: unused) */
-  IAMF_HIP_ROUTE_FAST_INTERLEAVED = 27   /* no table either (26: unused) */
+  IAMF_HIP_ROUTE_FAST_INTERLEAVED = 27,  /* no table either (26: unused) */
+  IAMF_HIP_ROUTE_FAST_RAGGED = 29        /* no table either (28: unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -863,7 +893,7 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * LPCM), which no table lists and whose launches show in no table's tally.  _instances: every row of the family;
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
- * the same way: rows and counters of its own, in no table; so is FAST_INTERLEAVED. */
+ * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED and FAST_RAGGED. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
