@@ -57,17 +57,23 @@ def test_wide4_exact_multi_stream_multi_call(hip, src, out):
 
 
 def test_wide4_state_handoff_between_kernels(hip):
-    """512-sample frames: calls of 1, 2, 3, 4 frames alternate between the 256-sample-chunk wide
-    kernel (total % 1024 != 0) and wide4 (total % 1024 == 0); the flush takes the generic kernel"""
+    """512-sample frames: calls of 1, 2, 3, 4, 2, 1 frames.  Every one of them ends on a whole 1024-sample chunk or on a short
+    chunk of 512 (>= 256) samples, so wide4 takes them all (the tally says so) and hands over to the generic kernel's flush.
+    Then 64-sample frames, calls of 16, 17, 16, 3, 20, 1: the totals 1088, 192 and 64 leave a short chunk below 256 samples
+    and go to the 256-sample-chunk wide kernel, so that wide4 and wide alternate (the tally names three launches of each);
+    the flush takes the generic kernel"""
     A, G = hip
-    fs, calls = 512, [1, 2, 3, 4, 2, 1]
-    F = sum(calls)
-    x = synth.hot(321, 12, F * fs, sigma=0.25, burst_phase=333, burst_period=1700)[None]
     oid = A.SS["J"]
-    got = G.hip_render(A.get_m2m_matrix(A.SS["L714"], oid), 12, x, frame_size=fs, flush=True,
-                       frames_per_call=calls)[0]
-    want = O.stream_run(O.get_m2m(O.SS["L714"], O.SS["J"]), 12, x[0], fs)
-    assert np.array_equal(got, want)
+    for fs, calls, tally in ((512, [1, 2, 3, 4, 2, 1], {("WIDE4", 0, 12, 12, 0): 6, R.gen(12): 1}),
+                             (64, [16, 17, 16, 3, 20, 1], {("WIDE4", 0, 12, 12, 0): 3, ("WIDE", 0, 12, 0, 0): 3, R.gen(12): 1})):
+        F = sum(calls)
+        x = synth.hot(321, 12, F * fs, sigma=0.25, burst_phase=333, burst_period=1700)[None]
+        A.route_reset()
+        got = G.hip_render(A.get_m2m_matrix(A.SS["L714"], oid), 12, x, frame_size=fs, flush=True,
+                           frames_per_call=calls)[0]
+        R.check_tally(A.route_tally(), tally)
+        want = O.stream_run(O.get_m2m(O.SS["L714"], O.SS["J"]), 12, x[0], fs)
+        assert np.array_equal(got, want), fs
 
 
 def test_wide4_mfma_state_handoff_within_1lsb(hip):
@@ -80,8 +86,11 @@ def test_wide4_mfma_state_handoff_within_1lsb(hip):
         for out in ("B", "J", "H"):
             oid = A.SS[out]
             ch = A.layout_channels(oid)
+            A.route_reset()
             got = G.hip_render(A.get_h2m_matrix(order, oid), ch, x[:, :m], frame_size=fs, flush=True,
                                frames_per_call=calls, projection=A.PROJ_MFMA)[0]
+            # the three calls ran the MFMA variant of wide4, the flush the generic kernel
+            R.check_tally(A.route_tally(), {("WIDE4", 1, m, ch, 0): 3, R.gen(m): 1})
             want = O.stream_run(O.get_h2m(order, O.SS[out]), ch, x[0, :m], fs)
             d = np.abs(got.astype(np.int32) - want.astype(np.int32))
             assert got.shape == want.shape and d.max() <= 1, (order, out, int(d.max()))
