@@ -21,6 +21,7 @@
 
 #include "IAMF_decoder.h"
 #include "iamf_hip.h"
+#include "facade_tu.h"
 
 #define MAX_ELEMENTS 8
 #define MAX_PRESENTATIONS 8
@@ -28,6 +29,10 @@
 #define MAX_SEGMENTS 16
 #define MAX_PARAMS 16
 #define MAX_FRAME_SIZE (1u << 20) /* samples; LPCM frames of real streams are <= 8192 */
+/* facade_tu.h speaks of the same things without this file's headers */
+_Static_assert(MAX_SUBSTREAMS == FTU_MAX_SUBSTREAMS && (int)AUDIO_ELEMENT_CHANNEL_BASED == FTU_CHANNEL_BASED &&
+                   (int)AUDIO_ELEMENT_SCENE_BASED == FTU_SCENE_BASED && (int)IAMF_ERR_BAD_ARG == IAMF_HIP_ERR_BAD_ARG,
+               "facade_tu.h");
 
 /* ---- byte reader: every field the path needs is byte aligned or the leading bits of a byte ---- */
 typedef struct {
@@ -265,6 +270,7 @@ struct IAMF_Decoder {
   size_t lp_row_bytes; /* the raw row: every sub-stream of element 0 at its width */
   iamf_hip_lpcm_layout lp_layout;
   float gain_set[2]; /* element / output constant gains the batch holds (iamf_hip_batch_set_gains synchronises: only on change) */
+  ftu_walk walk[2]; /* the sub-streams the stage of element e decodes: widths and first channels (alloc_staging) */
   float *tmp; /* [MAX_SUBSTREAMS * 2][frame_size] unpack scratch */
   void *h_pcm; /* pinned: the render kernels write it, decode copies the caller's share out */
   volatile uint32_t *h_done; /* pinned word a one-lane kernel writes behind the frame's launches (facade_wait) */
@@ -1010,13 +1016,12 @@ static int pre_decide(struct IAMF_Decoder *d, int ei, iamf_hip_matrix *mx) {
   return element_matrix(d, e, mx);
 }
 
-/* ... and its configuration on the batch that renders the element (projection de-mapping, IAMF_core_decoder.c:116-130;
- * iamf_stream_scale_demixer_configure, IAMF_decoder.c:2351-2386) plus the pinned per-frame records */
-static int pre_attach(struct IAMF_Decoder *d, int ei, iamf_hip_batch *batch) {
+/* ... the demixer's configuration (iamf_stream_scale_demixer_configure, IAMF_decoder.c:2351-2386) into q->dc_sig, with
+ * the stage's host state as a fresh stream decoder has it.  Host only */
+static int pre_plan(struct IAMF_Decoder *d, int ei) {
   const Element *e = d->sel_el[ei];
   Pre *q = &d->pre[ei];
   memset(&q->dc_sig, 0, sizeof(q->dc_sig));
-  if (e->amb_projection && iamf_hip_batch_set_projection(batch, e->proj, element_in_channels(e))) return IAMF_ERR_INTERNAL;
   if (q->use_demix) {
     iamf_hip_demix_config dc;
     int last = -1;
@@ -1064,13 +1069,32 @@ static int pre_attach(struct IAMF_Decoder *d, int ei, iamf_hip_batch *batch) {
     for (int i = 0; i < 12; ++i) q->rec_gain[i] = 1.f;
     memset(q->layer_rec_flags, 0, sizeof(q->layer_rec_flags));
     dc.frame_offset = 0; /* LPCM has no decoder delay: demixer_set_frame_offset(0), IAMF_decoder.c:2175-2183 */
-    if (iamf_hip_batch_set_demixer(batch, &dc)) return IAMF_ERR_INTERNAL;
     q->dc_sig = dc;
     iamf_hip_demix_state_init(&q->dmst);
     if (e->has_demix) iamf_hip_demix_set_info(&q->dmst, e->demix_default_mode, e->demix_default_w);
     q->dmx_mode = -1;
-    if (hipHostMalloc((void **)&q->h_demix, sizeof(iamf_hip_demix_frame), 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   }
+  return IAMF_OK;
+}
+
+/* The stage of element ei on the batch that renders it, for every stream of the batch: the projection de-mapping
+ * (IAMF_core_decoder.c:116-130) or the demixer pre_plan has configured.  The handle's own batches and a group's (whose
+ * handles agree in both, group_compatible) are set up here */
+static int stage_attach(const struct IAMF_Decoder *d, int ei, iamf_hip_batch *batch) {
+  const Element *e = d->sel_el[ei];
+  if (e->amb_projection && iamf_hip_batch_set_projection(batch, e->proj, element_in_channels(e))) return IAMF_ERR_INTERNAL;
+  if (d->pre[ei].use_demix && iamf_hip_batch_set_demixer(batch, &d->pre[ei].dc_sig)) return IAMF_ERR_INTERNAL;
+  return IAMF_OK;
+}
+
+/* A single handle's stage: plan, attach, and the pinned per-frame records.  (A projection element has no demixer, so
+ * the plan in front of the projection call answers nothing earlier than it did behind it) */
+static int pre_attach(struct IAMF_Decoder *d, int ei, iamf_hip_batch *batch) {
+  Pre *q = &d->pre[ei];
+  int rc = pre_plan(d, ei);
+  if (!rc) rc = stage_attach(d, ei, batch);
+  if (rc) return rc;
+  if (q->use_demix && hipHostMalloc((void **)&q->h_demix, sizeof(iamf_hip_demix_frame), 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   if (hipHostMalloc((void **)&q->h_dmx, sizeof(iamf_hip_dmx_frame), 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   return IAMF_OK;
 }
@@ -1131,13 +1155,12 @@ static void pre_frame(struct IAMF_Decoder *d, int ei, iamf_hip_dmx_frame *fr, ia
  * demixer of a scalable element has run, its recon-gain smoothing and weight index have moved on (iamf_stream_decoder_decode,
  * IAMF_decoder.c:3347) — and, unless the start or the end trim alone covers the whole frame (:3354-3357), rendered it: the
  * parametric down-mixer has stepped its weight (:2574-2583) and the HOA LFE generator's filter has run over the frame
- * (:2625-2636).  Returns 1 if the unit was rendered in the reference (the caller then advances the LFE generator). */
+ * (:2625-2636).  rendered: ftu_window::rendered; returned as it is (the caller then advances the LFE generator). */
 static int64_t time_transform(int64_t t1, int s1, int s2);
-static int dropped_unit_advance(struct IAMF_Decoder *d, int ns, iamf_hip_dmx_frame *fr[2], iamf_hip_demix_frame *dm[2]) {
+static int dropped_unit_advance(struct IAMF_Decoder *d, int rendered, iamf_hip_dmx_frame *fr[2], iamf_hip_demix_frame *dm[2]) {
   /* the caller's clock moves on by the samples trimmed from the start, kept frame or not (IAMF_decoder.c:3410-3415 stands
    * in front of the "nothing left" exit :3417-3422) */
   if (d->tu_trim_start > 0) d->pts += time_transform((int64_t)d->tu_trim_start, (int)d->rate, (int)d->pts_base);
-  const int rendered = !(d->tu_trim_start == (uint64_t)d->frame_size || d->tu_trim_end == (uint64_t)d->frame_size) && ns > 0;
   for (int k = 0; k < d->sel->nel; ++k) {
     const int e = d->sel->swapped ? d->sel->nel - 1 - k : k;
     if (e == 0 || d->aux) pre_frame_parts(d, e, fr[e], dm[e], rendered, 1);
@@ -1160,14 +1183,11 @@ static int layout_match_score(const struct IAMF_Decoder *d, int type, int ss) {
   return out_ch < chs ? 50 + (chs - out_ch) : 50 - (out_ch - chs);
 }
 
-static int setup_pipeline(struct IAMF_Decoder *d) {
-  iamf_hip_batch_config cfg;
+/* ---- setup_pipeline's steps: choose and order the elements, build the stages, allocate staging ---- */
+
+/* Which mix presentation is decoded, and what it names: its loudness, its elements, their gain parameters */
+static int choose_presentation(struct IAMF_Decoder *d) {
   Presentation *p = 0;
-  int resample, aux = 0; /* aux: element 1 needs a stage of its own */
-  free_runtime(d);
-  d->pre[1].use_dmx = d->pre[1].use_demix = 0;
-  if (!d->have_header || !d->have_codec || !d->nel || !d->npr) return IAMF_ERR_BUFFER_TOO_SMALL;
-  if (d->out_type == IAMF_LAYOUT_TYPE_NOT_DEFINED) return IAMF_ERR_BAD_ARG;
   /* iamf_decoder_get_best_mix_presentation, IAMF_decoder.c:3083-3111: the only one; else the one the caller named; else the
    * FIRST one with the highest matching score over its layouts (iamf_mix_presentation_matching_calculation, :3059-3081) */
   if (d->npr == 1) {
@@ -1214,32 +1234,15 @@ static int setup_pipeline(struct IAMF_Decoder *d) {
    * IAMF_decoder.c:3171); the -DSAMSUNG_TV layout switch does not touch it, and iamf_frame_gain applies the output mix
    * gain to that many channels (:1383-1408,3462-3469): after a switch to a wider layout the channels beyond it go without. */
   if (!d->frame_channels0) d->frame_channels0 = d->out_channels;
-  /* IAMF_decoder.c:3189-3199: a new presentation TAKES the resampler of the one before it (iamf_presentation_take_resampler)
-   * — its rates, its history, its phase — and opens one only if there was none and the rates differ.  A second IA sequence
-   * on a handle that resampled the first one therefore goes on through the SAME resampler: no latency is skipped again,
-   * and the first sequence's ratio stays even if the new stream's rate is another (a reference quirk; its buffer sized
-   * for the first sequence's frames is why it dies on some such streams).  Kept as long as the channel count is the same;
-   * the -DSAMSUNG_TV layout switch closes and re-opens it (:3872-3876, reopen_rs). */
-  if (d->rs && (d->reopen_rs || d->rs_channels != d->out_channels)) {
-    iamf_hip_resampler_destroy(d->rs);
-    d->rs = 0;
-  }
-  d->reopen_rs = 0;
-  d->rs_inherited = d->rs != 0; /* (a group builds its own resampler: such a handle stays single, iamf_hip_decoder_group_create) */
-  resample = d->rs != 0 || d->out_rate != d->rate;
-  d->info.max_frame_size = d->frame_size <= 1024 ? 6144 : 6 * d->frame_size; /* :1628-1630 */
+  return IAMF_OK;
+}
 
-  memset(&cfg, 0, sizeof(cfg));
-  cfg.n_streams = 1;
-  cfg.frame_size = (int32_t)d->frame_size;
-  cfg.sample_rate = (int32_t)d->rate;
-  cfg.out_channels = d->out_channels;
-  cfg.out_gain_channels = d->frame_channels0 < d->out_channels ? d->frame_channels0 : 0;
-  /* -DSAMSUNG_TV: every PCM frame is written with a 12-channel stride (IAMF_decoder.c:3492-3495) */
-  d->pcm_stride = d->tv ? 12 : d->out_channels;
-  d->pcm_extra = d->out_channels > d->pcm_stride ? d->out_channels - d->pcm_stride : 0;
-  cfg.projection = IAMF_HIP_PROJ_EXACT; /* a single decoder handle is not throughput bound */
-  /* Which layer of every channel-based element is decoded (iamf_stream_set_output_layout, IAMF_decoder.c:1776-1822) */
+/* Which layer of every channel-based element is decoded, and which of two elements is element 0 of the batch.  *aux:
+ * element 1 needs a stage of its own */
+static void order_elements(struct IAMF_Decoder *d, int *aux) {
+  Presentation *p = d->sel;
+  *aux = 0;
+  /* (iamf_stream_set_output_layout, IAMF_decoder.c:1776-1822) */
   for (int i = 0; i < p->nel; ++i) {
     Element *e = d->sel_el[i];
     if (e->type != AUDIO_ELEMENT_CHANNEL_BASED) continue;
@@ -1293,11 +1296,85 @@ static int setup_pipeline(struct IAMF_Decoder *d) {
       d->sel_el[1] = e;
       d->el_gain_p[1] = gp;
       p->swapped ^= 1; /* (a second configuration of the same descriptors finds them exchanged already) */
-      aux = needs[0];
+      *aux = needs[0];
     } else if (p->nel == 2 && needs[1]) {
-      aux = 1;
+      *aux = 1;
     }
   }
+}
+
+/* The resampler of the presentation before this one, if it can stay; returns whether the pipeline resamples */
+static int inherit_resampler(struct IAMF_Decoder *d) {
+  /* IAMF_decoder.c:3189-3199: a new presentation TAKES the resampler of the one before it (iamf_presentation_take_resampler)
+   * — its rates, its history, its phase — and opens one only if there was none and the rates differ.  A second IA sequence
+   * on a handle that resampled the first one therefore goes on through the SAME resampler: no latency is skipped again,
+   * and the first sequence's ratio stays even if the new stream's rate is another (a reference quirk; its buffer sized
+   * for the first sequence's frames is why it dies on some such streams).  Kept as long as the channel count is the same;
+   * the -DSAMSUNG_TV layout switch closes and re-opens it (:3872-3876, reopen_rs). */
+  if (d->rs && (d->reopen_rs || d->rs_channels != d->out_channels)) {
+    iamf_hip_resampler_destroy(d->rs);
+    d->rs = 0;
+  }
+  d->reopen_rs = 0;
+  d->rs_inherited = d->rs != 0; /* (a group builds its own resampler: such a handle stays single, iamf_hip_decoder_group_create) */
+  return d->rs != 0 || d->out_rate != d->rate;
+}
+
+
+/* Element 1 behind a stage of its own, for n streams — a handle's (n = 1; plan: the stage is planned here and gets its
+ * records) or a group's: a second batch, created from d0->aux_sig / aux_mat, renders the element — stage, matrix, its mix
+ * gain; no limiter, no loudness — into f32 sample-frames (*d_il, and planar in *d_pl), and `batch` takes those as its
+ * second element through the identity matrix with gain 1:  0 + 1 * y[c] + 0 * y[..]  is y[c] for every finite y, so what
+ * reaches the mixer is what the reference's renderer and iamf_frame_gain left for this element (IAMF_decoder.c:2536-2651,
+ * 639-664), bit for bit.  ones: n gains of 1 */
+static int aux_stage_create(struct IAMF_Decoder *d0, int n, int plan, iamf_hip_batch *batch, const float *ones,
+                            iamf_hip_batch **aux, float **d_il, float **d_pl) {
+  iamf_hip_batch_config ca = d0->aux_sig;
+  iamf_hip_matrix m2;
+  float eye[24 * 24];
+  const size_t bytes = sizeof(float) * (size_t)n * d0->frame_size * d0->out_channels;
+  int rc;
+  ca.n_streams = n;
+  ca.matrix.mat = d0->aux_mat;
+  if (iamf_hip_batch_create(&ca, aux)) return IAMF_ERR_INTERNAL;
+  /* both batches have a generator only if both matrices have an LFE slot — the same output layout: both or neither */
+  if (ca.lfe_hoa && iamf_hip_batch_share_lfe_state(*aux, batch) == IAMF_HIP_ERR_INVALID_STATE) return IAMF_ERR_INTERNAL;
+  rc = plan ? pre_attach(d0, 1, *aux) : stage_attach(d0, 1, *aux);
+  if (rc) return rc;
+  /* (a group sets the gains a batch starts with, 1, once more; a handle sets them at its first frame that differs) */
+  if (!plan && iamf_hip_batch_set_gains(*aux, ones, ones, 0)) return IAMF_ERR_INTERNAL;
+  ftu_identity_matrix(d0->out_channels, eye, &m2);
+  if (iamf_hip_batch_set_second_element(batch, &m2, ones)) return IAMF_ERR_INTERNAL;
+  if (hipMalloc((void **)d_il, bytes) != hipSuccess || hipMalloc((void **)d_pl, bytes) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
+  return IAMF_OK;
+}
+
+/* The stages behind the render batch of handles that resample, for n streams (a handle's: n = 1): the resampler — *rs
+ * stays if the handle brought one along — and the batch for loudness / limiter / pack over its interleaved f32 */
+static int last_stage_create(const struct IAMF_Decoder *d0, int n, iamf_hip_resampler **rs, iamf_hip_batch **batch3) {
+  float eye[24 * 24];
+  iamf_hip_batch_config c3;
+  if (!*rs && iamf_hip_resampler_create(n, d0->out_channels, (int)d0->rate, (int)d0->out_rate, rs)) return IAMF_ERR_INTERNAL;
+  ftu_last_stage_config(&c3, eye, n, (int)d0->out_rate, d0->out_channels, (int)d0->bit_depth, d0->pcm_stride, d0->limiter_on,
+                        d0->limiter_db, d0->norm_loudness != 0.f);
+  if (!iamf_hip_format_bytes(c3.out_format)) return IAMF_ERR_BAD_ARG;
+  return iamf_hip_batch_create(&c3, batch3) ? IAMF_ERR_INTERNAL : IAMF_OK;
+}
+
+/* The batches of the handle: `batch` with the stage of element 0, `aux` for an element 1 that needs one, the last stage
+ * behind a resampler */
+static int build_stages(struct IAMF_Decoder *d, int resample, int aux) {
+  const Presentation *p = d->sel;
+  iamf_hip_batch_config cfg;
+  const float one = 1.f, lg = db2lin(d->norm_loudness - d->mix_loudness);
+  int rc;
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.n_streams = 1;
+  cfg.frame_size = (int32_t)d->frame_size;
+  cfg.sample_rate = (int32_t)d->rate;
+  cfg.out_channels = d->out_channels;
+  cfg.out_gain_channels = d->frame_channels0 < d->out_channels ? d->frame_channels0 : 0;
+  cfg.projection = IAMF_HIP_PROJ_EXACT; /* a single decoder handle is not throughput bound */
   /* IAMF_decoder.c:2625-2633: scene-based element, LFE generator compiled in, layout with an LFE */
   if (d->lfe_hoa && d->out_type == IAMF_LAYOUT_TYPE_LOUDSPEAKERS_SS_CONVENTION)
     cfg.lfe_hoa = d->sel_el[0]->type == AUDIO_ELEMENT_SCENE_BASED;
@@ -1318,53 +1395,27 @@ static int setup_pipeline(struct IAMF_Decoder *d) {
   d->cfg_sig = cfg; /* a group of handles is formed from handles whose batches were created alike */
   d->cfg_mat = cfg.matrix.mat;
   d->cfg_sig.matrix.mat = 0;
-  {
-    int rc = pre_attach(d, 0, d->batch);
-    if (rc) return rc;
-  }
+  if ((rc = pre_attach(d, 0, d->batch))) return rc;
   if (p->nel == 2 && !aux) {
     iamf_hip_matrix m2;
-    float one = 1.f;
     if (element_matrix(d, d->sel_el[1], &m2) || iamf_hip_batch_set_second_element(d->batch, &m2, &one))
       return IAMF_ERR_INTERNAL;
   }
-  if (aux) {
-    /* Element 1 needs a stage of its own: a second batch renders it — stage, matrix, its mix gain; no limiter, no
-     * loudness — into f32 sample-frames, and `batch` takes those as its second element through the identity matrix with
-     * gain 1:  0 + 1 * y[c] + 0 * y[..]  is y[c] for every finite y, so what reaches the mixer is what the reference's
-     * renderer and iamf_frame_gain left for this element (IAMF_decoder.c:2536-2651, 639-664), bit for bit. */
-    iamf_hip_batch_config ca;
-    iamf_hip_matrix m2;
-    float eye[24 * 24], one = 1.f;
-    int rc;
-    memset(&ca, 0, sizeof(ca));
-    ca.n_streams = 1;
-    ca.frame_size = (int32_t)d->frame_size;
-    ca.sample_rate = (int32_t)d->rate;
-    ca.out_channels = d->out_channels;
-    ca.out_format = IAMF_HIP_FMT_F32;
-    ca.projection = IAMF_HIP_PROJ_EXACT;
-    ca.lfe_hoa = cfg.lfe_hoa && d->sel_el[1]->type == AUDIO_ELEMENT_SCENE_BASED; /* (then element 0 is scene-based too) */
-    if (pre_decide(d, 1, &ca.matrix) || iamf_hip_batch_create(&ca, &d->aux)) return IAMF_ERR_INTERNAL;
-    /* both batches have a generator only if both matrices have an LFE slot — the same output layout: both or neither */
-    if (ca.lfe_hoa && iamf_hip_batch_share_lfe_state(d->aux, d->batch) == IAMF_HIP_ERR_INVALID_STATE) return IAMF_ERR_INTERNAL;
-    d->aux_sig = ca;
-    d->aux_mat = ca.matrix.mat;
-    d->aux_sig.matrix.mat = 0;
-    rc = pre_attach(d, 1, d->aux);
-    if (rc) return rc;
+  if (aux) { /* what `aux` is created from (mat pointer apart), then the stage: aux_stage_create */
+    iamf_hip_batch_config *ca = &d->aux_sig;
+    memset(ca, 0, sizeof(*ca));
+    ca->n_streams = 1;
+    ca->frame_size = (int32_t)d->frame_size;
+    ca->sample_rate = (int32_t)d->rate;
+    ca->out_channels = d->out_channels;
+    ca->out_format = IAMF_HIP_FMT_F32;
+    ca->projection = IAMF_HIP_PROJ_EXACT;
+    ca->lfe_hoa = cfg.lfe_hoa && d->sel_el[1]->type == AUDIO_ELEMENT_SCENE_BASED; /* (then element 0 is scene-based too) */
+    if (pre_decide(d, 1, &ca->matrix)) return IAMF_ERR_INTERNAL;
+    d->aux_mat = ca->matrix.mat;
+    ca->matrix.mat = 0;
+    if ((rc = aux_stage_create(d, 1, 1, d->batch, &one, &d->aux, &d->d_aux_il, &d->d_aux_pl))) return rc;
     d->aux_gain_set = 1.f;
-    for (int i = 0; i < d->out_channels; ++i)
-      for (int j = 0; j < d->out_channels; ++j) eye[i * d->out_channels + j] = i == j ? 1.f : 0.f;
-    memset(&m2, 0, sizeof(m2));
-    m2.kind = IAMF_HIP_KIND_M2M;
-    m2.m = m2.n = m2.channels = d->out_channels;
-    m2.lfe1 = m2.lfe2 = -1;
-    m2.mat = eye;
-    if (iamf_hip_batch_set_second_element(d->batch, &m2, &one)) return IAMF_ERR_INTERNAL;
-    if (hipMalloc((void **)&d->d_aux_il, sizeof(float) * d->frame_size * d->out_channels) != hipSuccess ||
-        hipMalloc((void **)&d->d_aux_pl, sizeof(float) * d->frame_size * d->out_channels) != hipSuccess)
-      return IAMF_ERR_ALLOC_FAIL;
   }
   d->dmx_last = 0;
   d->dmx_static_s = 0.f;
@@ -1375,90 +1426,82 @@ static int setup_pipeline(struct IAMF_Decoder *d) {
     if (d->sel_el[e]->layout != IA_CHANNEL_LAYOUT_312) d->dmx_static_s = d->pre[e].dmx.gamma_w;
   }
   if (resample) {
-    float eye[24 * 24];
-    iamf_hip_batch_config c3;
-    for (int i = 0; i < d->out_channels; ++i)
-      for (int j = 0; j < d->out_channels; ++j) eye[i * d->out_channels + j] = i == j ? 1.f : 0.f;
-    if (!d->rs) {
-      if (iamf_hip_resampler_create(1, d->out_channels, (int)d->rate, (int)d->out_rate, &d->rs)) return IAMF_ERR_INTERNAL;
-      d->rs_channels = d->out_channels;
-    }
-    memset(&c3, 0, sizeof(c3));
-    c3.n_streams = 1;
-    c3.frame_size = 1; /* interleaved f32 in */
-    c3.sample_rate = (int32_t)d->out_rate;
-    c3.out_channels = d->out_channels;
-    c3.out_format = (int32_t)d->bit_depth;
-    c3.pcm_stride_channels = d->pcm_stride;
-    c3.matrix.kind = IAMF_HIP_KIND_M2M;
-    c3.matrix.m = c3.matrix.n = c3.matrix.channels = d->out_channels;
-    c3.matrix.lfe1 = c3.matrix.lfe2 = -1;
-    c3.matrix.mat = eye;
-    c3.limiter_enable = d->limiter_on;
-    c3.limiter_threshold_db = d->limiter_db;
-    c3.loudness_enable = d->norm_loudness != 0.f;
-    c3.projection = IAMF_HIP_PROJ_EXACT;
-    if (!iamf_hip_format_bytes(c3.out_format)) return IAMF_ERR_BAD_ARG;
-    if (iamf_hip_batch_create(&c3, &d->batch3)) return IAMF_ERR_INTERNAL;
+    const int had = d->rs != 0;
+    rc = last_stage_create(d, 1, &d->rs, &d->batch3);
+    if (!had && d->rs) d->rs_channels = d->out_channels;
+    if (rc) return rc;
   }
-  {
-    iamf_hip_batch *lb = d->batch3 ? d->batch3 : d->batch;
-    float one = 1.f, lg = db2lin(d->norm_loudness - d->mix_loudness);
-    if (iamf_hip_batch_set_gains(lb, d->batch3 ? &one : 0, d->batch3 ? &one : 0, &lg)) return IAMF_ERR_INTERNAL;
+  /* loudness belongs to the last stage, whichever batch that is */
+  if (iamf_hip_batch_set_gains(d->batch3 ? d->batch3 : d->batch, d->batch3 ? &one : 0, d->batch3 ? &one : 0, &lg))
+    return IAMF_ERR_INTERNAL;
+  return IAMF_OK;
+}
+
+/* Whether asking for the packet-fed form of the render kernel is worth it for the frames of d — a handle's own, or a
+ * group's, whose handles agree in every term (group_compatible).  The headline's kind of stream: its packets go to the
+ * render kernel as they are (the reference's LPCM decode, pcm/IAMF_pcm_decoder.c:64-83, happens where the kernel loads
+ * them): one scene-based element, mono-coded, 16 or 24 bit, or one single-layer channel-based element, 16 bit, that
+ * couples every pair of its layout (the kernel's coupled form) or is mono; little-endian, into one or two channels with
+ * the limiter on, no stage in front, no resampler behind.  The library decides per call whether the fused kernel takes it
+ * and unpacks on the device otherwise.  L: the raw row (ftu_raw_layout) — every channel is carried by a sub-stream, on the
+ * form's grid: runs of 8 bytes for 16-bit samples and coupled pairs, of 4 for 24-bit ones.  env_off: the environment
+ * variable that says "unpack first" */
+static int lp_worth_asking(const struct IAMF_Decoder *d, const iamf_hip_lpcm_layout *L, const char *env_off) {
+  const Element *e0 = d->sel_el[0];
+  const int common = d->sel->nel == 1 && !d->pre[0].use_dmx && !d->pre[0].use_demix && !d->rs && d->little_endian &&
+                     d->limiter_on && d->out_channels <= 2 && d->pcm_stride == d->out_channels && (d->frame_size & 63) == 0 &&
+                     !getenv(env_off);
+  const int lp_chan = e0->type == AUDIO_ELEMENT_CHANNEL_BASED && e0->nlayers == 1 && d->sample_size == 16 &&
+                      e0->nb_coupled == lp_canonical_coupled(e0->channels) && e0->nsub + e0->nb_coupled == e0->channels;
+  const int lp_scene = e0->type == AUDIO_ELEMENT_SCENE_BASED && !e0->amb_projection && (d->sample_size == 16 || d->sample_size == 24);
+  if (!common || !(lp_chan || lp_scene)) return 0;
+  for (int c = 0; c < L->channels; ++c) {
+    const int step = L->src_step[c], off = L->src_offset[c];
+    if (off < 0) return 0; /* a channel no sub-stream carries: the f32 form zeroes it */
+    if (lp_chan && step == 4 ? ((off - (off & 2)) & 7) != 0 : (step != L->sample_bytes || (off & (L->sample_bytes == 3 ? 3 : 7)))) return 0;
   }
+  return 1;
+}
+
+/* the sub-streams the stage of element ei decodes: the element's, or with a demixer those of the layers up to the decoded one */
+static int element_walk(const struct IAMF_Decoder *d, int ei, ftu_walk *w) {
+  const Element *e = d->sel_el[ei];
+  const int nl = d->pre[ei].use_demix ? d->pre[ei].demix_layer + 1 : 0;
+  int ln[MAX_LAYERS], lc[MAX_LAYERS];
+  for (int l = 0; l < nl; ++l) {
+    ln[l] = e->layer[l].nsub;
+    lc[l] = e->layer[l].ncoupled;
+  }
+  return ftu_walk_substreams(e->type, e->nsub, e->nb_coupled, e->amb_projection, e->amb_coupled, nl, ln, lc, w);
+}
+
+/* element ei's packets in a raw row behind `head` bytes (ftu_raw_layout, over d->walk[ei]) */
+static int element_raw_layout(const struct IAMF_Decoder *d, int ei, int head, int *slot_off, iamf_hip_lpcm_layout *L) {
+  const Element *e = d->sel_el[ei];
+  return ftu_raw_layout(&d->walk[ei], e->amb_projection || d->pre[ei].use_demix, e->type, e->channels, k_al_of_pl[e->layout],
+                        e->amb_map, (int)d->sample_size / 8, d->little_endian, (int)d->frame_size, head, slot_off, L);
+}
+
+/* The handle's stream, its pinned and device buffers */
+static int alloc_staging(struct IAMF_Decoder *d, int resample) {
+  const Presentation *p = d->sel;
+  int row;
   if (hipStreamCreate(&d->stream) != hipSuccess) return IAMF_ERR_INTERNAL;
   d->tmp = (float *)malloc(sizeof(float) * MAX_SUBSTREAMS * 2 * d->frame_size);
   if (!d->tmp) return IAMF_ERR_ALLOC_FAIL;
   for (int e = 0; e < p->nel; ++e) {
     size_t bytes = sizeof(float) * (size_t)element_in_channels(d->sel_el[e]) * d->frame_size;
+    if (element_walk(d, e, &d->walk[e])) return IAMF_ERR_INTERNAL; /* (parse_element: 1 .. MAX_SUBSTREAMS sub-streams) */
     if (hipHostMalloc((void **)&d->h_in[e], bytes, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
     memset(d->h_in[e], 0, bytes);
   }
   for (int i = 0; i < 4; ++i)
     if (hipHostMalloc((void **)&d->h_ramp[i], sizeof(float) * d->frame_size, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
-  {
-    /* the headline's kind of stream: its packets go to the render kernel as they are (the reference's LPCM decode,
-     * pcm/IAMF_pcm_decoder.c:64-83, happens where the kernel loads them).  The library decides per call whether the
-     * fused kernel takes it and unpacks on the device otherwise; here: whether asking is worth it */
-    const Element *e0 = d->sel_el[0];
-    iamf_hip_lpcm_layout *L = &d->lp_layout;
-    const int lp_common = p->nel == 1 && !d->pre[0].use_dmx && !d->pre[0].use_demix && !resample && d->little_endian && d->limiter_on &&
-                          d->out_channels <= 2 && d->pcm_stride == d->out_channels && (d->frame_size & 63) == 0 && e0->nsub > 0 &&
-                          e0->nsub <= MAX_SUBSTREAMS && !getenv("IAMF_HIP_FACADE_UNPACK");
-    /* a single-layer channel-based element, 16 bit, that couples every pair of its layout: the kernel's coupled form (a mono
-     * element: the mono-coded form, one channel) */
-    const int lp_chan = lp_common && e0->type == AUDIO_ELEMENT_CHANNEL_BASED && e0->nlayers == 1 && d->sample_size == 16 &&
-                        e0->nb_coupled == lp_canonical_coupled(e0->channels) && e0->nsub + e0->nb_coupled == e0->channels;
-    d->lp_ok = lp_chan || (lp_common && e0->type == AUDIO_ELEMENT_SCENE_BASED && !e0->amb_projection &&
-                           (d->sample_size == 16 || d->sample_size == 24) &&
-                           (e0->channels == 1 || e0->channels == 4 || e0->channels == 9 || e0->channels == 16));
-    /* (16 or 24 bit: sub-stream s at s * frame_size * bytes, a multiple of 8 / of 4 with the frame size one of 64) */
-    const int lp_bytes = d->sample_size == 24 ? 3 : 2;
-    memset(L, 0, sizeof(*L));
-    L->sample_bytes = lp_bytes;
-    L->little_endian = 1;
-    L->channels = e0->channels;
-    L->frame_size = (int32_t)d->frame_size;
-    d->lp_row_bytes = (size_t)e0->nsub * d->frame_size * lp_bytes;
-    for (int c = 0; c < e0->channels && d->lp_ok && !lp_chan; ++c) {
-      if (e0->amb_map[c] >= e0->nsub) d->lp_ok = 0; /* a channel no sub-stream carries: the f32 form zeroes it */
-      L->src_offset[c] = (int32_t)(e0->amb_map[c] * d->frame_size * lp_bytes);
-      L->src_step[c] = lp_bytes;
-    }
-    if (lp_chan) {
-      /* sub-streams at their width, one behind the other (coupled ones first: audio-layer channel a < 2 * nb_coupled is half
-       * a & 1 of sub-stream a >> 1); the renderer's order through k_al_of_pl as unpack_element.  Every offset a multiple of
-       * 8: the frame size is one of 64 */
-      const int nc = e0->nb_coupled;
-      d->lp_row_bytes = (size_t)e0->channels * d->frame_size * 2;
-      for (int c = 0; c < e0->channels; ++c) {
-        const int a = k_al_of_pl[e0->layout][c];
-        L->src_offset[c] = a < 2 * nc ? (int32_t)((a >> 1) * 4 * d->frame_size + (a & 1) * 2) : (int32_t)((nc * 4 + (a - 2 * nc) * 2) * d->frame_size);
-        L->src_step[c] = a < 2 * nc ? 4 : 2;
-      }
-    }
-    if (d->lp_ok && hipHostMalloc((void **)&d->h_raw, d->lp_row_bytes + 256, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
-  }
+  /* element 0's packets as a raw row, one sub-stream behind the other, for the packet-fed form of the render kernel */
+  row = element_raw_layout(d, 0, 0, 0, &d->lp_layout);
+  d->lp_row_bytes = row > 0 ? (size_t)row : 0;
+  d->lp_ok = row > 0 && lp_worth_asking(d, &d->lp_layout, "IAMF_HIP_FACADE_UNPACK");
+  if (d->lp_ok && hipHostMalloc((void **)&d->h_raw, d->lp_row_bytes + 256, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   d->pcm_cap = (size_t)4 * ((size_t)d->info.max_frame_size * d->pcm_stride + d->pcm_extra);
   if (hipHostMalloc(&d->h_pcm, d->pcm_cap, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   if (hipHostMalloc((void **)&d->h_done, 64, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
@@ -1471,6 +1514,23 @@ static int setup_pipeline(struct IAMF_Decoder *d) {
         hipMalloc((void **)&d->d_res, sizeof(float) * cap * d->out_channels) != hipSuccess)
       return IAMF_ERR_ALLOC_FAIL;
   }
+  return IAMF_OK;
+}
+
+static int setup_pipeline(struct IAMF_Decoder *d) {
+  int resample, aux, rc;
+  free_runtime(d);
+  d->pre[1].use_dmx = d->pre[1].use_demix = 0;
+  if (!d->have_header || !d->have_codec || !d->nel || !d->npr) return IAMF_ERR_BUFFER_TOO_SMALL;
+  if (d->out_type == IAMF_LAYOUT_TYPE_NOT_DEFINED) return IAMF_ERR_BAD_ARG;
+  if ((rc = choose_presentation(d))) return rc;
+  resample = inherit_resampler(d);
+  d->info.max_frame_size = d->frame_size <= 1024 ? 6144 : 6 * d->frame_size; /* :1628-1630 */
+  /* -DSAMSUNG_TV: every PCM frame is written with a 12-channel stride (IAMF_decoder.c:3492-3495) */
+  d->pcm_stride = d->tv ? 12 : d->out_channels;
+  d->pcm_extra = d->out_channels > d->pcm_stride ? d->out_channels - d->pcm_stride : 0;
+  order_elements(d, &aux);
+  if ((rc = build_stages(d, resample, aux)) || (rc = alloc_staging(d, resample))) return rc;
   d->timestamp = 0;
   d->flushed = 0;
   d->configured = 1;
@@ -1619,38 +1679,22 @@ static void lpcm_row(const struct IAMF_Decoder *d, const uint8_t *p, int step, i
 /* substreams -> planar f32 in the order the renderer expects; returns samples per channel */
 static int unpack_element(struct IAMF_Decoder *d, int ei) {
   const Element *e = d->sel_el[ei];
+  const ftu_walk *w = &d->walk[ei]; /* audio-layer order: coupled pairs first, then singles */
   const int bps = (int)d->sample_size / 8, fs = (int)d->frame_size;
-  float *dst = d->h_in[ei];
+  /* with a projection or a demixer the decoded channel order goes to the device: de-mapping / demixer run there */
+  const int decoded = e->amb_projection || d->pre[ei].use_demix;
+  float *dst = d->h_in[ei], *tmp = d->tmp;
   int ns = -1;
-  float *tmp = d->tmp;
-  /* audio-layer order: coupled pairs first, then singles */
-  int c = 0;
-  const int demix = d->pre[ei].use_demix;
-  const int nsub = demix ? d->pre[ei].demix_nsub : e->nsub;
-  int lay = 0, lay_s0 = 0; /* layer of sub-stream s and its first sub-stream */
-  for (int s = 0; s < nsub; ++s) {
-    int w;
-    if (demix) { /* every layer: coupled sub-streams first (iamf_stream_scale_decoder_decode, :2276-2322) */
-      while (s >= lay_s0 + e->layer[lay].nsub) lay_s0 += e->layer[lay++].nsub;
-      w = s - lay_s0 < e->layer[lay].ncoupled ? 2 : 1;
-    } else {
-      w = ((e->type == AUDIO_ELEMENT_CHANNEL_BASED && s < e->nb_coupled) ||
-           (e->amb_projection && s < e->amb_coupled)) ? 2 : 1;
-    }
-    const int n = (int)(d->pkt_len[ei][s] / (uint32_t)(w * bps));
+  for (int s = 0; s < w->nsub; ++s) {
+    const int wd = w->width[s], n = (int)(d->pkt_len[ei][s] / (uint32_t)(wd * bps));
     if (ns < 0) ns = n;
     if (n != ns || n > fs) return IAMF_ERR_INVALID_PACKET;
-    for (int k = 0; k < w; ++k) lpcm_row(d, d->pkt[ei][s] + (size_t)k * bps, w * bps, n, tmp + (size_t)(c + k) * fs);
-    c += w;
+    for (int k = 0; k < wd; ++k) lpcm_row(d, d->pkt[ei][s] + (size_t)k * bps, wd * bps, n, tmp + (size_t)(w->first[s] + k) * fs);
   }
   if (ns < 0) return IAMF_ERR_INVALID_PACKET; /* no sub-stream at all: nothing fixed the sample count */
-  if (e->amb_projection || demix) { /* decoded channel order goes to the device: de-mapping / demixer run there */
-    for (int l = 0; l < c; ++l) memcpy(dst + (size_t)l * fs, tmp + (size_t)l * fs, sizeof(float) * ns);
-    return ns;
-  }
-  for (int p = 0; p < e->channels; ++p) {
-    int src = e->type == AUDIO_ELEMENT_CHANNEL_BASED ? k_al_of_pl[e->layout][p] : e->amb_map[p];
-    if (src < c)
+  for (int p = 0; p < (decoded ? w->channels : e->channels); ++p) {
+    const int src = decoded ? p : ftu_channel_source(e->type, p, k_al_of_pl[e->layout], e->amb_map, w->channels);
+    if (src >= 0)
       memcpy(dst + (size_t)p * fs, tmp + (size_t)src * fs, sizeof(float) * ns);
     else
       memset(dst + (size_t)p * fs, 0, sizeof(float) * ns);
@@ -1658,17 +1702,15 @@ static int unpack_element(struct IAMF_Decoder *d, int ei) {
   return ns;
 }
 
-/* element 0's packets as they are -> the pinned raw row (sub-streams one behind the other, each frame_size * sample bytes *
- * its width: 2 for the coupled sub-streams of a channel-based element, which come first); unpack_element's checks; returns
- * samples per channel */
+/* element 0's packets as they are -> the pinned raw row (ftu_raw_layout without a head); unpack_element's checks;
+ * returns samples per channel */
 static int stage_lpcm_row(struct IAMF_Decoder *d) {
-  const Element *e = d->sel_el[0];
   const int fs = (int)d->frame_size;
   const unsigned bps = (unsigned)d->lp_layout.sample_bytes;
   int ns = -1;
   size_t off = 0;
-  for (int s = 0; s < e->nsub; ++s) {
-    const unsigned w = (e->type == AUDIO_ELEMENT_CHANNEL_BASED && s < e->nb_coupled) ? 2u : 1u;
+  for (int s = 0; s < d->walk[0].nsub; ++s) {
+    const unsigned w = (unsigned)d->walk[0].width[s];
     const int n = (int)(d->pkt_len[0][s] / (w * bps));
     if (ns < 0) ns = n;
     if (n != ns || n > fs) return IAMF_ERR_INVALID_PACKET;
@@ -1724,162 +1766,90 @@ static void meta_note_output(struct IAMF_Decoder *d, int n) {
   d->last_frame = (uint32_t)(n > 0 ? n : 0);
 }
 
-static int render_tu(struct IAMF_Decoder *d, void *pcm) {
-  iamf_hip_render_args a;
-  const int fs = (int)d->frame_size, bytes = (int)d->bit_depth / 8;
-  int ns = 0, n, keep, s0;
-  float cgain[3];
-  int ramp[3] = {0, 0, 0};
-  int lp = d->lp_ok && !d->group; /* the packets go to the render kernel as they are (decided per frame below) */
-  memset(&a, 0, sizeof(a));
-  if (lp) {
-    int r = stage_lpcm_row(d);
-    if (r < 0) return r;
-    ns = r;
-  } else {
-    for (int e = 0; e < d->sel->nel; ++e) {
-      int r = unpack_element(d, e);
-      if (r < 0) return r;
-      ns = r;
+/* The mix gains of a frame of `keep` samples whose first is sample s0 of its unit, for the element 0, element 1 and output
+ * stage (a handle's frame and a group's: they differ in where the rows lie).  ramp[k] = 1: stage k is a per-sample ramp,
+ * written to row[k][0 .. keep) and multiplied in unconditionally (iamf_frame_gain, IAMF_decoder.c:1401-1405).  Else the
+ * stage has a constant: 1 for a unit that iamf_frame_gain refuses (:1386-1390: no gain at all) and for an element 1 that is
+ * not there.  set[]: what iamf_hip_batch_set_gains gets for element 0 and the output — the constant, 1 under a ramp; the
+ * batch applies a constant only if it is != 1 and > 0 (:1392-1397).  cgain[k]: the constant as a row of a ramp launch
+ * carries it — that rule applied here: the constant or exactly 1, which multiplies to the same bits.  Element 1 always
+ * takes its gain through its row, constant (x * positive constant is the same product; filled here) or ramp. */
+static void frame_gain_plan(const struct IAMF_Decoder *d, int s0, int keep, float *const row[3], int ramp[3], float cgain[3],
+                            float set[2]) {
+  const Presentation *p = d->sel;
+  const uint64_t pt = d->timestamp + (uint64_t)s0;
+  const Param *par[3] = {d->el_gain_p[0], d->el_gain_p[1], d->out_gain_p};
+  const int16_t q[3] = {p->el_gain_q[0], p->el_gain_q[1], p->out_gain_q};
+  float raw[3];
+  for (int k = 0; k < 3; ++k) {
+    const int absent = k == 1 && p->nel < 2;
+    ramp[k] = absent ? 0 : mix_gain_unit(par[k], db2lin(q_to_float(q[k], 8)), pt, keep, (int)d->rate, &raw[k], row[k]);
+    if (absent || ramp[k] < 0) {
+      ramp[k] = 0;
+      raw[k] = 1.f;
     }
+    cgain[k] = (k == 1 || (raw[k] != 1.f && raw[k] > 0.f)) ? raw[k] : 1.f;
   }
-  /* iamf_frame_trim (IAMF_decoder.c:1361-1381): rendering is memoryless, so trimming the
-   * element PCM before the renderer equals trimming the rendered frame */
-  for (int e = 0; e < d->sel->nel; ++e)
-    for (int s = 0; s < d->sel_el[e]->nsub; ++s) d->pkt_have[e][s] = 0;
-  /* the trims are LEB128 fields of the OBU header: compared as uint64 BEFORE narrowing.  The reference
-   * refuses start < 0 || end < 0 || samples - start - end < 0 with IAMF_ERR_BAD_ARG and moves the
-   * stream time on (iamf_frame_trim :1364-1370, :3424-3428) */
-  if (d->tu_trim_start > (uint64_t)ns || d->tu_trim_end > (uint64_t)ns ||
-      d->tu_trim_start + d->tu_trim_end > (uint64_t)ns) {
-    d->timestamp += fs;
-    return IAMF_ERR_BAD_ARG;
+  if (!ramp[1] && p->nel > 1)
+    for (int j = 0; j < keep; ++j) row[1][j] = raw[1];
+  set[0] = ramp[0] ? 1.f : raw[0];
+  set[1] = ramp[2] ? 1.f : raw[2];
+}
+
+/* a unit that is trimmed away completely: nothing is emitted, the stages move on (dropped_unit_advance) */
+static int render_dropped_unit(struct IAMF_Decoder *d, int ns, int rendered) {
+  const int fs = (int)d->frame_size;
+  iamf_hip_dmx_frame *fr[2] = {d->pre[0].h_dmx, d->pre[1].h_dmx};
+  iamf_hip_demix_frame *dm[2] = {d->pre[0].h_demix, d->pre[1].h_demix};
+  if (dropped_unit_advance(d, rendered, fr, dm)) {
+    /* the LFE generator's filter over the frame the reference rendered before it cut it (element 1's batch first: it is
+     * the earlier element of the presentation when both feed the generator) */
+    if (d->aux && d->aux_sig.lfe_hoa &&
+        iamf_hip_batch_lfe_advance(d->aux, d->h_in[1], (int64_t)element_in_channels(d->sel_el[1]) * fs, ns, d->stream, 0, 1))
+      return IAMF_ERR_INTERNAL;
+    if (d->cfg_sig.lfe_hoa &&
+        iamf_hip_batch_lfe_advance(d->batch, d->h_in[0], (int64_t)element_in_channels(d->sel_el[0]) * fs, ns, d->stream, 0, 1))
+      return IAMF_ERR_INTERNAL;
+    if ((d->cfg_sig.lfe_hoa || (d->aux && d->aux_sig.lfe_hoa)) && facade_wait(d)) return IAMF_ERR_INTERNAL; /* h_in is reused */
   }
-  s0 = (int)d->tu_trim_start;
-  keep = ns - s0 - (int)d->tu_trim_end;
-  if (keep <= 0) {
-    iamf_hip_dmx_frame *fr[2] = {d->pre[0].h_dmx, d->pre[1].h_dmx};
-    iamf_hip_demix_frame *dm[2] = {d->pre[0].h_demix, d->pre[1].h_demix};
-    if (dropped_unit_advance(d, ns, fr, dm)) {
-      /* the LFE generator's filter over the frame the reference rendered before it cut it (element 1's batch first: it is
-       * the earlier element of the presentation when both feed the generator) */
-      if (d->aux && d->aux_sig.lfe_hoa &&
-          iamf_hip_batch_lfe_advance(d->aux, d->h_in[1], (int64_t)element_in_channels(d->sel_el[1]) * fs, ns, d->stream, 0, 1))
-        return IAMF_ERR_INTERNAL;
-      if (d->cfg_sig.lfe_hoa &&
-          iamf_hip_batch_lfe_advance(d->batch, d->h_in[0], (int64_t)element_in_channels(d->sel_el[0]) * fs, ns, d->stream, 0, 1))
-        return IAMF_ERR_INTERNAL;
-      if ((d->cfg_sig.lfe_hoa || (d->aux && d->aux_sig.lfe_hoa)) && facade_wait(d)) return IAMF_ERR_INTERNAL; /* h_in is reused */
-    }
-    d->timestamp += fs;
-    return 0;
+  d->timestamp += fs;
+  return 0;
+}
+
+/* element 1 through its own batch -> f32 sample-frames -> planar, where `batch` reads its second element */
+static int render_aux_element(struct IAMF_Decoder *d, const ftu_window *w, int ramp1, float cgain1) {
+  iamf_hip_render_args b;
+  const Pre *q = &d->pre[1];
+  const int fs = (int)d->frame_size, keep = w->keep;
+  const float eg = ramp1 ? 1.f : cgain1, one = 1.f;
+  ftu_element_stage_args(&b, d->h_in[1], element_in_channels(d->sel_el[1]), fs, d->aux_sig.lfe_hoa, w->s0, w->te, keep,
+                         q->use_dmx ? q->h_dmx : 0, q->use_demix ? q->h_demix : 0, d->stream);
+  if (eg != d->aux_gain_set) {
+    if (iamf_hip_batch_set_gains(d->aux, &eg, &one, 0)) return IAMF_ERR_INTERNAL;
+    d->aux_gain_set = eg;
   }
-  meta_note_frame(d, s0, d->tu_trim_end);
-  /* mix gains of this frame */
-  {
-    const uint64_t pt = d->timestamp + (uint64_t)s0;
-    float el_def[2] = {db2lin(q_to_float(d->sel->el_gain_q[0], 8)), db2lin(q_to_float(d->sel->el_gain_q[1], 8))};
-    float og_def = db2lin(q_to_float(d->sel->out_gain_q, 8));
-    ramp[0] = mix_gain_unit(d->el_gain_p[0], el_def[0], pt, keep, (int)d->rate, &cgain[0], d->h_ramp[0]);
-    ramp[1] = d->sel->nel > 1 ? mix_gain_unit(d->el_gain_p[1], el_def[1], pt, keep, (int)d->rate, &cgain[1], d->h_ramp[1]) : 0;
-    ramp[2] = mix_gain_unit(d->out_gain_p, og_def, pt, keep, (int)d->rate, &cgain[2], d->h_ramp[2]);
-    if (d->sel->nel < 2) cgain[1] = 1.f;
-    for (int i = 0; i < 3; ++i) {
-      if (ramp[i] < 0) { /* unit refused: no gain at all */
-        ramp[i] = 0;
-        cgain[i] = 1.f;
-      }
-      if (!ramp[i] && i == 1) /* element 1 takes its constant through the ramp: x * positive constant is the same product */
-        for (int k = 0; k < keep; ++k) d->h_ramp[i][k] = cgain[i];
-    }
+  if (ramp1) {
+    memcpy(d->h_ramp[3], d->h_ramp[1], sizeof(float) * keep);
+    b.d_element_ramp = d->h_ramp[3];
   }
-  if (lp && ((s0 & 3) || (keep & 63) || ramp[0] || ramp[2])) { /* not a call of the fused kernel: the f32 form after all */
-    int r = unpack_element(d, 0);
-    if (r < 0) return r;
-    lp = 0;
+  b.ramp_stream_stride = fs;
+  for (int k = 0; k < keep; ++k) d->h_ramp[1][k] = 1.f; /* `batch` takes the frame as it is */
+  b.d_pcm = d->d_aux_il;
+  b.pcm_stream_stride_bytes = (int64_t)sizeof(float) * fs * d->out_channels;
+  if (iamf_hip_batch_render_ex(d->aux, &b) != keep) return IAMF_ERR_INTERNAL;
+  if (iamf_hip_deinterleave_f32(d->d_aux_il, 0, d->out_channels, 1, keep, d->d_aux_pl, 0, fs, d->stream)) return IAMF_ERR_INTERNAL;
+  return IAMF_OK;
+}
+
+/* the frame's launches: the packets themselves, the f32 form, or render (f32) -> resample -> loudness / limiter / pack.
+ * Returns the sample-frames in h_pcm, negative if a call failed */
+static int render_launch(struct IAMF_Decoder *d, iamf_hip_render_args *a, int lp, int s0) {
+  const int fs = (int)d->frame_size;
+  int n, n2;
+  if (!d->rs) {
+    a->d_pcm = d->h_pcm;
+    a->pcm_stream_stride_bytes = (int64_t)d->pcm_cap;
   }
-  /* An element that feeds the HOA LFE generator keeps its whole frame: the reference renders first and trims the result
-   * (IAMF_decoder.c:3424-3430), so the generator's filter runs over the trimmed samples too — the batch gets a pointer to
-   * the first kept sample and how many lie in front of and behind the call (iamf_hip_render_args::lfe_pre_samples). */
-  const int lfe0 = d->cfg_sig.lfe_hoa, lfe1 = d->aux && d->aux_sig.lfe_hoa;
-  if (!lp)
-    for (int e = 0; e < d->sel->nel; ++e) {
-      const int ch = element_in_channels(d->sel_el[e]);
-      if (s0 && !(e == 0 ? lfe0 : lfe1))
-        for (int c = 0; c < ch; ++c) memmove(d->h_in[e] + (size_t)c * fs, d->h_in[e] + (size_t)c * fs + s0, sizeof(float) * keep);
-    }
-  a.d_in = lp ? 0 : d->h_in[0] + (lfe0 ? s0 : 0);
-  if (lfe0) {
-    a.lfe_pre_samples = s0;
-    a.lfe_post_samples = (int)d->tu_trim_end;
-  }
-  a.in_stream_stride = a.in_frame_stride = (int64_t)element_in_channels(d->sel_el[0]) * fs;
-  if (d->sel->nel > 1 && !d->aux) {
-    a.d_in2 = d->h_in[1];
-    a.in2_stream_stride = a.in2_frame_stride = (int64_t)d->sel_el[1]->channels * fs;
-  }
-  /* constant gains go through iamf_frame_gain's rule (only if != 1 and > 0); ramps unconditionally */
-  {
-    float eg = ramp[0] ? 1.f : cgain[0], og = ramp[2] ? 1.f : cgain[2];
-    if (eg != d->gain_set[0] || og != d->gain_set[1]) {
-      if (iamf_hip_batch_set_gains(d->batch, &eg, &og, 0)) return IAMF_ERR_INTERNAL;
-      d->gain_set[0] = eg;
-      d->gain_set[1] = og;
-    }
-    if (ramp[0]) a.d_element_ramp = d->h_ramp[0];
-    if (ramp[2]) a.d_output_ramp = d->h_ramp[2];
-    if (d->sel->nel > 1) a.d_element2_ramp = d->h_ramp[1]; /* element 1: constant or ramp, both exact */
-  }
-  a.ramp_stream_stride = fs;
-  for (int k = 0; k < d->sel->nel; ++k) { /* in the order the reference renders its streams (dmx_shared_coefficients) */
-    const int e = d->sel->swapped ? d->sel->nel - 1 - k : k;
-    if (e == 0 || d->aux) pre_frame(d, e, d->pre[e].h_dmx, d->pre[e].h_demix);
-  }
-  if (d->pre[0].use_dmx) a.d_dmx_frames = d->pre[0].h_dmx;
-  if (d->pre[0].use_demix) {
-    a.d_demix_frames = d->pre[0].h_demix;
-    a.demix_sample0 = s0;
-  }
-  if (d->aux) { /* element 1 through its own batch -> f32 sample-frames -> planar, where `batch` reads its second element */
-    iamf_hip_render_args b;
-    const float eg = ramp[1] ? 1.f : cgain[1], one = 1.f;
-    int n1;
-    memset(&b, 0, sizeof(b));
-    b.d_in = d->h_in[1] + (lfe1 ? s0 : 0);
-    b.in_stream_stride = b.in_frame_stride = (int64_t)element_in_channels(d->sel_el[1]) * fs;
-    if (lfe1) {
-      b.lfe_pre_samples = s0;
-      b.lfe_post_samples = (int)d->tu_trim_end;
-    }
-    if (eg != d->aux_gain_set) {
-      if (iamf_hip_batch_set_gains(d->aux, &eg, &one, 0)) return IAMF_ERR_INTERNAL;
-      d->aux_gain_set = eg;
-    }
-    if (ramp[1]) {
-      memcpy(d->h_ramp[3], d->h_ramp[1], sizeof(float) * keep);
-      b.d_element_ramp = d->h_ramp[3];
-    }
-    b.ramp_stream_stride = fs;
-    for (int k = 0; k < keep; ++k) d->h_ramp[1][k] = 1.f; /* `batch` takes the frame as it is */
-    if (d->pre[1].use_dmx) b.d_dmx_frames = d->pre[1].h_dmx;
-    if (d->pre[1].use_demix) {
-      b.d_demix_frames = d->pre[1].h_demix;
-      b.demix_sample0 = s0;
-    }
-    b.n_frames = 1;
-    b.n_samples = keep < fs ? keep : 0;
-    b.stream = d->stream;
-    b.d_pcm = d->d_aux_il;
-    b.pcm_stream_stride_bytes = (int64_t)sizeof(float) * fs * d->out_channels;
-    n1 = iamf_hip_batch_render_ex(d->aux, &b);
-    if (n1 != keep) return IAMF_ERR_INTERNAL;
-    if (iamf_hip_deinterleave_f32(d->d_aux_il, 0, d->out_channels, 1, keep, d->d_aux_pl, 0, fs, d->stream)) return IAMF_ERR_INTERNAL;
-    a.d_in2 = d->d_aux_pl;
-    a.in2_stream_stride = a.in2_frame_stride = (int64_t)d->out_channels * fs;
-  }
-  a.n_frames = 1;
-  a.n_samples = keep < fs ? keep : 0;
-  a.stream = d->stream;
   if (lp) {
     iamf_hip_lpcm_input in;
     memset(&in, 0, sizeof(in));
@@ -1887,28 +1857,91 @@ static int render_tu(struct IAMF_Decoder *d, void *pcm) {
     in.raw_stream_stride = in.raw_frame_stride = (int64_t)d->lp_row_bytes;
     in.first_sample = s0;
     in.layout = d->lp_layout;
-    a.d_pcm = d->h_pcm;
-    a.pcm_stream_stride_bytes = (int64_t)d->pcm_cap;
-    n = iamf_hip_batch_render_lpcm(d->batch, &in, &a);
-  } else if (!d->rs) {
-    a.d_pcm = d->h_pcm;
-    a.pcm_stream_stride_bytes = (int64_t)d->pcm_cap;
-    n = iamf_hip_batch_render_ex(d->batch, &a);
-  } else { /* render (f32) -> resample -> loudness / limiter / pack */
-    int n2;
-    a.d_pcm = d->d_mid;
-    a.pcm_stream_stride_bytes = (int64_t)sizeof(float) * fs * d->out_channels;
-    n = iamf_hip_batch_render_ex(d->batch, &a);
-    if (n < 0) return IAMF_ERR_INTERNAL;
-    n2 = iamf_hip_resampler_process(d->rs, d->d_mid, (int64_t)fs * d->out_channels, n, d->d_res,
-                                    (int64_t)(iamf_hip_resampler_out_capacity(d->rs, fs) + 512) * d->out_channels, d->stream);
-    if (n2 < 0) return IAMF_ERR_INTERNAL;
-    n = n2 ? iamf_hip_batch_render(d->batch3, d->d_res, 0, d->out_channels, n2, d->h_pcm, (int64_t)d->pcm_cap, d->stream) : 0;
+    return iamf_hip_batch_render_lpcm(d->batch, &in, a);
   }
+  if (!d->rs) return iamf_hip_batch_render_ex(d->batch, a);
+  a->d_pcm = d->d_mid;
+  a->pcm_stream_stride_bytes = (int64_t)sizeof(float) * fs * d->out_channels;
+  n = iamf_hip_batch_render_ex(d->batch, a);
+  if (n < 0) return n;
+  n2 = iamf_hip_resampler_process(d->rs, d->d_mid, (int64_t)fs * d->out_channels, n, d->d_res,
+                                  (int64_t)(iamf_hip_resampler_out_capacity(d->rs, fs) + 512) * d->out_channels, d->stream);
+  if (n2 <= 0) return n2;
+  return iamf_hip_batch_render(d->batch3, d->d_res, 0, d->out_channels, n2, d->h_pcm, (int64_t)d->pcm_cap, d->stream);
+}
+
+static int render_tu(struct IAMF_Decoder *d, void *pcm) {
+  iamf_hip_render_args a;
+  ftu_window w;
+  const int fs = (int)d->frame_size, bytes = (int)d->bit_depth / 8, nel = d->sel->nel;
+  /* an element that feeds the HOA LFE generator keeps its whole frame (ftu_element_stage_args) */
+  const int lfe[2] = {d->cfg_sig.lfe_hoa, d->aux && d->aux_sig.lfe_hoa};
+  int ns = 0, n, rc, ramp[3];
+  float cgain[3], set[2];
+  int lp = d->lp_ok && !d->group; /* the packets go to the render kernel as they are (decided per frame below) */
+  if (lp) {
+    int r = stage_lpcm_row(d);
+    if (r < 0) return r;
+    ns = r;
+  } else {
+    for (int e = 0; e < nel; ++e) {
+      int r = unpack_element(d, e);
+      if (r < 0) return r;
+      ns = r;
+    }
+  }
+  /* iamf_frame_trim (IAMF_decoder.c:1361-1381): rendering is memoryless, so trimming the
+   * element PCM before the renderer equals trimming the rendered frame */
+  for (int e = 0; e < nel; ++e)
+    for (int s = 0; s < d->sel_el[e]->nsub; ++s) d->pkt_have[e][s] = 0;
+  rc = ftu_trim_window(ns, d->tu_trim_start, d->tu_trim_end, fs, &w);
+  if (rc < 0) { /* refused, and the stream time moves on (iamf_frame_trim :1364-1370, :3424-3428) */
+    d->timestamp += fs;
+    return IAMF_ERR_BAD_ARG;
+  }
+  if (rc == FTU_DROPPED) return render_dropped_unit(d, ns, w.rendered);
+  meta_note_frame(d, w.s0, d->tu_trim_end);
+  frame_gain_plan(d, w.s0, w.keep, d->h_ramp, ramp, cgain, set);
+  if (lp && ((w.s0 & 3) || (w.keep & 63) || ramp[0] || ramp[2])) { /* not a call of the fused kernel: the f32 form after all */
+    int r = unpack_element(d, 0);
+    if (r < 0) return r;
+    lp = 0;
+  }
+  if (!lp && w.s0)
+    for (int e = 0; e < nel; ++e) {
+      const int ch = element_in_channels(d->sel_el[e]);
+      for (int c = 0; c < ch && !lfe[e]; ++c)
+        memmove(d->h_in[e] + (size_t)c * fs, d->h_in[e] + (size_t)c * fs + w.s0, sizeof(float) * w.keep);
+    }
+  ftu_element_stage_args(&a, lp ? 0 : d->h_in[0], element_in_channels(d->sel_el[0]), fs, lfe[0], w.s0, w.te, w.keep,
+                         d->pre[0].use_dmx ? d->pre[0].h_dmx : 0, d->pre[0].use_demix ? d->pre[0].h_demix : 0, d->stream);
+  if (nel > 1 && !d->aux) {
+    a.d_in2 = d->h_in[1];
+    a.in2_stream_stride = a.in2_frame_stride = (int64_t)d->sel_el[1]->channels * fs;
+  }
+  if (set[0] != d->gain_set[0] || set[1] != d->gain_set[1]) { /* (iamf_hip_batch_set_gains synchronises: only on change) */
+    if (iamf_hip_batch_set_gains(d->batch, &set[0], &set[1], 0)) return IAMF_ERR_INTERNAL;
+    d->gain_set[0] = set[0];
+    d->gain_set[1] = set[1];
+  }
+  if (ramp[0]) a.d_element_ramp = d->h_ramp[0];
+  if (ramp[2]) a.d_output_ramp = d->h_ramp[2];
+  if (nel > 1) a.d_element2_ramp = d->h_ramp[1]; /* element 1: constant or ramp, both exact */
+  a.ramp_stream_stride = fs;
+  for (int k = 0; k < nel; ++k) { /* in the order the reference renders its streams (dmx_shared_coefficients) */
+    const int e = d->sel->swapped ? nel - 1 - k : k;
+    if (e == 0 || d->aux) pre_frame(d, e, d->pre[e].h_dmx, d->pre[e].h_demix);
+  }
+  if (d->aux) {
+    if (render_aux_element(d, &w, ramp[1], cgain[1])) return IAMF_ERR_INTERNAL;
+    a.d_in2 = d->d_aux_pl;
+    a.in2_stream_stride = a.in2_frame_stride = (int64_t)d->out_channels * fs;
+  }
+  n = render_launch(d, &a, lp, w.s0);
   if (n < 0) return IAMF_ERR_INTERNAL;
   if (facade_wait(d)) return IAMF_ERR_INTERNAL;
   if (n > 0) memcpy(pcm, d->h_pcm, ((size_t)n * d->pcm_stride + d->pcm_extra) * bytes);
-  params_time_elapse(d, (uint64_t)keep); /* IAMF_decoder.c:3471: the mixed frame's length */
+  params_time_elapse(d, (uint64_t)w.keep); /* IAMF_decoder.c:3471: the mixed frame's length */
   d->timestamp += fs;
   meta_note_output(d, n);
   return n;

@@ -57,7 +57,8 @@ struct iamf_hip_decoder_group {
   float *d_in[2];                 /* [n][ch][fs], written by the device unpacker */
   /* LPCM packets as uploaded: per element [n][raw_stride] bytes, sub-stream s of a handle at slot_off[s] */
   iamf_hip_lpcm_layout lay[2];
-  int nsub_eff[2], sub_w[2][MAX_SUBSTREAMS], slot_off[2][MAX_SUBSTREAMS];
+  const ftu_walk *walk[2];        /* handle 0's: the sub-streams of element e and their widths */
+  int slot_off[2][MAX_SUBSTREAMS];
   size_t raw_stride[2];
   uint8_t *h_raw[2];
   void *d_raw[2];
@@ -77,6 +78,7 @@ struct iamf_hip_decoder_group {
   int *action, *keep, *s0, *result, *rampf;  /* rampf: bit k = stage k is a per-sample ramp in this frame */
   int *te;                        /* samples trimmed off the END of the frame (the LFE generator's filter runs over them) */
   int lfe[2];                     /* element e feeds the HOA LFE generator: its frames are unpacked whole (group_prepare_tu) */
+  int rampu, unpacked;            /* of the round: stages applied through their ramp rows (bits); the device unpacker has run */
   int64_t *pos;                   /* samples the stream has consumed in the batch */
   const uint8_t *const *data;
   const int32_t *sizes;
@@ -239,56 +241,13 @@ static void group_join(iamf_hip_decoder_group *g) {
   pthread_mutex_unlock(&g->mu);
 }
 
-/* Where the device unpacker finds every channel of element ei (unpack_element's loop without the data): sub-stream s of a
- * handle is copied to a fixed slot of the handle's raw row; audio-layer order -> the renderer's channel order as there. */
+/* Where the device unpacker finds every channel of element ei: sub-stream s of a handle is copied to a fixed slot of the
+ * handle's raw row, behind the row's head (element_raw_layout: the single handle's packet row is laid out by the same) */
 static int group_build_layout(iamf_hip_decoder_group *g, const struct IAMF_Decoder *d, int ei) {
-  const Element *e = d->sel_el[ei];
-  const int bps = (int)d->sample_size / 8, fs = g->fs;
-  const int demix = d->pre[ei].use_demix;
-  const int nsub = demix ? d->pre[ei].demix_nsub : e->nsub;
-  int c = 0, lay = 0, lay_s0 = 0, off = kRawHead;
-  int ch_off[MAX_SUBSTREAMS * 2], ch_step[MAX_SUBSTREAMS * 2];
-  iamf_hip_lpcm_layout *L = &g->lay[ei];
-  if (nsub <= 0 || nsub > MAX_SUBSTREAMS || (fs & 3)) return 1;
-  for (int s = 0; s < nsub; ++s) {
-    int w;
-    if (demix) {
-      while (s >= lay_s0 + e->layer[lay].nsub) lay_s0 += e->layer[lay++].nsub;
-      w = s - lay_s0 < e->layer[lay].ncoupled ? 2 : 1;
-    } else {
-      w = ((e->type == AUDIO_ELEMENT_CHANNEL_BASED && s < e->nb_coupled) || (e->amb_projection && s < e->amb_coupled)) ? 2 : 1;
-    }
-    g->sub_w[ei][s] = w;
-    g->slot_off[ei][s] = off;
-    for (int k = 0; k < w; ++k) {
-      ch_off[c + k] = off + k * bps;
-      ch_step[c + k] = w * bps;
-    }
-    off += w * bps * fs;
-    c += w;
-  }
-  g->nsub_eff[ei] = nsub;
-  g->raw_stride[ei] = ((size_t)off + 255) & ~(size_t)255;
-  memset(L, 0, sizeof(*L));
-  L->sample_bytes = bps;
-  L->little_endian = d->little_endian;
-  L->frame_size = fs;
-  if (e->amb_projection || demix) { /* decoded channel order goes to the device: de-mapping / demixer run there */
-    L->channels = c;
-    if (c > IAMF_HIP_LPCM_MAX_CHANNELS || c > g->in_ch[ei]) return 1;
-    for (int l = 0; l < c; ++l) {
-      L->src_offset[l] = ch_off[l];
-      L->src_step[l] = ch_step[l];
-    }
-    return 0;
-  }
-  L->channels = e->channels;
-  if (e->channels > IAMF_HIP_LPCM_MAX_CHANNELS || e->channels > g->in_ch[ei]) return 1;
-  for (int p = 0; p < e->channels; ++p) {
-    const int src = e->type == AUDIO_ELEMENT_CHANNEL_BASED ? k_al_of_pl[e->layout][p] : e->amb_map[p];
-    L->src_offset[p] = src < c ? ch_off[src] : -1;
-    L->src_step[p] = src < c ? ch_step[src] : bps;
-  }
+  const int row = (g->fs & 3) ? -1 : element_raw_layout(d, ei, kRawHead, g->slot_off[ei], &g->lay[ei]);
+  if (row < 0 || g->lay[ei].channels > g->in_ch[ei]) return 1;
+  g->walk[ei] = &d->walk[ei];
+  g->raw_stride[ei] = ((size_t)row + 255) & ~(size_t)255;
   return 0;
 }
 
@@ -298,8 +257,8 @@ static int group_stage_raw(iamf_hip_decoder_group *g, int i, int ei) {
   const int bps = (int)d->sample_size / 8, fs = g->fs;
   uint8_t *row = g->h_raw[ei] + (size_t)i * g->raw_stride[ei];
   int ns = -1;
-  for (int s = 0; s < g->nsub_eff[ei]; ++s) {
-    const int w = g->sub_w[ei][s];
+  for (int s = 0; s < g->walk[ei]->nsub; ++s) {
+    const int w = g->walk[ei]->width[s];
     const int n = (int)(d->pkt_len[ei][s] / (uint32_t)(w * bps));
     if (ns < 0) ns = n;
     if (n != ns || n > fs) return IAMF_ERR_INVALID_PACKET;
@@ -309,7 +268,8 @@ static int group_stage_raw(iamf_hip_decoder_group *g, int i, int ei) {
   return ns;
 }
 
-/* what two handles must share to sit in one batch: everything setup_pipeline derives the batch from */
+/* what two handles must share to sit in one batch: everything build_stages derives the batches from, and the walk of
+ * their sub-streams (element_walk) */
 static int group_compatible(const struct IAMF_Decoder *a, const struct IAMF_Decoder *b) {
   if (a->frame_size != b->frame_size || a->rate != b->rate || a->out_rate != b->out_rate || a->sample_size != b->sample_size ||
       a->little_endian != b->little_endian || /* the batch's one unpack layout is built from handle 0's byte order */
@@ -438,211 +398,150 @@ void iamf_hip_decoder_group_destroy(iamf_hip_decoder_group *g) {
   free(g);
 }
 
-int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads, iamf_hip_decoder_group **out) {
-  iamf_hip_decoder_group *g;
-  struct IAMF_Decoder *d0;
-  iamf_hip_batch_config cfg;
-  if (!handles || n <= 0 || !out) return IAMF_ERR_BAD_ARG;
-  *out = 0;
+/* ---- iamf_hip_decoder_group_create's steps: validate, host arrays, stages, staging, threads ---- */
+
+static int group_validate(void *const *handles, int n) {
   for (int i = 0; i < n; ++i) {
     const struct IAMF_Decoder *d = (const struct IAMF_Decoder *)handles[i];
     if (!d) return IAMF_ERR_BAD_ARG;
     if (!d->configured || d->need_reconf || d->group || d->timestamp != 0 || d->flushed) return IAMF_ERR_INVALID_STATE;
-    if (d->rs_inherited) return IAMF_ERR_INVALID_STATE; /* its resampler carries an earlier IA sequence's history (setup_pipeline) */
+    if (d->rs_inherited) return IAMF_ERR_INVALID_STATE; /* its resampler carries an earlier IA sequence's history (inherit_resampler) */
     for (int k = 0; k < i; ++k)
       if (handles[k] == handles[i]) return IAMF_ERR_BAD_ARG;
   }
-  d0 = (struct IAMF_Decoder *)handles[0];
   for (int i = 1; i < n; ++i)
-    if (!group_compatible(d0, (const struct IAMF_Decoder *)handles[i])) return IAMF_ERR_BAD_ARG;
+    if (!group_compatible((const struct IAMF_Decoder *)handles[0], (const struct IAMF_Decoder *)handles[i])) return IAMF_ERR_BAD_ARG;
+  return IAMF_OK;
+}
 
-  g = (iamf_hip_decoder_group *)calloc(1, sizeof(*g));
-  if (!g) return IAMF_ERR_ALLOC_FAIL;
-  g->n = n;
+/* what the group knows of its handles' one topology (handle 0's), and its per-handle host arrays */
+static int group_alloc_host(iamf_hip_decoder_group *g, const struct IAMF_Decoder *d0) {
+  const size_t n = (size_t)g->n;
+  int ok = 1;
   g->fs = (int)d0->frame_size;
   g->nel = d0->sel->nel;
   g->bytes = (int)d0->bit_depth / 8;
-  g->d = (struct IAMF_Decoder **)calloc((size_t)n, sizeof(*g->d));
-  for (int sl = 0; sl < 2; ++sl) {
-    g->slot[sl].action = (int *)calloc((size_t)n, sizeof(int));
-    g->slot[sl].keep = (int *)calloc((size_t)n, sizeof(int));
-    g->slot[sl].s0 = (int *)calloc((size_t)n, sizeof(int));
-    g->slot[sl].result = (int *)calloc((size_t)n, sizeof(int));
-    g->slot[sl].rampf = (int *)calloc((size_t)n, sizeof(int));
-    g->slot[sl].te = (int *)calloc((size_t)n, sizeof(int));
-    g->slot[sl].pcm_out = (void **)calloc((size_t)n, sizeof(void *));
-    if (!g->slot[sl].action || !g->slot[sl].keep || !g->slot[sl].s0 || !g->slot[sl].result || !g->slot[sl].rampf ||
-        !g->slot[sl].te || !g->slot[sl].pcm_out) {
-      iamf_hip_decoder_group_destroy(g);
-      return IAMF_ERR_ALLOC_FAIL;
-    }
-  }
   g->lfe[0] = d0->cfg_sig.lfe_hoa;
   g->lfe[1] = d0->aux && d0->aux_sig.lfe_hoa;
-  g->pos = (int64_t *)calloc((size_t)n, sizeof(int64_t));
-  g->pos3 = (int64_t *)calloc((size_t)n, sizeof(int64_t));
   g->out_ch = d0->out_channels;
   g->limiter_on = d0->limiter_on;
+  g->d = (struct IAMF_Decoder **)calloc(n, sizeof(*g->d));
+  for (int sl = 0; sl < 2; ++sl) {
+    int **per[6] = {&g->slot[sl].action, &g->slot[sl].keep, &g->slot[sl].s0, &g->slot[sl].result, &g->slot[sl].rampf, &g->slot[sl].te};
+    for (int k = 0; k < 6; ++k) ok &= (*per[k] = (int *)calloc(n, sizeof(int))) != 0;
+    ok &= (g->slot[sl].pcm_out = (void **)calloc(n, sizeof(void *))) != 0;
+  }
+  g->pos = (int64_t *)calloc(n, sizeof(int64_t));
+  g->pos3 = (int64_t *)calloc(n, sizeof(int64_t));
   g->gain_cur = (float *)malloc(sizeof(float) * 2 * n);
   g->gain_new = (float *)malloc(sizeof(float) * 2 * n);
-  if (!g->d || !g->pos || !g->pos3 || !g->gain_cur || !g->gain_new) {
-    iamf_hip_decoder_group_destroy(g);
-    return IAMF_ERR_ALLOC_FAIL;
+  return ok && g->d && g->pos && g->pos3 && g->gain_cur && g->gain_new ? IAMF_OK : IAMF_ERR_ALLOC_FAIL;
+}
+
+/* element 1's stage for n streams (aux_stage_create, as a handle's), with what a group launch of it reads */
+static int group_create_aux(iamf_hip_decoder_group *g, struct IAMF_Decoder *d0, const float *ones) {
+  const size_t n = (size_t)g->n, row = sizeof(float) * n * g->fs;
+  float *h1;
+  if (aux_stage_create(d0, g->n, 0, g->batch, ones, &g->aux, &g->d_aux_il, &g->d_aux_pl)) return 1;
+  if (hipMalloc((void **)&g->d_ones, row) != hipSuccess || hipMalloc((void **)&g->d_dmx1, sizeof(iamf_hip_dmx_frame) * n) != hipSuccess ||
+      hipMalloc((void **)&g->d_demix1, sizeof(iamf_hip_demix_frame) * n) != hipSuccess)
+    return 1;
+  for (int sl = 0; sl < 2; ++sl)
+    if (hipHostMalloc((void **)&g->slot[sl].h_dmx1, sizeof(iamf_hip_dmx_frame) * n, 0) != hipSuccess ||
+        hipHostMalloc((void **)&g->slot[sl].h_demix1, sizeof(iamf_hip_demix_frame) * n, 0) != hipSuccess)
+      return 1;
+  /* the ones, through the ramp rows' own upload path (h_ramp is not allocated yet: a scratch vector) */
+  if (!(h1 = (float *)malloc(row))) return 1;
+  for (size_t k = 0; k < n * g->fs; ++k) h1[k] = 1.f;
+  const int rc = hipMemcpy(g->d_ones, h1, row, hipMemcpyHostToDevice) != hipSuccess;
+  free(h1);
+  return rc;
+}
+
+/* the stages behind the render batch for n streams (last_stage_create, as a handle's) and the buffers between them.
+ * Loudness belongs to the last stage: ones[n ..] go there and are 1 afterwards, for the render batch */
+static int group_create_last(iamf_hip_decoder_group *g, const struct IAMF_Decoder *d0, float *ones) {
+  const int n = g->n;
+  if (last_stage_create(d0, n, &g->rs, &g->batch3)) return 1;
+  g->mid_stride = (int64_t)g->fs * g->out_ch;
+  g->res_stride = (int64_t)(iamf_hip_resampler_out_capacity(g->rs, g->fs) + iamf_hip_resampler_flush_capacity(g->rs) + 512) * g->out_ch;
+  if (hipMalloc((void **)&g->d_mid, sizeof(float) * (size_t)n * g->mid_stride) != hipSuccess ||
+      hipMalloc((void **)&g->d_res, sizeof(float) * (size_t)n * g->res_stride) != hipSuccess)
+    return 1;
+  if (iamf_hip_batch_set_gains(g->batch3, ones, ones, ones + n) || !(g->loud3 = (float *)malloc(sizeof(float) * (size_t)n))) return 1;
+  for (int i = 0; i < n; ++i) {
+    g->loud3[i] = ones[n + i];
+    ones[n + i] = 1.f;
   }
-#define GCHK(x)                              \
-  do {                                       \
-    if (x) {                                 \
-      iamf_hip_decoder_group_destroy(g);     \
-      return IAMF_ERR_INTERNAL;              \
-    }                                        \
-  } while (0)
-  /* the batch of setup_pipeline, for n streams */
-  cfg = d0->cfg_sig;
+  return 0;
+}
+
+/* the handles' batches, for n streams: the render batch (build_stages) with element 0's stage, element 1's, the last */
+static int group_create_stages(iamf_hip_decoder_group *g, void *const *handles) {
+  struct IAMF_Decoder *d0 = (struct IAMF_Decoder *)handles[0];
+  iamf_hip_batch_config cfg = d0->cfg_sig;
+  const int n = g->n;
+  float *ones;
+  int rc = 0;
   cfg.n_streams = n;
   cfg.matrix.mat = d0->cfg_mat;
-  GCHK(iamf_hip_batch_create(&cfg, &g->batch));
-  if (d0->sel_el[0]->amb_projection)
-    GCHK(iamf_hip_batch_set_projection(g->batch, d0->sel_el[0]->proj, element_in_channels(d0->sel_el[0])));
-  if (d0->pre[0].use_demix) GCHK(iamf_hip_batch_set_demixer(g->batch, &d0->pre[0].dc_sig));
-  {
-    float *ones = (float *)malloc(sizeof(float) * 2 * n);
-    int rc = 0;
-    if (!ones) GCHK(1);
-    for (int i = 0; i < n; ++i) {
-      ones[i] = 1.f;
-      ones[n + i] = db2lin(((struct IAMF_Decoder *)handles[i])->norm_loudness - ((struct IAMF_Decoder *)handles[i])->mix_loudness);
-    }
-    if (g->nel == 2 && !d0->aux) {
-      iamf_hip_matrix m2;
-      rc = element_matrix(d0, d0->sel_el[1], &m2) || iamf_hip_batch_set_second_element(g->batch, &m2, ones);
-    }
-    if (d0->aux) { /* setup_pipeline's second batch, for n streams */
-      iamf_hip_batch_config ca = d0->aux_sig;
-      iamf_hip_matrix m2;
-      float eye[24 * 24];
-      const int oc = d0->out_channels;
-      const size_t fr = (size_t)n * g->fs * oc;
-      ca.n_streams = n;
-      ca.matrix.mat = d0->aux_mat;
-      rc = iamf_hip_batch_create(&ca, &g->aux);
-      if (!rc && ca.lfe_hoa && iamf_hip_batch_share_lfe_state(g->aux, g->batch) == IAMF_HIP_ERR_INVALID_STATE) rc = 1;
-      if (!rc && d0->sel_el[1]->amb_projection)
-        rc = iamf_hip_batch_set_projection(g->aux, d0->sel_el[1]->proj, element_in_channels(d0->sel_el[1]));
-      if (!rc && d0->pre[1].use_demix) rc = iamf_hip_batch_set_demixer(g->aux, &d0->pre[1].dc_sig);
-      rc = rc || iamf_hip_batch_set_gains(g->aux, ones, ones, 0);
-      for (int i = 0; i < oc; ++i)
-        for (int j = 0; j < oc; ++j) eye[i * oc + j] = i == j ? 1.f : 0.f;
-      memset(&m2, 0, sizeof(m2));
-      m2.kind = IAMF_HIP_KIND_M2M;
-      m2.m = m2.n = m2.channels = oc;
-      m2.lfe1 = m2.lfe2 = -1;
-      m2.mat = eye;
-      rc = rc || iamf_hip_batch_set_second_element(g->batch, &m2, ones);
-      rc = rc || hipMalloc((void **)&g->d_aux_il, sizeof(float) * fr) != hipSuccess ||
-           hipMalloc((void **)&g->d_aux_pl, sizeof(float) * fr) != hipSuccess ||
-           hipMalloc((void **)&g->d_ones, sizeof(float) * (size_t)n * g->fs) != hipSuccess ||
-           hipHostMalloc((void **)&g->slot[0].h_dmx1, sizeof(iamf_hip_dmx_frame) * (size_t)n, 0) != hipSuccess ||
-           hipHostMalloc((void **)&g->slot[1].h_dmx1, sizeof(iamf_hip_dmx_frame) * (size_t)n, 0) != hipSuccess ||
-           hipMalloc((void **)&g->d_dmx1, sizeof(iamf_hip_dmx_frame) * (size_t)n) != hipSuccess ||
-           hipHostMalloc((void **)&g->slot[0].h_demix1, sizeof(iamf_hip_demix_frame) * (size_t)n, 0) != hipSuccess ||
-           hipHostMalloc((void **)&g->slot[1].h_demix1, sizeof(iamf_hip_demix_frame) * (size_t)n, 0) != hipSuccess ||
-           hipMalloc((void **)&g->d_demix1, sizeof(iamf_hip_demix_frame) * (size_t)n) != hipSuccess;
-      if (!rc) { /* the ones, through the ramp rows' own upload path (h_ramp is not allocated yet: a scratch vector) */
-        float *h1 = (float *)malloc(sizeof(float) * (size_t)n * g->fs);
-        rc = !h1;
-        for (size_t k = 0; h1 && k < (size_t)n * g->fs; ++k) h1[k] = 1.f;
-        rc = rc || hipMemcpy(g->d_ones, h1, sizeof(float) * (size_t)n * g->fs, hipMemcpyHostToDevice) != hipSuccess;
-        free(h1);
-      }
-    }
-    if (d0->rs) { /* the stages behind the render batch, as setup_pipeline builds them for one stream */
-      float eye[24 * 24];
-      iamf_hip_batch_config c3;
-      const int oc = d0->out_channels;
-      for (int i = 0; i < oc; ++i)
-        for (int j = 0; j < oc; ++j) eye[i * oc + j] = i == j ? 1.f : 0.f;
-      rc = rc || iamf_hip_resampler_create(n, oc, (int)d0->rate, (int)d0->out_rate, &g->rs);
-      memset(&c3, 0, sizeof(c3));
-      c3.n_streams = n;
-      c3.frame_size = 1; /* interleaved f32 in */
-      c3.sample_rate = (int32_t)d0->out_rate;
-      c3.out_channels = oc;
-      c3.out_format = (int32_t)d0->bit_depth;
-      c3.pcm_stride_channels = d0->pcm_stride;
-      c3.matrix.kind = IAMF_HIP_KIND_M2M;
-      c3.matrix.m = c3.matrix.n = c3.matrix.channels = oc;
-      c3.matrix.lfe1 = c3.matrix.lfe2 = -1;
-      c3.matrix.mat = eye;
-      c3.limiter_enable = d0->limiter_on;
-      c3.limiter_threshold_db = d0->limiter_db;
-      c3.loudness_enable = d0->norm_loudness != 0.f;
-      c3.projection = IAMF_HIP_PROJ_EXACT;
-      rc = rc || iamf_hip_batch_create(&c3, &g->batch3);
-      if (!rc) {
-        g->mid_stride = (int64_t)g->fs * oc;
-        g->res_stride = (int64_t)(iamf_hip_resampler_out_capacity(g->rs, g->fs) + iamf_hip_resampler_flush_capacity(g->rs) + 512) * oc;
-        rc = hipMalloc((void **)&g->d_mid, sizeof(float) * (size_t)n * g->mid_stride) != hipSuccess ||
-             hipMalloc((void **)&g->d_res, sizeof(float) * (size_t)n * g->res_stride) != hipSuccess;
-      }
-      /* loudness belongs to the last stage; the render batch applies the element / output gains only */
-      rc = rc || iamf_hip_batch_set_gains(g->batch3, ones, ones, ones + n);
-      g->loud3 = (float *)malloc(sizeof(float) * (size_t)n);
-      rc = rc || !g->loud3;
-      for (int i = 0; i < n && g->loud3; ++i) g->loud3[i] = ones[n + i];
-      for (int i = 0; i < n && !rc; ++i) ones[n + i] = 1.f;
-    }
-    rc = rc || iamf_hip_batch_set_gains(g->batch, ones, ones, ones + n);
-    for (int i = 0; i < 2 * n; ++i) g->gain_cur[i] = 1.f;
-    free(ones);
-    GCHK(rc);
+  if (iamf_hip_batch_create(&cfg, &g->batch) || stage_attach(d0, 0, g->batch)) return 1;
+  if (!(ones = (float *)malloc(sizeof(float) * 2 * n))) return 1;
+  for (int i = 0; i < n; ++i) {
+    ones[i] = 1.f;
+    ones[n + i] = db2lin(((struct IAMF_Decoder *)handles[i])->norm_loudness - ((struct IAMF_Decoder *)handles[i])->mix_loudness);
   }
-  GCHK(hipStreamCreate(&g->stream) != hipSuccess);
+  if (g->nel == 2 && !d0->aux) {
+    iamf_hip_matrix m2;
+    rc = element_matrix(d0, d0->sel_el[1], &m2) || iamf_hip_batch_set_second_element(g->batch, &m2, ones);
+  }
+  if (!rc && d0->aux) rc = group_create_aux(g, d0, ones);
+  if (!rc && d0->rs) rc = group_create_last(g, d0, ones);
+  rc = rc || iamf_hip_batch_set_gains(g->batch, ones, ones, ones + n);
+  for (int i = 0; i < 2 * n; ++i) g->gain_cur[i] = 1.f;
+  free(ones);
+  return rc;
+}
+
+/* the stream, the device buffers of a round and the pinned rows of its two slots; the handles' packets go straight to
+ * their rows from here on */
+static int group_alloc_staging(iamf_hip_decoder_group *g, void *const *handles) {
+  struct IAMF_Decoder *d0 = (struct IAMF_Decoder *)handles[0];
+  const size_t n = (size_t)g->n;
+  if (hipStreamCreate(&g->stream) != hipSuccess) return 1;
   for (int e = 0; e < g->nel; ++e) {
     g->in_ch[e] = element_in_channels(d0->sel_el[e]);
-    GCHK(group_build_layout(g, d0, e));
-    GCHK(hipMalloc((void **)&g->d_in[e], sizeof(float) * (size_t)n * g->in_ch[e] * g->fs) != hipSuccess);
+    if (group_build_layout(g, d0, e)) return 1;
     /* rows of channels that no sub-stream carries in a projection / demixer element are never written: keep them defined */
-    GCHK(hipMemset(g->d_in[e], 0, sizeof(float) * (size_t)n * g->in_ch[e] * g->fs) != hipSuccess);
+    if (hipMalloc((void **)&g->d_in[e], sizeof(float) * n * g->in_ch[e] * g->fs) != hipSuccess ||
+        hipMemset(g->d_in[e], 0, sizeof(float) * n * g->in_ch[e] * g->fs) != hipSuccess)
+      return 1;
     for (int sl = 0; sl < 2; ++sl) {
-      GCHK(hipHostMalloc((void **)&g->slot[sl].h_raw[e], g->raw_stride[e] * (size_t)n, 0) != hipSuccess);
-      memset(g->slot[sl].h_raw[e], 0, g->raw_stride[e] * (size_t)n);
+      if (hipHostMalloc((void **)&g->slot[sl].h_raw[e], g->raw_stride[e] * n, 0) != hipSuccess) return 1;
+      memset(g->slot[sl].h_raw[e], 0, g->raw_stride[e] * n);
     }
-    GCHK(hipMalloc(&g->d_raw[e], g->raw_stride[e] * (size_t)n) != hipSuccess);
+    if (hipMalloc(&g->d_raw[e], g->raw_stride[e] * n) != hipSuccess) return 1;
   }
-  /* One mono-coded ambisonics element in 16-bit or 24-bit little-endian LPCM into one or two channels with the limiter on: the
-   * headline kernel reads the packets themselves (iamf_hip_batch_render_lpcm_range, fused: no unpacked copy, no unpack
-   * launch).  The library decides per call (and falls back to its own unpacker); this only says when asking is worth it. */
-  g->lp_ok = g->nel == 1 && !d0->pre[0].use_dmx && !d0->pre[0].use_demix && !d0->sel_el[0]->amb_projection &&
-             (d0->sample_size == 16 || d0->sample_size == 24) &&
-             d0->little_endian && d0->limiter_on && d0->out_channels <= 2 && d0->pcm_stride == d0->out_channels &&
-             (g->fs & 63) == 0 && !d0->rs && !getenv("IAMF_HIP_GROUP_UNPACK");
-  /* ... or one single-layer channel-based element, 16 bit, that couples every pair of its layout (the kernel's coupled
-   * form: group_build_layout has laid the pairs out as it wants them) or is mono */
-  const int lp_chan = d0->sel_el[0]->type == AUDIO_ELEMENT_CHANNEL_BASED && d0->sel_el[0]->nlayers == 1 && d0->sample_size == 16 &&
-                      d0->sel_el[0]->nb_coupled == lp_canonical_coupled(d0->sel_el[0]->channels) &&
-                      d0->sel_el[0]->nsub + d0->sel_el[0]->nb_coupled == d0->sel_el[0]->channels;
-  if (d0->sel_el[0]->type != AUDIO_ELEMENT_SCENE_BASED && !lp_chan) g->lp_ok = 0;
-  /* (contiguous runs on the form's grid: 8 bytes for 16-bit samples, 4 for 24-bit ones; a coupled pair's run: 8 bytes) */
-  for (int c = 0; c < g->lay[0].channels && g->lp_ok; ++c) {
-    const int step = g->lay[0].src_step[c], off = g->lay[0].src_offset[c];
-    if (off < 0) g->lp_ok = 0;
-    else if (lp_chan && step == 4) g->lp_ok = ((off - (off & 2)) & 7) == 0;
-    else if (step != g->lay[0].sample_bytes || (off & (g->lay[0].sample_bytes == 3 ? 3 : 7))) g->lp_ok = 0;
-  }
-  for (int k = 0; k < 3; ++k) GCHK(!(g->cgain[k] = (float *)calloc((size_t)n, sizeof(float))));
-  /* upload chunks: at most eight per round, at least eight handles each (an upload call costs ~4 us of host time) */
-  g->chunk = (n + 7) / 8 < 8 ? 8 : (n + 7) / 8;
-  g->nchunks = (n + g->chunk - 1) / g->chunk;
-  GCHK(!(g->chunk_done = (int *)calloc((size_t)g->nchunks, sizeof(int))));
+  /* element 0's packets straight into the render kernel (iamf_hip_batch_render_lpcm_range: no unpacked copy, no unpack
+   * launch): when asking is worth it is the single handle's question too */
+  g->lp_ok = lp_worth_asking(d0, &g->lay[0], "IAMF_HIP_GROUP_UNPACK");
   for (int k = 0; k < 3; ++k)
-    GCHK(hipMalloc((void **)&g->d_ramp[k], sizeof(float) * (size_t)n * g->fs) != hipSuccess);
-  GCHK(hipMalloc((void **)&g->d_dmx, sizeof(iamf_hip_dmx_frame) * (size_t)n) != hipSuccess ||
-       hipMalloc((void **)&g->d_demix, sizeof(iamf_hip_demix_frame) * (size_t)n) != hipSuccess);
+    if (!(g->cgain[k] = (float *)calloc(n, sizeof(float)))) return 1;
+  /* upload chunks: at most eight per round, at least eight handles each (an upload call costs ~4 us of host time) */
+  g->chunk = (g->n + 7) / 8 < 8 ? 8 : (g->n + 7) / 8;
+  g->nchunks = (g->n + g->chunk - 1) / g->chunk;
+  if (!(g->chunk_done = (int *)calloc((size_t)g->nchunks, sizeof(int)))) return 1;
+  for (int k = 0; k < 3; ++k)
+    if (hipMalloc((void **)&g->d_ramp[k], sizeof(float) * n * g->fs) != hipSuccess) return 1;
+  if (hipMalloc((void **)&g->d_dmx, sizeof(iamf_hip_dmx_frame) * n) != hipSuccess ||
+      hipMalloc((void **)&g->d_demix, sizeof(iamf_hip_demix_frame) * n) != hipSuccess)
+    return 1;
   for (int sl = 0; sl < 2; ++sl) {
     for (int k = 0; k < 3; ++k)
-      GCHK(hipHostMalloc((void **)&g->slot[sl].h_ramp[k], sizeof(float) * (size_t)n * g->fs, 0) != hipSuccess);
-    GCHK(hipHostMalloc((void **)&g->slot[sl].h_dmx, sizeof(iamf_hip_dmx_frame) * (size_t)n, 0) != hipSuccess ||
-         hipHostMalloc((void **)&g->slot[sl].h_demix, sizeof(iamf_hip_demix_frame) * (size_t)n, 0) != hipSuccess);
+      if (hipHostMalloc((void **)&g->slot[sl].h_ramp[k], sizeof(float) * n * g->fs, 0) != hipSuccess) return 1;
+    if (hipHostMalloc((void **)&g->slot[sl].h_dmx, sizeof(iamf_hip_dmx_frame) * n, 0) != hipSuccess ||
+        hipHostMalloc((void **)&g->slot[sl].h_demix, sizeof(iamf_hip_demix_frame) * n, 0) != hipSuccess)
+      return 1;
   }
   /* one call emits at most one frame (or the 240-sample tail) per stream */
   g->pcm_cap = (size_t)g->bytes * ((size_t)(g->fs > 240 ? g->fs : 240) * d0->pcm_stride + d0->pcm_extra);
@@ -651,64 +550,86 @@ int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads,
     g->pcm_cap = (size_t)g->bytes * ((a > b ? a : b) * d0->pcm_stride + d0->pcm_extra);
   }
   g->pcm_cap = (g->pcm_cap + 255) & ~(size_t)255;
-  for (int sl = 0; sl < 2; ++sl) GCHK(hipHostMalloc((void **)&g->slot[sl].h_pcm, g->pcm_cap * n, 0) != hipSuccess);
-  GCHK(hipHostMalloc((void **)&g->h_sig, 64, 0) != hipSuccess);
+  for (int sl = 0; sl < 2; ++sl)
+    if (hipHostMalloc((void **)&g->slot[sl].h_pcm, g->pcm_cap * n, 0) != hipSuccess) return 1;
+  if (hipHostMalloc((void **)&g->h_sig, 64, 0) != hipSuccess) return 1;
   *g->h_sig = 0;
   group_use_slot(g, 0);
-  for (int i = 0; i < n; ++i) {
+  for (int i = 0; i < g->n; ++i) {
     struct IAMF_Decoder *d = (struct IAMF_Decoder *)handles[i];
     g->d[i] = d;
     d->group = g;
     for (int e = 0; e < g->nel; ++e) /* decode_parse copies a packet straight into its slot of the handle's row */
-      for (int s2 = 0; s2 < g->nsub_eff[e]; ++s2) {
+      for (int s2 = 0; s2 < g->walk[e]->nsub; ++s2) {
         d->pkt_ext[e][s2] = g->h_raw[e] + (size_t)i * g->raw_stride[e] + g->slot_off[e][s2];
-        d->pkt_ext_cap[e][s2] = (uint32_t)(g->sub_w[e][s2] * ((int)d->sample_size / 8) * g->fs);
+        d->pkt_ext_cap[e][s2] = (uint32_t)(g->walk[e]->width[s2] * ((int)d->sample_size / 8) * g->fs);
         d->pkt_in_ext[e][s2] = 0;
       }
   }
-  /* host threads: 0 = as many as the process may run on (its CPU quota less two), at most 16 and at most one per 4 handles */
-  {
-    int nt = host_threads;
-    if (nt <= 0) {
-      long c = sysconf(_SC_NPROCESSORS_ONLN);
-      FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r"); /* a container's CPU quota: workers that poll beyond it get the whole group throttled */
-      if (f) {
-        long q = 0, per = 0;
-        if (fscanf(f, "%ld %ld", &q, &per) == 2 && q > 0 && per > 0 && q / per < c) c = q / per;
-        fclose(f);
-      }
-      c -= 2; /* the calling thread and the HIP runtime's own */
-      nt = c > 16 ? 16 : (c < 1 ? 1 : (int)c);
+  return 0;
+}
+
+/* host threads: 0 = as many as the process may run on (its CPU quota less two), at most 16 and at most one per 4 handles */
+static int group_start_threads(iamf_hip_decoder_group *g, int host_threads) {
+  int nt = host_threads;
+  if (nt <= 0) {
+    long c = sysconf(_SC_NPROCESSORS_ONLN);
+    FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r"); /* a container's CPU quota: workers that poll beyond it get the whole group throttled */
+    if (f) {
+      long q = 0, per = 0;
+      if (fscanf(f, "%ld %ld", &q, &per) == 2 && q > 0 && per > 0 && q / per < c) c = q / per;
+      fclose(f);
     }
-    if (nt > (n + 3) / 4) nt = (n + 3) / 4;
-    g->nthreads = nt - 1; /* the calling thread is one of them */
-    if (g->nthreads > 0) {
-      pthread_mutex_init(&g->mu, 0);
-      pthread_cond_init(&g->cv_work, 0);
-      pthread_cond_init(&g->cv_done, 0);
-      g->threads = (pthread_t *)calloc((size_t)g->nthreads, sizeof(pthread_t));
-      if (!g->threads) GCHK(1);
-      for (int t = 0; t < g->nthreads; ++t)
-        if (pthread_create(&g->threads[t], 0, group_worker, g)) {
-          g->nthreads = t;
-          GCHK(1);
-        }
-    }
+    c -= 2; /* the calling thread and the HIP runtime's own */
+    nt = c > 16 ? 16 : (c < 1 ? 1 : (int)c);
   }
-#undef GCHK
+  if (nt > (g->n + 3) / 4) nt = (g->n + 3) / 4;
+  g->nthreads = nt - 1; /* the calling thread is one of them */
+  if (g->nthreads <= 0) return 0;
+  pthread_mutex_init(&g->mu, 0);
+  pthread_cond_init(&g->cv_work, 0);
+  pthread_cond_init(&g->cv_done, 0);
+  g->threads = (pthread_t *)calloc((size_t)g->nthreads, sizeof(pthread_t));
+  if (!g->threads) return 1;
+  for (int t = 0; t < g->nthreads; ++t)
+    if (pthread_create(&g->threads[t], 0, group_worker, g)) {
+      g->nthreads = t;
+      return 1;
+    }
+  return 0;
+}
+
+int iamf_hip_decoder_group_create(void *const *handles, int n, int host_threads, iamf_hip_decoder_group **out) {
+  iamf_hip_decoder_group *g;
+  int rc;
+  if (!handles || n <= 0 || !out) return IAMF_ERR_BAD_ARG;
+  *out = 0;
+  if ((rc = group_validate(handles, n))) return rc;
+  g = (iamf_hip_decoder_group *)calloc(1, sizeof(*g));
+  if (!g) return IAMF_ERR_ALLOC_FAIL;
+  g->n = n;
+  rc = group_alloc_host(g, (const struct IAMF_Decoder *)handles[0]);
+  if (!rc && (group_create_stages(g, handles) || group_alloc_staging(g, handles) || group_start_threads(g, host_threads)))
+    rc = IAMF_ERR_INTERNAL;
+  if (rc) {
+    iamf_hip_decoder_group_destroy(g);
+    return rc;
+  }
   *out = g;
   return IAMF_OK;
 }
 
-/* The host half of render_tu for handle i: unpacking, trimming, this frame's gains and parameter records go to the
- * group's staging rows.  Returns 1 if the stream has a frame to render (g->keep / g->s0 / g->rampf set), else the value
- * IAMF_decoder_decode returns for this call (0 or an error). */
+/* The host half of a temporal unit for handle i — render_tu's, up to its launches, over the same pieces (ftu_trim_window,
+ * dropped_unit_advance, frame_gain_plan, pre_frame): packets, trim, this frame's gains and parameter records go to the
+ * group's staging rows.  Returns 1 if the stream has a frame to render (g->keep / g->s0 / g->rampf set), 2 if only the LFE
+ * generator's filter runs, else the value IAMF_decoder_decode returns for this call (0 or an error). */
 static int group_prepare_tu(iamf_hip_decoder_group *g, int i) {
   struct IAMF_Decoder *d = g->d[i];
   const int fs = g->fs;
-  int ns = 0, keep, s0;
-  float cgain[3];
-  int ramp[3] = {0, 0, 0};
+  ftu_window w;
+  int ns = 0, rc, ramp[3];
+  float cgain[3], set[2];
+  float *row[3] = {g->h_ramp[0] + (size_t)i * fs, g->h_ramp[1] + (size_t)i * fs, g->h_ramp[2] + (size_t)i * fs};
   for (int e = 0; e < d->sel->nel; ++e) {
     int r = group_stage_raw(g, i, e);
     if (r < 0) return r;
@@ -716,78 +637,52 @@ static int group_prepare_tu(iamf_hip_decoder_group *g, int i) {
   }
   for (int e = 0; e < d->sel->nel; ++e)
     for (int s = 0; s < d->sel_el[e]->nsub; ++s) d->pkt_have[e][s] = 0;
-  if (d->tu_trim_start > (uint64_t)ns || d->tu_trim_end > (uint64_t)ns || d->tu_trim_start + d->tu_trim_end > (uint64_t)ns) {
+  rc = ftu_trim_window(ns, d->tu_trim_start, d->tu_trim_end, fs, &w);
+  if (rc < 0) {
     d->timestamp += fs;
     return IAMF_ERR_BAD_ARG;
   }
-  s0 = (int)d->tu_trim_start;
-  keep = ns - s0 - (int)d->tu_trim_end;
-  if (keep <= 0) { /* nothing is emitted, but the reference has decoded and (mostly) rendered the unit: dropped_unit_advance */
+  if (rc == FTU_DROPPED) { /* nothing is emitted, but the reference has decoded and (mostly) rendered the unit */
     iamf_hip_dmx_frame *fr[2] = {&g->h_dmx[i], g->aux ? &g->h_dmx1[i] : 0};
     iamf_hip_demix_frame *dm[2] = {&g->h_demix[i], g->aux ? &g->h_demix1[i] : 0};
-    const int rendered = dropped_unit_advance(d, ns, fr, dm);
+    const int rendered = dropped_unit_advance(d, w.rendered, fr, dm);
     d->timestamp += fs;
-    if (rendered && (g->lfe[0] || g->lfe[1])) { /* the generator's filter runs over the whole frame: unpacked whole, no render */
-      for (int e = 0; e < d->sel->nel; ++e) {
-        int32_t *head = (int32_t *)(g->h_raw[e] + (size_t)i * g->raw_stride[e]);
-        head[0] = 0;
-        head[1] = g->lfe[e] ? ns : 0;
-      }
-      g->keep[i] = 0;
-      g->s0[i] = 0;
-      g->te[i] = ns;
-      return 2;
+    if (!rendered || !(g->lfe[0] || g->lfe[1])) return 0;
+    for (int e = 0; e < d->sel->nel; ++e) { /* the generator's filter runs over the whole frame: unpacked whole, no render */
+      int32_t *head = (int32_t *)(g->h_raw[e] + (size_t)i * g->raw_stride[e]);
+      head[0] = 0;
+      head[1] = g->lfe[e] ? ns : 0;
     }
-    return 0;
+    g->keep[i] = 0;
+    g->s0[i] = 0;
+    g->te[i] = ns;
+    return 2;
   }
-  meta_note_frame(d, s0, d->tu_trim_end);
+  meta_note_frame(d, w.s0, d->tu_trim_end);
   for (int e = 0; e < d->sel->nel; ++e) { /* iamf_frame_trim: the device unpacker starts at the first kept sample */
     int32_t *head = (int32_t *)(g->h_raw[e] + (size_t)i * g->raw_stride[e]);
-    /* ... except for an element that feeds the LFE generator, whose filter runs over the whole frame (render_tu) */
-    head[0] = g->lfe[e] ? 0 : s0;
-    head[1] = g->lfe[e] ? ns : keep;
+    /* ... except for an element that feeds the LFE generator, whose filter runs over the whole frame (ftu_element_stage_args) */
+    head[0] = g->lfe[e] ? 0 : w.s0;
+    head[1] = g->lfe[e] ? ns : w.keep;
   }
-  g->te[i] = (int)d->tu_trim_end;
-  {
-    const uint64_t pt = d->timestamp + (uint64_t)s0;
-    float el_def[2] = {db2lin(q_to_float(d->sel->el_gain_q[0], 8)), db2lin(q_to_float(d->sel->el_gain_q[1], 8))};
-    float og_def = db2lin(q_to_float(d->sel->out_gain_q, 8));
-    float *row[3] = {g->h_ramp[0] + (size_t)i * fs, g->h_ramp[1] + (size_t)i * fs, g->h_ramp[2] + (size_t)i * fs};
-    ramp[0] = mix_gain_unit(d->el_gain_p[0], el_def[0], pt, keep, (int)d->rate, &cgain[0], row[0]);
-    ramp[1] = d->sel->nel > 1 ? mix_gain_unit(d->el_gain_p[1], el_def[1], pt, keep, (int)d->rate, &cgain[1], row[1]) : 0;
-    ramp[2] = mix_gain_unit(d->out_gain_p, og_def, pt, keep, (int)d->rate, &cgain[2], row[2]);
-    if (d->sel->nel < 2) cgain[1] = 1.f;
-    g->rampf[i] = 0;
-    for (int k = 0; k < 3; ++k) {
-      if (ramp[k] < 0) { /* unit refused: no gain at all */
-        ramp[k] = 0;
-        cgain[k] = 1.f;
-      }
-      if (ramp[k]) g->rampf[i] |= 1 << k;
-    }
-    /* a constant gain is applied only if != 1 and > 0 (iamf_frame_gain, IAMF_decoder.c:1392-1397): as a row of a ramp
-     * launch it is that constant or exactly 1, which multiplies to the same bits.  The row is written only if some
-     * handle of the round is on a ramp in that stage (group_fill_constant_rows, once all are parsed); element 1 always
-     * takes its gain through its row */
-    for (int k = 0; k < 3; ++k)
-      if (!ramp[k]) {
-        const float c = (k == 1 || (cgain[k] != 1.f && cgain[k] > 0.f)) ? cgain[k] : 1.f;
-        g->cgain[k][i] = c;
-        if (k == 1 && d->sel->nel > 1)
-          for (int j = 0; j < keep; ++j) row[k][j] = c;
-      }
-    g->gain_new[i] = ramp[0] ? 1.f : cgain[0];
-    g->gain_new[g->n + i] = ramp[2] ? 1.f : cgain[2];
-  }
+  /* A constant gain travels as a row only if some handle of the round is on a ramp in that stage: the row is written once
+   * all are parsed (group_upload_params) from g->cgain; element 1's row is always written (frame_gain_plan) */
+  frame_gain_plan(d, w.s0, w.keep, row, ramp, cgain, set);
+  g->rampf[i] = ramp[0] | ramp[1] << 1 | ramp[2] << 2; /* bit k = stage k is a per-sample ramp in this frame */
+  for (int k = 0; k < 3; ++k) g->cgain[k][i] = cgain[k];
+  g->gain_new[i] = set[0];
+  g->gain_new[g->n + i] = set[1];
   for (int k = 0; k < d->sel->nel; ++k) { /* in the order the reference renders its streams (dmx_shared_coefficients) */
     const int e = d->sel->swapped ? d->sel->nel - 1 - k : k;
     if (e == 0) pre_frame(d, 0, &g->h_dmx[i], &g->h_demix[i]);
     else if (g->aux) pre_frame(d, 1, &g->h_dmx1[i], &g->h_demix1[i]);
   }
-  g->keep[i] = keep;
-  g->s0[i] = s0;
+  g->keep[i] = w.keep;
+  g->s0[i] = w.s0;
+  g->te[i] = w.te;
   return 1;
 }
+
 
 /* the end of IAMF_decoder_decode for handle i: its PCM (the clocks have moved at submit, group_advance_clocks) */
 static void group_copy_out_one(iamf_hip_decoder_group *g, int i) {
@@ -826,7 +721,7 @@ static int group_parse_one(iamf_hip_decoder_group *g, int i) {
    * packets arrived over earlier calls has them in the slot of the handle's last submit (which a round in flight may
    * still upload from: it is only read here): they move along into this slot's row */
   for (int e = 0; e < g->nel; ++e)
-    for (int s2 = 0; s2 < g->nsub_eff[e]; ++s2) {
+    for (int s2 = 0; s2 < g->walk[e]->nsub; ++s2) {
       uint8_t *mine = g->h_raw[e] + (size_t)i * g->raw_stride[e] + g->slot_off[e][s2];
       if (d->pkt_ext[e][s2] == mine) continue;
       if (d->pkt_in_ext[e][s2] && d->pkt_have[e][s2]) memcpy(mine, d->pkt_ext[e][s2], d->pkt_len[e][s2]);
@@ -864,32 +759,23 @@ static int group_parse_one(iamf_hip_decoder_group *g, int i) {
  * exceptions synchronise themselves: iamf_hip_batch_set_gains waits for the batch's last render (quiesce) — in a round
  * whose constant gains change it therefore waits for the round before it, a bubble in the pipeline — and a buffer that
  * grows with the largest call seen is replaced after a hipStreamSynchronize. */
-static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes, uint32_t *rsizes,
-                              void *const *pcm, int32_t *results) {
-  int any_render = 0, any = 0, rampu = 0, gains_changed = 0;
-  const int n = g->n, fs = g->fs;
-  const int sl = (int)((g->issued + 1) & 1);
-  group_use_slot(g, sl);
-  memcpy(g->pcm_out, pcm, sizeof(void *) * (size_t)n);
-  g->slot[sl].dev = 0;
-  g->data = data;
-  g->sizes = sizes;
-  g->rsizes = rsizes;
-  double t0 = group_now(), t1;
+/* ---- group_submit_round's steps.  Each returns nonzero if a device call failed (the caller: group_fail) ---- */
+
+/* Parse, packet staging, parameter timelines: per handle, on the pool.  The calling thread uploads each chunk of rows
+ * as soon as the pool has completed it, so the PCIe time of chunk c lies beside the parsing of chunk c + 1 (256
+ * handles: 0.21 ms of host work and 0.17 ms of upload per round, one after the other before); it takes handles itself
+ * only when there is no pool.  The upload is a KERNEL that reads the pinned rows over PCIe (iamf_hip_upload_by_kernel):
+ * everything of a round stays on the compute queue.  Measured on the GPU box (tools/debug/copy_latency_probe.hip):
+ * a pinned hipMemcpyAsync costs 8-9 us per call on top of its bytes, a copy -> kernel -> copy sequence 22-26 us for the
+ * hand-overs between the copy engine and the compute queue, and a kernel reads pinned memory as fast as the engine
+ * copies it (8 MB + a kernel + the download: 172 us against 187).  For the same reason the render kernel writes its
+ * PCM straight into the pinned buffer the handles are served from: no download. */
+static int group_upload_chunks(iamf_hip_decoder_group *g) {
   int dev_err = 0;
-  /* Parse, packet staging, parameter timelines: per handle, on the pool.  The calling thread uploads each chunk of rows
-   * as soon as the pool has completed it, so the PCIe time of chunk c lies beside the parsing of chunk c + 1 (256
-   * handles: 0.21 ms of host work and 0.17 ms of upload per round, one after the other before); it takes handles itself
-   * only when there is no pool.  The upload is a KERNEL that reads the pinned rows over PCIe (iamf_hip_upload_by_kernel):
-   * everything of a round stays on the compute queue.  Measured on the GPU box (tools/debug/copy_latency_probe.hip):
-   * a pinned hipMemcpyAsync costs 8-9 us per call on top of its bytes, a copy -> kernel -> copy sequence 22-26 us for the
-   * hand-overs between the copy engine and the compute queue, and a kernel reads pinned memory as fast as the engine
-   * copies it (8 MB + a kernel + the download: 172 us against 187).  For the same reason the render kernel writes its
-   * PCM straight into the pinned buffer the handles are served from: no download. */
   group_start(g, 0);
   if (g->nthreads <= 0) group_help(g);
   for (int c = 0; c < g->nchunks; ++c) {
-    const int c0 = c * g->chunk, cn = c0 + g->chunk <= n ? g->chunk : n - c0;
+    const int c0 = c * g->chunk, cn = c0 + g->chunk <= g->n ? g->chunk : g->n - c0;
     int wanted = 0;
     for (int spin = 0; __atomic_load_n(&g->chunk_done[c], __ATOMIC_ACQUIRE) < cn; ++spin) {
       if (spin < kGroupSpin) group_relax(); else sched_yield();
@@ -902,6 +788,211 @@ static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *d
     }
   }
   group_join(g);
+  return dev_err;
+}
+
+/* what the round's render launches read beside the packets: ramp rows, stage records, constant gains */
+static int group_upload_params(iamf_hip_decoder_group *g, int gains_changed) {
+  const struct IAMF_Decoder *d0 = g->d[0];
+  const size_t n = (size_t)g->n;
+  /* a stage that is on a ramp in SOME stream is applied through its rows in all: the others' rows carry their constant */
+  for (int k = 0; k < 3; ++k)
+    if ((g->rampu >> k) & 1 && !(k == 1 && g->nel > 1))
+      for (int i = 0; i < g->n; ++i)
+        if (g->action[i] == GA_RENDER && !((g->rampf[i] >> k) & 1)) {
+          float *row = g->h_ramp[k] + (size_t)i * g->fs;
+          const float c = g->cgain[k][i];
+          for (int j = 0; j < g->keep[i]; ++j) row[j] = c;
+        }
+  if (g->nel > 1) g->rampu |= 2; /* element 1 takes its gain through its ramp row, constant or not */
+  for (int k = 0; k < 3; ++k)
+    if ((g->rampu >> k) & 1 &&
+        hipMemcpyAsync(g->d_ramp[k], g->h_ramp[k], sizeof(float) * n * g->fs, hipMemcpyHostToDevice, g->stream) != hipSuccess)
+      return 1;
+  if (d0->pre[0].use_dmx && hipMemcpyAsync(g->d_dmx, g->h_dmx, sizeof(iamf_hip_dmx_frame) * n, hipMemcpyHostToDevice, g->stream) != hipSuccess)
+    return 1;
+  if (d0->pre[0].use_demix && hipMemcpyAsync(g->d_demix, g->h_demix, sizeof(iamf_hip_demix_frame) * n, hipMemcpyHostToDevice, g->stream) != hipSuccess)
+    return 1;
+  if (g->aux && d0->pre[1].use_dmx && hipMemcpyAsync(g->d_dmx1, g->h_dmx1, sizeof(iamf_hip_dmx_frame) * n, hipMemcpyHostToDevice, g->stream) != hipSuccess)
+    return 1;
+  if (g->aux && d0->pre[1].use_demix && hipMemcpyAsync(g->d_demix1, g->h_demix1, sizeof(iamf_hip_demix_frame) * n, hipMemcpyHostToDevice, g->stream) != hipSuccess)
+    return 1;
+  if (gains_changed) { /* constant gains of the streams that are not on a ramp this time (synchronous, rare) */
+    if (iamf_hip_batch_set_gains(g->batch, g->gain_new, g->gain_new + n, 0)) return 1;
+    memcpy(g->gain_cur, g->gain_new, sizeof(float) * 2 * n);
+  }
+  return 0;
+}
+
+/* The device unpacker over every row, once per round and only if a launch reads its output (it is skipped when every
+ * launch reads the packets itself).  (Rows of chunks that had nothing to render were not uploaded: the device still holds
+ * their previous round's, and the unpacker may rewrite element PCM that no launch of this round reads) */
+static int group_unpack_once(iamf_hip_decoder_group *g) {
+  for (int e = 0; e < g->nel && !g->unpacked; ++e)
+    if (iamf_hip_lpcm_unpack(&g->lay[e], g->d_raw[e], (int64_t)g->raw_stride[e], (const int32_t *)g->d_raw[e],
+                             (int64_t)(g->raw_stride[e] / 4), g->d_in[e], (int64_t)g->in_ch[e] * g->fs, g->n, g->stream))
+      return 1;
+  g->unpacked = 1;
+  return 0;
+}
+
+/* the launchers, one per kind of run: streams [i, j) do the same thing from the same position */
+
+/* the LFE generator's filter over frames that are trimmed away completely (te = their length) */
+static int group_run_advance(iamf_hip_decoder_group *g, int i, int j) {
+  if (group_unpack_once(g)) return 1;
+  if (g->aux && g->lfe[1] && iamf_hip_batch_lfe_advance(g->aux, g->d_in[1], (int64_t)g->in_ch[1] * g->fs, g->te[i], g->stream, i, j - i))
+    return 1;
+  if (g->lfe[0] && iamf_hip_batch_lfe_advance(g->batch, g->d_in[0], (int64_t)g->in_ch[0] * g->fs, g->te[i], g->stream, i, j - i))
+    return 1;
+  for (int s = i; s < j; ++s) g->result[s] = 0;
+  return 0;
+}
+
+static int group_run_flush(iamf_hip_decoder_group *g, int i, int j) {
+  const int r = iamf_hip_batch_flush_range(g->batch, g->h_pcm, (int64_t)g->pcm_cap, g->stream, i, j - i);
+  for (int s = i; s < j && r >= 0; ++s) {
+    g->result[s] = r;
+    g->pos[s] += 240;
+  }
+  return r < 0;
+}
+
+/* n2 sample-frames per stream of the run behind the resampler through the last stage; returns what it emits */
+static int group_last_stage(iamf_hip_decoder_group *g, int i, int j, int n2) {
+  iamf_hip_render_args a3;
+  if (n2 <= 0) return 0;
+  ftu_last_stage_args(&a3, g->d_res, g->res_stride, g->out_ch, n2, g->h_pcm, (int64_t)g->pcm_cap, g->stream);
+  return iamf_hip_batch_render_range(g->batch3, &a3, i, j - i);
+}
+
+/* iamf_delay_buffer_handle, IAMF_decoder.c:3250-3301: the resampler's tail + the limiter's (flush_tail) */
+static int group_run_flush_resampled(iamf_hip_decoder_group *g, int i, int j) {
+  const int extra = g->limiter_on ? 240 : 0;
+  int n2, r;
+  if (hipMemsetAsync(g->d_res + (size_t)i * g->res_stride, 0, sizeof(float) * (size_t)(j - i) * g->res_stride, g->stream) != hipSuccess)
+    return 1;
+  n2 = iamf_hip_resampler_flush_range(g->rs, g->d_res, g->res_stride, g->stream, i, j - i);
+  if (n2 < 0) return 1;
+  if (g->d[i]->norm_loudness != 0.f) { /* the resampler's tail is not normalised (flush_tail; IAMF_decoder.c:3271-3287) */
+    for (int s = i; s < j; ++s) g->loud3[s] = 1.f;
+    if (iamf_hip_batch_set_gains(g->batch3, 0, 0, g->loud3)) return 1;
+  }
+  r = group_last_stage(g, i, j, n2 + extra);
+  for (int s = i; s < j && r >= 0; ++s) {
+    g->result[s] = r;
+    g->pos3[s] += n2 + extra;
+  }
+  return r < 0;
+}
+
+/* the run's packets straight into the render kernel: first kept sample s0, keep samples (uniform over the run) */
+static int group_run_lpcm(iamf_hip_decoder_group *g, int i, int j) {
+  iamf_hip_render_args a;
+  iamf_hip_lpcm_input in;
+  int r;
+  memset(&in, 0, sizeof(in));
+  in.d_raw = g->d_raw[0];
+  in.raw_stream_stride = in.raw_frame_stride = (int64_t)g->raw_stride[0];
+  in.first_sample = g->s0[i];
+  in.layout = g->lay[0];
+  ftu_element_stage_args(&a, 0, 0, g->fs, 0, g->s0[i], g->te[i], g->keep[i], 0, 0, g->stream);
+  a.d_pcm = g->h_pcm;
+  a.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
+  r = iamf_hip_batch_render_lpcm_range(g->batch, &in, &a, i, j - i);
+  for (int s = i; s < j && r >= 0; ++s) {
+    g->result[s] = r;
+    g->pos[s] += g->keep[s];
+  }
+  return r < 0;
+}
+
+/* the run from unpacked f32: element 1 through its own batch first (stage, matrix, its gain row -> planar f32), the render
+ * batch, and behind a resampler render (f32) -> resample -> loudness / limiter / pack — render_tu's launches, as ranges */
+static int group_run_f32(iamf_hip_decoder_group *g, int i, int j) {
+  const struct IAMF_Decoder *d0 = g->d[0];
+  const int fs = g->fs, s0 = g->s0[i], te = g->te[i], keep = g->keep[i];
+  iamf_hip_render_args a;
+  int r;
+  if (group_unpack_once(g)) return 1;
+  ftu_element_stage_args(&a, g->d_in[0], g->in_ch[0], fs, g->lfe[0], s0, te, keep, d0->pre[0].use_dmx ? g->d_dmx : 0,
+                         d0->pre[0].use_demix ? g->d_demix : 0, g->stream);
+  if (g->aux) {
+    iamf_hip_render_args b;
+    const int64_t st = (int64_t)fs * g->out_ch;
+    ftu_element_stage_args(&b, g->d_in[1], g->in_ch[1], fs, g->lfe[1], s0, te, keep, d0->pre[1].use_dmx ? g->d_dmx1 : 0,
+                           d0->pre[1].use_demix ? g->d_demix1 : 0, g->stream);
+    b.d_element_ramp = g->d_ramp[1];
+    b.ramp_stream_stride = fs;
+    b.d_pcm = g->d_aux_il;
+    b.pcm_stream_stride_bytes = (int64_t)sizeof(float) * st;
+    if (iamf_hip_batch_render_range(g->aux, &b, i, j - i) != keep) return 1;
+    if (iamf_hip_deinterleave_f32(g->d_aux_il + (int64_t)i * st, st, g->out_ch, j - i, keep, g->d_aux_pl + (int64_t)i * st, st, fs, g->stream))
+      return 1;
+    a.d_in2 = g->d_aux_pl;
+    a.in2_stream_stride = a.in2_frame_stride = st;
+    a.d_element2_ramp = g->d_ones;
+  } else if (g->nel > 1) {
+    a.d_in2 = g->d_in[1];
+    a.in2_stream_stride = a.in2_frame_stride = (int64_t)g->in_ch[1] * fs;
+    a.d_element2_ramp = g->d_ramp[1];
+  }
+  if (g->rampu & 1) a.d_element_ramp = g->d_ramp[0];
+  if (g->rampu & 4) a.d_output_ramp = g->d_ramp[2];
+  a.ramp_stream_stride = fs;
+  a.d_pcm = g->rs ? (void *)g->d_mid : (void *)g->h_pcm;
+  a.pcm_stream_stride_bytes = g->rs ? (int64_t)sizeof(float) * g->mid_stride : (int64_t)g->pcm_cap;
+  r = iamf_hip_batch_render_range(g->batch, &a, i, j - i);
+  if (r < 0) return 1;
+  if (g->rs) {
+    const int n2 = iamf_hip_resampler_process_range(g->rs, g->d_mid, g->mid_stride, r, g->d_res, g->res_stride, g->stream, i, j - i);
+    if (n2 < 0 || (r = group_last_stage(g, i, j, n2)) < 0) return 1;
+    for (int s = i; s < j; ++s) g->pos3[s] += n2;
+  }
+  for (int s = i; s < j; ++s) {
+    g->result[s] = r;
+    g->pos[s] += g->keep[s];
+  }
+  return 0;
+}
+
+/* the end of the run that starts at stream i: neighbouring streams that do the same thing from the same position */
+static int group_run_end(const iamf_hip_decoder_group *g, int i) {
+  int j = i + 1;
+  while (j < g->n && g->action[j] == g->action[i] && g->pos[j] == g->pos[i] &&
+         (g->action[i] == GA_FLUSH || (g->keep[j] == g->keep[i] && g->s0[j] == g->s0[i] &&
+                                       (!(g->lfe[0] || g->lfe[1]) || g->te[j] == g->te[i]))) &&
+         /* resampling: one launch = one phase of the resampler and one position of the last stage */
+         (!g->rs || (g->pos3[j] == g->pos3[i] && iamf_hip_resampler_same_state(g->rs, i, j))))
+    ++j;
+  while (g->action[i] == GA_ADVANCE && j < g->n && g->action[j] == GA_ADVANCE && g->te[j] == g->te[i]) ++j;
+  return j;
+}
+
+/* Round `ticket`'s host half: parse, stage into slot ticket & 1, queue the device work, move the clocks.  Every device
+ * call of a round goes to g->stream; the batch and the resampler take what a launch needs by value (the kernels'
+ * parameter structs) or from device buffers they advance in stream order (iamf_render.hip: p.fir_hist / fir_cur,
+ * d_lim, d_lfe_state; iamf_resample.hip: d_hist[cur], whose host-side phase walk is the only host state), so a launch
+ * reads no host memory after it returns — which a round already relied on: it queues several range launches with no
+ * synchronisation between them.  What they read from the host is the group's pinned staging (h_raw through
+ * iamf_hip_upload_by_kernel, h_ramp / h_dmx / h_demix through hipMemcpyAsync), and that has a copy per slot.  The
+ * exceptions synchronise themselves: iamf_hip_batch_set_gains waits for the batch's last render (quiesce) — in a round
+ * whose constant gains change it therefore waits for the round before it, a bubble in the pipeline — and a buffer that
+ * grows with the largest call seen is replaced after a hipStreamSynchronize. */
+static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes, uint32_t *rsizes,
+                              void *const *pcm, int32_t *results) {
+  int any_render = 0, any = 0, gains_changed = 0;
+  const int n = g->n;
+  const int sl = (int)((g->issued + 1) & 1);
+  double t0 = group_now(), t1;
+  group_use_slot(g, sl);
+  memcpy(g->pcm_out, pcm, sizeof(void *) * (size_t)n);
+  g->slot[sl].dev = 0;
+  g->data = data;
+  g->sizes = sizes;
+  g->rsizes = rsizes;
+  g->rampu = g->unpacked = 0;
+  const int dev_err = group_upload_chunks(g);
   t1 = group_now();
   g->t_phase[0] += t1 - t0;
   t0 = t1;
@@ -911,7 +1002,7 @@ static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *d
     results[i] = g->result[i];
     if (g->action[i] == GA_RENDER) {
       any_render = 1;
-      rampu |= g->rampf[i];
+      g->rampu |= g->rampf[i];
       if (g->gain_new[i] != g->gain_cur[i] || g->gain_new[n + i] != g->gain_cur[n + i]) gains_changed = 1;
     } else { /* not rendered: its constant gains stay what they are */
       g->gain_new[i] = g->gain_cur[i];
@@ -923,216 +1014,18 @@ static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *d
     g->t_phase[1] += group_now() - t0;
     return IAMF_OK;
   }
-  int unpacked = 0; /* the device unpacker has run this round (it is skipped when every launch reads the packets itself) */
-  if (any_render) {
-    /* a stage that is on a ramp in SOME stream is applied through its rows in all: the others' rows carry their constant */
-    for (int k = 0; k < 3; ++k)
-      if ((rampu >> k) & 1 && !(k == 1 && g->nel > 1))
-        for (int i = 0; i < n; ++i)
-          if (g->action[i] == GA_RENDER && !((g->rampf[i] >> k) & 1)) {
-            float *row = g->h_ramp[k] + (size_t)i * fs;
-            const float c = g->cgain[k][i];
-            for (int j = 0; j < g->keep[i]; ++j) row[j] = c;
-          }
-    if (g->nel > 1) rampu |= 2; /* element 1 takes its gain through its ramp row, constant or not */
-    for (int k = 0; k < 3; ++k)
-      if ((rampu >> k) & 1)
-        if (hipMemcpyAsync(g->d_ramp[k], g->h_ramp[k], sizeof(float) * (size_t)n * fs, hipMemcpyHostToDevice, g->stream) != hipSuccess)
-          return group_fail(g);
-    if (g->d[0]->pre[0].use_dmx && hipMemcpyAsync(g->d_dmx, g->h_dmx, sizeof(iamf_hip_dmx_frame) * (size_t)n, hipMemcpyHostToDevice, g->stream) != hipSuccess)
-      return group_fail(g);
-    if (g->d[0]->pre[0].use_demix && hipMemcpyAsync(g->d_demix, g->h_demix, sizeof(iamf_hip_demix_frame) * (size_t)n, hipMemcpyHostToDevice, g->stream) != hipSuccess)
-      return group_fail(g);
-    if (g->aux && g->d[0]->pre[1].use_dmx && hipMemcpyAsync(g->d_dmx1, g->h_dmx1, sizeof(iamf_hip_dmx_frame) * (size_t)n, hipMemcpyHostToDevice, g->stream) != hipSuccess)
-      return group_fail(g);
-    if (g->aux && g->d[0]->pre[1].use_demix && hipMemcpyAsync(g->d_demix1, g->h_demix1, sizeof(iamf_hip_demix_frame) * (size_t)n, hipMemcpyHostToDevice, g->stream) != hipSuccess)
-      return group_fail(g);
-    if (gains_changed) { /* constant gains of the streams that are not on a ramp this time (synchronous, rare) */
-      if (iamf_hip_batch_set_gains(g->batch, g->gain_new, g->gain_new + n, 0)) return group_fail(g);
-      memcpy(g->gain_cur, g->gain_new, sizeof(float) * 2 * n);
-    }
-  }
-  /* launches: maximal runs of neighbouring streams that do the same thing from the same position */
-  for (int i = 0; i < n;) {
-    int j = i + 1, r;
+  if (any_render && group_upload_params(g, gains_changed)) return group_fail(g);
+  for (int i = 0, j; i < n; i = j) { /* launches: maximal runs */
     if (g->action[i] == GA_NONE) {
-      ++i;
+      j = i + 1;
       continue;
     }
-    while (j < n && g->action[j] == g->action[i] && g->pos[j] == g->pos[i] &&
-           (g->action[i] == GA_FLUSH || (g->keep[j] == g->keep[i] && g->s0[j] == g->s0[i] &&
-                                         (!(g->lfe[0] || g->lfe[1]) || g->te[j] == g->te[i]) &&
-                                         /* a ramp launch multiplies every stream's rows in: equal kinds of launch only */
-                                         1)) &&
-           /* resampling: one launch = one phase of the resampler and one position of the last stage */
-           (!g->rs || (g->pos3[j] == g->pos3[i] && iamf_hip_resampler_same_state(g->rs, i, j))))
-      ++j;
-    if (g->action[i] == GA_ADVANCE) { /* the LFE generator's filter over frames that are trimmed away completely (te = their length) */
-      while (j < n && g->action[j] == GA_ADVANCE && g->te[j] == g->te[i]) ++j;
-      if (!unpacked) {
-        for (int e = 0; e < g->nel; ++e)
-          if (iamf_hip_lpcm_unpack(&g->lay[e], g->d_raw[e], (int64_t)g->raw_stride[e], (const int32_t *)g->d_raw[e],
-                                   (int64_t)(g->raw_stride[e] / 4), g->d_in[e], (int64_t)g->in_ch[e] * fs, n, g->stream))
-            return group_fail(g);
-        unpacked = 1;
-      }
-      if (g->aux && g->lfe[1] && iamf_hip_batch_lfe_advance(g->aux, g->d_in[1], (int64_t)g->in_ch[1] * fs, g->te[i], g->stream, i, j - i))
-        return group_fail(g);
-      if (g->lfe[0] && iamf_hip_batch_lfe_advance(g->batch, g->d_in[0], (int64_t)g->in_ch[0] * fs, g->te[i], g->stream, i, j - i))
-        return group_fail(g);
-      for (int s = i; s < j; ++s) g->result[s] = 0;
-      i = j;
-      continue;
-    }
-    if (g->action[i] == GA_FLUSH && g->rs) { /* iamf_delay_buffer_handle, IAMF_decoder.c:3250-3301: the resampler's tail + the limiter's */
-      const int extra = g->limiter_on ? 240 : 0;
-      iamf_hip_render_args a3;
-      int n2;
-      if (hipMemsetAsync(g->d_res + (size_t)i * g->res_stride, 0, sizeof(float) * (size_t)(j - i) * g->res_stride, g->stream) != hipSuccess)
-        return group_fail(g);
-      n2 = iamf_hip_resampler_flush_range(g->rs, g->d_res, g->res_stride, g->stream, i, j - i);
-      if (n2 < 0) return group_fail(g);
-      if (g->d[i]->norm_loudness != 0.f) { /* the resampler's tail is not normalised (flush_tail; IAMF_decoder.c:3271-3287) */
-        for (int s = i; s < j; ++s) g->loud3[s] = 1.f;
-        if (iamf_hip_batch_set_gains(g->batch3, 0, 0, g->loud3)) return group_fail(g);
-      }
-      r = 0;
-      if (n2 + extra > 0) {
-        memset(&a3, 0, sizeof(a3));
-        a3.d_in = g->d_res;
-        a3.in_stream_stride = g->res_stride;
-        a3.in_frame_stride = g->out_ch;
-        a3.n_frames = n2 + extra;
-        a3.stream = g->stream;
-        a3.d_pcm = g->h_pcm;
-        a3.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
-        r = iamf_hip_batch_render_range(g->batch3, &a3, i, j - i);
-        if (r < 0) return group_fail(g);
-      }
-      for (int s = i; s < j; ++s) {
-        g->result[s] = r;
-        g->pos3[s] += n2 + extra;
-      }
-    } else if (g->action[i] == GA_FLUSH) {
-      r = iamf_hip_batch_flush_range(g->batch, g->h_pcm, (int64_t)g->pcm_cap, g->stream, i, j - i);
-      if (r < 0) return group_fail(g);
-      for (int s = i; s < j; ++s) {
-        g->result[s] = r;
-        g->pos[s] += 240;
-      }
-    } else {
-      iamf_hip_render_args a;
-      memset(&a, 0, sizeof(a));
-      if (g->lp_ok && !rampu && !(g->s0[i] & 3) && !(g->keep[i] & 63)) {
-        /* the run's packets straight into the render kernel: first kept sample s0, keep samples (uniform over the run) */
-        iamf_hip_lpcm_input in;
-        memset(&in, 0, sizeof(in));
-        in.d_raw = g->d_raw[0];
-        in.raw_stream_stride = in.raw_frame_stride = (int64_t)g->raw_stride[0];
-        in.first_sample = g->s0[i];
-        in.layout = g->lay[0];
-        a.n_frames = 1;
-        a.n_samples = g->keep[i] < fs ? g->keep[i] : 0;
-        a.stream = g->stream;
-        a.d_pcm = g->h_pcm;
-        a.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
-        r = iamf_hip_batch_render_lpcm_range(g->batch, &in, &a, i, j - i);
-        if (r < 0) return group_fail(g);
-        for (int s = i; s < j; ++s) {
-          g->result[s] = r;
-          g->pos[s] += g->keep[s];
-        }
-        i = j;
-        continue;
-      }
-      if (!unpacked) {
-        /* (rows of chunks that had nothing to render were not uploaded: the device still holds their previous round's, and
-         * the unpacker may rewrite element PCM that no launch of this round reads) */
-        for (int e = 0; e < g->nel; ++e)
-          if (iamf_hip_lpcm_unpack(&g->lay[e], g->d_raw[e], (int64_t)g->raw_stride[e], (const int32_t *)g->d_raw[e],
-                                   (int64_t)(g->raw_stride[e] / 4), g->d_in[e], (int64_t)g->in_ch[e] * fs, n, g->stream))
-            return group_fail(g);
-        unpacked = 1;
-      }
-      a.d_in = g->d_in[0] + (g->lfe[0] ? g->s0[i] : 0);
-      a.in_stream_stride = a.in_frame_stride = (int64_t)g->in_ch[0] * fs;
-      if (g->lfe[0]) {
-        a.lfe_pre_samples = g->s0[i];
-        a.lfe_post_samples = g->te[i];
-      }
-      if (g->aux) { /* element 1 of the run through its own batch (stage, matrix, its gain row) -> planar f32, as render_tu */
-        iamf_hip_render_args b;
-        const int64_t st = (int64_t)fs * g->out_ch;
-        memset(&b, 0, sizeof(b));
-        b.d_in = g->d_in[1] + (g->lfe[1] ? g->s0[i] : 0);
-        b.in_stream_stride = b.in_frame_stride = (int64_t)g->in_ch[1] * fs;
-        if (g->lfe[1]) {
-          b.lfe_pre_samples = g->s0[i];
-          b.lfe_post_samples = g->te[i];
-        }
-        b.d_element_ramp = g->d_ramp[1];
-        b.ramp_stream_stride = fs;
-        if (g->d[0]->pre[1].use_dmx) b.d_dmx_frames = g->d_dmx1;
-        if (g->d[0]->pre[1].use_demix) {
-          b.d_demix_frames = g->d_demix1;
-          b.demix_sample0 = g->s0[i];
-        }
-        b.n_frames = 1;
-        b.n_samples = g->keep[i] < fs ? g->keep[i] : 0;
-        b.stream = g->stream;
-        b.d_pcm = g->d_aux_il;
-        b.pcm_stream_stride_bytes = (int64_t)sizeof(float) * st;
-        if (iamf_hip_batch_render_range(g->aux, &b, i, j - i) != g->keep[i]) return group_fail(g);
-        if (iamf_hip_deinterleave_f32(g->d_aux_il + (int64_t)i * st, st, g->out_ch, j - i, g->keep[i], g->d_aux_pl + (int64_t)i * st, st, fs, g->stream))
-          return group_fail(g);
-        a.d_in2 = g->d_aux_pl;
-        a.in2_stream_stride = a.in2_frame_stride = st;
-        a.d_element2_ramp = g->d_ones;
-      } else if (g->nel > 1) {
-        a.d_in2 = g->d_in[1];
-        a.in2_stream_stride = a.in2_frame_stride = (int64_t)g->in_ch[1] * fs;
-        a.d_element2_ramp = g->d_ramp[1];
-      }
-      if (rampu & 1) a.d_element_ramp = g->d_ramp[0];
-      if (rampu & 4) a.d_output_ramp = g->d_ramp[2];
-      a.ramp_stream_stride = fs;
-      if (g->d[0]->pre[0].use_dmx) a.d_dmx_frames = g->d_dmx;
-      if (g->d[0]->pre[0].use_demix) {
-        a.d_demix_frames = g->d_demix;
-        a.demix_sample0 = g->s0[i];
-      }
-      a.n_frames = 1;
-      a.n_samples = g->keep[i] < fs ? g->keep[i] : 0;
-      a.stream = g->stream;
-      a.d_pcm = g->rs ? (void *)g->d_mid : (void *)g->h_pcm;
-      a.pcm_stream_stride_bytes = g->rs ? (int64_t)sizeof(float) * g->mid_stride : (int64_t)g->pcm_cap;
-      r = iamf_hip_batch_render_range(g->batch, &a, i, j - i);
-      if (r < 0) return group_fail(g);
-      if (g->rs) { /* render (f32) -> resample -> loudness / limiter / pack, as render_tu */
-        iamf_hip_render_args a3;
-        const int n2 = iamf_hip_resampler_process_range(g->rs, g->d_mid, g->mid_stride, r, g->d_res, g->res_stride, g->stream, i, j - i);
-        if (n2 < 0) return group_fail(g);
-        r = 0;
-        if (n2 > 0) {
-          memset(&a3, 0, sizeof(a3));
-          a3.d_in = g->d_res;
-          a3.in_stream_stride = g->res_stride;
-          a3.in_frame_stride = g->out_ch;
-          a3.n_frames = n2;
-          a3.stream = g->stream;
-          a3.d_pcm = g->h_pcm;
-          a3.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
-          r = iamf_hip_batch_render_range(g->batch3, &a3, i, j - i);
-          if (r < 0) return group_fail(g);
-        }
-        for (int s = i; s < j; ++s) g->pos3[s] += n2;
-      }
-      for (int s = i; s < j; ++s) {
-        g->result[s] = r;
-        g->pos[s] += g->keep[s];
-      }
-    }
-    i = j;
+    j = group_run_end(g, i);
+    if (g->action[i] == GA_ADVANCE ? group_run_advance(g, i, j)
+        : g->action[i] == GA_FLUSH ? (g->rs ? group_run_flush_resampled(g, i, j) : group_run_flush(g, i, j))
+        : g->lp_ok && !g->rampu && !(g->s0[i] & 3) && !(g->keep[i] & 63) ? group_run_lpcm(g, i, j)
+                                                                         : group_run_f32(g, i, j))
+      return group_fail(g);
   }
   /* the round is queued: a one-lane kernel behind its last launch writes the ticket into the pinned word (what _complete
    * and _poll wait for: this round only, not the one submitted after it) */
@@ -1144,6 +1037,7 @@ static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *d
   g->t_phase[1] += group_now() - t0;
   return IAMF_OK;
 }
+
 
 int iamf_hip_decoder_group_submit(iamf_hip_decoder_group *g, const uint8_t *const *data, const int32_t *sizes,
                                   uint32_t *rsizes, void *const *pcm, int32_t *results, uint64_t *ticket) {

@@ -85,7 +85,8 @@ def stub_lib():
     os.makedirs(os.path.join(STUB, "build"), exist_ok=True)
     so = os.path.join(STUB, "build", "libfacade_stub.so")
     srcs = [os.path.join(ROOT, "iac_amd", "csrc", "iamf_decoder_facade.c"), os.path.join(STUB, "device_stub.c")]
-    deps = srcs + [os.path.join(ROOT, "iac_amd", "csrc", "iamf_decoder_group.inc"), os.path.join(ROOT, "include", "iamf_hip.h")]
+    deps = srcs + [os.path.join(ROOT, "iac_amd", "csrc", "iamf_decoder_group.inc"), os.path.join(ROOT, "iac_amd", "csrc", "facade_tu.h"),
+                   os.path.join(ROOT, "include", "iamf_hip.h")]
     if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in deps):
         subprocess.check_call(["gcc", "-g", "-O1", "-std=gnu11", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
                                "-I/opt/rocm/include"] + srcs + ["-lm", "-lpthread", "-o", so])

@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STUB = os.path.join(ROOT, "tests", "group_async_stub")
 SRCS = [os.path.join(ROOT, "iac_amd", "csrc", "iamf_decoder_facade.c"), os.path.join(STUB, "async_stub.c"),
         os.path.join(STUB, "group_async_driver.c")]
-DEPS = SRCS + [os.path.join(ROOT, "iac_amd", "csrc", "iamf_decoder_group.inc"), os.path.join(ROOT, "include", "iamf_hip.h"),
+DEPS = SRCS + [os.path.join(ROOT, "iac_amd", "csrc", "iamf_decoder_group.inc"), os.path.join(ROOT, "iac_amd", "csrc", "facade_tu.h"),
+               os.path.join(ROOT, "include", "iamf_hip.h"),
                os.path.join(ROOT, "tests", "facade_stub", "device_stub.c")]
 STREAMS = ["toa_binaural_s16", "l714_J_ramps", "stereo_plus_scalable_C_ramps", "l714dmx_plus_l714dmx_C_trim", "stereo_441_to_48k"]
 
