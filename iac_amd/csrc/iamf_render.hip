@@ -394,6 +394,7 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
     case Family::Lpcm: launched = iamf_hip_fast_lpcm_launch(&p, m, r.variant, st); break;
     case Family::Lpcm24: launched = iamf_hip_fast_lpcm24_launch(&p, m, r.variant, st); break;
     case Family::LpcmCoupled: launched = iamf_hip_fast_lpcm_coupled_launch(&p, m, r.variant, st); break;
+    case Family::Lpcm24Coupled: launched = iamf_hip_fast_lpcm24_coupled_launch(&p, m, r.variant, st); break;
     case Family::LpcmMix:
       launched = p.lpcm_coupled ? iamf_hip_fast_lpcm_mix_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_lpcm_mix_launch(&p, m, r.variant, st);
       break;
@@ -456,12 +457,13 @@ struct LpcmIn {
   int64_t stream_stride, frame_stride;
   int32_t off[16];
   int32_t bytes;   // per sample: 2 or 3 (lpcm_form.hpp)
-  int32_t coupled; // 1: LpcmForm::S16C, off[] of a pair's two channels 2 bytes apart
+  int32_t coupled; // 1: LpcmForm::S16C, off[] of a pair's two channels 2 bytes apart; 2: LpcmForm::S24C, 3 bytes apart
 };
 constexpr int kNotFused = INT32_MIN;
 // the family a packet call must route to for a fused kernel to read its packets (lp2: the second element's, or null)
 Family lpcm_family(const LpcmIn *lp, const LpcmIn *lp2) {
   if (lp2) return Family::LpcmMix;
+  if (lp->coupled == 2) return Family::Lpcm24Coupled;
   if (lp->coupled) return Family::LpcmCoupled;
   return lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm;
 }
@@ -527,6 +529,8 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   if (lp2 && (!lp || !b->has2 || !b->lp2_scale_ok ||
               (b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels)))
     return kNotFused;
+  // the coupled 24-bit form (iamf_hip_batch_render_packets) keeps away from a fixed PCM channel stride as well
+  if (lp && lp->coupled == 2 && b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) return kNotFused;
   if (!range_ok(b, s0, cnt)) return IAMF_HIP_ERR_BAD_ARG;
   if (a.lfe_pre_samples < 0 || a.lfe_post_samples < 0 ||
       ((a.lfe_pre_samples || a.lfe_post_samples) &&
@@ -635,8 +639,9 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     for (int m = 0; m < 16; ++m) p.lpcm_off[m] = lp->off[m];
     p.lpcm_bytes = lp->bytes;
     p.lpcm_coupled = lp->coupled;
-    if (lp->bytes == 3 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
-    if (lp->coupled && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
+    if (lp->bytes == 3 && !lp->coupled && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
+    if (lp->coupled == 1 && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
+    if (lp->coupled == 2 && (lp2 || !lpcm24_coupled_fused(cnt))) return kNotFused;
     if (lp2) {   // the kernel reads RenderMixParams; pick_route the packets' place in the in2 fields (strides in bytes)
       p.lpcm_mix = lp2->coupled ? 2 : 1;
       p.in2 = reinterpret_cast<const float *>(lp2->raw);
@@ -1166,9 +1171,10 @@ int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in,
 // still indexed by the stream's number in the batch)
 // The packet-form checks of an LPCM call of nf frames (n_samples as iamf_hip_render_args::n_samples): an error, or
 // IAMF_HIP_OK with the trim {first, count} and whether the packets have the form the fused kernels read
-// (ch: the channels of the element the packets hold — element 0's, or the second element's for iamf_hip_batch_render_lpcm_mix)
+// (ch: the channels of the element the packets hold — element 0's, or the second element's for iamf_hip_batch_render_lpcm_mix;
+//  packets: the call came through iamf_hip_batch_render_packets, which also takes LpcmForm::S24C)
 static int lpcm_form_check_ch(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int ch, int nf, int n_samples, LpcmForm *form_out,
-                              int *first_out, int *count_out) {
+                              int *first_out, int *count_out, bool packets = false) {
   const iamf_hip_lpcm_layout &L = in->layout;
   const int fs = b->cfg.frame_size;
   if (L.sample_bytes < 2 || L.sample_bytes > 4 || L.channels != ch || ch > IAMF_HIP_LPCM_MAX_CHANNELS || L.frame_size != fs ||
@@ -1183,15 +1189,16 @@ static int lpcm_form_check_ch(const iamf_hip_batch *b, const iamf_hip_lpcm_input
       return IAMF_HIP_ERR_BAD_ARG;
   }
   // which form, if any, the fused kernels can load as it lies (lpcm_form.hpp; pinned by tests/route_host)
-  *form_out = lpcm_form(L, ch, in->raw_stream_stride, in->raw_frame_stride, reinterpret_cast<uintptr_t>(in->d_raw), first);
+  *form_out = (packets ? lpcm_form_packets : lpcm_form)(L, ch, in->raw_stream_stride, in->raw_frame_stride,
+                                                        reinterpret_cast<uintptr_t>(in->d_raw), first);
   *first_out = first;
   *count_out = count;
   return IAMF_HIP_OK;
 }
 
 static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int n_samples, LpcmForm *form_out,
-                           int *first_out, int *count_out) {
-  return lpcm_form_check_ch(b, in, element_channels(b), nf, n_samples, form_out, first_out, count_out);
+                           int *first_out, int *count_out, bool packets = false) {
+  return lpcm_form_check_ch(b, in, element_channels(b), nf, n_samples, form_out, first_out, count_out, packets);
 }
 
 // packets of the fusable form as the fused kernels take them
@@ -1201,7 +1208,7 @@ static void lpcm_in_of(const iamf_hip_lpcm_input *in, int ch, int first, LpcmFor
   lp.stream_stride = in->raw_stream_stride;
   lp.frame_stride = in->raw_frame_stride;
   lp.bytes = in->layout.sample_bytes;
-  lp.coupled = form == LpcmForm::S16C;
+  lp.coupled = form == LpcmForm::S16C ? 1 : (form == LpcmForm::S24C ? 2 : 0);
   // (src_step: the sample bytes of a contiguous run, twice that for the halves of a coupled pair)
   for (int c = 0; c < ch; ++c) lp.off[c] = in->layout.src_offset[c] + in->layout.src_step[c] * first;
 }
@@ -1243,8 +1250,9 @@ static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, i
   return IAMF_HIP_OK;
 }
 
-int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
-                                     int32_t stream0, int32_t n_streams) {
+// (packets: iamf_hip_batch_render_packets — the form is asked of lpcm_form_packets(); everything else is the one path)
+static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
+                                  int32_t stream0, int32_t n_streams, bool packets) {
   if (!b || !in || !args || !in->d_raw || args->d_in || !args->d_pcm || args->n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
   if (!range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
@@ -1252,7 +1260,7 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
   const int ch = element_channels(b), nf = args->n_frames;
   LpcmForm form = LpcmForm::None;
   int first = 0, count = 0;
-  const int fc = lpcm_form_check(b, in, nf, args->n_samples, &form, &first, &count);
+  const int fc = lpcm_form_check(b, in, nf, args->n_samples, &form, &first, &count, packets);
   if (fc != IAMF_HIP_OK) return fc;
   iamf_hip_render_args a = *args;
   if (form != LpcmForm::None) {
@@ -1274,6 +1282,21 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
   const int ur = lpcm_unpack_range(b, in, nf, first, count, stream0, n_streams, static_cast<hipStream_t>(args->stream), a);
   if (ur != IAMF_HIP_OK) return ur;
   return render_range_impl(b, &a, stream0, n_streams, nullptr);
+}
+
+int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
+                                     int32_t stream0, int32_t n_streams) {
+  return render_lpcm_range_impl(b, in, args, stream0, n_streams, false);
+}
+
+// Element 0 as LPCM packets of every form a fused kernel reads (include/iamf_hip.h): iamf_hip_batch_render_lpcm_range with
+// leave to take render_fast_kernel<.., LP, EARLY, 3, LPC> (Family::Lpcm24Coupled) where the packets have the coupled 24-bit
+// form (lpcm_form_packets) and render_prepare and pick_route let the call through.  The same checks in the same order, the
+// same path for everything else.
+int iamf_hip_batch_render_packets(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, true);
 }
 
 // Both elements of a mix as LPCM packets (include/iamf_hip.h).  Fused (render_fast_kernel<.., LP2>: Family::LpcmMix) when

@@ -4,7 +4,7 @@
 // names depend on it), hence `const void *params`: the caller's RenderParams / FanParams, the same definition on both
 // sides (render_params.hpp, render_fanout.hpp).  Each returns 1 if it launched, 0 if (m, the block's channel counts) is
 // not in the instance list the caller has already consulted (render_route.hpp).  The units that feed render_fast_kernel
-// another input form (the seven iamf_hip_fast_*_launch entries) share their launchers: render_fast_unit.hpp.  Behind the
+// another input form (the eight iamf_hip_fast_*_launch entries) share their launchers: render_fast_unit.hpp.  Behind the
 // launch entries: the unpacker's, and the one entry through which every launcher counts what it ran (iamf_route.hip).
 #pragma once
 
@@ -26,6 +26,9 @@ IAMF_INTERNAL int iamf_hip_fast_lpcm24_launch(const void *params, int m, int ear
 // iamf_render_lpcm_coupled.hip: the same for the coupled 16-bit form (params->lpcm_coupled); early: Route::variant of
 // Family::LpcmCoupled
 IAMF_INTERNAL int iamf_hip_fast_lpcm_coupled_launch(const void *params, int m, int early, hipStream_t st);
+// iamf_render_lpcm24_coupled.hip: the same for the coupled 24-bit form (params->lpcm_coupled == 2, lpcm_bytes == 3); early:
+// Route::variant of Family::Lpcm24Coupled
+IAMF_INTERNAL int iamf_hip_fast_lpcm24_coupled_launch(const void *params, int m, int early, hipStream_t st);
 // iamf_render_lpcm_mix.hip, iamf_render_lpcm_mix_coupled.hip: both elements as 16-bit packets, element 0 mono-coded / coupled
 // (params->lpcm_coupled); params: a RenderMixParams; lp2: Route::variant of Family::LpcmMix
 IAMF_INTERNAL int iamf_hip_fast_lpcm_mix_launch(const void *params, int m, int lp2, hipStream_t st);

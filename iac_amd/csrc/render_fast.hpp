@@ -229,12 +229,15 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       channel is consumed; everything behind the projection is shared.
 //       Sixteen more dwords of input are live than in the 16-bit form: <16, 2> with the late prefetch (all sixteen channels
 //       requested at once) does not fit 128 registers without spilling and is built for three workgroups per CU instead.
-// LPC:  (LP, LPB == 2) the coupled form: the channel pairs of a loudspeaker layout — lpcm_coupled_paired(M, m), lpcm_form.hpp:
+// LPC:  (LP) the coupled form (LPB == 2 here; LPB == 3 below): the channel pairs of a loudspeaker layout — lpcm_coupled_paired(M, m), lpcm_form.hpp:
 //       (0,1) and, from six channels on, (4,5) .. (M-2, M-1) — are coupled sub-streams, the two channels interleaved sample
 //       by sample.  A lane's four sample-frames of a pair are 16 contiguous bytes L0 R0 L1 R1 L2 R2 L3 R3, ONE load on the
 //       8-byte grid into the four dwords the two channels' packets would have held; L is cut out of the low halves where
 //       channel m is consumed, R out of the sign-extended high halves where m + 1 is.  Channels 2 and 3 (C, LFE) are mono
 //       runs as above.  The pairing is a compile-time function of M: no run-time branch per channel.
+//       LPB == 3 (lpcm_form.hpp, S24C): a pair's four sample-frames are 24 contiguous bytes on the dword grid, TWO 12-byte loads
+//       (the second 12 bytes on) into xr3[m], xr3[m + 1]: each triple holds four samples L R L R in exactly the 24-bit form's
+//       a, b, c pattern, so the cut is that form's — channel m takes samples 0 and 2 of both triples, m + 1 samples 1 and 3.
 // LP2:  (LP, LPB == 2, IN2, EARLY) the second element arrives as 16-bit packets too (RenderMixParams::lpcm2, iamf_hip_batch_render_lpcm_mix):
 //       1: mono-coded runs, m2 = 1 or 4 at run time, one 8-byte load per channel and lane; 2: ONE coupled stereo pair
 //       (m2 == 2), one 16-byte load per lane, L out of the low halves and R out of the sign-extended high halves as LPC does.
@@ -265,7 +268,7 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   static_assert(LP2 == 0 || ((LP2 == 1 || LP2 == 2) && LP && IN2 && EARLY && LPB == 2), "a packet-fed second element joins a 16-bit packet-fed first one");
   static_assert(!(IN2 && (FIR || DOWN)), "the second element joins a matrix-rendered first one");
   static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
-  static_assert(!LPC || (LP && LPB == 2 && lpcm_coupled_m(M)), "coupled pairs: 16-bit packets of a loudspeaker layout");
+  static_assert(!LPC || (LP && (LPB == 2 || (LPB == 3 && LP2 == 0)) && lpcm_coupled_m(M)), "coupled pairs: 16- or 24-bit packets of a loudspeaker layout");
   static_assert(!IL || (!FIR && !DOWN && !IN2 && !LP && EARLY && M <= 2), "interleaved f32 feeds the plain matrix variant, one or two channels");
   static_assert(!RAG || IL || (!FIR && !DOWN && !IN2 && !LP && EARLY), "ragged calls: the interleaved form, or the plain planar f32 one");
   constexpr bool LP3 = LP && LPB == 3;
@@ -462,7 +465,27 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   const __amdgpu_buffer_rsrc_t rs_none = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void *>(LP ? static_cast<const void *>(lp_s) : static_cast<const void *>(in_s)), 0, 0, 0x00020000);
   auto load_lp_one = [&](int m, int f, int i, __amdgpu_buffer_rsrc_t rs) {
-    if constexpr (LP3) {
+    if constexpr (LP3 && LPC) {
+      // a 24-bit pair is loaded once, when its first channel is named: 24 bytes on the dword grid (the pair's run offset is
+      // a multiple of 4 — lpcm_form.hpp, S24C — and 6 * i one of 24) as two 12-byte loads, L0 R0 L1 R1 in xr3[m] and
+      // L2 R2 L3 R3 in xr3[m + 1]; C and LFE are the 24-bit form's mono runs
+      if (lpcm_coupled_paired(M, m)) {
+        if (!(m & 1)) {
+          const int vo = f * (int)p.lpcm_frame_stride + 6 * i;
+          const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, vo, p.lpcm_off[m], 2 /* nt */);
+          const auto w = __builtin_amdgcn_raw_buffer_load_b96(rs, vo + 12, p.lpcm_off[m], 2 /* nt */);
+          // (member by member: assigned as two lp_u3 temporaries, the early variants of M >= 6 kept four to eight dwords of
+          //  xr3 in scratch)
+          const int m1 = m + 1 < M ? m + 1 : m;
+          xr3[m].a = v[0], xr3[m].b = v[1], xr3[m].c = v[2];
+          xr3[m1].a = w[0], xr3[m1].b = w[1], xr3[m1].c = w[2];
+        }
+      } else {
+        const int vo = f * (int)p.lpcm_frame_stride + 3 * i;
+        const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, vo, p.lpcm_off[m], 2 /* nt */);
+        xr3[m] = lp_u3{v[0], v[1], v[2]};
+      }
+    } else if constexpr (LP3) {
       // (dword-aligned: the stream's base, the frame stride and the run offsets are multiples of 4 — lpcm_form.hpp —
       //  and 3 * i is one of 12)
       const int vo = f * (int)p.lpcm_frame_stride + 3 * i;
@@ -629,7 +652,35 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
             }
           }
         }
-        if constexpr (LP3) {
+        if constexpr (LP3 && LPC) {
+          if (lpcm_coupled_paired(M, m)) {   // (m is a constant of the unrolled loop)
+            // half m & 1 of the pair whose six dwords lie in xr3[m & ~1], xr3[m | 1] (the ordering fence of the 16-bit coupled
+            // form below, on all six): each triple is cut as the 24-bit form's, L takes its samples 0 and 2, R 1 and 3
+            const int m0 = m & ~1, m1 = (m | 1) < M ? (m | 1) : m;
+            if constexpr (OC == 2)
+              asm volatile("" : "+v"(xr3[m0].a), "+v"(xr3[m0].b), "+v"(xr3[m0].c), "+v"(xr3[m1].a), "+v"(xr3[m1].b), "+v"(xr3[m1].c),
+                                "+v"(prj[0]), "+v"(prj[1]), "+v"(prj[2]), "+v"(prj[3]));
+            else
+              asm volatile("" : "+v"(xr3[m0].a), "+v"(xr3[m0].b), "+v"(xr3[m0].c), "+v"(xr3[m1].a), "+v"(xr3[m1].b), "+v"(xr3[m1].c),
+                                "+v"(prj[0]), "+v"(prj[1]));
+            const unsigned a = xr3[m0].a, b = xr3[m0].b, c = xr3[m0].c, d = xr3[m1].a, e = xr3[m1].b, g = xr3[m1].c;
+            if ((m & 1) == 0) {
+              xa = f2{(float)((int)(a << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(c, b, 16) << 8) >> 8)};
+              xb = f2{(float)((int)(d << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(g, e, 16) << 8) >> 8)};
+            } else {
+              xa = f2{(float)((int)(__builtin_amdgcn_alignbit(b, a, 24) << 8) >> 8), (float)((int)c >> 8)};
+              xb = f2{(float)((int)(__builtin_amdgcn_alignbit(e, d, 24) << 8) >> 8), (float)((int)g >> 8)};
+            }
+          } else {   // C, LFE: a mono run, the 24-bit form's conversion below
+            if constexpr (OC == 2)
+              asm volatile("" : "+v"(xr3[m].a), "+v"(xr3[m].b), "+v"(xr3[m].c), "+v"(prj[0]), "+v"(prj[1]), "+v"(prj[2]), "+v"(prj[3]));
+            else
+              asm volatile("" : "+v"(xr3[m].a), "+v"(xr3[m].b), "+v"(xr3[m].c), "+v"(prj[0]), "+v"(prj[1]));
+            const unsigned a = xr3[m].a, b = xr3[m].b, c = xr3[m].c;
+            xa = f2{(float)((int)(a << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(b, a, 24) << 8) >> 8)};
+            xb = f2{(float)((int)(__builtin_amdgcn_alignbit(c, b, 16) << 8) >> 8), (float)((int)c >> 8)};
+          }
+        } else if constexpr (LP3) {
           // (the same ordering fence as the 16-bit form below, for the same reason)
           if constexpr (OC == 2)
             asm volatile("" : "+v"(xr3[m].a), "+v"(xr3[m].b), "+v"(xr3[m].c), "+v"(prj[0]), "+v"(prj[1]), "+v"(prj[2]), "+v"(prj[3]));

@@ -1,5 +1,5 @@
 // render_fast_unit.hpp — what the translation units that feed render_fast_kernel (render_fast.hpp) another input form share:
-// iamf_render_lpcm.hip, _lpcm24.hip, _lpcm_coupled.hip, _lpcm_mix.hip, _lpcm_mix_coupled.hip, iamf_render_interleaved.hip and
+// iamf_render_lpcm.hip, _lpcm24.hip, _lpcm_coupled.hip, _lpcm24_coupled.hip, _lpcm_mix.hip, _lpcm_mix_coupled.hip, iamf_render_interleaved.hip and
 // iamf_render_ragged.hip.
 // The units stay separate, so that they compile side by side; each includes this header at file scope and nothing else, and
 // holds its head comment and its entry of render_entry.hpp: the parameter sanity test and one call of a launcher below, in
@@ -29,7 +29,7 @@ namespace {
 #include "render_fast.hpp"
 
 // One element as LPCM packets: render_fast_kernel<M, OC, 0, false, false, LP = true, EARLY, LPB, LPC>.  LPB: bytes per sample
-// (2 or 3), LPC: the coupled 16-bit form; early: the per-channel (per-pair) prefetch (pick_route says when).
+// (2 or 3), LPC: the coupled form; early: the per-channel (per-pair) prefetch (pick_route says when).
 template <class MList, class OCList, int LPB, bool LPC>
 bool launch_fast_lp(const RenderParams &p, int m, bool early, hipStream_t st) {
   return dispatch(MList{}, m, [&](auto M) {

@@ -51,7 +51,8 @@ struct RenderParams {
   // input m; sparse = less than half of those bits are set (then all-zero weight batches are skipped)
   uint32_t nz_mask[6];
   int32_t sparse;
-  int32_t lpcm_coupled;     // (LPCM block below) 1: the packets have the coupled 16-bit form (lpcm_form.hpp, S16C); 0: as before.
+  int32_t lpcm_coupled;     // (LPCM block below) 1: the packets have the coupled 16-bit form (lpcm_form.hpp, S16C); 2: the coupled
+                            // 24-bit form (S24C, with lpcm_bytes == 3: iamf_hip_batch_render_packets); 0: as before.
                             // Host only — the kernels know it at compile time — and kept HERE, in what was padding in front
                             // of the next pointer, like lpcm_bytes: no kernel's arguments move
   // ---- optional extras (generic kernel only) ----
@@ -135,7 +136,7 @@ struct RenderParams {
   //      lpcm + s * lpcm_stream_stride + f * lpcm_frame_stride + lpcm_off[m] + 2 * i (bytes; every term a multiple of 8
   //      for i a multiple of 4).  `in` is not read then.  lpcm_bytes == 3 (above): 24-bit samples, 3 * i, every term a
   //      multiple of 4 (lpcm_form.hpp).  lpcm_coupled (above): channels m, m + 1 of a pair are interleaved, sample i of
-  //      the pair's first channel at lpcm_off[m] + 4 * i and its partner's 2 bytes on ----
+  //      the pair's first channel at lpcm_off[m] + 4 * i and its partner's 2 bytes on (S24C: 6 * i, 3 bytes on) ----
   const uint8_t *lpcm;
   int64_t lpcm_stream_stride, lpcm_frame_stride;
   int32_t lpcm_off[16];

@@ -47,6 +47,7 @@ using LpcmM = Ints<1, 4, 9, 16>;
 using LpcmOC = Ints<1, 2>;
 // render_fast_kernel<.., LP, EARLY, 2, LPC>: channel-based elements whose pairs are coupled sub-streams (lpcm_form.hpp,
 // S16C) — stereo, 5.1, 5.1.2 / 7.1, 5.1.4 / 7.1.2, 7.1.4 — into LpcmOC
+// (and, with 24-bit samples, render_fast_kernel<.., LP, EARLY, 3, LPC>: lpcm_form.hpp, S24C — the same lists)
 using LpcmCoupledM = Ints<2, 6, 8, 10, 12>;
 // The coupled form's pairing, a function of the channel count alone.  In the renderer's (playback) order every loudspeaker
 // layout of LpcmCoupledM reads L R [C LFE, then pairs]: channels (0,1) are a coupled pair, 2 and 3 mono sub-streams,
@@ -261,6 +262,8 @@ enum class Family {
                 // RenderParams::interleaved.  Set 5, listed by family only
   FastRagged,   // render_fast_kernel<M, OC, .., IL = false, RAG = true> (iamf_render_ragged.hip): planar f32 of any call length that
                 // is no whole number of 64-sample blocks, RenderParams::ragged.  Set 6, listed by family only
+  Lpcm24Coupled,  // render_fast_kernel<.., LP, EARLY, 3, LPC> (iamf_render_lpcm24_coupled.hip): RenderParams::lpcm_coupled == 2,
+                // which only iamf_hip_batch_render_packets sets; variant as Lpcm.  Set 7 (kRouteSetsAll), listed by family only
 };
 struct Route {
   Family family;
@@ -307,6 +310,29 @@ inline bool lpcm_coupled_early(int n_launch) {
 // its spread against itself at most 0.0027 — every measured size wins, so every size is fused; this is where a size that
 // stops winning would be cut.
 inline bool lpcm_coupled_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
+// Which prefetch variant a launch of n_launch workgroups of the coupled 24-bit form (RenderParams::lpcm_coupled == 2) takes,
+// under the rule of lpcm_coupled_early(): the faster one per size as measured by tools/lpcm24_coupled_rate.py (stereo / 5.1 /
+// 7.1.4 element into stereo s16, 64 frames x 1024, profiles/r15_lpcm24_coupled_rate.json).
+// Measured on an MI355X: the early per-pair prefetch at every size and for every element — 7.1.4, 512 / 2048 / 4096 streams:
+// 0.711 / 1.620 / 3.086 ms against 0.790 / 1.756 / 3.378 ms for the late one; 5.1: 0.516 / 1.124 / 2.159 against 0.567 / 1.195 /
+// 2.316; stereo: 0.303 / 0.664 / 1.285 against 0.336 / 0.714 / 1.393 — by 6 to 11 %, the baseline's run-to-run spread being at
+// most 0.6 %.  (All twenty instances are built for four workgroups per CU: DESIGN.md 4.1h.)  No cut, so the rule is the constant.
+// The late instances stay reachable by IAMF_HIP_LP_LATE=1, and IAMF_HIP_LP_EARLY=1 forces the early one (pick_route).
+inline bool lpcm24_coupled_early(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+// Whether a range of n_launch streams takes the coupled 24-bit form at all (render_prepare asks), under the rule of
+// lpcm_coupled_fused(): a size at which it does not beat what the call ran before — unpack, then the f32 kernel, timed from a
+// build of the parent commit in the same process — by more than that pair's own run-to-run spread is not fused.
+// Same run, same file: the pair takes 1.47 / 1.93 / 1.96 (stereo), 1.84 / 2.59 / 2.62 (5.1) and 2.31 / 3.23 / 3.38 (7.1.4) times
+// the fused call's time at 512 / 2048 / 4096 streams, its spread against itself at most 0.0055 — every measured (shape, size)
+// wins, so every size is fused; this is where a size that stops winning would be cut.
+inline bool lpcm24_coupled_fused(int n_launch) {
   (void)n_launch;
   return true;
 }
@@ -385,6 +411,13 @@ inline Route pick_route(const RenderParams &p, int m) {
       if (((int64_t)p.total / p.frame_size + 2) * p.in2_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31)
         return refuse(IAMF_HIP_ERR_INVALID_STATE);
       return take(Family::LpcmMix, p.lpcm_mix);
+    }
+    // the coupled 24-bit form (lpcm_coupled == 2, set by iamf_hip_batch_render_packets alone, and 24-bit samples — 2 with any
+    // other sample size names no form): the coupled instances' lists under exactly the refusals of Family::Lpcm24
+    if (p.lpcm_coupled == 2) {
+      if (p.lpcm_bytes != 3 || !LpcmCoupledM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on)
+        return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      return take(Family::Lpcm24Coupled, !getenv("IAMF_HIP_LP_LATE") && (getenv("IAMF_HIP_LP_EARLY") || lpcm24_coupled_early(p.n_launch)));
     }
     // the coupled 16-bit form: its own instances (the pairing is a function of m: lpcm_form.hpp), the same refusals
     if (p.lpcm_coupled) {
@@ -533,6 +566,13 @@ void for_each_render_instance_ragged(F &&f) {
   for_each_int(RaggedM{}, [&](int m) { for_each_int(RaggedOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_FAST_RAGGED, 0, m, oc, 0); }); });
 }
 
+// The coupled 24-bit LPCM form (iamf_hip_route_family_instances), walking LpcmCoupledM x LpcmOC as its launcher does.
+template <class F>
+void for_each_render_instance_lpcm24_coupled(F &&f) {
+  for (int early = 0; early < 2; ++early)
+    for_each_int(LpcmCoupledM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM24_COUPLED, early, m, oc, 0); }); });
+}
+
 // The row sets behind the listing, by number: f as above for every instance of set `set`.  Sets 0 .. kRouteTables - 1 are
 // the numbered tables of iamf_hip_route_table_instances — their count and the rows of each are pinned — and the sets behind
 // them are listed by family only (iamf_hip_route_family_instances), in this order.  The only place that maps a set number
@@ -550,6 +590,16 @@ void for_each_instance_of_set(int set, F &&f) {
     case 5: for_each_render_instance_interleaved(f); break;
     case 6: for_each_render_instance_ragged(f); break;
   }
+}
+
+// The sets for_each_instance_of_set walks are pinned at seven, and so is the answer "no row" for every other number.  Sets added
+// since are walked here: numbers kRouteSets .. kRouteSetsAll - 1, listed by family only like the sets behind the numbered
+// tables.  What iamf_route.hip builds and counts by.
+constexpr int kRouteSetsAll = 8;
+template <class F>
+void for_each_instance_of_any_set(int set, F &&f) {
+  if (set == 7) for_each_render_instance_lpcm24_coupled(f);
+  else for_each_instance_of_set(set, f);
 }
 
 // the row of the kernel launch() runs for a route, and the set that lists it: what iamf_hip_route_count takes (a FirSplit
@@ -579,6 +629,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::LpcmMix: return {IAMF_HIP_ROUTE_LPCM_MIX, 0, m, p.out_ch, r.variant, 4};   // a family listing's row, k = LP2
     case Family::FastInterleaved: return {IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, p.out_ch, 0, 5};   // a family listing's row
     case Family::FastRagged: return {IAMF_HIP_ROUTE_FAST_RAGGED, 0, m, p.out_ch, 0, 6};   // a family listing's row
+    case Family::Lpcm24Coupled: return {IAMF_HIP_ROUTE_LPCM24_COUPLED, r.variant, m, p.out_ch, 0, 7};   // a family listing's row
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

@@ -82,6 +82,10 @@ class RaggedCall(C.Structure):   # iamf_hip_ragged_call
     _fields_ = [("args", RenderArgs), ("reserved", C.c_int32 * 4)]
 
 
+class PacketCall(C.Structure):   # iamf_hip_packet_call
+    _fields_ = [("in_", LpcmInput), ("args", RenderArgs), ("reserved", C.c_int32 * 4)]
+
+
 class FanoutReport(C.Structure):   # iamf_hip_fanout_report
     _fields_ = [("n_fused", C.c_int32), ("input_fused", C.c_int32), ("n_unpacks", C.c_int32), ("reserved", C.c_int32)]
 
@@ -95,7 +99,9 @@ class RouteRow(C.Structure):   # iamf_hip_route_row
 ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, WIDE4_DEMIX=7, WIDE4_DOWN=8, WIDE4_MIX=9,
              WIDE4_LFE=10, LPCM=11, FANOUT=12, FIR_SPLIT=13, FIR_FUSED=14, FANOUT_LPCM=15, LPCM24=16, LPCM_COUPLED=17,
              RS_PLAIN=20, RS_TILE=21, RS_BLOCK=22, RS_DIRECT=23, LPCM_MIX=25, FAST_INTERLEAVED=27, FAST_RAGGED=29)
-ROUTE_NAME = {v: k for k, v in ROUTE.items()}
+# families that no table and none of the by-family listings above names (ROUTE's keys are pinned by their callers)
+ROUTE_BY_FAMILY_ONLY = dict(LPCM24_COUPLED=31)
+ROUTE_NAME = {v: k for k, v in list(ROUTE.items()) + list(ROUTE_BY_FAMILY_ONLY.items())}
 
 
 class StreamGains(C.Structure):   # iamf_hip_stream_gains: host arrays of the RANGE's length, NULL = leave that gain
@@ -193,6 +199,7 @@ def lib():
         L.iamf_hip_batch_render_lpcm_mix.argtypes = [C.c_void_p, C.POINTER(LpcmMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_interleaved.argtypes = [C.c_void_p, C.POINTER(InterleavedCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_ragged.argtypes = [C.c_void_p, C.POINTER(RaggedCall), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_packets.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_resampler_destroy.argtypes = [C.c_void_p]
@@ -375,7 +382,9 @@ def route_table_tally(t, reset=False):
 
 
 def _family_id(family):
-    return ROUTE[family] if isinstance(family, str) else int(family)
+    if isinstance(family, str):
+        return ROUTE[family] if family in ROUTE else ROUTE_BY_FAMILY_ONLY[family]
+    return int(family)
 
 
 def route_family_instances(family):
@@ -597,6 +606,17 @@ class Batch:
         r = lib().iamf_hip_batch_render_ragged(self.h, C.byref(call), s0, n)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_ragged")
+        return r
+
+    def render_packets(self, inp, args, stream0=0, n_streams=None):
+        """iamf_hip_batch_render_packets: element 0 as LPCM packets of any form (LpcmInput), `args` a RenderArgs with d_in =
+        d_in2 = None; the whole batch unless a range is named"""
+        call = PacketCall()
+        call.in_, call.args = inp, args
+        n = self.cfg.n_streams - stream0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_packets(self.h, C.byref(call), stream0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_packets")
         return r
 
     def render_range(self, args, stream0, n_streams):

@@ -749,6 +749,36 @@ typedef struct {
 } iamf_hip_ragged_call;
 int iamf_hip_batch_render_ragged(iamf_hip_batch *b, const iamf_hip_ragged_call *call, int32_t stream0, int32_t n_streams);
 
+/* Element 0 as LPCM packets, every packet form the fused kernels read: what iamf_hip_batch_render_lpcm_range takes and, beyond
+ * it, 24-bit packets of a channel-based element whose channel pairs are coupled sub-streams.  On any batch and any packet
+ * layout the call leaves the batch, d_pcm and its return value exactly as
+ *   iamf_hip_batch_render_lpcm_range(b, &call->in, &call->args, stream0, n_streams)
+ * does, bit for bit, persisted stream state included — so calls of either entry, flushes, restarts, exports and imports may
+ * follow one another on one batch.
+ *   in        as for iamf_hip_batch_render_lpcm.
+ *   args      as for iamf_hip_batch_render_lpcm: d_in and d_in2 NULL.
+ *   reserved  0.
+ * One pass of the headline kernel over the packets as they lie (IAMF_HIP_ROUTE_LPCM24_COUPLED, 3 * channels + 4 instead of
+ * 11 * channels + 4 bytes per sample-frame into s16 stereo) when the packets have the coupled 24-bit form: little-endian
+ * 24-bit samples of 2, 6, 8, 10 or 12 channels in playback order, every channel present; channels (0,1) and, from six
+ * channels on, (4,5) .. (n-2, n-1) each ONE run of interleaved samples (src_step 6, the partner's src_offset 3 bytes behind the
+ * first's), channels 2 and 3 (C, LFE) contiguous runs (src_step 3); d_raw 16-byte aligned, both strides multiples of 4; a
+ * pair's src_offset + 6 * first_sample and a mono run's src_offset + 3 * first_sample multiples of 4 — and the call is one
+ * the fused 16-bit coupled form would take: one or two output channels, limiter on, whole 64-sample blocks, no second
+ * element, ramps, down-mixer, demixer, projection, pre-matrix, HRTF stage or LFE generator, the streams' position a multiple
+ * of 16 or at least 240, (n_frames + 2) * raw_frame_stride + 2^24 below 2^31.  Every other call takes exactly the path of
+ * iamf_hip_batch_render_lpcm_range, its fused forms included; IAMF_HIP_LPCM_UNFUSED=1 forces the unpacker and the f32
+ * kernels, as everywhere.
+ * Returns the sample-frames emitted per stream.  IAMF_HIP_ERR_BAD_ARG, before anything is queued, allocated or changed: a NULL
+ * batch or call, non-zero reserved, a non-NULL d_in or d_in2; and, with its own code, whatever
+ * iamf_hip_batch_render_lpcm_range refuses. */
+typedef struct {
+  iamf_hip_lpcm_input in;
+  iamf_hip_render_args args;   /* d_in, d_in2 NULL */
+  int32_t reserved[4];         /* 0 */
+} iamf_hip_packet_call;
+int iamf_hip_batch_render_packets(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams);
+
 /* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
  * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
  *
@@ -826,6 +856,8 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *                          (iamf_hip_route_family_instances only)
  *     FAST_RAGGED          planar f32 of any call length (iamf_hip_batch_render_ragged): m, c; variant 0
  *                          (iamf_hip_route_family_instances only)
+ *     LPCM24_COUPLED       the coupled 24-bit form (iamf_hip_batch_render_packets): variant, m, c as LPCM
+ *                          (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -861,7 +893,8 @@ enum {
   IAMF_HIP_ROUTE_RS_DIRECT = 23,
   IAMF_HIP_ROUTE_LPCM_MIX = 25,      /* no table: iamf_hip_route_family_instances / _family_tally (18, 19, 24: unused) */
   IAMF_HIP_ROUTE_FAST_INTERLEAVED = 27,  /* no table either (26: unused) */
-  IAMF_HIP_ROUTE_FAST_RAGGED = 29        /* no table either (28: unused) */
+  IAMF_HIP_ROUTE_FAST_RAGGED = 29,       /* no table either (28: unused) */
+  IAMF_HIP_ROUTE_LPCM24_COUPLED = 31     /* no table either (30 stays unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -893,7 +926,7 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * LPCM), which no table lists and whose launches show in no table's tally.  _instances: every row of the family;
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
- * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED and FAST_RAGGED. */
+ * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED and LPCM24_COUPLED. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
