@@ -398,6 +398,9 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
     case Family::LpcmMix:
       launched = p.lpcm_coupled ? iamf_hip_fast_lpcm_mix_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_lpcm_mix_launch(&p, m, r.variant, st);
       break;
+    case Family::Lpcm24Mix:
+      launched = p.lpcm_coupled ? iamf_hip_fast_lpcm24_mix_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_lpcm24_mix_launch(&p, m, r.variant, st);
+      break;
     case Family::FastInterleaved: launched = iamf_hip_fast_interleaved_launch(&p, m, st); break;
     case Family::FastRagged: launched = iamf_hip_fast_ragged_launch(&p, m, st); break;
     case Family::FirSplit: {
@@ -462,7 +465,7 @@ struct LpcmIn {
 constexpr int kNotFused = INT32_MIN;
 // the family a packet call must route to for a fused kernel to read its packets (lp2: the second element's, or null)
 Family lpcm_family(const LpcmIn *lp, const LpcmIn *lp2) {
-  if (lp2) return Family::LpcmMix;
+  if (lp2) return lp->bytes == 3 ? Family::Lpcm24Mix : Family::LpcmMix;   // (24-bit: iamf_hip_batch_render_packets_mix only)
   if (lp->coupled == 2) return Family::Lpcm24Coupled;
   if (lp->coupled) return Family::LpcmCoupled;
   return lp->bytes == 3 ? Family::Lpcm24 : Family::Lpcm;
@@ -506,7 +509,7 @@ int lfe_prepass(iamf_hip_batch *b, const float *d_in, int64_t in_stream_stride, 
 // stride, the `done` event, the emitted count) — so that iamf_hip_batch_render_fanout can prepare every member, launch
 // once, and commit each, and restates none of it.
 struct PreparedCall {
-  RenderMixParams p;   // (the part behind RenderParams: set for Family::LpcmMix only)
+  RenderMixParams p;   // (the part behind RenderParams: set for Family::LpcmMix and Family::Lpcm24Mix only)
   iamf_hip_render_args a;
   int m_eff;
   size_t lds;
@@ -639,11 +642,14 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     for (int m = 0; m < 16; ++m) p.lpcm_off[m] = lp->off[m];
     p.lpcm_bytes = lp->bytes;
     p.lpcm_coupled = lp->coupled;
-    if (lp->bytes == 3 && !lp->coupled && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
+    if (lp->bytes == 3 && !lp->coupled && !lp2 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     if (lp->coupled == 1 && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
-    if (lp->coupled == 2 && (lp2 || !lpcm24_coupled_fused(cnt))) return kNotFused;
+    if (lp->coupled == 2 && !lp2 && !lpcm24_coupled_fused(cnt)) return kNotFused;
     if (lp2) {   // the kernel reads RenderMixParams; pick_route the packets' place in the in2 fields (strides in bytes)
-      p.lpcm_mix = lp2->coupled ? 2 : 1;
+      // 24-bit packets on both elements (iamf_hip_batch_render_packets_mix alone hands them over): the form's own values
+      if (lp->bytes != lp2->bytes) return kNotFused;
+      p.lpcm_mix = (lp->bytes == 3 ? 4 : 0) | (lp2->coupled ? 2 : 1);
+      if (lp->bytes == 3 && !lpcm24_mix_fused(cnt)) return kNotFused;
       p.in2 = reinterpret_cast<const float *>(lp2->raw);
       p.in2_stream_stride = lp2->stream_stride;
       p.in2_frame_stride = lp2->frame_stride;
@@ -651,7 +657,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       pc.p.lpcm2_stream_stride = lp2->stream_stride;
       pc.p.lpcm2_frame_stride = lp2->frame_stride;
       for (int m = 0; m < 4; ++m) pc.p.lpcm2_off[m] = lp2->off[m];
-      if (!lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
+      if (lp->bytes != 3 && !lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     }
     if (pick_route(p, m_eff).family != lpcm_family(lp, lp2)) return kNotFused;
   }
@@ -1172,7 +1178,7 @@ int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in,
 // The packet-form checks of an LPCM call of nf frames (n_samples as iamf_hip_render_args::n_samples): an error, or
 // IAMF_HIP_OK with the trim {first, count} and whether the packets have the form the fused kernels read
 // (ch: the channels of the element the packets hold — element 0's, or the second element's for iamf_hip_batch_render_lpcm_mix;
-//  packets: the call came through iamf_hip_batch_render_packets, which also takes LpcmForm::S24C)
+//  packets: the call came through iamf_hip_batch_render_packets or _packets_mix, which also take LpcmForm::S24C)
 static int lpcm_form_check_ch(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int ch, int nf, int n_samples, LpcmForm *form_out,
                               int *first_out, int *count_out, bool packets = false) {
   const iamf_hip_lpcm_layout &L = in->layout;
@@ -1304,10 +1310,10 @@ int iamf_hip_batch_render_packets(iamf_hip_batch *b, const iamf_hip_packet_call 
 // S16 with 1 or 4 channels or S16C with 2 (lpcm_form() on each element's own layout) — and pick_route takes the call; in
 // every other case both elements are unpacked, each into a buffer of the batch, and the f32 path renders them.  Both ways
 // give the same PCM and leave the same stream state, bit for bit.  Every refusal comes before the first launch.
-int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_call *call, int32_t stream0, int32_t n_streams) {
-  if (!b || !call) return IAMF_HIP_ERR_BAD_ARG;
-  const iamf_hip_lpcm_input *in0 = &call->in[0], *in1 = &call->in[1];
-  const iamf_hip_render_args *args = &call->args;
+// (packets: iamf_hip_batch_render_packets_mix — the forms are asked of lpcm_form_packets(), and 24-bit packets on both
+//  elements are a fused form as well; everything else is the one path)
+static int render_lpcm_mix_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in0, const iamf_hip_lpcm_input *in1,
+                                const iamf_hip_render_args *args, int32_t stream0, int32_t n_streams, bool packets) {
   if (!b->has2 || args->d_in || args->d_in2 || !in0->d_raw || !in1->d_raw || in0->first_sample != in1->first_sample ||
       !args->d_pcm || args->n_frames < 0)
     return IAMF_HIP_ERR_BAD_ARG;
@@ -1317,9 +1323,9 @@ int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_ca
   const int ch = element_channels(b), nf = args->n_frames;
   LpcmForm form0 = LpcmForm::None, form1 = LpcmForm::None;
   int first = 0, count = 0, first1 = 0, count1 = 0;
-  int fc = lpcm_form_check_ch(b, in0, ch, nf, args->n_samples, &form0, &first, &count);
+  int fc = lpcm_form_check_ch(b, in0, ch, nf, args->n_samples, &form0, &first, &count, packets);
   if (fc != IAMF_HIP_OK) return fc;
-  fc = lpcm_form_check_ch(b, in1, b->m2, nf, args->n_samples, &form1, &first1, &count1);
+  fc = lpcm_form_check_ch(b, in1, b->m2, nf, args->n_samples, &form1, &first1, &count1, packets);
   if (fc != IAMF_HIP_OK) return fc;
   // Everything the render call would refuse is refused here, in front of the fused attempt and of the first unpack launch
   // (the two packet buffers stand in for d_in / d_in2: "not a flush", "a second element is given")
@@ -1330,9 +1336,13 @@ int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_ca
   int64_t total = 0;
   const int rc = range_args_check(b, &a, stream0, n_streams, &total);
   if (rc != IAMF_HIP_OK || total == 0) return rc;
-  const bool form0_ok = (form0 == LpcmForm::S16 && LpcmM::has(ch)) || form0 == LpcmForm::S16C;
-  const bool form1_ok = (form1 == LpcmForm::S16 || form1 == LpcmForm::S16C) &&
-                        lpcm_mix_m2_ok(form1 == LpcmForm::S16C ? 2 : 1, b->m2);
+  bool form0_ok = (form0 == LpcmForm::S16 && LpcmM::has(ch)) || form0 == LpcmForm::S16C;
+  bool form1_ok = (form1 == LpcmForm::S16 || form1 == LpcmForm::S16C) &&
+                  lpcm_mix_m2_ok(form1 == LpcmForm::S16C ? 2 : 1, b->m2);
+  if (packets && !(form0_ok && form1_ok)) {   // the 24-bit mix form: both elements 24-bit, each in a form its side reads
+    form0_ok = (form0 == LpcmForm::S24 && LpcmM::has(ch)) || form0 == LpcmForm::S24C;
+    form1_ok = (form1 == LpcmForm::S24 || form1 == LpcmForm::S24C) && lpcm_mix_m2_ok(form1 == LpcmForm::S24C ? 2 : 1, b->m2);
+  }
   if (form0_ok && form1_ok) {
     LpcmIn lp0, lp1;
     lpcm_in_of(in0, ch, first, form0, lp0);
@@ -1346,6 +1356,22 @@ int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_ca
   ur = lpcm_unpack_range(b, in1, nf, first, count, stream0, n_streams, st, a, true);
   if (ur != IAMF_HIP_OK) return ur;
   return render_range_impl(b, &a, stream0, n_streams, nullptr);
+}
+
+int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, false);
+}
+
+// Both elements of a mix as LPCM packets of every form a fused kernel reads (include/iamf_hip.h): iamf_hip_batch_render_lpcm_mix
+// with leave to take render_fast_kernel<.., LP, true, 3, LPC, LP2> (Family::Lpcm24Mix) where both elements hold 24-bit packets
+// — element 0: S24 with LpcmM channels or S24C; element 1: S24 with 1 or 4 channels or S24C with 2 (lpcm_form_packets() on
+// each element's own layout) — and render_prepare and pick_route let the call through.  The same checks in the same order,
+// the same path for everything else.
+int iamf_hip_batch_render_packets_mix(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, true);
 }
 
 // Interleaved f32 of any call length (include/iamf_hip.h): iamf_hip_batch_render_range with leave to take

@@ -4,7 +4,7 @@
 // names depend on it), hence `const void *params`: the caller's RenderParams / FanParams, the same definition on both
 // sides (render_params.hpp, render_fanout.hpp).  Each returns 1 if it launched, 0 if (m, the block's channel counts) is
 // not in the instance list the caller has already consulted (render_route.hpp).  The units that feed render_fast_kernel
-// another input form (the eight iamf_hip_fast_*_launch entries) share their launchers: render_fast_unit.hpp.  Behind the
+// another input form (the ten iamf_hip_fast_*_launch entries) share their launchers: render_fast_unit.hpp.  Behind the
 // launch entries: the unpacker's, and the one entry through which every launcher counts what it ran (iamf_route.hip).
 #pragma once
 
@@ -33,6 +33,10 @@ IAMF_INTERNAL int iamf_hip_fast_lpcm24_coupled_launch(const void *params, int m,
 // (params->lpcm_coupled); params: a RenderMixParams; lp2: Route::variant of Family::LpcmMix
 IAMF_INTERNAL int iamf_hip_fast_lpcm_mix_launch(const void *params, int m, int lp2, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fast_lpcm_mix_coupled_launch(const void *params, int m, int lp2, hipStream_t st);
+// iamf_render_lpcm24_mix.hip, iamf_render_lpcm24_mix_coupled.hip: the same with 24-bit packets on both elements
+// (params->lpcm_bytes == 3, lpcm_mix == (4 | lp2), lpcm_coupled 0 / 2); lp2: Route::variant of Family::Lpcm24Mix
+IAMF_INTERNAL int iamf_hip_fast_lpcm24_mix_launch(const void *params, int m, int lp2, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_fast_lpcm24_mix_coupled_launch(const void *params, int m, int lp2, hipStream_t st);
 // iamf_render_interleaved.hip: render_fast_kernel<M, OC, .., IL, RAG>, interleaved f32 of any call length (params->interleaved)
 IAMF_INTERNAL int iamf_hip_fast_interleaved_launch(const void *params, int m, hipStream_t st);
 // iamf_render_ragged.hip: render_fast_kernel<M, OC, .., IL = false, RAG>, planar f32 of any call length (params->ragged)

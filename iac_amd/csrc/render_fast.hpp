@@ -238,12 +238,16 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       LPB == 3 (lpcm_form.hpp, S24C): a pair's four sample-frames are 24 contiguous bytes on the dword grid, TWO 12-byte loads
 //       (the second 12 bytes on) into xr3[m], xr3[m + 1]: each triple holds four samples L R L R in exactly the 24-bit form's
 //       a, b, c pattern, so the cut is that form's — channel m takes samples 0 and 2 of both triples, m + 1 samples 1 and 3.
-// LP2:  (LP, LPB == 2, IN2, EARLY) the second element arrives as 16-bit packets too (RenderMixParams::lpcm2, iamf_hip_batch_render_lpcm_mix):
+// LP2:  (LP, IN2, EARLY; LPB == 2 here, LPB == 3 below) the second element arrives as 16-bit packets too (RenderMixParams::lpcm2, iamf_hip_batch_render_lpcm_mix):
 //       1: mono-coded runs, m2 = 1 or 4 at run time, one 8-byte load per channel and lane; 2: ONE coupled stereo pair
 //       (m2 == 2), one 16-byte load per lane, L out of the low halves and R out of the sign-extended high halves as LPC does.
 //       Through a buffer resource of its own; converted where the mixing stage consumes it, "/ 32768" folded into the staged
 //       mat2 weights as it is into mat.  Everything behind the two projections is the IN2 body.  Element 0's next chunk is
 //       requested channel by channel under the projection (kEarly); element 1's and the ramps' behind the mixing stage.
+//       LPB == 3 (iamf_hip_batch_render_packets_mix): both elements hold 24-bit samples.  Element 0 is read exactly as the
+//       single-element 24-bit forms read it (LPC or not); element 1 — 1: one 12-byte load per channel and lane, cut with the
+//       24-bit form's a / b / c expressions; 2: the pair's 24 bytes as two 12-byte loads, L taking samples 0 and 2 of both
+//       triples and R 1 and 3, as LPB == 3 with LPC does — and "/ 2^23" is folded into mat2 as it is into mat.
 // IL:   (plain matrix variant, frame size 1: iamf_hip_batch_render_interleaved) the element arrives as ordinary interleaved
 //       f32, [sample-frame][channel] with the sample-frames dense.  A lane's four sample-frames are 16 * M contiguous bytes
 //       of the stream's buffer resource: one 16-byte load for M = 1, two for M = 2, transposed in registers into the x[m]
@@ -261,14 +265,14 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       the frames' rows: the host only sends calls whose frame size is a multiple of 4 (pick_route, ragged_shape_ok).
 template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2, bool LPC = false,
           int LP2 = 0, bool IL = false, bool RAG = false>
-__global__ __launch_bounds__(FIR == 1 ? 512 : 256, LP2 ? lpcm_mix_wgs(M, OC, LP2) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
+__global__ __launch_bounds__(FIR == 1 ? 512 : 256, LP2 ? (LPB == 3 ? lpcm24_mix_wgs(M, OC, LP2) : lpcm_mix_wgs(M, OC, LP2)) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
 void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, RenderParams> p) {
   static_assert(!(FIR && DOWN), "one renderer");
   static_assert(!(LP && (FIR || DOWN || (IN2 && !LP2))) && (!LP || M <= 16), "the LPCM input feeds the plain matrix variant");
-  static_assert(LP2 == 0 || ((LP2 == 1 || LP2 == 2) && LP && IN2 && EARLY && LPB == 2), "a packet-fed second element joins a 16-bit packet-fed first one");
+  static_assert(LP2 == 0 || ((LP2 == 1 || LP2 == 2) && LP && IN2 && EARLY), "a packet-fed second element joins a packet-fed first one of its sample size");
   static_assert(!(IN2 && (FIR || DOWN)), "the second element joins a matrix-rendered first one");
   static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
-  static_assert(!LPC || (LP && (LPB == 2 || (LPB == 3 && LP2 == 0)) && lpcm_coupled_m(M)), "coupled pairs: 16- or 24-bit packets of a loudspeaker layout");
+  static_assert(!LPC || (LP && lpcm_coupled_m(M)), "coupled pairs: 16- or 24-bit packets of a loudspeaker layout");
   static_assert(!IL || (!FIR && !DOWN && !IN2 && !LP && EARLY && M <= 2), "interleaved f32 feeds the plain matrix variant, one or two channels");
   static_assert(!RAG || IL || (!FIR && !DOWN && !IN2 && !LP && EARLY), "ragged calls: the interleaved form, or the plain planar f32 one");
   constexpr bool LP3 = LP && LPB == 3;
@@ -342,7 +346,8 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
       const int f = p.src_feed2[c];
       mat2[t] = (f >= 0 && m < p.m2) ? p.matrix2[f * p.m2 + m] : 0.f;
       // LP2: the decoder's "/ 32768" of element 1 folded into its weights, as into mat above (iamf_hip_batch::lp2_scale_ok)
-      if constexpr (LP2 != 0) mat2[t] *= 1.0f / 32768.0f;
+      // (LPB == 3: "/ 2^23", under the same host check, as for mat)
+      if constexpr (LP2 != 0) mat2[t] *= LPB == 3 ? 1.0f / 8388608.0f : 1.0f / 32768.0f;
     }
     chain_wave_publish(misc + 12);
   }
@@ -376,6 +381,12 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   // in x2r[0], x2r[1] — converted where the mixing stage consumes them
   using lp2_u2 = __attribute__((ext_vector_type(2))) unsigned;
   lp2_u2 x2r[LP2 == 1 ? kFIn2 : (LP2 == 2 ? 2 : 1)];
+  // LPB == 3: four 24-bit samples in three dwords — a[23:0], {b[15:0], a[31:24]}, {c[7:0], b[31:16]}, c[31:8]
+  struct lp_u3 {
+    unsigned a, b, c;
+  };
+  // LP2 with 24-bit samples: 1: channel m's four samples in x2r3[m]; 2: the pair's L0 R0 L1 R1 in x2r3[0], L2 R2 L3 R3 in x2r3[1]
+  lp_u3 x2r3[(LP3 && LP2 == 1) ? kFIn2 : ((LP3 && LP2 == 2) ? 2 : 1)];
   const auto lp2_rsrc = [&]() {
     if constexpr (LP2 != 0)
       return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.lpcm2 + (int64_t)s * p.lpcm2_stream_stride), 0, 0x7fffffff, 0x00020000);
@@ -385,7 +396,25 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   const auto rs_in2 = lp2_rsrc();   // (32-bit offsets inside a stream's region of one call: pick_route bounds them)
   (void)rs_in2;
   auto load_x2 = [&](int f, int i) {  // the lane's 4 samples of the second element's channels (frame f, position i)
-    if constexpr (LP2 == 1) {
+    if constexpr (LP2 == 1 && LP3) {
+      // (dword-aligned: element 1's base, strides and run offsets are multiples of 4 — pick_route, lpcm_form.hpp — and 3 * i
+      //  one of 12)
+      const int vo = f * (int)p.lpcm2_frame_stride + 3 * i;
+#pragma unroll
+      for (int m = 0; m < kFIn2; ++m) {
+        x2r3[m] = lp_u3{0u, 0u, 0u};
+        if (m < p.m2) {
+          const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs_in2, vo, p.lpcm2_off[m], 2 /* nt */);
+          x2r3[m] = lp_u3{v[0], v[1], v[2]};
+        }
+      }
+    } else if constexpr (LP2 == 2 && LP3) {
+      const int vo = f * (int)p.lpcm2_frame_stride + 6 * i;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs_in2, vo, p.lpcm2_off[0], 2 /* nt */);
+      const auto w = __builtin_amdgcn_raw_buffer_load_b96(rs_in2, vo + 12, p.lpcm2_off[0], 2 /* nt */);
+      x2r3[0] = lp_u3{v[0], v[1], v[2]};
+      x2r3[1] = lp_u3{w[0], w[1], w[2]};
+    } else if constexpr (LP2 == 1) {
       const int vo = f * (int)p.lpcm2_frame_stride + 2 * i;
 #pragma unroll
       for (int m = 0; m < kFIn2; ++m) {
@@ -432,11 +461,7 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   // the chunk that uses them: (float)sample * (1 / 32768), the expression of iamf_hip_lpcm_unpack and of the reference
   using lp_u2 = __attribute__((ext_vector_type(2))) unsigned;
   lp_u2 xr[(LP && !LP3) ? M : 1];
-  // LPB == 3: four 24-bit samples in three dwords — a[23:0], {b[15:0], a[31:24]}, {c[7:0], b[31:16]}, c[31:8]
-  struct lp_u3 {
-    unsigned a, b, c;
-  };
-  lp_u3 xr3[LP3 ? M : 1];
+  lp_u3 xr3[LP3 ? M : 1];   // LPB == 3: lp_u3, above
   const uint8_t *lp_s = LP ? p.lpcm + (int64_t)s * p.lpcm_stream_stride : nullptr;
   // The element's input goes through BUFFER loads: one resource per stream (base = the stream's region), the lane's byte
   // offset in one register for all channels, the channel's offset as the instruction's scalar offset — no address
@@ -575,6 +600,8 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
       for (int m = 0; m < (IN2 ? kFIn2 : 0); ++m) x2[m] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int m = 0; m < (LP2 == 1 ? kFIn2 : (LP2 == 2 ? 2 : 0)); ++m) x2r[m] = lp2_u2{0u, 0u};
+#pragma unroll
+      for (int m = 0; m < (!LP3 ? 0 : (LP2 == 1 ? kFIn2 : (LP2 == 2 ? 2 : 0))); ++m) x2r3[m] = lp_u3{0u, 0u, 0u};
     }
     load_drec(k / fs);
   }
@@ -779,7 +806,20 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
       downmix_factors(drec, k - (k / fs) * fs, cf);
       downmix4<M, OC>(x, yd, cf, p.dmx_in_layout, p.dmx_out_layout);
     }
-    if constexpr (LP2 == 1) {   // (the scale 2^-15 sits in the mat2 weights; channels at or beyond m2 hold zeros)
+    if constexpr (LP2 == 1 && LP3) {   // (the scale 2^-23 sits in the mat2 weights; channels at or beyond m2 hold zeros)
+#pragma unroll
+      for (int m = 0; m < kFIn2; ++m) {
+        const unsigned a = x2r3[m].a, b = x2r3[m].b, c = x2r3[m].c;
+        x2[m] = make_float4((float)((int)(a << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(b, a, 24) << 8) >> 8),
+                            (float)((int)(__builtin_amdgcn_alignbit(c, b, 16) << 8) >> 8), (float)((int)c >> 8));
+      }
+    } else if constexpr (LP2 == 2 && LP3) {   // each triple is L R L R: L takes its samples 0 and 2, R 1 and 3
+      const unsigned a = x2r3[0].a, b = x2r3[0].b, c = x2r3[0].c, d = x2r3[1].a, e = x2r3[1].b, g = x2r3[1].c;
+      x2[0] = make_float4((float)((int)(a << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(c, b, 16) << 8) >> 8),
+                          (float)((int)(d << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(g, e, 16) << 8) >> 8));
+      x2[1] = make_float4((float)((int)(__builtin_amdgcn_alignbit(b, a, 24) << 8) >> 8), (float)((int)c >> 8),
+                          (float)((int)(__builtin_amdgcn_alignbit(e, d, 24) << 8) >> 8), (float)((int)g >> 8));
+    } else if constexpr (LP2 == 1) {   // (the scale 2^-15 sits in the mat2 weights; channels at or beyond m2 hold zeros)
 #pragma unroll
       for (int m = 0; m < kFIn2; ++m) {
         const unsigned a = x2r[m].x, b = x2r[m].y;

@@ -1,5 +1,6 @@
 // render_fast_unit.hpp — what the translation units that feed render_fast_kernel (render_fast.hpp) another input form share:
-// iamf_render_lpcm.hip, _lpcm24.hip, _lpcm_coupled.hip, _lpcm24_coupled.hip, _lpcm_mix.hip, _lpcm_mix_coupled.hip, iamf_render_interleaved.hip and
+// iamf_render_lpcm.hip, _lpcm24.hip, _lpcm_coupled.hip, _lpcm24_coupled.hip, _lpcm_mix.hip, _lpcm_mix_coupled.hip, _lpcm24_mix.hip,
+// _lpcm24_mix_coupled.hip, iamf_render_interleaved.hip and
 // iamf_render_ragged.hip.
 // The units stay separate, so that they compile side by side; each includes this header at file scope and nothing else, and
 // holds its head comment and its entry of render_entry.hpp: the parameter sanity test and one call of a launcher below, in
@@ -43,17 +44,18 @@ bool launch_fast_lp(const RenderParams &p, int m, bool early, hipStream_t st) {
   });
 }
 
-// Both elements of a mix as 16-bit packets: render_fast_kernel<M, OC, 0, false, IN2 = true, LP = true, EARLY = true, 2, LPC,
-// LP2> with LP2 = lp2 out of KList.  LPC: element 0 is coupled.
-template <class MList, class OCList, bool LPC, class KList>
+// Both elements of a mix as packets of LPB bytes per sample: render_fast_kernel<M, OC, 0, false, IN2 = true, LP = true,
+// EARLY = true, LPB, LPC, LP2> with LP2 = lp2 out of KList.  LPC: element 0 is coupled.
+template <class MList, class OCList, bool LPC, class KList, int LPB = 2>
 bool launch_fast_lp_mix(const RenderMixParams &p, int m, int lp2, hipStream_t st) {
   return dispatch(MList{}, m, [&](auto M) {
     return dispatch(OCList{}, p.out_ch, [&](auto OC) {
       return dispatch(KList{}, lp2, [&](auto K) {
         constexpr int m_ = decltype(M)::value, oc_ = decltype(OC)::value, lp2_ = decltype(K)::value;
         constexpr size_t lds = sizeof(float) * (size_t)fast_lds_floats(oc_, m_);   // (the second element's matrix rows are in it)
-        static_assert(lds * lpcm_mix_wgs(m_, oc_, lp2_) <= 160 * 1024, "the workgroups the instance is built for fit a CU's LDS");
-        launch_big_lds<&render_fast_kernel<m_, oc_, 0, false, true, true, true, 2, LPC, lp2_>, 80 * 1024>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
+        static_assert(lds * (LPB == 3 ? lpcm24_mix_wgs(m_, oc_, lp2_) : lpcm_mix_wgs(m_, oc_, lp2_)) <= 160 * 1024,
+                      "the workgroups the instance is built for fit a CU's LDS");
+        launch_big_lds<&render_fast_kernel<m_, oc_, 0, false, true, true, true, LPB, LPC, lp2_>, 80 * 1024>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
       });
     });
   });

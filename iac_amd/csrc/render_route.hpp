@@ -66,6 +66,18 @@ IAMF_HD constexpr int lpcm_mix_wgs(int m, int oc, int lp2) {
   (void)m, (void)oc, (void)lp2;
   return 4;
 }
+// render_fast_kernel<.., LP, true, 3, LPC, LP2>: both elements as 24-bit packets (iamf_hip_batch_render_packets_mix) — the same
+// lists, element 1 of element 0's sample size.  Workgroups per CU the instance <M, OC, LP2> is built for, under the rule of
+// lpcm_mix_wgs(): the highest of 4 / 3 / 2 at which the compiler reports no scratch and no vector spill (M tells the
+// mono-coded element 0, LpcmM, from the coupled one, LpcmCoupledM: the lists share no number).  DESIGN.md 4.1i has the table.
+// Five instances keep 12 to 92 bytes of scratch per lane at four (the 24-bit form holds a dword more per channel than the 16-bit
+// one, whose <16, 2, 1> already uses 127 registers) and are built for three: <16, 2, 1>, <16, 2, 2>, <16, 1, 1>, <12, 2, 1>,
+// <10, 2, 1>.
+IAMF_HD constexpr int lpcm24_mix_wgs(int m, int oc, int lp2) {
+  if (m == 16 && (oc == 2 || lp2 == 1)) return 3;
+  if ((m == 12 || m == 10) && oc == 2 && lp2 == 1) return 3;
+  return 4;
+}
 // render_fast_kernel<.., IL, RAG>: ordinary interleaved f32 of any call length (iamf_hip_batch_render_interleaved): the stage
 // behind the resampler, mono or stereo in and out
 using InterleavedM = Ints<1, 2>;
@@ -264,6 +276,9 @@ enum class Family {
                 // is no whole number of 64-sample blocks, RenderParams::ragged.  Set 6, listed by family only
   Lpcm24Coupled,  // render_fast_kernel<.., LP, EARLY, 3, LPC> (iamf_render_lpcm24_coupled.hip): RenderParams::lpcm_coupled == 2,
                 // which only iamf_hip_batch_render_packets sets; variant as Lpcm.  Set 7 (kRouteSetsAll), listed by family only
+  Lpcm24Mix,    // render_fast_kernel<.., LP, true, 3, LPC, LP2> (iamf_render_lpcm24_mix.hip, iamf_render_lpcm24_mix_coupled.hip): both
+                // elements of a mix as 24-bit packets, RenderParams::lpcm_mix == (4 | LP2), which only
+                // iamf_hip_batch_render_packets_mix sets; variant = LP2.  Set 8 (kRouteSetsBuilt), listed by family only
 };
 struct Route {
   Family family;
@@ -350,6 +365,20 @@ inline bool lpcm_mix_fused(int n_launch) {
   return true;
 }
 
+// Whether a range of n_launch streams takes the two-element 24-bit packet form at all (render_prepare asks), under the rule of
+// lpcm_mix_fused(): a (shape, size) at which it does not beat what the call ran before — two iamf_hip_lpcm_unpack passes and the
+// f32 mixing kernel, timed from a build of the parent commit in the same process through iamf_hip_batch_render_lpcm_mix — by
+// more than that baseline's own run-to-run spread is not fused (tools/lpcm24_mix_rate.py, profiles/r16_lpcm24_mix_rate.json).
+// Measured on an MI355X, into stereo s16, 64 frames x 1024: the baseline takes 3.92 / 4.13 / 4.51 (3rd-order bed + coupled
+// stereo), 1.96 / 2.67 / 2.74 (5.1 + mono) and 2.42 / 3.70 / 3.89 (7.1.4 + coupled stereo) times the fused call's time at 512 /
+// 2048 / 4096 streams, its spread against itself at most 0.0052 — every measured (shape, size) wins, so every size is fused;
+// this is where one that stops winning would be cut.  (<16, 2, 2> and the others of lpcm24_mix_wgs() run at three workgroups
+// per CU: the 3rd-order bed is among the measured shapes.)
+inline bool lpcm24_mix_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Whether a range of n_launch streams that came through iamf_hip_batch_render_interleaved takes the interleaved form at all
 // (render_prepare asks), under the rule of lpcm_coupled_fused(): a size at which it does not beat what the call ran before —
 // iamf_hip_batch_render_range on a twin batch in the same process, the general kernel — by more than that baseline's own
@@ -401,6 +430,21 @@ inline Route pick_route(const RenderParams &p, int m) {
     // both elements as 16-bit packets (RenderParams::lpcm_mix, zero unless iamf_hip_batch_render_lpcm_mix set it): the
     // refusals of the single-element forms, element 1's packets on the same grid and inside the same 32-bit offset bound as
     // element 0's (fast_shape_ok), ramps under fast_shape_ok's rules
+    // both elements as 24-bit packets (lpcm_mix == (4 | LP2) with lpcm_bytes == 3, lpcm_coupled == 2 for a coupled bed: values of
+    // the form's own, set by iamf_hip_batch_render_packets_mix alone — 4 | LP2 with any other sample size or coupling names
+    // no form): the refusals of Family::LpcmMix, element 1's packets on the dword grid and inside the same 32-bit bound
+    if (p.lpcm_mix >= 4) {
+      const int lp2 = p.lpcm_mix - 4;
+      if (p.lpcm_bytes != 3 || (p.lpcm_coupled != 0 && p.lpcm_coupled != 2) ||
+          !(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m)) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on)
+        return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if (!p.in2 || !LpcmMixK::has(lp2) || !lpcm_mix_m2_ok(lp2, p.m2)) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if ((reinterpret_cast<uintptr_t>(p.in2) & 15) || (p.in2_stream_stride & 3) || (p.in2_frame_stride & 3))
+        return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if (((int64_t)p.total / p.frame_size + 2) * p.in2_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31)
+        return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      return take(Family::Lpcm24Mix, lp2);
+    }
     if (p.lpcm_mix) {
       if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m)) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on ||
           p.lpcm_bytes == 3)
@@ -602,6 +646,27 @@ void for_each_instance_of_any_set(int set, F &&f) {
   else for_each_instance_of_set(set, f);
 }
 
+// The two-element 24-bit packet form (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x LpcmOC x LpcmMixK
+// as its two launchers do; k = LP2.
+template <class F>
+void for_each_render_instance_lpcm24_mix(F &&f) {
+  const auto rows = [&](int m) {
+    for_each_int(LpcmOC{}, [&](int oc) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_LPCM24_MIX, 0, m, oc, k); }); });
+  };
+  for_each_int(LpcmM{}, rows);
+  for_each_int(LpcmCoupledM{}, rows);
+}
+
+// The answers of for_each_instance_of_any_set are pinned in their turn — eight sets, "no row" for every other number — so the
+// sets added since are walked by a third walker: numbers kRouteSetsAll .. kRouteSetsBuilt - 1, listed by family only.  What
+// iamf_route.hip builds and counts by.
+constexpr int kRouteSetsBuilt = 9;
+template <class F>
+void for_each_instance_of_built_set(int set, F &&f) {
+  if (set == 8) for_each_render_instance_lpcm24_mix(f);
+  else for_each_instance_of_any_set(set, f);
+}
+
 // the row of the kernel launch() runs for a route, and the set that lists it: what iamf_hip_route_count takes (a FirSplit
 // call launches render_fast_kernel<2, 2> behind it as well: launch() counts that row too)
 struct RouteKey {
@@ -630,6 +695,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::FastInterleaved: return {IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, p.out_ch, 0, 5};   // a family listing's row
     case Family::FastRagged: return {IAMF_HIP_ROUTE_FAST_RAGGED, 0, m, p.out_ch, 0, 6};   // a family listing's row
     case Family::Lpcm24Coupled: return {IAMF_HIP_ROUTE_LPCM24_COUPLED, r.variant, m, p.out_ch, 0, 7};   // a family listing's row
+    case Family::Lpcm24Mix: return {IAMF_HIP_ROUTE_LPCM24_MIX, 0, m, p.out_ch, r.variant, 8};   // a family listing's row, k = LP2
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

@@ -86,6 +86,10 @@ class PacketCall(C.Structure):   # iamf_hip_packet_call
     _fields_ = [("in_", LpcmInput), ("args", RenderArgs), ("reserved", C.c_int32 * 4)]
 
 
+class PacketMixCall(C.Structure):   # iamf_hip_packet_mix_call
+    _fields_ = [("in_", LpcmInput * 2), ("args", RenderArgs), ("reserved", C.c_int32 * 4)]
+
+
 class FanoutReport(C.Structure):   # iamf_hip_fanout_report
     _fields_ = [("n_fused", C.c_int32), ("input_fused", C.c_int32), ("n_unpacks", C.c_int32), ("reserved", C.c_int32)]
 
@@ -102,6 +106,14 @@ ROUTE = dict(NONE=0, GENERIC=1, NOLIM=2, FAST=3, FAST_DOWN=4, WIDE=5, WIDE4=6, W
 # families that no table and none of the by-family listings above names (ROUTE's keys are pinned by their callers)
 ROUTE_BY_FAMILY_ONLY = dict(LPCM24_COUPLED=31)
 ROUTE_NAME = {v: k for k, v in list(ROUTE.items()) + list(ROUTE_BY_FAMILY_ONLY.items())}
+# families added since (the three dicts above are pinned by their callers, length included): _family_id and the by-family
+# listings below consult this one where those do not know a family
+ROUTE_FAMILY_MORE = dict(LPCM24_MIX=33)
+_ROUTE_NAME_MORE = {v: k for k, v in ROUTE_FAMILY_MORE.items()}
+
+
+def _family_name(fam):
+    return ROUTE_NAME[fam] if fam in ROUTE_NAME else _ROUTE_NAME_MORE[fam]
 
 
 class StreamGains(C.Structure):   # iamf_hip_stream_gains: host arrays of the RANGE's length, NULL = leave that gain
@@ -200,6 +212,7 @@ def lib():
         L.iamf_hip_batch_render_interleaved.argtypes = [C.c_void_p, C.POINTER(InterleavedCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_ragged.argtypes = [C.c_void_p, C.POINTER(RaggedCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_packets_mix.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_resampler_destroy.argtypes = [C.c_void_p]
@@ -383,7 +396,10 @@ def route_table_tally(t, reset=False):
 
 def _family_id(family):
     if isinstance(family, str):
-        return ROUTE[family] if family in ROUTE else ROUTE_BY_FAMILY_ONLY[family]
+        for names in (ROUTE, ROUTE_BY_FAMILY_ONLY):
+            if family in names:
+                return names[family]
+        return ROUTE_FAMILY_MORE[family]
     return int(family)
 
 
@@ -397,7 +413,7 @@ def route_family_instances(family):
         raise IamfHipError(n, "iamf_hip_route_family_instances")
     rows = (RouteRow * max(n, 1))()
     n = min(n, L.iamf_hip_route_family_instances(fam, rows, n))
-    return [(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k) for r in rows[:n]]
+    return [(_family_name(r.family), r.variant, r.m, r.c, r.k) for r in rows[:n]]
 
 
 def route_family_tally(family, reset=False):
@@ -410,7 +426,7 @@ def route_family_tally(family, reset=False):
         raise IamfHipError(cap, "iamf_hip_route_family_tally")
     rows = (RouteRow * max(cap, 1))()
     n = L.iamf_hip_route_family_tally(fam, rows, cap, 1 if reset else 0)
-    return {(ROUTE_NAME[r.family], r.variant, r.m, r.c, r.k): r.launches for r in rows[:min(n, cap)]}
+    return {(_family_name(r.family), r.variant, r.m, r.c, r.k): r.launches for r in rows[:min(n, cap)]}
 
 
 FANOUT_MAX = 4   # IAMF_HIP_FANOUT_MAX
@@ -617,6 +633,17 @@ class Batch:
         r = lib().iamf_hip_batch_render_packets(self.h, C.byref(call), stream0, n)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_packets")
+        return r
+
+    def render_packets_mix(self, in0, in1, args, stream0=0, n_streams=None):
+        """iamf_hip_batch_render_packets_mix: element 0 and the second element as LPCM packets of any form (two LpcmInput),
+        `args` a RenderArgs with d_in = d_in2 = None; the whole batch unless a range is named"""
+        call = PacketMixCall()
+        call.in_[0], call.in_[1], call.args = in0, in1, args
+        n = self.cfg.n_streams - stream0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_packets_mix(self.h, C.byref(call), stream0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_packets_mix")
         return r
 
     def render_range(self, args, stream0, n_streams):

@@ -779,6 +779,39 @@ typedef struct {
 } iamf_hip_packet_call;
 int iamf_hip_batch_render_packets(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams);
 
+/* BOTH elements of a two-element mix as LPCM packets, every packet form the fused kernels read: what
+ * iamf_hip_batch_render_lpcm_mix takes and, beyond it, 24-bit packets on both elements.  On any batch with a second element
+ * and any packet layouts the call leaves the batch, d_pcm and its return value exactly as
+ *   iamf_hip_batch_render_lpcm_mix on {call->in[0], call->in[1], call->args}, stream0, n_streams
+ * does, bit for bit, persisted stream state included — so calls of either entry, the single-element packet calls, the f32
+ * calls, flushes, restarts, exports and imports may follow one another on one batch.
+ *   in[0], in[1]  as for iamf_hip_batch_render_lpcm_mix; both first_sample must be equal.
+ *   args          as for iamf_hip_batch_render_lpcm_mix: d_in and d_in2 NULL.
+ *   reserved      0.
+ * One pass of the headline kernel over both elements' packets as they lie (IAMF_HIP_ROUTE_LPCM24_MIX, 3 * (channels +
+ * channels2) + 4 instead of 11 * (channels + channels2) + 4 bytes per sample-frame into s16 stereo) when both elements hold
+ * little-endian 24-bit samples: element 0 mono-coded runs of 1 / 4 / 9 / 16 channels (the 24-bit form of
+ * iamf_hip_batch_render_lpcm) or the coupled form of 2 / 6 / 8 / 10 / 12 (iamf_hip_batch_render_packets); element 1 with
+ * d_raw 16-byte aligned and both strides multiples of 4, either mono-coded runs of 1 or 4 channels (src_step 3, src_offset +
+ * 3 * first_sample a multiple of 4) or ONE coupled stereo pair (src_step 6, the partner's src_offset 3 bytes behind the
+ * first's, src_offset + 6 * first_sample a multiple of 4) — and the call is one the fused 16-bit mix would take: one or two
+ * output channels, limiter on, whole 64-sample blocks, no fixed PCM channel stride, ramps 16-byte aligned with
+ * ramp_stream_stride a multiple of 4, no down-mixer, demixer, projection, pre-matrix, HRTF stage or LFE generator, no weight
+ * of either matrix outside 2^-100 .. 2^100, the streams' position a multiple of 16 or at least 240, (n_frames + 2) *
+ * raw_frame_stride + 2^24 below 2^31 for both elements.  Every other call — 16 bits on one element and 24 on the other,
+ * big-endian or 32-bit samples, a stereo second element coded as two mono runs, a trimmed start off a form's grid, ... —
+ * takes exactly the path of iamf_hip_batch_render_lpcm_mix, its fused 16-bit form included; IAMF_HIP_LPCM_UNFUSED=1 forces
+ * the two unpacks and the f32 kernels, as everywhere.
+ * Returns the sample-frames emitted per stream.  IAMF_HIP_ERR_BAD_ARG, before anything is queued, allocated or changed: a NULL
+ * batch or call, non-zero reserved, a non-NULL d_in or d_in2; and, with its own code, whatever
+ * iamf_hip_batch_render_lpcm_mix refuses. */
+typedef struct {
+  iamf_hip_lpcm_input in[2];
+  iamf_hip_render_args args;   /* d_in, d_in2 NULL */
+  int32_t reserved[4];         /* 0 */
+} iamf_hip_packet_mix_call;
+int iamf_hip_batch_render_packets_mix(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams);
+
 /* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
  * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
  *
@@ -858,6 +891,8 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *                          (iamf_hip_route_family_instances only)
  *     LPCM24_COUPLED       the coupled 24-bit form (iamf_hip_batch_render_packets): variant, m, c as LPCM
  *                          (iamf_hip_route_family_instances only)
+ *     LPCM24_MIX           both elements as 24-bit packets (iamf_hip_batch_render_packets_mix): m, c, k as LPCM_MIX;
+ *                          variant 0 (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -894,7 +929,8 @@ enum {
   IAMF_HIP_ROUTE_LPCM_MIX = 25,      /* no table: iamf_hip_route_family_instances / _family_tally (18, 19, 24: unused) */
   IAMF_HIP_ROUTE_FAST_INTERLEAVED = 27,  /* no table either (26: unused) */
   IAMF_HIP_ROUTE_FAST_RAGGED = 29,       /* no table either (28: unused) */
-  IAMF_HIP_ROUTE_LPCM24_COUPLED = 31     /* no table either (30 stays unused) */
+  IAMF_HIP_ROUTE_LPCM24_COUPLED = 31,    /* no table either (30 stays unused) */
+  IAMF_HIP_ROUTE_LPCM24_MIX = 33         /* no table either (32 stays unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -926,7 +962,8 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * LPCM), which no table lists and whose launches show in no table's tally.  _instances: every row of the family;
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
- * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED and LPCM24_COUPLED. */
+ * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED, LPCM24_COUPLED
+ * and LPCM24_MIX. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
