@@ -263,7 +263,7 @@ struct IAMF_Decoder {
   /* pinned host memory that the kernels read and write directly (a frame is 64 KB in, 4 KB out: over PCIe inside the
    * one render launch, instead of three copies around it — each ~9 us of call and ~12 us of engine hand-over) */
   float *h_in[2], *h_ramp[4], *d_mid, *d_res; /* ramps: element 0, element 1 for `batch`, output, element 1 for `aux` */
-  /* element 0's packets as they are, pinned, for the fused LPCM form of the render kernel (iamf_hip_batch_render_lpcm):
+  /* element 0's packets as they are, pinned, for the fused LPCM forms of the render kernel (iamf_hip_batch_render_packets_ragged):
    * one mono-coded ambisonics element in 16-bit little-endian LPCM into one or two channels with the limiter on */
   uint8_t *h_raw;
   int lp_ok;
@@ -1442,14 +1442,15 @@ static int build_stages(struct IAMF_Decoder *d, int resample, int aux) {
  * render kernel as they are (the reference's LPCM decode, pcm/IAMF_pcm_decoder.c:64-83, happens where the kernel loads
  * them): one scene-based element, mono-coded, 16 or 24 bit, or one single-layer channel-based element, 16 bit, that
  * couples every pair of its layout (the kernel's coupled form) or is mono; little-endian, into one or two channels with
- * the limiter on, no stage in front, no resampler behind.  The library decides per call whether the fused kernel takes it
- * and unpacks on the device otherwise.  L: the raw row (ftu_raw_layout) — every channel is carried by a sub-stream, on the
+ * the limiter on, no stage in front, no resampler behind; frames of any multiple of 4 samples (1000, 480, 240: a call need be
+ * no whole number of 64-sample blocks, iamf_hip_batch_render_packets_ragged).  The library decides per call whether a fused
+ * kernel takes it and unpacks on the device otherwise.  L: the raw row (ftu_raw_layout) — every channel is carried by a sub-stream, on the
  * form's grid: runs of 8 bytes for 16-bit samples and coupled pairs, of 4 for 24-bit ones.  env_off: the environment
  * variable that says "unpack first" */
 static int lp_worth_asking(const struct IAMF_Decoder *d, const iamf_hip_lpcm_layout *L, const char *env_off) {
   const Element *e0 = d->sel_el[0];
   const int common = d->sel->nel == 1 && !d->pre[0].use_dmx && !d->pre[0].use_demix && !d->rs && d->little_endian &&
-                     d->limiter_on && d->out_channels <= 2 && d->pcm_stride == d->out_channels && (d->frame_size & 63) == 0 &&
+                     d->limiter_on && d->out_channels <= 2 && d->pcm_stride == d->out_channels && (d->frame_size & 3) == 0 &&
                      !getenv(env_off);
   const int lp_chan = e0->type == AUDIO_ELEMENT_CHANNEL_BASED && e0->nlayers == 1 && d->sample_size == 16 &&
                       e0->nb_coupled == lp_canonical_coupled(e0->channels) && e0->nsub + e0->nb_coupled == e0->channels;
@@ -1841,6 +1842,18 @@ static int render_aux_element(struct IAMF_Decoder *d, const ftu_window *w, int r
   return IAMF_OK;
 }
 
+/* Element 0's packets of a call of any length -> the batch.  iamf_hip_batch_render_packets_ragged is total: whole blocks take
+ * the fused whole-block forms, any other length the ragged packet form, and what neither takes is unpacked on the device — the
+ * same PCM every way.  This file is also built against device layers that are no part of the library (the CPU stand-in of
+ * tests/facade_stub, which restates the batch ABI the façade uses): the reference to the entry is weak, and a device layer
+ * without it gets iamf_hip_batch_render_lpcm_range, which is the same call bit for bit for the packets the façade hands over
+ * (16- and 24-bit mono-coded, 16-bit coupled).  In libiamf_hip.so the entry is always there. */
+#pragma weak iamf_hip_batch_render_packets_ragged
+static int render_packets_any_length(iamf_hip_batch *b, const iamf_hip_packet_call *c, int32_t stream0, int32_t n_streams) {
+  if (iamf_hip_batch_render_packets_ragged) return iamf_hip_batch_render_packets_ragged(b, c, stream0, n_streams);
+  return iamf_hip_batch_render_lpcm_range(b, &c->in, &c->args, stream0, n_streams);
+}
+
 /* the frame's launches: the packets themselves, the f32 form, or render (f32) -> resample -> loudness / limiter / pack.
  * Returns the sample-frames in h_pcm, negative if a call failed */
 static int render_launch(struct IAMF_Decoder *d, iamf_hip_render_args *a, int lp, int s0) {
@@ -1851,13 +1864,14 @@ static int render_launch(struct IAMF_Decoder *d, iamf_hip_render_args *a, int lp
     a->pcm_stream_stride_bytes = (int64_t)d->pcm_cap;
   }
   if (lp) {
-    iamf_hip_lpcm_input in;
-    memset(&in, 0, sizeof(in));
-    in.d_raw = d->h_raw;
-    in.raw_stream_stride = in.raw_frame_stride = (int64_t)d->lp_row_bytes;
-    in.first_sample = s0;
-    in.layout = d->lp_layout;
-    return iamf_hip_batch_render_lpcm(d->batch, &in, a);
+    iamf_hip_packet_call c; /* (any number of kept samples: render_packets_any_length) */
+    memset(&c, 0, sizeof(c));
+    c.in.d_raw = d->h_raw;
+    c.in.raw_stream_stride = c.in.raw_frame_stride = (int64_t)d->lp_row_bytes;
+    c.in.first_sample = s0;
+    c.in.layout = d->lp_layout;
+    c.args = *a;
+    return render_packets_any_length(d->batch, &c, 0, 1);
   }
   if (!d->rs) return iamf_hip_batch_render_ex(d->batch, a);
   a->d_pcm = d->d_mid;
@@ -1902,7 +1916,8 @@ static int render_tu(struct IAMF_Decoder *d, void *pcm) {
   if (rc == FTU_DROPPED) return render_dropped_unit(d, ns, w.rendered);
   meta_note_frame(d, w.s0, d->tu_trim_end);
   frame_gain_plan(d, w.s0, w.keep, d->h_ramp, ramp, cgain, set);
-  if (lp && ((w.s0 & 3) || (w.keep & 63) || ramp[0] || ramp[2])) { /* not a call of the fused kernel: the f32 form after all */
+  /* (any number of kept samples: a trimmed end or a frame of 1000 takes the ragged packet form of the render kernel) */
+  if (lp && ((w.s0 & 3) || ramp[0] || ramp[2])) { /* not a call of the fused kernels: the f32 form after all */
     int r = unpack_element(d, 0);
     if (r < 0) return r;
     lp = 0;

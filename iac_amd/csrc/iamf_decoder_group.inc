@@ -18,7 +18,7 @@
  * handle's PCM is what it would have returned alone (tests/test_gpu_group.py: the e2e goldens over 64 handles).
  *
  * Streams of one mono-coded ambisonics element in 16-bit LPCM into one or two channels skip the unpacker: the render kernel reads
- * the uploaded packets itself (iamf_hip_batch_render_lpcm_range; IAMF_HIP_GROUP_UNPACK=1 in the environment: unpack first).
+ * the uploaded packets itself (iamf_hip_batch_render_packets_ragged; IAMF_HIP_GROUP_UNPACK=1 in the environment: unpack first).
  *
  * Handles that resample (stream rate != output rate: IAMF_decoder.c:3193-3199,3223-3248) render through three stages as the
  * single handle does — the batch into planar-per-stream f32, the resampler (one phase and history per stream,
@@ -64,7 +64,7 @@ struct iamf_hip_decoder_group {
   void *d_raw[2];
   /* every raw row starts with kRawHead bytes: int32 first sample (a trimmed start), int32 samples to unpack (0: not this round) */
   float *cgain[3];                /* [n]: this frame's constant gain of stage k where the stage is not on a ramp */
-  int lp_ok;                      /* element 0's packets can go straight into the render kernel (iamf_hip_batch_render_lpcm_range) */
+  int lp_ok;                      /* element 0's packets can go straight into the render kernel (iamf_hip_batch_render_packets_ragged) */
   int chunk, nchunks;             /* handles per upload chunk; the uploads of chunk c run beside the parsing of chunk c + 1 */
   int *chunk_done;                /* [nchunks]: handles of the chunk the pool has finished (atomic) */
   int job;                        /* what the pool does this time: 0 parse + stage, 1 hand out the PCM */
@@ -522,7 +522,7 @@ static int group_alloc_staging(iamf_hip_decoder_group *g, void *const *handles) 
     }
     if (hipMalloc(&g->d_raw[e], g->raw_stride[e] * n) != hipSuccess) return 1;
   }
-  /* element 0's packets straight into the render kernel (iamf_hip_batch_render_lpcm_range: no unpacked copy, no unpack
+  /* element 0's packets straight into the render kernel (iamf_hip_batch_render_packets_ragged: no unpacked copy, no unpack
    * launch): when asking is worth it is the single handle's question too */
   g->lp_ok = lp_worth_asking(d0, &g->lay[0], "IAMF_HIP_GROUP_UNPACK");
   for (int k = 0; k < 3; ++k)
@@ -888,18 +888,17 @@ static int group_run_flush_resampled(iamf_hip_decoder_group *g, int i, int j) {
 
 /* the run's packets straight into the render kernel: first kept sample s0, keep samples (uniform over the run) */
 static int group_run_lpcm(iamf_hip_decoder_group *g, int i, int j) {
-  iamf_hip_render_args a;
-  iamf_hip_lpcm_input in;
+  iamf_hip_packet_call c; /* (the entry is total: any number of kept samples, render_launch of the single handle) */
   int r;
-  memset(&in, 0, sizeof(in));
-  in.d_raw = g->d_raw[0];
-  in.raw_stream_stride = in.raw_frame_stride = (int64_t)g->raw_stride[0];
-  in.first_sample = g->s0[i];
-  in.layout = g->lay[0];
-  ftu_element_stage_args(&a, 0, 0, g->fs, 0, g->s0[i], g->te[i], g->keep[i], 0, 0, g->stream);
-  a.d_pcm = g->h_pcm;
-  a.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
-  r = iamf_hip_batch_render_lpcm_range(g->batch, &in, &a, i, j - i);
+  memset(&c, 0, sizeof(c));
+  c.in.d_raw = g->d_raw[0];
+  c.in.raw_stream_stride = c.in.raw_frame_stride = (int64_t)g->raw_stride[0];
+  c.in.first_sample = g->s0[i];
+  c.in.layout = g->lay[0];
+  ftu_element_stage_args(&c.args, 0, 0, g->fs, 0, g->s0[i], g->te[i], g->keep[i], 0, 0, g->stream);
+  c.args.d_pcm = g->h_pcm;
+  c.args.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
+  r = render_packets_any_length(g->batch, &c, i, j - i);
   for (int s = i; s < j && r >= 0; ++s) {
     g->result[s] = r;
     g->pos[s] += g->keep[s];
@@ -1023,7 +1022,7 @@ static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *d
     j = group_run_end(g, i);
     if (g->action[i] == GA_ADVANCE ? group_run_advance(g, i, j)
         : g->action[i] == GA_FLUSH ? (g->rs ? group_run_flush_resampled(g, i, j) : group_run_flush(g, i, j))
-        : g->lp_ok && !g->rampu && !(g->s0[i] & 3) && !(g->keep[i] & 63) ? group_run_lpcm(g, i, j)
+        : g->lp_ok && !g->rampu && !(g->s0[i] & 3) ? group_run_lpcm(g, i, j)
                                                                          : group_run_f32(g, i, j))
       return group_fail(g);
   }

@@ -403,6 +403,10 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
       break;
     case Family::FastInterleaved: launched = iamf_hip_fast_interleaved_launch(&p, m, st); break;
     case Family::FastRagged: launched = iamf_hip_fast_ragged_launch(&p, m, st); break;
+    case Family::PacketsRagged:   // the four single-element packet forms, a unit each
+      if (p.lpcm_bytes == 3) launched = p.lpcm_coupled ? iamf_hip_fast_packets_ragged24_coupled_launch(&p, m, st) : iamf_hip_fast_packets_ragged24_launch(&p, m, st);
+      else launched = p.lpcm_coupled ? iamf_hip_fast_packets_ragged_coupled_launch(&p, m, st) : iamf_hip_fast_packets_ragged_launch(&p, m, st);
+      break;
     case Family::FirSplit: {
       const int e = launch_fir_split(p, m, grid, st);
       if (e != IAMF_HIP_OK) return e;
@@ -463,8 +467,11 @@ struct LpcmIn {
   int32_t coupled; // 1: LpcmForm::S16C, off[] of a pair's two channels 2 bytes apart; 2: LpcmForm::S24C, 3 bytes apart
 };
 constexpr int kNotFused = INT32_MIN;
-// the family a packet call must route to for a fused kernel to read its packets (lp2: the second element's, or null)
-Family lpcm_family(const LpcmIn *lp, const LpcmIn *lp2) {
+// the family a packet call must route to for a fused kernel to read its packets (lp2: the second element's, or null;
+// prag: the call carries the mark of iamf_hip_batch_render_packets_ragged — RenderParams::ragged == 2 — and is no whole number
+// of 64-sample blocks, which only the ragged packet form takes)
+Family lpcm_family(const LpcmIn *lp, const LpcmIn *lp2, bool prag = false) {
+  if (prag && !lp2) return Family::PacketsRagged;
   if (lp2) return lp->bytes == 3 ? Family::Lpcm24Mix : Family::LpcmMix;   // (24-bit: iamf_hip_batch_render_packets_mix only)
   if (lp->coupled == 2) return Family::Lpcm24Coupled;
   if (lp->coupled) return Family::LpcmCoupled;
@@ -522,8 +529,10 @@ struct PreparedCall {
 // lp2 (with lp, iamf_hip_batch_render_lpcm_mix): the second element as packets too; a.d_in2 is then a non-null placeholder.
 // il (iamf_hip_batch_render_interleaved): the call may take the interleaved form of the fast kernel; everything else as without.
 // rag (iamf_hip_batch_render_ragged): the call may take the planar ragged form; everything else as without.
+// prag (with lp, iamf_hip_batch_render_packets_ragged; first: iamf_hip_lpcm_input::first_sample): the call may take the ragged
+// packet form; everything else as without.
 int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc,
-                   const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false) {
+                   const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
   if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || !b->lp_scale_ok || getenv("IAMF_HIP_LPCM_UNFUSED")))
     return kNotFused;
@@ -642,9 +651,12 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     for (int m = 0; m < 16; ++m) p.lpcm_off[m] = lp->off[m];
     p.lpcm_bytes = lp->bytes;
     p.lpcm_coupled = lp->coupled;
-    if (lp->bytes == 3 && !lp->coupled && !lp2 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
-    if (lp->coupled == 1 && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
-    if (lp->coupled == 2 && !lp2 && !lpcm24_coupled_fused(cnt)) return kNotFused;
+    // (the size cuts of the whole-block forms say nothing about a ragged call of iamf_hip_batch_render_packets_ragged, which no
+    //  whole-block form takes: the ragged packet form has its own measurement and its own cut, packets_ragged_fused below)
+    const bool whole_blocks = !(prag && !lp2 && (total & 63));
+    if (whole_blocks && lp->bytes == 3 && !lp->coupled && !lp2 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
+    if (whole_blocks && lp->coupled == 1 && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
+    if (whole_blocks && lp->coupled == 2 && !lp2 && !lpcm24_coupled_fused(cnt)) return kNotFused;
     if (lp2) {   // the kernel reads RenderMixParams; pick_route the packets' place in the in2 fields (strides in bytes)
       // 24-bit packets on both elements (iamf_hip_batch_render_packets_mix alone hands them over): the form's own values
       if (lp->bytes != lp2->bytes) return kNotFused;
@@ -659,7 +671,14 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       for (int m = 0; m < 4; ++m) pc.p.lpcm2_off[m] = lp2->off[m];
       if (lp->bytes != 3 && !lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     }
-    if (pick_route(p, m_eff).family != lpcm_family(lp, lp2)) return kNotFused;
+    // the mark of iamf_hip_batch_render_packets_ragged, with the trimmed frame's first sample where pick_route looks for it
+    // (render_route.hpp, packets_ragged_shape_ok).  The form packs into the caller's buffer itself: a fixed PCM channel stride
+    // stays unfused, as for the coupled 24-bit form
+    if (prag && !lp2 && !(b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) && packets_ragged_fused(cnt)) {
+      p.ragged = 2;
+      p.demix_i0 = first;
+    }
+    if (pick_route(p, m_eff).family != lpcm_family(lp, lp2, p.ragged == 2 && (total & 63))) return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -712,7 +731,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   // the interleaved form packs into the caller's buffer itself and knows no LFE slot; pick_route has the call's other rules
   p.interleaved = (il && !restride && !b->lfe && interleaved_fused(cnt)) ? 1 : 0;
   // so does the planar ragged form (an LFE slot: pick_route sees p.lfe)
-  p.ragged = (rag && !restride && ragged_fused(cnt)) ? 1 : 0;
+  if (p.ragged != 2) p.ragged = (rag && !restride && ragged_fused(cnt)) ? 1 : 0;
   pc.a = a;
   pc.m_eff = m_eff;
   pc.lds = lds;
@@ -761,11 +780,11 @@ int render_finish(iamf_hip_batch *b, const PreparedCall &pc) {
   return r != IAMF_HIP_OK ? r : render_commit(b, pc);
 }
 
-// the whole call (lp, lp2, il, rag: as render_prepare, whose kNotFused comes back before anything is changed or launched)
+// the whole call (lp, lp2, il, rag, prag, first: as render_prepare, whose kNotFused comes back before anything is changed or launched)
 int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr,
-                const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false) {
+                const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0) {
   PreparedCall pc;
-  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il, rag);
+  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il, rag, prag, first);
   return r != IAMF_HIP_OK ? r : render_finish(b, pc);
 }
 
@@ -1151,11 +1170,13 @@ static int range_args_check(const iamf_hip_batch *b, const iamf_hip_render_args 
   return IAMF_HIP_OK;
 }
 
-static int render_range_impl(iamf_hip_batch *b, const iamf_hip_render_args *a, int32_t stream0, int32_t n_streams, const LpcmIn *lp) {
+// (prag, first: as render_prepare — iamf_hip_batch_render_packets_ragged)
+static int render_range_impl(iamf_hip_batch *b, const iamf_hip_render_args *a, int32_t stream0, int32_t n_streams, const LpcmIn *lp,
+                             bool prag = false, int first = 0) {
   int64_t total = 0;
   const int rc = range_args_check(b, a, stream0, n_streams, &total);
   if (rc != IAMF_HIP_OK || total == 0) return rc;
-  return render_call(b, *a, (int)total, stream0, n_streams, lp);
+  return render_call(b, *a, (int)total, stream0, n_streams, lp, nullptr, false, false, prag, first);
 }
 
 int iamf_hip_batch_render_range(iamf_hip_batch *b, const iamf_hip_render_args *a, int32_t stream0, int32_t n_streams) {
@@ -1256,9 +1277,10 @@ static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, i
   return IAMF_HIP_OK;
 }
 
-// (packets: iamf_hip_batch_render_packets — the form is asked of lpcm_form_packets(); everything else is the one path)
+// (packets: iamf_hip_batch_render_packets — the form is asked of lpcm_form_packets(); everything else is the one path.
+//  prag: iamf_hip_batch_render_packets_ragged — the fused attempt carries its mark; everything else is the one path)
 static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
-                                  int32_t stream0, int32_t n_streams, bool packets) {
+                                  int32_t stream0, int32_t n_streams, bool packets, bool prag = false) {
   if (!b || !in || !args || !in->d_raw || args->d_in || !args->d_pcm || args->n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
   if (!range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
@@ -1274,7 +1296,7 @@ static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *
     lpcm_in_of(in, ch, first, form, lp);
     a.d_in = reinterpret_cast<const float *>(in->d_raw);   // not read by the fused kernel; non-null = "not a flush"
     a.in_stream_stride = a.in_frame_stride = 0;
-    const int r = render_range_impl(b, &a, stream0, n_streams, &lp);
+    const int r = render_range_impl(b, &a, stream0, n_streams, &lp, prag, first);
     if (r != kNotFused) return r;
   }
   // Unfused: unpack, then the f32 path.  Everything the render call would refuse is refused here first, so that no unpack
@@ -1303,6 +1325,16 @@ int iamf_hip_batch_render_packets(iamf_hip_batch *b, const iamf_hip_packet_call 
   if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
   if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
   return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, true);
+}
+
+// Element 0 as LPCM packets of any call length (include/iamf_hip.h): iamf_hip_batch_render_packets with leave to take
+// render_fast_kernel<.., LP, true, LPB, LPC, 0, false, RAG> (Family::PacketsRagged) where the call is no whole number of 64-sample
+// blocks, the packets have one of the four fused forms and render_prepare and pick_route let the call through.  The same
+// checks in the same order, the same path for everything else.
+int iamf_hip_batch_render_packets_ragged(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, true, true);
 }
 
 // Both elements of a mix as LPCM packets (include/iamf_hip.h).  Fused (render_fast_kernel<.., LP2>: Family::LpcmMix) when

@@ -263,9 +263,15 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       first samples.  Both are replaced by zeros by a SELECT on the rendered quad, in front of the maxima: nothing loaded
 //       for an absent sample reaches a reduction over lanes, the ring, the vote or the PCM.  The loads themselves stay inside
 //       the frames' rows: the host only sends calls whose frame size is a multiple of 4 (pick_route, ragged_shape_ok).
+//       With LP, without IN2 / LP2 (iamf_hip_batch_render_packets_ragged, iamf_render_packets_ragged*.hip): one element as
+//       packets of every single-element form — LPB 2 or 3, LPC or not — early prefetch only.  Only the loads differ from the
+//       f32 form, and they are the packet forms' own: the last quad of a call with total & 3 != 0 loads the up to 3 packet
+//       samples that lie behind n_samples in the channel's run (any bytes: they convert to finite numbers), which the same
+//       SELECT replaces by zeros.  The loads stay inside the frames' runs: frame size a multiple of 4 and, for a trimmed
+//       frame, first_sample + ((n_samples + 3) & ~3) <= frame_size (pick_route, packets_ragged_shape_ok).
 template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2, bool LPC = false,
           int LP2 = 0, bool IL = false, bool RAG = false>
-__global__ __launch_bounds__(FIR == 1 ? 512 : 256, LP2 ? (LPB == 3 ? lpcm24_mix_wgs(M, OC, LP2) : lpcm_mix_wgs(M, OC, LP2)) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
+__global__ __launch_bounds__(FIR == 1 ? 512 : 256, (RAG && LP) ? packets_ragged_wgs(M, OC, LPB, LPC) : LP2 ?(LPB == 3 ? lpcm24_mix_wgs(M, OC, LP2) : lpcm_mix_wgs(M, OC, LP2)) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
 void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, RenderParams> p) {
   static_assert(!(FIR && DOWN), "one renderer");
   static_assert(!(LP && (FIR || DOWN || (IN2 && !LP2))) && (!LP || M <= 16), "the LPCM input feeds the plain matrix variant");
@@ -274,7 +280,7 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
   static_assert(!LPC || (LP && lpcm_coupled_m(M)), "coupled pairs: 16- or 24-bit packets of a loudspeaker layout");
   static_assert(!IL || (!FIR && !DOWN && !IN2 && !LP && EARLY && M <= 2), "interleaved f32 feeds the plain matrix variant, one or two channels");
-  static_assert(!RAG || IL || (!FIR && !DOWN && !IN2 && !LP && EARLY), "ragged calls: the interleaved form, or the plain planar f32 one");
+  static_assert(!RAG || IL || (!FIR && !DOWN && !IN2 && EARLY), "ragged calls: the interleaved form, the plain planar f32 one, or one element as packets");
   constexpr bool LP3 = LP && LPB == 3;
   extern __shared__ float lds[];
   constexpr int R = kFRing;

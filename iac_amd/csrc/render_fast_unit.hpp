@@ -1,7 +1,8 @@
 // render_fast_unit.hpp — what the translation units that feed render_fast_kernel (render_fast.hpp) another input form share:
 // iamf_render_lpcm.hip, _lpcm24.hip, _lpcm_coupled.hip, _lpcm24_coupled.hip, _lpcm_mix.hip, _lpcm_mix_coupled.hip, _lpcm24_mix.hip,
-// _lpcm24_mix_coupled.hip, iamf_render_interleaved.hip and
-// iamf_render_ragged.hip.
+// _lpcm24_mix_coupled.hip, iamf_render_interleaved.hip,
+// iamf_render_ragged.hip and iamf_render_packets_ragged.hip, _packets_ragged_coupled.hip, _packets_ragged24.hip,
+// _packets_ragged24_coupled.hip.
 // The units stay separate, so that they compile side by side; each includes this header at file scope and nothing else, and
 // holds its head comment and its entry of render_entry.hpp: the parameter sanity test and one call of a launcher below, in
 // which the form's template arguments are written once.  A launcher dispatches over the lists it is given, which are the
@@ -72,6 +73,20 @@ bool launch_fast_rag(const RenderParams &p, int m, hipStream_t st) {
       // built for the four workgroups per CU of the planar f32 form <M, OC> (render_fast_kernel's launch bounds)
       static_assert(lds * 4 <= 160 * 1024, "the workgroups the instance is built for fit a CU's LDS");
       launch_big_lds<&render_fast_kernel<m_, oc_, 0, false, false, false, true, 2, false, 0, IL, true>, 80 * 1024>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
+    });
+  });
+}
+
+// One element as LPCM packets of any call length: render_fast_kernel<M, OC, 0, false, false, LP = true, EARLY = true, LPB, LPC,
+// 0, IL = false, RAG = true> (iamf_render_packets_ragged*.hip).  LPB, LPC as launch_fast_lp; the early prefetch only.
+template <class MList, class OCList, int LPB, bool LPC>
+bool launch_fast_lp_rag(const RenderParams &p, int m, hipStream_t st) {
+  return dispatch(MList{}, m, [&](auto M) {
+    return dispatch(OCList{}, p.out_ch, [&](auto OC) {
+      constexpr int m_ = decltype(M)::value, oc_ = decltype(OC)::value;
+      constexpr size_t lds = sizeof(float) * (size_t)fast_lds_floats(oc_, m_);
+      static_assert(lds * packets_ragged_wgs(m_, oc_, LPB, LPC) <= 160 * 1024, "the workgroups the instance is built for fit a CU's LDS");
+      launch_big_lds<&render_fast_kernel<m_, oc_, 0, false, false, true, true, LPB, LPC, 0, false, true>, 80 * 1024>(dim3((unsigned)p.n_launch), dim3(256), lds, st, p);
     });
   });
 }

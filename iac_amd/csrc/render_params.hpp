@@ -108,6 +108,10 @@ struct RenderParams {
                             // blocks, may take render_fast_kernel<.., IL = false, RAG = true> (pick_route: Family::FastRagged); 0:
                             // every rule as it stood.  Host only, and kept HERE, in the 4 bytes of padding in front of the
                             // double, like lpcm_bytes: the block keeps its size and every other field its offset
+                            // 2: the call came through iamf_hip_batch_render_packets_ragged with element 0 as packets (`lpcm`) and,
+                            // where it is no whole number of blocks, may take render_fast_kernel<.., LP, .., RAG = true> (pick_route:
+                            // Family::PacketsRagged); demix_i0 then holds iamf_hip_lpcm_input::first_sample (no demixer runs
+                            // beside packets)
   double lfe_div;           // sqrt(n) of h2m_rdr.c:1162; 0 = the `* 0.5` form (n <= 2)
   int32_t lfe_mask;         // bit c: output slot c is an LFE slot (src_feed[c] == -2), for render_wide4.hpp
   // ---- HRTF FIR renderer (render_fast_kernel<M, 2, true>): matrix = h[2][M][fir_taps] ----

@@ -78,6 +78,15 @@ IAMF_HD constexpr int lpcm24_mix_wgs(int m, int oc, int lp2) {
   if ((m == 12 || m == 10) && oc == 2 && lp2 == 1) return 3;
   return 4;
 }
+// render_fast_kernel<.., LP, true, LPB, LPC, 0, IL = false, RAG = true>: one element as packets of any call length
+// (iamf_hip_batch_render_packets_ragged) — LpcmM (mono-coded) or LpcmCoupledM (coupled) x LpcmOC x {16, 24 bit}, the early
+// prefetch only.  Workgroups per CU the instance <M, OC, LPB, LPC> is built for, under the rule of lpcm_mix_wgs(): the highest of
+// 4 / 3 / 2 at which the compiler reports no scratch and no vector spill.  Every one of the 36 instances fits four (at most
+// 111 vector registers: <16, 2, LPB = 3>; DESIGN.md 4.1j has the table); an instance that stops fitting gets its own answer here.
+IAMF_HD constexpr int packets_ragged_wgs(int m, int oc, int lpb, bool lpc) {
+  (void)m, (void)oc, (void)lpb, (void)lpc;
+  return 4;
+}
 // render_fast_kernel<.., IL, RAG>: ordinary interleaved f32 of any call length (iamf_hip_batch_render_interleaved): the stage
 // behind the resampler, mono or stereo in and out
 using InterleavedM = Ints<1, 2>;
@@ -197,7 +206,7 @@ inline bool interleaved_shape_ok(const RenderParams &p, int m, bool force_generi
 // below `total` ends inside its row (iamf_render_ragged.hip).  IAMF_HIP_RAGGED_UNFUSED=1 sends every such call down the
 // rules below.
 inline bool ragged_shape_ok(const RenderParams &p, int m, bool force_generic) {
-  if (!p.ragged || force_generic || getenv("IAMF_HIP_RAGGED_UNFUSED")) return false;
+  if (p.ragged != 1 || force_generic || getenv("IAMF_HIP_RAGGED_UNFUSED")) return false;   // (2: the packet entry's mark, below)
   if (!p.limiter_on || !p.in || !RaggedOC::has(p.out_ch) || !RaggedM::has(m) || p.og_ch < p.out_ch || p.n_end < kFWin) return false;
   if (p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe || p.lpcm)
     return false;
@@ -208,6 +217,45 @@ inline bool ragged_shape_ok(const RenderParams &p, int m, bool force_generic) {
   // the kernel addresses a stream's input of one call with 32-bit byte offsets: fast_shape_ok's bound
   const int64_t frames = (int64_t)p.total / p.frame_size + 2;
   if (frames * p.in_frame_stride * 4 + 100 * (int64_t)p.frame_size >= (int64_t)1 << 31) return false;
+  return true;
+}
+
+// What the ragged packet form of the fast kernel (render_fast.hpp, RAG with LP) needs of a call that came through
+// iamf_hip_batch_render_packets_ragged (RenderParams::ragged == 2, which that entry alone sets): everything fast_shape_ok asks
+// of a single packet-fed element, with "whole 64-sample blocks" replaced by "any length >= 1 that is NOT a whole number of
+// blocks"; the packet form named by (lpcm_bytes, lpcm_coupled) as the four whole-block families name it, on that form's own
+// grid (lpcm_form.hpp: 8 bytes for 16-bit samples, 4 for 24-bit ones — strides and every run's start, first_sample included);
+// and, what keeps the loads of a trimmed frame inside its runs, first + ((total + 3) & ~3) <= frame_size where the call is
+// shorter than a frame (one frame, n_samples set; `first`, iamf_hip_lpcm_input::first_sample, travels in demix_i0 — "frame
+// position of the call's first sample" — which no packet-fed kernel reads).  A call of whole blocks, and every call this
+// rule does not take, is left to the rules below.  IAMF_HIP_PACKETS_RAGGED_UNFUSED=1 sends every such call down them.
+inline bool packets_ragged_shape_ok(const RenderParams &p, int m, bool force_generic) {
+  if (p.ragged != 2 || !p.lpcm || force_generic || getenv("IAMF_HIP_PACKETS_RAGGED_UNFUSED")) return false;
+  if (!p.limiter_on || !p.in || !LpcmOC::has(p.out_ch) || p.og_ch < p.out_ch || p.n_end < kFWin) return false;
+  if (p.in2 || p.lpcm_mix || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe)
+    return false;
+  if (p.total < 1 || !(p.total & 63) || p.frame_size < 4 || (p.frame_size & 3)) return false;
+  if ((p.pos0 & 15) && p.pos0 < kDelay) return false;
+  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (reinterpret_cast<uintptr_t>(p.lpcm) & 15)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  // the form: 16-bit mono-coded (LpcmM), 16-bit coupled (lpcm_coupled == 1), 24-bit mono-coded, 24-bit coupled (== 2)
+  const bool s24 = p.lpcm_bytes == 3;
+  if (!s24 && p.lpcm_bytes != 0 && p.lpcm_bytes != 2) return false;
+  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (s24 ? 2 : 1)) return false;
+  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
+  const int grid = s24 ? 3 : 7;
+  if ((p.lpcm_stream_stride & grid) || (p.lpcm_frame_stride & grid) || p.lpcm_frame_stride <= 0) return false;
+  for (int c = 0; c < m; ++c) {   // a pair's second channel lies sample_bytes behind its first: the pair's one run starts at the first
+    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
+      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + (s24 ? 3 : 2)) return false;
+    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
+  }
+  // a trimmed frame: the last quad that starts below `total` ends inside the run of frame_size samples
+  if (p.demix_i0 < 0 || (p.demix_i0 > 0 && p.total >= p.frame_size)) return false;
+  if (p.total < p.frame_size && (int64_t)p.demix_i0 + ((p.total + 3) & ~3) > p.frame_size) return false;
+  // the kernel addresses a stream's packets of one call with 32-bit byte offsets: fast_shape_ok's bound
+  const int64_t frames = (int64_t)p.total / p.frame_size + 2;
+  if (frames * p.lpcm_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
   return true;
 }
 
@@ -279,6 +327,9 @@ enum class Family {
   Lpcm24Mix,    // render_fast_kernel<.., LP, true, 3, LPC, LP2> (iamf_render_lpcm24_mix.hip, iamf_render_lpcm24_mix_coupled.hip): both
                 // elements of a mix as 24-bit packets, RenderParams::lpcm_mix == (4 | LP2), which only
                 // iamf_hip_batch_render_packets_mix sets; variant = LP2.  Set 8 (kRouteSetsBuilt), listed by family only
+  PacketsRagged,  // render_fast_kernel<.., LP, true, LPB, LPC, 0, false, RAG = true> (iamf_render_packets_ragged*.hip): one element as
+                // packets of any call length that is no whole number of 64-sample blocks, RenderParams::ragged == 2, which only
+                // iamf_hip_batch_render_packets_ragged sets; variant 0.  Set 9 (kRouteSetsLaunched), listed by family only
 };
 struct Route {
   Family family;
@@ -407,6 +458,23 @@ inline bool ragged_fused(int n_launch) {
   return true;
 }
 
+// Whether a range of n_launch streams that came through iamf_hip_batch_render_packets_ragged takes the ragged packet form at
+// all (render_prepare asks), under the rule of lpcm_coupled_fused(): a (shape, size) at which it does not beat what the call
+// ran before — iamf_hip_batch_render_packets on a twin batch in the same process: iamf_hip_lpcm_unpack, then the general
+// kernel — by more than that baseline's own run-to-run spread is not fused (tools/packets_ragged_rate.py,
+// profiles/r17_packets_ragged_rate.json).
+// Measured on an MI355X, into stereo s16, 64 one-frame calls per stream and step: the baseline takes 2.83 / 2.83 / 3.65 (3rd order,
+// 16-bit mono-coded), 2.87 / 2.87 / 3.65 (3rd order, 24 bit), 2.30 / 2.27 / 1.89 and 2.29 / 2.24 / 1.92 (5.1 coupled, 16 / 24 bit),
+// 2.18 / 2.30 / 2.44 and 2.19 / 2.21 / 2.50 (7.1.4 coupled, 16 / 24 bit) times the new entry's time in calls of 1000 samples at
+// 512 / 2048 / 4096 streams, and 2.37 / 2.24 / 2.09, 2.39 / 2.30 / 2.23, 1.85 / 1.93 / 1.53, 1.86 / 1.86 / 1.54, 2.22 / 2.26 / 2.00 and
+// 2.17 / 2.18 / 2.00 in calls of 480; its spread against itself at most 0.0033 — every measured (shape, size) wins, so every size
+// is fused; this is where one that stops winning would be cut.  (One call of 64 frames of 1000 is 1000 whole blocks: both
+// entries run the form's whole-block family there, 0.996 to 1.014 of each other.)
+inline bool packets_ragged_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
 // rules.  The environment switches are read at every call (the tests set and unset them within one process).
@@ -424,6 +492,10 @@ inline Route pick_route(const RenderParams &p, int m) {
   // planar f32 that is no whole number of 64-sample blocks (RenderParams::ragged, zero unless iamf_hip_batch_render_ragged set
   // it): the same way
   if (ragged_shape_ok(p, m, force_generic)) return take(Family::FastRagged);
+
+  // one element as packets, no whole number of 64-sample blocks (RenderParams::ragged == 2, which only
+  // iamf_hip_batch_render_packets_ragged sets): the same way, in front of the packet rules, which refuse such a length
+  if (packets_ragged_shape_ok(p, m, force_generic)) return take(Family::PacketsRagged);
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
@@ -667,6 +739,27 @@ void for_each_instance_of_built_set(int set, F &&f) {
   else for_each_instance_of_any_set(set, f);
 }
 
+// The ragged packet form (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x LpcmOC as its launchers do, the
+// 16-bit units first; k = bytes per packet sample (m tells mono-coded from coupled: the two lists share no number).
+template <class F>
+void for_each_render_instance_packets_ragged(F &&f) {
+  for (int k = 2; k <= 3; ++k) {
+    const auto rows = [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_PACKETS_RAGGED, 0, m, oc, k); }); };
+    for_each_int(LpcmM{}, rows);
+    for_each_int(LpcmCoupledM{}, rows);
+  }
+}
+
+// The answers of for_each_instance_of_built_set are pinned as well — nine sets, "no row" for every other number — so the sets
+// added since are walked by a fourth walker: numbers kRouteSetsBuilt .. kRouteSetsLaunched - 1, listed by family only.  What
+// iamf_route.hip builds and counts by.
+constexpr int kRouteSetsLaunched = 10;
+template <class F>
+void for_each_instance_of_launched_set(int set, F &&f) {
+  if (set == 9) for_each_render_instance_packets_ragged(f);
+  else for_each_instance_of_built_set(set, f);
+}
+
 // the row of the kernel launch() runs for a route, and the set that lists it: what iamf_hip_route_count takes (a FirSplit
 // call launches render_fast_kernel<2, 2> behind it as well: launch() counts that row too)
 struct RouteKey {
@@ -696,6 +789,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::FastRagged: return {IAMF_HIP_ROUTE_FAST_RAGGED, 0, m, p.out_ch, 0, 6};   // a family listing's row
     case Family::Lpcm24Coupled: return {IAMF_HIP_ROUTE_LPCM24_COUPLED, r.variant, m, p.out_ch, 0, 7};   // a family listing's row
     case Family::Lpcm24Mix: return {IAMF_HIP_ROUTE_LPCM24_MIX, 0, m, p.out_ch, r.variant, 8};   // a family listing's row, k = LP2
+    case Family::PacketsRagged: return {IAMF_HIP_ROUTE_PACKETS_RAGGED, 0, m, p.out_ch, p.lpcm_bytes == 3 ? 3 : 2, 9};   // a family listing's row, k = sample bytes
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

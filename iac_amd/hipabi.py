@@ -109,7 +109,9 @@ ROUTE_NAME = {v: k for k, v in list(ROUTE.items()) + list(ROUTE_BY_FAMILY_ONLY.i
 # families added since (the three dicts above are pinned by their callers, length included): _family_id and the by-family
 # listings below consult this one where those do not know a family
 ROUTE_FAMILY_MORE = dict(LPCM24_MIX=33)
-_ROUTE_NAME_MORE = {v: k for k, v in ROUTE_FAMILY_MORE.items()}
+# (that one is pinned by now as well: families added behind it)
+ROUTE_FAMILY_LATER = dict(PACKETS_RAGGED=37)
+_ROUTE_NAME_MORE = {v: k for k, v in list(ROUTE_FAMILY_MORE.items()) + list(ROUTE_FAMILY_LATER.items())}
 
 
 def _family_name(fam):
@@ -212,6 +214,7 @@ def lib():
         L.iamf_hip_batch_render_interleaved.argtypes = [C.c_void_p, C.POINTER(InterleavedCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_ragged.argtypes = [C.c_void_p, C.POINTER(RaggedCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_packets_ragged.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets_mix.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
@@ -399,7 +402,7 @@ def _family_id(family):
         for names in (ROUTE, ROUTE_BY_FAMILY_ONLY):
             if family in names:
                 return names[family]
-        return ROUTE_FAMILY_MORE[family]
+        return ROUTE_FAMILY_MORE[family] if family in ROUTE_FAMILY_MORE else ROUTE_FAMILY_LATER[family]
     return int(family)
 
 
@@ -633,6 +636,17 @@ class Batch:
         r = lib().iamf_hip_batch_render_packets(self.h, C.byref(call), stream0, n)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_packets")
+        return r
+
+    def render_packets_ragged(self, inp, args, stream0=0, n_streams=None):
+        """iamf_hip_batch_render_packets_ragged: as render_packets, a call of any length; the whole batch unless a range is
+        named"""
+        call = PacketCall()
+        call.in_, call.args = inp, args
+        n = self.cfg.n_streams - stream0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_packets_ragged(self.h, C.byref(call), stream0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_packets_ragged")
         return r
 
     def render_packets_mix(self, in0, in1, args, stream0=0, n_streams=None):

@@ -779,6 +779,37 @@ typedef struct {
 } iamf_hip_packet_call;
 int iamf_hip_batch_render_packets(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams);
 
+/* Element 0 as LPCM packets of ANY call length: an LPCM stream whose frames hold 1000, 480, 240 or 120 samples, rendered frame
+ * by frame, or the first or last frame of any stream, which arrives trimmed (n_frames == 1, n_samples set, first_sample).  On
+ * any batch, any packet layout and any length the call leaves the batch, d_pcm and its return value exactly as
+ *   iamf_hip_batch_render_packets(b, call, stream0, n_streams)
+ * does, bit for bit, persisted stream state included — so calls of every entry, flushes, restarts, gain changes, exports and
+ * imports may follow one another on one batch.
+ *   call      as for iamf_hip_batch_render_packets.
+ * One pass of the FOUR-samples-per-lane kernel over the packets as they lie (IAMF_HIP_ROUTE_PACKETS_RAGGED) when the call's
+ * samples per stream (n_frames * frame_size, or n_samples) are at least 1 and NO multiple of 64, and:
+ *   - the packets have one of the four forms the fused whole-block kernels read, little-endian, every channel present, d_raw
+ *     16-byte aligned: 16-bit mono-coded (1, 4, 9 or 16 contiguous runs, src_step 2; both strides and every src_offset + 2 *
+ *     first_sample multiples of 8), 16-bit coupled (2, 6, 8, 10 or 12 channels in playback order, pairs (0,1), (4,5) ..
+ *     interleaved with src_step 4 and the partner 2 bytes behind, C and LFE runs of src_step 2; strides, a pair's src_offset +
+ *     4 * first_sample and a run's src_offset + 2 * first_sample multiples of 8), 24-bit mono-coded (src_step 3; strides and
+ *     src_offset + 3 * first_sample multiples of 4) or 24-bit coupled (src_step 6 / 3, the partner 3 bytes behind; strides, a
+ *     pair's src_offset + 6 * first_sample and a run's src_offset + 3 * first_sample multiples of 4);
+ *   - limiter on; one or two output channels; no second element, ramps, down-mixer, demixer, projection, pre-matrix, HRTF
+ *     stage, LFE generator, reduced out_gain_channels or fixed PCM channel stride; matrix weights that take the packets'
+ *     scale (as the whole-block forms); frame_size a multiple of 4; d_pcm and pcm_stream_stride_bytes multiples of 16; the
+ *     streams' position a multiple of 16 or at least 240; (n_frames + 2) * raw_frame_stride + 2^24 below 2^31;
+ *   - for a frame trimmed to n_samples: first_sample + ((n_samples + 3) & ~3) <= frame_size.
+ * The kernel loads whole quads of four samples: for a frame trimmed to n_samples it reads up to 3 packet samples BEHIND
+ * n_samples in every run, which must therefore be readable — a frame's runs hold frame_size samples each from src_offset on,
+ * whether the frame is trimmed or not, as iamf_hip_lpcm_layout has it.  It reads no byte outside those runs of the call's
+ * frames, and what lies behind n_samples or between the runs changes nothing.  Every other call, a call of whole 64-sample
+ * blocks included, takes exactly the path of iamf_hip_batch_render_packets, that entry's fused whole-block forms included;
+ * IAMF_HIP_PACKETS_RAGGED_UNFUSED=1 forces that, and IAMF_HIP_LPCM_UNFUSED=1 the unpacker and the f32 kernels, as everywhere.
+ * Returns the sample-frames emitted per stream.  Refusals are those of iamf_hip_batch_render_packets, with their codes,
+ * before anything is queued, allocated or changed. */
+int iamf_hip_batch_render_packets_ragged(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams);
+
 /* BOTH elements of a two-element mix as LPCM packets, every packet form the fused kernels read: what
  * iamf_hip_batch_render_lpcm_mix takes and, beyond it, 24-bit packets on both elements.  On any batch with a second element
  * and any packet layouts the call leaves the batch, d_pcm and its return value exactly as
@@ -893,6 +924,9 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *                          (iamf_hip_route_family_instances only)
  *     LPCM24_MIX           both elements as 24-bit packets (iamf_hip_batch_render_packets_mix): m, c, k as LPCM_MIX;
  *                          variant 0 (iamf_hip_route_family_instances only)
+ *     PACKETS_RAGGED       one element as packets of any call length (iamf_hip_batch_render_packets_ragged): m (1, 4, 9, 16:
+ *                          mono-coded; 2, 6, 8, 10, 12: coupled), c, k = bytes per packet sample (2, 3); variant 0
+ *                          (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -930,7 +964,8 @@ enum {
   IAMF_HIP_ROUTE_FAST_INTERLEAVED = 27,  /* no table either (26: unused) */
   IAMF_HIP_ROUTE_FAST_RAGGED = 29,       /* no table either (28: unused) */
   IAMF_HIP_ROUTE_LPCM24_COUPLED = 31,    /* no table either (30 stays unused) */
-  IAMF_HIP_ROUTE_LPCM24_MIX = 33         /* no table either (32 stays unused) */
+  IAMF_HIP_ROUTE_LPCM24_MIX = 33,        /* no table either (32 stays unused) */
+  IAMF_HIP_ROUTE_PACKETS_RAGGED = 37     /* no table either (34, 35 and 36 stay unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -962,8 +997,8 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * LPCM), which no table lists and whose launches show in no table's tally.  _instances: every row of the family;
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
- * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED, LPCM24_COUPLED
- * and LPCM24_MIX. */
+ * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED, LPCM24_COUPLED,
+ * LPCM24_MIX and PACKETS_RAGGED. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
