@@ -265,10 +265,11 @@ struct IAMF_Decoder {
   float *h_in[2], *h_ramp[4], *d_mid, *d_res; /* ramps: element 0, element 1 for `batch`, output, element 1 for `aux` */
   /* element 0's packets as they are, pinned, for the fused LPCM forms of the render kernel (iamf_hip_batch_render_packets_ragged):
    * one mono-coded ambisonics element in 16-bit little-endian LPCM into one or two channels with the limiter on */
-  uint8_t *h_raw;
+  /* (two elements: element 1's packets the same way, for the two-element forms — iamf_hip_batch_render_packets_mix_ragged) */
+  uint8_t *h_raw[2];
   int lp_ok;
-  size_t lp_row_bytes; /* the raw row: every sub-stream of element 0 at its width */
-  iamf_hip_lpcm_layout lp_layout;
+  size_t lp_row_bytes[2]; /* the raw row: every sub-stream of element e at its width */
+  iamf_hip_lpcm_layout lp_layout[2];
   float gain_set[2]; /* element / output constant gains the batch holds (iamf_hip_batch_set_gains synchronises: only on change) */
   ftu_walk walk[2]; /* the sub-streams the stage of element e decodes: widths and first channels (alloc_staging) */
   float *tmp; /* [MAX_SUBSTREAMS * 2][frame_size] unpack scratch */
@@ -874,8 +875,10 @@ static void free_runtime(struct IAMF_Decoder *d) {
   if (d->batch) iamf_hip_batch_destroy(d->batch);
   if (d->batch3) iamf_hip_batch_destroy(d->batch3);
   d->batch = d->batch3 = 0; /* (the resampler stays: setup_pipeline decides what becomes of it) */
-  if (d->h_raw) (void)hipHostFree(d->h_raw);
-  d->h_raw = 0;
+  for (int e = 0; e < 2; ++e) {
+    if (d->h_raw[e]) (void)hipHostFree(d->h_raw[e]);
+    d->h_raw[e] = 0;
+  }
   d->lp_ok = 0;
   for (int e = 0; e < 2; ++e) {
     if (d->h_in[e]) (void)hipHostFree(d->h_in[e]);
@@ -1447,20 +1450,39 @@ static int build_stages(struct IAMF_Decoder *d, int resample, int aux) {
  * kernel takes it and unpacks on the device otherwise.  L: the raw row (ftu_raw_layout) — every channel is carried by a sub-stream, on the
  * form's grid: runs of 8 bytes for 16-bit samples and coupled pairs, of 4 for 24-bit ones.  env_off: the environment
  * variable that says "unpack first" */
-static int lp_worth_asking(const struct IAMF_Decoder *d, const iamf_hip_lpcm_layout *L, const char *env_off) {
-  const Element *e0 = d->sel_el[0];
-  const int common = d->sel->nel == 1 && !d->pre[0].use_dmx && !d->pre[0].use_demix && !d->rs && d->little_endian &&
-                     d->limiter_on && d->out_channels <= 2 && d->pcm_stride == d->out_channels && (d->frame_size & 3) == 0 &&
-                     !getenv(env_off);
-  const int lp_chan = e0->type == AUDIO_ELEMENT_CHANNEL_BASED && e0->nlayers == 1 && d->sample_size == 16 &&
-                      e0->nb_coupled == lp_canonical_coupled(e0->channels) && e0->nsub + e0->nb_coupled == e0->channels;
-  const int lp_scene = e0->type == AUDIO_ELEMENT_SCENE_BASED && !e0->amb_projection && (d->sample_size == 16 || d->sample_size == 24);
-  if (!common || !(lp_chan || lp_scene)) return 0;
+/* (two elements — a bed plus dialogue or commentary: both elements' packets go to the two-element forms of the render kernel,
+ * iamf_hip_batch_render_packets_mix_ragged, under the same terms and with no batch of its own for element 1.  Element 0: a
+ * mono-coded scene-based element or a channel-based one that couples every pair of its layout, 16 or 24 bit; element 1: a mono
+ * element, a mono-coded scene-based element of 1 or 4 channels, or one coupled stereo sub-stream.  Elements are not exchanged to
+ * make a pair fit.  The reference to that entry is weak — render_packets_mix below — and a device layer without it keeps the
+ * f32 path.)  L: the raw rows of the presentation's elements, [nel] */
+#pragma weak iamf_hip_batch_render_packets_mix_ragged
+static int lp_element_fits(const struct IAMF_Decoder *d, int ei, const iamf_hip_lpcm_layout *L, int mix) {
+  const Element *e = d->sel_el[ei];
+  const int sb = L->sample_bytes, grid = sb == 3 ? 3 : 7;
+  /* (a lone channel-based element: 16 bit only — render_packets_any_length's older entry knows no coupled 24-bit form) */
+  const int lp_chan = e->type == AUDIO_ELEMENT_CHANNEL_BASED && e->nlayers == 1 && (d->sample_size == 16 || (mix && d->sample_size == 24)) &&
+                      e->nb_coupled == lp_canonical_coupled(e->channels) && e->nsub + e->nb_coupled == e->channels;
+  const int lp_scene = e->type == AUDIO_ELEMENT_SCENE_BASED && !e->amb_projection && (d->sample_size == 16 || d->sample_size == 24);
+  if (d->pre[ei].use_dmx || d->pre[ei].use_demix || !(lp_chan || lp_scene)) return 0;
+  if (ei == 1 && !(lp_chan ? e->channels <= 2 : (e->channels == 1 || e->channels == 4))) return 0;
   for (int c = 0; c < L->channels; ++c) {
     const int step = L->src_step[c], off = L->src_offset[c];
     if (off < 0) return 0; /* a channel no sub-stream carries: the f32 form zeroes it */
-    if (lp_chan && step == 4 ? ((off - (off & 2)) & 7) != 0 : (step != L->sample_bytes || (off & (L->sample_bytes == 3 ? 3 : 7)))) return 0;
+    /* (a pair's partner lies one sample behind its first channel, which is on the grid) */
+    if (lp_chan && step == 2 * sb ? ((off - (off & (sb == 3 ? 3 : 2))) & grid) != 0 : (step != sb || (off & grid))) return 0;
   }
+  return 1;
+}
+
+static int lp_worth_asking(const struct IAMF_Decoder *d, const iamf_hip_lpcm_layout *L, const char *env_off) {
+  const int nel = d->sel->nel;
+  const int common = (nel == 1 || (nel == 2 && !d->aux && iamf_hip_batch_render_packets_mix_ragged)) && !d->rs && d->little_endian &&
+                     d->limiter_on && d->out_channels <= 2 && d->pcm_stride == d->out_channels && (d->frame_size & 3) == 0 &&
+                     !getenv(env_off);
+  if (!common) return 0;
+  for (int e = 0; e < nel; ++e)
+    if (!lp_element_fits(d, e, &L[e], nel == 2)) return 0;
   return 1;
 }
 
@@ -1498,11 +1520,16 @@ static int alloc_staging(struct IAMF_Decoder *d, int resample) {
   }
   for (int i = 0; i < 4; ++i)
     if (hipHostMalloc((void **)&d->h_ramp[i], sizeof(float) * d->frame_size, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
-  /* element 0's packets as a raw row, one sub-stream behind the other, for the packet-fed form of the render kernel */
-  row = element_raw_layout(d, 0, 0, 0, &d->lp_layout);
-  d->lp_row_bytes = row > 0 ? (size_t)row : 0;
-  d->lp_ok = row > 0 && lp_worth_asking(d, &d->lp_layout, "IAMF_HIP_FACADE_UNPACK");
-  if (d->lp_ok && hipHostMalloc((void **)&d->h_raw, d->lp_row_bytes + 256, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
+  /* every element's packets as a raw row, one sub-stream behind the other, for the packet-fed forms of the render kernel */
+  d->lp_ok = p->nel <= 2;
+  for (int e = 0; e < p->nel && e < 2; ++e) {
+    row = element_raw_layout(d, e, 0, 0, &d->lp_layout[e]);
+    d->lp_row_bytes[e] = row > 0 ? (size_t)row : 0;
+    d->lp_ok = d->lp_ok && row > 0;
+  }
+  d->lp_ok = d->lp_ok && lp_worth_asking(d, d->lp_layout, "IAMF_HIP_FACADE_UNPACK");
+  for (int e = 0; e < p->nel && d->lp_ok; ++e)
+    if (hipHostMalloc((void **)&d->h_raw[e], d->lp_row_bytes[e] + 256, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   d->pcm_cap = (size_t)4 * ((size_t)d->info.max_frame_size * d->pcm_stride + d->pcm_extra);
   if (hipHostMalloc(&d->h_pcm, d->pcm_cap, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
   if (hipHostMalloc((void **)&d->h_done, 64, 0) != hipSuccess) return IAMF_ERR_ALLOC_FAIL;
@@ -1703,19 +1730,19 @@ static int unpack_element(struct IAMF_Decoder *d, int ei) {
   return ns;
 }
 
-/* element 0's packets as they are -> the pinned raw row (ftu_raw_layout without a head); unpack_element's checks;
+/* element ei's packets as they are -> its pinned raw row (ftu_raw_layout without a head); unpack_element's checks;
  * returns samples per channel */
-static int stage_lpcm_row(struct IAMF_Decoder *d) {
+static int stage_lpcm_row(struct IAMF_Decoder *d, int ei) {
   const int fs = (int)d->frame_size;
-  const unsigned bps = (unsigned)d->lp_layout.sample_bytes;
+  const unsigned bps = (unsigned)d->lp_layout[ei].sample_bytes;
   int ns = -1;
   size_t off = 0;
-  for (int s = 0; s < d->walk[0].nsub; ++s) {
-    const unsigned w = (unsigned)d->walk[0].width[s];
-    const int n = (int)(d->pkt_len[0][s] / (w * bps));
+  for (int s = 0; s < d->walk[ei].nsub; ++s) {
+    const unsigned w = (unsigned)d->walk[ei].width[s];
+    const int n = (int)(d->pkt_len[ei][s] / (w * bps));
     if (ns < 0) ns = n;
     if (n != ns || n > fs) return IAMF_ERR_INVALID_PACKET;
-    memcpy(d->h_raw + off, d->pkt[0][s], (size_t)n * w * bps);
+    memcpy(d->h_raw[ei] + off, d->pkt[ei][s], (size_t)n * w * bps);
     off += (size_t)fs * w * bps;
   }
   return ns < 0 ? IAMF_ERR_INVALID_PACKET : ns;
@@ -1863,13 +1890,25 @@ static int render_launch(struct IAMF_Decoder *d, iamf_hip_render_args *a, int lp
     a->d_pcm = d->h_pcm;
     a->pcm_stream_stride_bytes = (int64_t)d->pcm_cap;
   }
+  if (lp && d->sel->nel > 1) {
+    iamf_hip_packet_mix_call c; /* (both elements' packets, any number of kept samples; lp_worth_asking has seen the entry) */
+    memset(&c, 0, sizeof(c));
+    for (int e = 0; e < 2; ++e) {
+      c.in[e].d_raw = d->h_raw[e];
+      c.in[e].raw_stream_stride = c.in[e].raw_frame_stride = (int64_t)d->lp_row_bytes[e];
+      c.in[e].first_sample = s0;
+      c.in[e].layout = d->lp_layout[e];
+    }
+    c.args = *a;
+    return iamf_hip_batch_render_packets_mix_ragged(d->batch, &c, 0, 1);
+  }
   if (lp) {
     iamf_hip_packet_call c; /* (any number of kept samples: render_packets_any_length) */
     memset(&c, 0, sizeof(c));
-    c.in.d_raw = d->h_raw;
-    c.in.raw_stream_stride = c.in.raw_frame_stride = (int64_t)d->lp_row_bytes;
+    c.in.d_raw = d->h_raw[0];
+    c.in.raw_stream_stride = c.in.raw_frame_stride = (int64_t)d->lp_row_bytes[0];
     c.in.first_sample = s0;
-    c.in.layout = d->lp_layout;
+    c.in.layout = d->lp_layout[0];
     c.args = *a;
     return render_packets_any_length(d->batch, &c, 0, 1);
   }
@@ -1894,9 +1933,11 @@ static int render_tu(struct IAMF_Decoder *d, void *pcm) {
   float cgain[3], set[2];
   int lp = d->lp_ok && !d->group; /* the packets go to the render kernel as they are (decided per frame below) */
   if (lp) {
-    int r = stage_lpcm_row(d);
-    if (r < 0) return r;
-    ns = r;
+    for (int e = 0; e < nel; ++e) {
+      int r = stage_lpcm_row(d, e);
+      if (r < 0) return r;
+      ns = r;
+    }
   } else {
     for (int e = 0; e < nel; ++e) {
       int r = unpack_element(d, e);
@@ -1917,9 +1958,12 @@ static int render_tu(struct IAMF_Decoder *d, void *pcm) {
   meta_note_frame(d, w.s0, d->tu_trim_end);
   frame_gain_plan(d, w.s0, w.keep, d->h_ramp, ramp, cgain, set);
   /* (any number of kept samples: a trimmed end or a frame of 1000 takes the ragged packet form of the render kernel) */
-  if (lp && ((w.s0 & 3) || ramp[0] || ramp[2])) { /* not a call of the fused kernels: the f32 form after all */
-    int r = unpack_element(d, 0);
-    if (r < 0) return r;
+  /* (two elements: the mix forms take ramps on all three stages, so only a start off the grid sends the frame to f32) */
+  if (lp && ((w.s0 & 3) || (nel == 1 && (ramp[0] || ramp[2])))) { /* not a call of the fused kernels: the f32 form after all */
+    for (int e = 0; e < nel; ++e) {
+      int r = unpack_element(d, e);
+      if (r < 0) return r;
+    }
     lp = 0;
   }
   if (!lp && w.s0)
@@ -1930,7 +1974,7 @@ static int render_tu(struct IAMF_Decoder *d, void *pcm) {
     }
   ftu_element_stage_args(&a, lp ? 0 : d->h_in[0], element_in_channels(d->sel_el[0]), fs, lfe[0], w.s0, w.te, w.keep,
                          d->pre[0].use_dmx ? d->pre[0].h_dmx : 0, d->pre[0].use_demix ? d->pre[0].h_demix : 0, d->stream);
-  if (nel > 1 && !d->aux) {
+  if (nel > 1 && !d->aux && !lp) {
     a.d_in2 = d->h_in[1];
     a.in2_stream_stride = a.in2_frame_stride = (int64_t)d->sel_el[1]->channels * fs;
   }

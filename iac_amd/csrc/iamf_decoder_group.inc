@@ -19,6 +19,7 @@
  *
  * Streams of one mono-coded ambisonics element in 16-bit LPCM into one or two channels skip the unpacker: the render kernel reads
  * the uploaded packets itself (iamf_hip_batch_render_packets_ragged; IAMF_HIP_GROUP_UNPACK=1 in the environment: unpack first).
+ * So do streams of two elements whose packets the two-element forms read (iamf_hip_batch_render_packets_mix_ragged; lp_worth_asking).
  *
  * Handles that resample (stream rate != output rate: IAMF_decoder.c:3193-3199,3223-3248) render through three stages as the
  * single handle does — the batch into planar-per-stream f32, the resampler (one phase and history per stream,
@@ -524,7 +525,7 @@ static int group_alloc_staging(iamf_hip_decoder_group *g, void *const *handles) 
   }
   /* element 0's packets straight into the render kernel (iamf_hip_batch_render_packets_ragged: no unpacked copy, no unpack
    * launch): when asking is worth it is the single handle's question too */
-  g->lp_ok = lp_worth_asking(d0, &g->lay[0], "IAMF_HIP_GROUP_UNPACK");
+  g->lp_ok = lp_worth_asking(d0, g->lay, "IAMF_HIP_GROUP_UNPACK"); /* (two elements: both rows, iamf_hip_batch_render_packets_mix_ragged) */
   for (int k = 0; k < 3; ++k)
     if (!(g->cgain[k] = (float *)calloc(n, sizeof(float)))) return 1;
   /* upload chunks: at most eight per round, at least eight handles each (an upload call costs ~4 us of host time) */
@@ -906,6 +907,34 @@ static int group_run_lpcm(iamf_hip_decoder_group *g, int i, int j) {
   return r < 0;
 }
 
+/* a two-element run's packets, both elements', straight into the render kernel (lp_worth_asking has seen the entry: no batch
+ * of its own for element 1).  Element 1 takes its gain through its ramp row, constant or not, as in group_run_f32; the other two
+ * stages through theirs where the round applies them so (rampu) */
+static int group_run_lpcm_mix(iamf_hip_decoder_group *g, int i, int j) {
+  iamf_hip_packet_mix_call c;
+  int r;
+  memset(&c, 0, sizeof(c));
+  for (int e = 0; e < 2; ++e) {
+    c.in[e].d_raw = g->d_raw[e];
+    c.in[e].raw_stream_stride = c.in[e].raw_frame_stride = (int64_t)g->raw_stride[e];
+    c.in[e].first_sample = g->s0[i];
+    c.in[e].layout = g->lay[e];
+  }
+  ftu_element_stage_args(&c.args, 0, 0, g->fs, 0, g->s0[i], g->te[i], g->keep[i], 0, 0, g->stream);
+  c.args.d_element2_ramp = g->d_ramp[1];
+  if (g->rampu & 1) c.args.d_element_ramp = g->d_ramp[0];
+  if (g->rampu & 4) c.args.d_output_ramp = g->d_ramp[2];
+  c.args.ramp_stream_stride = g->fs;
+  c.args.d_pcm = g->h_pcm;
+  c.args.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
+  r = iamf_hip_batch_render_packets_mix_ragged(g->batch, &c, i, j - i);
+  for (int s = i; s < j && r >= 0; ++s) {
+    g->result[s] = r;
+    g->pos[s] += g->keep[s];
+  }
+  return r < 0;
+}
+
 /* the run from unpacked f32: element 1 through its own batch first (stage, matrix, its gain row -> planar f32), the render
  * batch, and behind a resampler render (f32) -> resample -> loudness / limiter / pack — render_tu's launches, as ranges */
 static int group_run_f32(iamf_hip_decoder_group *g, int i, int j) {
@@ -1022,6 +1051,7 @@ static int group_submit_round(iamf_hip_decoder_group *g, const uint8_t *const *d
     j = group_run_end(g, i);
     if (g->action[i] == GA_ADVANCE ? group_run_advance(g, i, j)
         : g->action[i] == GA_FLUSH ? (g->rs ? group_run_flush_resampled(g, i, j) : group_run_flush(g, i, j))
+        : g->lp_ok && g->nel > 1 && !(g->s0[i] & 3) ? group_run_lpcm_mix(g, i, j) /* (the mix forms take ramps) */
         : g->lp_ok && !g->rampu && !(g->s0[i] & 3) ? group_run_lpcm(g, i, j)
                                                                          : group_run_f32(g, i, j))
       return group_fail(g);

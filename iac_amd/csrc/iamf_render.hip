@@ -407,6 +407,12 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
       if (p.lpcm_bytes == 3) launched = p.lpcm_coupled ? iamf_hip_fast_packets_ragged24_coupled_launch(&p, m, st) : iamf_hip_fast_packets_ragged24_launch(&p, m, st);
       else launched = p.lpcm_coupled ? iamf_hip_fast_packets_ragged_coupled_launch(&p, m, st) : iamf_hip_fast_packets_ragged_launch(&p, m, st);
       break;
+    case Family::PacketsMixRagged:   // the four two-element packet forms, a unit each
+      if (p.lpcm_bytes == 3)
+        launched = p.lpcm_coupled ? iamf_hip_fast_packets_mix_ragged24_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_packets_mix_ragged24_launch(&p, m, r.variant, st);
+      else
+        launched = p.lpcm_coupled ? iamf_hip_fast_packets_mix_ragged_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_packets_mix_ragged_launch(&p, m, r.variant, st);
+      break;
     case Family::FirSplit: {
       const int e = launch_fir_split(p, m, grid, st);
       if (e != IAMF_HIP_OK) return e;
@@ -469,9 +475,10 @@ struct LpcmIn {
 constexpr int kNotFused = INT32_MIN;
 // the family a packet call must route to for a fused kernel to read its packets (lp2: the second element's, or null;
 // prag: the call carries the mark of iamf_hip_batch_render_packets_ragged — RenderParams::ragged == 2 — and is no whole number
-// of 64-sample blocks, which only the ragged packet form takes)
+// of 64-sample blocks, which only the ragged packet form takes; with lp2, the mark of iamf_hip_batch_render_packets_mix_ragged —
+// ragged == 3 — and the ragged two-element form)
 Family lpcm_family(const LpcmIn *lp, const LpcmIn *lp2, bool prag = false) {
-  if (prag && !lp2) return Family::PacketsRagged;
+  if (prag) return lp2 ? Family::PacketsMixRagged : Family::PacketsRagged;
   if (lp2) return lp->bytes == 3 ? Family::Lpcm24Mix : Family::LpcmMix;   // (24-bit: iamf_hip_batch_render_packets_mix only)
   if (lp->coupled == 2) return Family::Lpcm24Coupled;
   if (lp->coupled) return Family::LpcmCoupled;
@@ -530,7 +537,7 @@ struct PreparedCall {
 // il (iamf_hip_batch_render_interleaved): the call may take the interleaved form of the fast kernel; everything else as without.
 // rag (iamf_hip_batch_render_ragged): the call may take the planar ragged form; everything else as without.
 // prag (with lp, iamf_hip_batch_render_packets_ragged; first: iamf_hip_lpcm_input::first_sample): the call may take the ragged
-// packet form; everything else as without.
+// packet form; everything else as without.  With lp2 (iamf_hip_batch_render_packets_mix_ragged): the ragged two-element form.
 int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc,
                    const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
@@ -653,7 +660,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     p.lpcm_coupled = lp->coupled;
     // (the size cuts of the whole-block forms say nothing about a ragged call of iamf_hip_batch_render_packets_ragged, which no
     //  whole-block form takes: the ragged packet form has its own measurement and its own cut, packets_ragged_fused below)
-    const bool whole_blocks = !(prag && !lp2 && (total & 63));
+    const bool whole_blocks = !(prag && (total & 63));
     if (whole_blocks && lp->bytes == 3 && !lp->coupled && !lp2 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     if (whole_blocks && lp->coupled == 1 && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
     if (whole_blocks && lp->coupled == 2 && !lp2 && !lpcm24_coupled_fused(cnt)) return kNotFused;
@@ -661,7 +668,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       // 24-bit packets on both elements (iamf_hip_batch_render_packets_mix alone hands them over): the form's own values
       if (lp->bytes != lp2->bytes) return kNotFused;
       p.lpcm_mix = (lp->bytes == 3 ? 4 : 0) | (lp2->coupled ? 2 : 1);
-      if (lp->bytes == 3 && !lpcm24_mix_fused(cnt)) return kNotFused;
+      if (whole_blocks && lp->bytes == 3 && !lpcm24_mix_fused(cnt)) return kNotFused;
       p.in2 = reinterpret_cast<const float *>(lp2->raw);
       p.in2_stream_stride = lp2->stream_stride;
       p.in2_frame_stride = lp2->frame_stride;
@@ -669,7 +676,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       pc.p.lpcm2_stream_stride = lp2->stream_stride;
       pc.p.lpcm2_frame_stride = lp2->frame_stride;
       for (int m = 0; m < 4; ++m) pc.p.lpcm2_off[m] = lp2->off[m];
-      if (lp->bytes != 3 && !lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
+      if (whole_blocks && lp->bytes != 3 && !lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     }
     // the mark of iamf_hip_batch_render_packets_ragged, with the trimmed frame's first sample where pick_route looks for it
     // (render_route.hpp, packets_ragged_shape_ok).  The form packs into the caller's buffer itself: a fixed PCM channel stride
@@ -678,7 +685,13 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       p.ragged = 2;
       p.demix_i0 = first;
     }
-    if (pick_route(p, m_eff).family != lpcm_family(lp, lp2, p.ragged == 2 && (total & 63))) return kNotFused;
+    // the mark of iamf_hip_batch_render_packets_mix_ragged, the same way (packets_mix_ragged_shape_ok; a fixed PCM channel
+    // stride has been sent away above, with every two-element packet call)
+    if (prag && lp2 && packets_mix_ragged_fused(cnt)) {
+      p.ragged = 3;
+      p.demix_i0 = first;
+    }
+    if (pick_route(p, m_eff).family != lpcm_family(lp, lp2, p.ragged >= 2 && (total & 63))) return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -731,7 +744,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   // the interleaved form packs into the caller's buffer itself and knows no LFE slot; pick_route has the call's other rules
   p.interleaved = (il && !restride && !b->lfe && interleaved_fused(cnt)) ? 1 : 0;
   // so does the planar ragged form (an LFE slot: pick_route sees p.lfe)
-  if (p.ragged != 2) p.ragged = (rag && !restride && ragged_fused(cnt)) ? 1 : 0;
+  if (p.ragged < 2) p.ragged = (rag && !restride && ragged_fused(cnt)) ? 1 : 0;
   pc.a = a;
   pc.m_eff = m_eff;
   pc.lds = lds;
@@ -1343,9 +1356,10 @@ int iamf_hip_batch_render_packets_ragged(iamf_hip_batch *b, const iamf_hip_packe
 // every other case both elements are unpacked, each into a buffer of the batch, and the f32 path renders them.  Both ways
 // give the same PCM and leave the same stream state, bit for bit.  Every refusal comes before the first launch.
 // (packets: iamf_hip_batch_render_packets_mix — the forms are asked of lpcm_form_packets(), and 24-bit packets on both
-//  elements are a fused form as well; everything else is the one path)
+//  elements are a fused form as well; everything else is the one path.
+//  prag: iamf_hip_batch_render_packets_mix_ragged — the fused attempt carries its mark; everything else is the one path)
 static int render_lpcm_mix_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in0, const iamf_hip_lpcm_input *in1,
-                                const iamf_hip_render_args *args, int32_t stream0, int32_t n_streams, bool packets) {
+                                const iamf_hip_render_args *args, int32_t stream0, int32_t n_streams, bool packets, bool prag = false) {
   if (!b->has2 || args->d_in || args->d_in2 || !in0->d_raw || !in1->d_raw || in0->first_sample != in1->first_sample ||
       !args->d_pcm || args->n_frames < 0)
     return IAMF_HIP_ERR_BAD_ARG;
@@ -1379,7 +1393,7 @@ static int render_lpcm_mix_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in
     LpcmIn lp0, lp1;
     lpcm_in_of(in0, ch, first, form0, lp0);
     lpcm_in_of(in1, b->m2, first, form1, lp1);
-    const int r = render_call(b, a, (int)total, stream0, n_streams, &lp0, &lp1);
+    const int r = render_call(b, a, (int)total, stream0, n_streams, &lp0, &lp1, false, false, prag, first);
     if (r != kNotFused) return r;
   }
   const hipStream_t st = static_cast<hipStream_t>(args->stream);
@@ -1404,6 +1418,16 @@ int iamf_hip_batch_render_packets_mix(iamf_hip_batch *b, const iamf_hip_packet_m
   if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
   if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
   return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, true);
+}
+
+// Both elements of a mix as LPCM packets of any call length (include/iamf_hip.h): iamf_hip_batch_render_packets_mix with leave to
+// take render_fast_kernel<.., IN2, LP, true, LPB, LPC, LP2, false, RAG> (Family::PacketsMixRagged) where the call is no whole number of
+// 64-sample blocks, both elements' packets have a form the whole-block mix kernels read and render_prepare and pick_route let the
+// call through.  The same checks in the same order, the same path for everything else.
+int iamf_hip_batch_render_packets_mix_ragged(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, true, true);
 }
 
 // Interleaved f32 of any call length (include/iamf_hip.h): iamf_hip_batch_render_range with leave to take

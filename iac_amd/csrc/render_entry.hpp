@@ -4,7 +4,7 @@
 // names depend on it), hence `const void *params`: the caller's RenderParams / FanParams, the same definition on both
 // sides (render_params.hpp, render_fanout.hpp).  Each returns 1 if it launched, 0 if (m, the block's channel counts) is
 // not in the instance list the caller has already consulted (render_route.hpp).  The units that feed render_fast_kernel
-// another input form (the fourteen iamf_hip_fast_*_launch entries) share their launchers: render_fast_unit.hpp.  Behind the
+// another input form (the eighteen iamf_hip_fast_*_launch entries) share their launchers: render_fast_unit.hpp.  Behind the
 // launch entries: the unpacker's, and the one entry through which every launcher counts what it ran (iamf_route.hip).
 #pragma once
 
@@ -49,6 +49,14 @@ IAMF_INTERNAL int iamf_hip_fast_packets_ragged_launch(const void *params, int m,
 IAMF_INTERNAL int iamf_hip_fast_packets_ragged_coupled_launch(const void *params, int m, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fast_packets_ragged24_launch(const void *params, int m, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fast_packets_ragged24_coupled_launch(const void *params, int m, hipStream_t st);
+// iamf_render_packets_mix_ragged.hip, _packets_mix_ragged_coupled.hip, _packets_mix_ragged24.hip, _packets_mix_ragged24_coupled.hip:
+// render_fast_kernel<M, OC, .., IN2, LP, true, LPB, LPC, LP2, IL = false, RAG>, both elements of a mix as packets of any call length
+// (params->ragged == 3, params: RenderMixParams); the four two-element packet forms by params->lpcm_bytes and params->lpcm_coupled
+// as above, lp2 = LP2
+IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged_launch(const void *params, int m, int lp2, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged_coupled_launch(const void *params, int m, int lp2, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged24_launch(const void *params, int m, int lp2, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged24_coupled_launch(const void *params, int m, int lp2, hipStream_t st);
 // iamf_render_fir_m2b.hip: render_fast_kernel<M, 2, stage> / the FFT stage alone (fir_fft_kernel)
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch(const void *params, int m, int stage, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch_fft(const void *params, int m, hipStream_t st);

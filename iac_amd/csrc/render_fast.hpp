@@ -269,9 +269,15 @@ __device__ __forceinline__ int ring_wrap(int i) {  // i in [-R, 2R)
 //       samples that lie behind n_samples in the channel's run (any bytes: they convert to finite numbers), which the same
 //       SELECT replaces by zeros.  The loads stay inside the frames' runs: frame size a multiple of 4 and, for a trimmed
 //       frame, first_sample + ((n_samples + 3) & ~3) <= frame_size (pick_route, packets_ragged_shape_ok).
+//       With LP, IN2 and LP2 (iamf_hip_batch_render_packets_mix_ragged, iamf_render_packets_mix_ragged*.hip): both elements of a
+//       mix as packets, every whole-block mix form — LPB 2 or 3, LPC or not, LP2 1 or 2.  Both elements' loads are the mix
+//       forms' own and stay inside the frames' runs by the same two conditions, which hold for both elements (one frame
+//       size, one first_sample); what they bring in for an absent sample is finite and leaves through the same SELECT, which
+//       sits behind the mixing stage.  The ramp rows alone end with the call: the last quad of a ramp is loaded float by
+//       float, no float at or behind index `total` of a stream's row (load_x2).
 template <int M, int OC, int FIR = 0, bool DOWN = false, bool IN2 = false, bool LP = false, bool EARLY = true, int LPB = 2, bool LPC = false,
           int LP2 = 0, bool IL = false, bool RAG = false>
-__global__ __launch_bounds__(FIR == 1 ? 512 : 256, (RAG && LP) ? packets_ragged_wgs(M, OC, LPB, LPC) : LP2 ?(LPB == 3 ? lpcm24_mix_wgs(M, OC, LP2) : lpcm_mix_wgs(M, OC, LP2)) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
+__global__ __launch_bounds__(FIR == 1 ? 512 : 256, (RAG && LP) ? (LP2 ? packets_mix_ragged_wgs(M, OC, LPB, LP2) : packets_ragged_wgs(M, OC, LPB, LPC)) : LP2 ?(LPB == 3 ? lpcm24_mix_wgs(M, OC, LP2) : lpcm_mix_wgs(M, OC, LP2)) : (FIR >= 2 ? 2 : ((LP && LPB == 3 && M == 16 && OC == 2 && !EARLY) ? 3 : ((FIR || (M <= 16 && !IN2)) ? 4 : 2))))
 void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, RenderParams> p) {
   static_assert(!(FIR && DOWN), "one renderer");
   static_assert(!(LP && (FIR || DOWN || (IN2 && !LP2))) && (!LP || M <= 16), "the LPCM input feeds the plain matrix variant");
@@ -280,7 +286,8 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
   static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
   static_assert(!LPC || (LP && lpcm_coupled_m(M)), "coupled pairs: 16- or 24-bit packets of a loudspeaker layout");
   static_assert(!IL || (!FIR && !DOWN && !IN2 && !LP && EARLY && M <= 2), "interleaved f32 feeds the plain matrix variant, one or two channels");
-  static_assert(!RAG || IL || (!FIR && !DOWN && !IN2 && EARLY), "ragged calls: the interleaved form, the plain planar f32 one, or one element as packets");
+  static_assert(!RAG || IL || (!FIR && !DOWN && (!IN2 || LP2 != 0) && EARLY),
+                "ragged calls: the interleaved form, the plain planar f32 one, one element as packets, or both elements as packets");
   constexpr bool LP3 = LP && LPB == 3;
   extern __shared__ float lds[];
   constexpr int R = kFRing;
@@ -444,9 +451,28 @@ void render_fast_kernel(const std::conditional_t<LP2 != 0, RenderMixParams, Rend
           x2[m] = m < p.m2 ? ld_stream4(src + (int64_t)m * fs) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
       const int64_t ro = (int64_t)s * p.ramp_stream_stride + (int64_t)f * fs + i;  // sample index inside the call
-      if (p.elem_ramp) rmp[0] = ld_stream4(p.elem_ramp + ro);
-      if (p.elem2_ramp) rmp[1] = ld_stream4(p.elem2_ramp + ro);
-      if (p.out_ramp) rmp[2] = ld_stream4(p.out_ramp + ro);
+      if constexpr (RAG) {
+        // the call's last quad may be ragged: a ramp row holds `total` floats per stream and not one more (the unfused path
+        // reads none behind them), so the quad that reaches past the row's end is loaded float by float, the absent ones
+        // staying 1 (their samples are replaced by zeros behind the mixing stage).  f * fs + i is the quad's sample index
+        // inside the call, below `total` for every lane that gets here
+        const int left = p.total - (f * fs + i);
+        const auto ld_ramp = [&](const float *r) {
+          if (left >= 4) return ld_stream4(r + ro);
+          float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
+          v.x = __builtin_nontemporal_load(r + ro);
+          if (left > 1) v.y = __builtin_nontemporal_load(r + ro + 1);
+          if (left > 2) v.z = __builtin_nontemporal_load(r + ro + 2);
+          return v;
+        };
+        if (p.elem_ramp) rmp[0] = ld_ramp(p.elem_ramp);
+        if (p.elem2_ramp) rmp[1] = ld_ramp(p.elem2_ramp);
+        if (p.out_ramp) rmp[2] = ld_ramp(p.out_ramp);
+      } else {
+        if (p.elem_ramp) rmp[0] = ld_stream4(p.elem_ramp + ro);
+        if (p.elem2_ramp) rmp[1] = ld_stream4(p.elem2_ramp + ro);
+        if (p.out_ramp) rmp[2] = ld_stream4(p.out_ramp + ro);
+      }
     }
   };
   if constexpr (IN2) {

@@ -87,6 +87,19 @@ IAMF_HD constexpr int packets_ragged_wgs(int m, int oc, int lpb, bool lpc) {
   (void)m, (void)oc, (void)lpb, (void)lpc;
   return 4;
 }
+// render_fast_kernel<.., IN2, LP, true, LPB, LPC, LP2, IL = false, RAG = true>: both elements of a mix as packets of any call length
+// (iamf_hip_batch_render_packets_mix_ragged) — (LpcmM + LpcmCoupledM) x LpcmOC x LpcmMixK x {16, 24 bit}, 72 instances.
+// Workgroups per CU the instance <M, OC, LPB, LP2> is built for, under the rule of lpcm_mix_wgs(): the highest of 4 / 3 / 2 at
+// which the compiler reports no scratch and no vector spill (M tells the mono-coded element 0 from the coupled one).  DESIGN.md
+// 4.1k has the table.  The 36 16-bit instances all fit four (at most 127 vector registers: <16, 2, 2, 1>).  Of the 24-bit ones,
+// six keep 12 to 116 bytes of scratch per lane at four and are built for three, without scratch: the five that
+// lpcm24_mix_wgs() builds for three — <16, 2, 3, 1>, <16, 2, 3, 2>, <16, 1, 3, 1>, <12, 2, 3, 1>, <10, 2, 3, 1> — and
+// <16, 1, 3, 2>, which the ragged form's tail (the select, the ramps' single loads) pushes over by 32 bytes.
+IAMF_HD constexpr int packets_mix_ragged_wgs(int m, int oc, int lpb, int lp2) {
+  if (lpb == 3 && m == 16) return 3;
+  if (lpb == 3 && (m == 12 || m == 10) && oc == 2 && lp2 == 1) return 3;
+  return 4;
+}
 // render_fast_kernel<.., IL, RAG>: ordinary interleaved f32 of any call length (iamf_hip_batch_render_interleaved): the stage
 // behind the resampler, mono or stereo in and out
 using InterleavedM = Ints<1, 2>;
@@ -259,6 +272,59 @@ inline bool packets_ragged_shape_ok(const RenderParams &p, int m, bool force_gen
   return true;
 }
 
+// What the ragged two-element packet form of the fast kernel (render_fast.hpp, RAG with LP and LP2) needs of a call that came
+// through iamf_hip_batch_render_packets_mix_ragged (RenderParams::ragged == 3, which that entry alone sets): everything the
+// whole-block mix rules (Family::LpcmMix, Family::Lpcm24Mix) ask of the call, with "whole 64-sample blocks" replaced by "any
+// length >= 1 that is NOT a whole number of blocks".  lpcm_mix names element 1's form (LP2, or 4 | LP2 with 24-bit samples on
+// both elements) and matches lpcm_bytes; the bed is in LpcmM or LpcmCoupledM, element 1 as lpcm_mix_m2_ok() has it; both
+// elements on their sample size's grid (8 bytes / 4 bytes: the buffers, the strides, element 0's run starts with first_sample in
+// them — element 1's run starts travel behind this block, RenderMixParams::lpcm2_off, and are held to the same grid by the
+// form check that let the call come here, lpcm_form.hpp); ramp rows on the 16-byte grid with a stride that is a multiple of
+// 4; and, what keeps the loads of a trimmed frame inside the runs of both elements, first + ((total + 3) & ~3) <= frame_size
+// where the call is shorter than a frame (`first` travels in demix_i0, as for packets_ragged_shape_ok: the two inputs of a
+// mix call share it).  A call of whole blocks, and every call this rule does not take, is left to the rules below.
+// IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED=1 sends every such call down them.
+inline bool packets_mix_ragged_shape_ok(const RenderParams &p, int m, bool force_generic) {
+  if (p.ragged != 3 || !p.lpcm || force_generic || getenv("IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED")) return false;
+  if (!p.limiter_on || !p.in || !LpcmOC::has(p.out_ch) || p.og_ch < p.out_ch || p.n_end < kFWin) return false;
+  if (p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe) return false;
+  if (p.total < 1 || !(p.total & 63) || p.frame_size < 4 || (p.frame_size & 3)) return false;
+  if ((p.pos0 & 15) && p.pos0 < kDelay) return false;
+  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (reinterpret_cast<uintptr_t>(p.lpcm) & 15)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  // the forms: 16 bit (lpcm_mix == LP2) or 24 bit (lpcm_mix == 4 | LP2) on both elements, the bed mono-coded or coupled
+  const bool s24 = p.lpcm_bytes == 3;
+  if (!s24 && p.lpcm_bytes != 0 && p.lpcm_bytes != 2) return false;
+  const int lp2 = p.lpcm_mix & 3;
+  if (p.lpcm_mix != ((s24 ? 4 : 0) | lp2) || !LpcmMixK::has(lp2)) return false;
+  if (!p.in2 || !lpcm_mix_m2_ok(lp2, p.m2)) return false;
+  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (s24 ? 2 : 1)) return false;
+  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
+  const int grid = s24 ? 3 : 7;
+  if ((p.lpcm_stream_stride & grid) || (p.lpcm_frame_stride & grid) || p.lpcm_frame_stride <= 0) return false;
+  for (int c = 0; c < m; ++c) {   // a pair's second channel lies sample_bytes behind its first: the pair's one run starts at the first
+    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
+      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + (s24 ? 3 : 2)) return false;
+    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
+  }
+  if ((reinterpret_cast<uintptr_t>(p.in2) & 15) || (p.in2_stream_stride & grid) || (p.in2_frame_stride & grid) || p.in2_frame_stride <= 0)
+    return false;
+  // per-sample gains: read four at a time, the call's last quad float by float
+  if (p.elem_ramp || p.elem2_ramp || p.out_ramp) {
+    if (p.ramp_stream_stride & 3) return false;
+    if ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) | reinterpret_cast<uintptr_t>(p.out_ramp)) & 15)
+      return false;
+  }
+  // a trimmed frame: the last quad that starts below `total` ends inside the run of frame_size samples, in both elements
+  if (p.demix_i0 < 0 || (p.demix_i0 > 0 && p.total >= p.frame_size)) return false;
+  if (p.total < p.frame_size && (int64_t)p.demix_i0 + ((p.total + 3) & ~3) > p.frame_size) return false;
+  // the kernel addresses a stream's packets of one call with 32-bit byte offsets, either element's: fast_shape_ok's bound
+  const int64_t frames = (int64_t)p.total / p.frame_size + 2;
+  if (frames * p.lpcm_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
+  if (frames * p.in2_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
+  return true;
+}
+
 // What the wide kernels (render_wide.hpp, render_wide4.hpp) share: 3..24 output channels, limiter on, aligned calls.
 // (Not looked at here: the stream position and the stages in front — demixer, down-mixer, mixer — which differ
 // between the two: pick_route.)
@@ -330,6 +396,10 @@ enum class Family {
   PacketsRagged,  // render_fast_kernel<.., LP, true, LPB, LPC, 0, false, RAG = true> (iamf_render_packets_ragged*.hip): one element as
                 // packets of any call length that is no whole number of 64-sample blocks, RenderParams::ragged == 2, which only
                 // iamf_hip_batch_render_packets_ragged sets; variant 0.  Set 9 (kRouteSetsLaunched), listed by family only
+  PacketsMixRagged,  // render_fast_kernel<.., IN2, LP, true, LPB, LPC, LP2, false, RAG = true> (iamf_render_packets_mix_ragged*.hip):
+                // both elements of a mix as packets of any call length that is no whole number of 64-sample blocks,
+                // RenderParams::ragged == 3, which only iamf_hip_batch_render_packets_mix_ragged sets; variant = LP2.  Set 10
+                // (kRouteSetsListed), listed by family only
 };
 struct Route {
   Family family;
@@ -475,6 +545,23 @@ inline bool packets_ragged_fused(int n_launch) {
   return true;
 }
 
+// Whether a range of n_launch streams that came through iamf_hip_batch_render_packets_mix_ragged takes the ragged two-element
+// packet form at all (render_prepare asks), under the rule of lpcm_mix_fused(): a (shape, size) at which it does not beat what
+// the call ran before — iamf_hip_batch_render_packets_mix on a twin batch in the same process: two iamf_hip_lpcm_unpack passes,
+// then the general kernel — by more than that baseline's own run-to-run spread is not fused (tools/packets_mix_ragged_rate.py,
+// profiles/r18_packets_mix_ragged_rate.json).
+// Measured on an MI355X, into stereo s16, 64 one-frame calls per stream and step (5 steps per region, 3 regions): the baseline takes
+// 3.05 / 3.11 / 3.89 (3rd-order bed + coupled stereo, 16 bit), 2.80 / 2.64 / 3.11 (24 bit), 2.28 / 2.26 / 1.90 and 2.29 / 2.27 / 1.96 (5.1 + mono, 16 / 24 bit),
+// 2.51 / 2.65 / 2.85 and 2.41 / 2.45 / 2.75 (7.1.4 + coupled stereo, 16 / 24 bit) times the new entry's time in calls of 1000 samples at
+// 512 / 2048 / 4096 streams, and 2.40 / 2.34 / 2.15, 2.14 / 1.79 / 1.76, 1.93 / 1.98 / 1.63, 1.97 / 1.94 / 1.66, 2.24 / 2.29 / 1.99 and
+// 2.18 / 2.17 / 1.95 in calls of 480; its spread against itself at most 0.0035 — every measured (shape, size) wins, so every size
+// is fused; this is where one that stops winning would be cut.  (One call of 64 frames of 1000 is 1000 whole blocks: both
+// entries run the whole-block mix family there, 0.990 to 1.010 of each other.)
+inline bool packets_mix_ragged_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
 // rules.  The environment switches are read at every call (the tests set and unset them within one process).
@@ -496,6 +583,9 @@ inline Route pick_route(const RenderParams &p, int m) {
   // one element as packets, no whole number of 64-sample blocks (RenderParams::ragged == 2, which only
   // iamf_hip_batch_render_packets_ragged sets): the same way, in front of the packet rules, which refuse such a length
   if (packets_ragged_shape_ok(p, m, force_generic)) return take(Family::PacketsRagged);
+  // both elements of a mix as packets, no whole number of 64-sample blocks (RenderParams::ragged == 3, which only
+  // iamf_hip_batch_render_packets_mix_ragged sets): the same way, in front of the packet-mix rules, which refuse such a length
+  if (packets_mix_ragged_shape_ok(p, m, force_generic)) return take(Family::PacketsMixRagged, p.lpcm_mix & 3);
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
@@ -760,6 +850,30 @@ void for_each_instance_of_launched_set(int set, F &&f) {
   else for_each_instance_of_built_set(set, f);
 }
 
+// The ragged two-element packet form (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x LpcmOC x LpcmMixK as
+// its launchers do, the 16-bit units first; variant = bytes per packet sample, k = LP2 (m tells a mono-coded bed from a coupled
+// one: the two lists share no number).
+template <class F>
+void for_each_render_instance_packets_mix_ragged(F &&f) {
+  for (int v = 2; v <= 3; ++v) {
+    const auto rows = [&](int m) {
+      for_each_int(LpcmOC{}, [&](int oc) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED, v, m, oc, k); }); });
+    };
+    for_each_int(LpcmM{}, rows);
+    for_each_int(LpcmCoupledM{}, rows);
+  }
+}
+
+// The answers of for_each_instance_of_launched_set are pinned too — ten sets, "no row" for every other number — so the sets
+// added since are walked by a fifth walker: numbers kRouteSetsLaunched .. kRouteSetsListed - 1, listed by family only.  What
+// iamf_route.hip builds and counts by.
+constexpr int kRouteSetsListed = 11;
+template <class F>
+void for_each_instance_of_listed_set(int set, F &&f) {
+  if (set == 10) for_each_render_instance_packets_mix_ragged(f);
+  else for_each_instance_of_launched_set(set, f);
+}
+
 // the row of the kernel launch() runs for a route, and the set that lists it: what iamf_hip_route_count takes (a FirSplit
 // call launches render_fast_kernel<2, 2> behind it as well: launch() counts that row too)
 struct RouteKey {
@@ -790,6 +904,8 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::Lpcm24Coupled: return {IAMF_HIP_ROUTE_LPCM24_COUPLED, r.variant, m, p.out_ch, 0, 7};   // a family listing's row
     case Family::Lpcm24Mix: return {IAMF_HIP_ROUTE_LPCM24_MIX, 0, m, p.out_ch, r.variant, 8};   // a family listing's row, k = LP2
     case Family::PacketsRagged: return {IAMF_HIP_ROUTE_PACKETS_RAGGED, 0, m, p.out_ch, p.lpcm_bytes == 3 ? 3 : 2, 9};   // a family listing's row, k = sample bytes
+    case Family::PacketsMixRagged:   // a family listing's row, variant = sample bytes, k = LP2
+      return {IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED, p.lpcm_bytes == 3 ? 3 : 2, m, p.out_ch, r.variant, 10};
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

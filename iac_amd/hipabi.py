@@ -111,7 +111,9 @@ ROUTE_NAME = {v: k for k, v in list(ROUTE.items()) + list(ROUTE_BY_FAMILY_ONLY.i
 ROUTE_FAMILY_MORE = dict(LPCM24_MIX=33)
 # (that one is pinned by now as well: families added behind it)
 ROUTE_FAMILY_LATER = dict(PACKETS_RAGGED=37)
-_ROUTE_NAME_MORE = {v: k for k, v in list(ROUTE_FAMILY_MORE.items()) + list(ROUTE_FAMILY_LATER.items())}
+# (and so is that one)
+ROUTE_FAMILY_NEWER = dict(PACKETS_MIX_RAGGED=39)
+_ROUTE_NAME_MORE = {v: k for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER) for k, v in names.items()}
 
 
 def _family_name(fam):
@@ -216,6 +218,7 @@ def lib():
         L.iamf_hip_batch_render_packets.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets_ragged.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets_mix.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_packets_mix_ragged.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_resampler_destroy.argtypes = [C.c_void_p]
@@ -402,7 +405,10 @@ def _family_id(family):
         for names in (ROUTE, ROUTE_BY_FAMILY_ONLY):
             if family in names:
                 return names[family]
-        return ROUTE_FAMILY_MORE[family] if family in ROUTE_FAMILY_MORE else ROUTE_FAMILY_LATER[family]
+        for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER):
+            if family in names:
+                return names[family]
+        return ROUTE_FAMILY_NEWER[family]
     return int(family)
 
 
@@ -658,6 +664,17 @@ class Batch:
         r = lib().iamf_hip_batch_render_packets_mix(self.h, C.byref(call), stream0, n)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_packets_mix")
+        return r
+
+    def render_packets_mix_ragged(self, in0, in1, args, stream0=0, n_streams=None):
+        """iamf_hip_batch_render_packets_mix_ragged: as render_packets_mix, a call of any length; the whole batch unless a
+        range is named"""
+        call = PacketMixCall()
+        call.in_[0], call.in_[1], call.args = in0, in1, args
+        n = self.cfg.n_streams - stream0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_packets_mix_ragged(self.h, C.byref(call), stream0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_packets_mix_ragged")
         return r
 
     def render_range(self, args, stream0, n_streams):

@@ -843,6 +843,41 @@ typedef struct {
 } iamf_hip_packet_mix_call;
 int iamf_hip_batch_render_packets_mix(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams);
 
+/* BOTH elements of a two-element mix as LPCM packets, a call of ANY length: a mix whose frames hold 1000, 480, 240 or 120
+ * samples, rendered frame by frame, or the first or last frame of any stream, which arrives trimmed (n_frames == 1, n_samples
+ * set, first_sample).  On any batch, any pair of packet layouts and any length the call leaves the batch, d_pcm and its
+ * return value exactly as
+ *   iamf_hip_batch_render_packets_mix(b, call, stream0, n_streams)
+ * does, bit for bit, persisted stream state included — so calls of every entry, flushes, restarts, gain changes, exports and
+ * imports may follow one another on one batch.
+ *   call      as for iamf_hip_batch_render_packets_mix.
+ * One pass of the FOUR-samples-per-lane kernel over both elements' packets as they lie (IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED) when
+ * the call's samples per stream (n_frames * frame_size, or n_samples) are at least 1 and NO multiple of 64, and:
+ *   - both elements hold little-endian samples of one size, 16 or 24 bit, every channel present, each d_raw 16-byte aligned, each
+ *     in a form the whole-block mix kernels read (iamf_hip_batch_render_lpcm_mix, iamf_hip_batch_render_packets_mix): element 0
+ *     mono-coded runs of 1 / 4 / 9 / 16 channels or the coupled form of 2 / 6 / 8 / 10 / 12; element 1 mono-coded runs of 1 or
+ *     4 channels or ONE coupled stereo pair; strides and every run's src_offset + src_step * first_sample multiples of 8 (16
+ *     bit) or 4 (24 bit);
+ *   - limiter on; one or two output channels; no down-mixer, demixer, projection, pre-matrix, HRTF stage, LFE generator,
+ *     reduced out_gain_channels or fixed PCM channel stride; matrix weights of both elements that take the packets' scale (as
+ *     the whole-block forms); frame_size a multiple of 4; d_pcm and pcm_stream_stride_bytes multiples of 16; the streams'
+ *     position a multiple of 16 or at least 240; (n_frames + 2) * raw_frame_stride + 2^24 below 2^31 for both elements;
+ *   - ramps (d_element_ramp, d_element2_ramp, d_output_ramp), where given, 16-byte aligned with ramp_stream_stride a
+ *     multiple of 4: they are fused as in the whole-block forms;
+ *   - for a frame trimmed to n_samples: first_sample + ((n_samples + 3) & ~3) <= frame_size.
+ * The kernel loads whole quads of four samples: for a frame trimmed to n_samples it reads up to 3 packet samples BEHIND
+ * n_samples in every run of BOTH elements, which must therefore be readable — a frame's runs hold frame_size samples each
+ * from src_offset on, whether the frame is trimmed or not, as iamf_hip_lpcm_layout has it.  It reads no byte outside those
+ * runs of the call's frames, and what lies behind n_samples or between the runs changes nothing.  It reads NO ramp float
+ * behind the call's last sample: a ramp row need hold the call's samples per stream and not one float more, as for every
+ * other entry.  Every other call, a call of whole 64-sample blocks included, takes exactly the path of
+ * iamf_hip_batch_render_packets_mix, that entry's fused whole-block forms included; IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED=1
+ * forces that, and IAMF_HIP_LPCM_UNFUSED=1 the unpacker and the f32 kernels, as everywhere.
+ * Returns the sample-frames emitted per stream.  Refusals are those of iamf_hip_batch_render_packets_mix, with their codes,
+ * before anything is queued, allocated or changed. */
+int iamf_hip_batch_render_packets_mix_ragged(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0,
+                                             int32_t n_streams);
+
 /* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
  * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
  *
@@ -927,6 +962,8 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *     PACKETS_RAGGED       one element as packets of any call length (iamf_hip_batch_render_packets_ragged): m (1, 4, 9, 16:
  *                          mono-coded; 2, 6, 8, 10, 12: coupled), c, k = bytes per packet sample (2, 3); variant 0
  *                          (iamf_hip_route_family_instances only)
+ *     PACKETS_MIX_RAGGED   both elements as packets of any call length (iamf_hip_batch_render_packets_mix_ragged): m, c, k as
+ *                          LPCM_MIX; variant = bytes per packet sample (2, 3) (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -965,7 +1002,8 @@ enum {
   IAMF_HIP_ROUTE_FAST_RAGGED = 29,       /* no table either (28: unused) */
   IAMF_HIP_ROUTE_LPCM24_COUPLED = 31,    /* no table either (30 stays unused) */
   IAMF_HIP_ROUTE_LPCM24_MIX = 33,        /* no table either (32 stays unused) */
-  IAMF_HIP_ROUTE_PACKETS_RAGGED = 37     /* no table either (34, 35 and 36 stay unused) */
+  IAMF_HIP_ROUTE_PACKETS_RAGGED = 37,    /* no table either (34, 35 and 36 stay unused) */
+  IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED = 39 /* no table either (38 stays unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -998,7 +1036,7 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
  * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED, LPCM24_COUPLED,
- * LPCM24_MIX and PACKETS_RAGGED. */
+ * LPCM24_MIX, PACKETS_RAGGED and PACKETS_MIX_RAGGED. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 

@@ -1,0 +1,423 @@
+// Host-only check of the ragged two-element packet form: its routing (pick_route() in iac_amd/csrc/render_route.hpp,
+// Family::PacketsMixRagged, reached through the value 3 of the host-only field RenderParams::ragged, which
+// iamf_hip_batch_render_packets_mix_ragged alone sets).  One row per clause of packets_mix_ragged_shape_ok, with one field
+// changed and nothing else: the form's kernel on the near side, on the far side exactly what the same RenderParams get with
+// ragged == 0 — what iamf_hip_batch_render_packets_mix is given, and what render_prepare answers with the two unpackers.
+// render_fast_kernel<.., IN2, LP, .., LP2, false, RAG = true> loads a lane's four samples of either element as 8, 12, 16 or 2 x 12
+// bytes at 32-bit offsets, and a ramp's four floats as 16 bytes, and trusts the host that a quad which starts inside a call
+// ends inside its run: a wrong row here is a misaligned or stray load on the GPU, not a slower rate.
+// Driven by tests/test_route_host_packets_mix_ragged.py.
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <initializer_list>
+#include <type_traits>
+
+#include "../../include/iamf_hip.h"
+
+namespace {
+#include "../../iac_amd/csrc/render_params.hpp"
+#include "../../iac_amd/csrc/render_route.hpp"
+
+int g_failed = 0, g_cases = 0;
+
+void row(const char *what, bool ok) {
+  printf("%-118s %s\n", what, ok ? "ok" : "WRONG");
+  ++g_cases;
+  g_failed += ok ? 0 : 1;
+}
+
+uint8_t *const kRaw = reinterpret_cast<uint8_t *>(0x10000);       // never dereferenced: routing looks at alignment only
+uint8_t *const kRaw2 = reinterpret_cast<uint8_t *>(0x800000);
+float *const kRamp = reinterpret_cast<float *>(0x20000);
+uint8_t *const kPcm = reinterpret_cast<uint8_t *>(0x40000);
+
+// the bed's four forms: bytes per sample, coupled
+struct Form {
+  const char *name;
+  int bytes, coupled;   // coupled: RenderParams::lpcm_coupled (0, 1 with 16-bit samples, 2 with 24-bit ones)
+};
+const Form kForms[4] = {{"16-bit mono-coded", 2, 0}, {"16-bit coupled", 2, 1}, {"24-bit mono-coded", 3, 0}, {"24-bit coupled", 3, 2}};
+
+// a live service: one frame of `total` samples per call (frame size = total rounded up to 4 unless given), a bed of m channels
+// as packets of form f laid out as lpcm_util.rows does, a second element of form lp2 (1: mono-coded runs, m2 = 1 for odd m, 4
+// for even; 2: one coupled pair) of the same sample size in a buffer of its own, first_sample `first`
+RenderParams call(const Form &f, int m, int out_ch, int lp2, int total = 1000, int64_t pos0 = 1000, int frame_size = 0, int first = 0) {
+  RenderParams p;
+  memset(&p, 0, sizeof(p));
+  p.frame_size = frame_size ? frame_size : (total + 3) & ~3;
+  p.total = total;
+  p.pos0 = pos0;
+  p.lpcm = kRaw;
+  p.in = reinterpret_cast<const float *>(kRaw);   // the placeholder render_lpcm_mix_impl sets: "not a flush"
+  p.lpcm_bytes = f.bytes;
+  p.lpcm_coupled = f.coupled;
+  int off = 16;
+  for (int c = 0; c < m; ++c) {
+    const bool paired = f.coupled && lpcm_coupled_paired(m, c);
+    const int step = paired ? 2 * f.bytes : f.bytes;
+    if (paired && (c & 1)) {
+      p.lpcm_off[c] = p.lpcm_off[c - 1] + f.bytes;
+      off += 2 * f.bytes * p.frame_size;
+    } else {
+      p.lpcm_off[c] = off + step * first;
+      if (!paired) off += f.bytes * p.frame_size;
+    }
+    off = paired && !(c & 1) ? off : (off + 7) & ~7;
+  }
+  p.lpcm_frame_stride = (off + 15) & ~15;
+  p.lpcm_stream_stride = p.lpcm_frame_stride * (total / p.frame_size + 1);
+  p.demix_i0 = first;
+  // the second element: pick_route sees its place in the in2 fields, strides in bytes
+  p.m2 = lp2 == 2 ? 2 : ((m & 1) ? 1 : 4);
+  p.in2 = reinterpret_cast<const float *>(kRaw2);
+  p.in2_frame_stride = (16 + p.m2 * f.bytes * p.frame_size + 15) & ~15;
+  p.in2_stream_stride = p.in2_frame_stride * (total / p.frame_size + 1);
+  p.lpcm_mix = (f.bytes == 3 ? 4 : 0) | lp2;
+  p.pcm = kPcm;
+  p.out_ch = p.og_ch = out_ch;
+  p.out_format = IAMF_HIP_FMT_S16;
+  p.pcm_stream_stride = (((int64_t)total * out_ch * 4) + 15) & ~(int64_t)15;
+  p.n_streams = p.n_launch = 64;
+  p.limiter_on = 1;
+  p.n_atk = 48;
+  p.n_end = 9649;
+  p.ragged = 3;
+  return p;
+}
+template <class F>
+RenderParams with(RenderParams p, F f) {
+  f(p);
+  return p;
+}
+bool same_key(const RouteKey &k, int f, int v, int m, int c, int kk) {
+  return f == k.family && v == k.variant && m == k.m && c == k.c && kk == k.k;
+}
+bool same_route(const Route &a, const Route &b) { return a.family == b.family && a.variant == b.variant && a.err == b.err; }
+
+// the sets that list a key, as a bit mask
+int sets_of(const RouteKey &k) {
+  int mask = 0;
+  for (int s = 0; s < kRouteSetsListed; ++s)
+    for_each_instance_of_listed_set(s, [&](int f, int v, int km, int kc, int kk) { mask |= same_key(k, f, v, km, kc, kk) ? 1 << s : 0; });
+  return mask;
+}
+
+// fused: the form's family, a row of set 10 and of no other set.  Else: exactly what the same call gets with the mark at 0 —
+// what iamf_hip_batch_render_packets_mix is given —, which must be `fallback` (what the parent commit gives the call: a ragged
+// two-element packet call is refused, and render_prepare unpacks both elements).
+void expect(const char *what, const RenderParams &p, int m, const char *env, bool fused, Family fallback = Family::Refused) {
+  if (env) setenv(env, "1", 1);
+  const Route r = pick_route(p, m);
+  RenderParams q = p;
+  q.ragged = 0;
+  const Route r0 = pick_route(q, m);
+  if (env) unsetenv(env);
+  bool ok = r0.family == fallback;
+  if (fused) {
+    const RouteKey k = route_key(r, p, m);
+    const int lp2 = p.lpcm_mix & 3;
+    ok = ok && r.family == Family::PacketsMixRagged && r.variant == lp2 && r.err == IAMF_HIP_OK && k.set == 10 && sets_of(k) == 1 << 10 &&
+         k.family == IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED && k.variant == (p.lpcm_bytes == 3 ? 3 : 2) && k.m == m && k.c == p.out_ch && k.k == lp2;
+  } else {
+    ok = ok && same_route(r, r0);
+  }
+  row(what, ok);
+}
+
+}  // namespace
+
+int main() {
+  const char *const switches[] = {"IAMF_HIP_FORCE_GENERIC",          "IAMF_HIP_NO_WIDE4", "IAMF_HIP_RAGGED_UNFUSED", "IAMF_HIP_INTERLEAVED_UNFUSED",
+                                  "IAMF_HIP_PACKETS_RAGGED_UNFUSED", "IAMF_HIP_LP_LATE",  "IAMF_HIP_LP_EARLY",       "IAMF_HIP_LPCM_UNFUSED",
+                                  "IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED"};
+  for (const char *e : switches) unsetenv(e);
+  char what[240];
+  const Form &S16 = kForms[0], &S16C = kForms[1], &S24 = kForms[2], &S24C = kForms[3];
+
+  // ---- the number, the block, the sets ----
+  static_assert(IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED == 39, "stable number");
+  static_assert(IAMF_HIP_ROUTE_PACKETS_RAGGED == 37 && IAMF_HIP_ROUTE_LPCM24_MIX == 33 && IAMF_HIP_ROUTE_LPCM24_COUPLED == 31 &&
+                    IAMF_HIP_ROUTE_FAST_RAGGED == 29 && IAMF_HIP_ROUTE_FAST_INTERLEAVED == 27 && IAMF_HIP_ROUTE_LPCM_MIX == 25,
+                "the numbers in use keep their values");
+  static_assert(sizeof(RenderParams) == 616, "the block keeps its size");
+  static_assert(offsetof(RenderParams, ragged) == 412 && offsetof(RenderParams, lfe_div) == 416 && offsetof(RenderParams, lpcm) == 528 &&
+                    offsetof(RenderParams, lpcm_off) == 552 && offsetof(RenderParams, interleaved) == 380,
+                "every field keeps its offset: the mark is a new VALUE of `ragged`, the first sample travels in demix_i0");
+  static_assert(sizeof(RenderMixParams) == 616 + 8 + 16 + 16, "the mixing block behind it too");
+  static_assert((int)Family::PacketsMixRagged == (int)Family::PacketsRagged + 1, "added at the end of the enum");
+  static_assert(kRouteSets == 7 && kRouteSetsAll == 8 && kRouteSetsBuilt == 9 && kRouteSetsLaunched == 10 && kRouteSetsListed == 11 &&
+                    kRouteTables == 3,
+                "an eleventh set behind the pinned walkers, three tables");
+
+  // ---- every instance, and the workgroups it is built for ----
+  int rows = 0, at3 = 0;
+  for_each_render_instance_packets_mix_ragged([&](int f, int v, int m, int oc, int k) {
+    const bool mono = LpcmM::has(m), cpl = LpcmCoupledM::has(m);
+    rows += (f == IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED && (v == 2 || v == 3) && (mono != cpl) && LpcmOC::has(oc) && LpcmMixK::has(k)) ? 1 : 1000;
+    const int wgs = packets_mix_ragged_wgs(m, oc, v, k);
+    rows += (wgs == 3 || wgs == 4) ? 0 : 1000;
+    at3 += wgs == 3;
+    const Form &form = kForms[(v == 3 ? 2 : 0) + (cpl ? 1 : 0)];
+    snprintf(what, sizeof(what), "%s, %d channel(s) into %d, second element of form %d, one frame of 1000: PacketsMixRagged", form.name, m, oc, k);
+    expect(what, call(form, m, oc, k), m, nullptr, true);
+  });
+  row("the family's listing: ({1, 4, 9, 16} + {2, 6, 8, 10, 12}) x {1, 2} x {1, 2} x {2, 3 bytes} = 72 rows of family 39", rows == 72);
+  row("six instances are built for three workgroups per CU, the rest for four", at3 == 6);
+  {
+    bool only10 = true;
+    int n10 = 0;
+    for_each_instance_of_listed_set(10, [&](int f, int v, int m, int c, int k) {
+      ++n10;
+      only10 = only10 && sets_of(RouteKey{f, v, m, c, k}) == 1 << 10;
+    });
+    row("every key of set 10 is in that set only", only10 && n10 == 72);
+    bool none39 = true;
+    int before = 0, after = 0;
+    for (int s = 0; s < 10; ++s) {
+      for_each_instance_of_listed_set(s, [&](int f, int, int, int, int) { none39 = none39 && f != IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED, ++after; });
+      for_each_instance_of_launched_set(s, [&](int, int, int, int, int) { ++before; });
+    }
+    row("no other set holds a row of family 39, and sets 0 .. 9 are the fourth walker's", none39 && before == after);
+    int n = 0;
+    for_each_instance_of_launched_set(10, [&](int, int, int, int, int) { ++n; });
+    for_each_instance_of_listed_set(11, [&](int, int, int, int, int) { ++n; });
+    row("the fourth walker has no set 10, the fifth no set 11", n == 0);
+  }
+  row("packets_mix_ragged_fused: every size up to 65536", [&] {
+    for (int n = 1; n <= 65536; ++n)
+      if (!packets_mix_ragged_fused(n)) return false;
+    return true;
+  }());
+
+  // ---- lengths ----
+  const Family wholes[4] = {Family::LpcmMix, Family::LpcmMix, Family::Lpcm24Mix, Family::Lpcm24Mix};
+  for (int i = 0; i < 4; ++i) {
+    const Form &f = kForms[i];
+    const int m = f.coupled ? 6 : 16, lp2 = f.coupled ? 1 : 2;
+    for (int total : {1, 3, 4, 5, 63, 65, 145, 240, 480, 1000, 1023, 1025, 2049}) {
+      snprintf(what, sizeof(what), "  %s: %d samples in one frame of 2052: fused", f.name, total);
+      expect(what, call(f, m, 2, lp2, total, 1000, 2052), m, nullptr, true);
+    }
+    snprintf(what, sizeof(what), "  %s: 5 frames of 120 (a chunk spans frames): fused", f.name);
+    expect(what, call(f, m, 2, lp2, 600, 600, 120), m, nullptr, true);
+    snprintf(what, sizeof(what), "  %s: 3 frames of 1000: fused", f.name);
+    expect(what, call(f, m, 2, lp2, 3000, 3000, 1000), m, nullptr, true);
+    for (int total : {64, 1024, 4096}) {
+      snprintf(what, sizeof(what), "  %s: %d samples, whole blocks, the mark set: the whole-block mix family, as without the mark", f.name, total);
+      expect(what, call(f, m, 2, lp2, total, 1024), m, nullptr, false, wholes[i]);
+    }
+    snprintf(what, sizeof(what), "  %s: 8 frames of 1000 = 125 blocks: the whole-block mix family", f.name);
+    expect(what, call(f, m, 2, lp2, 8000, 8000, 1000), m, nullptr, false, wholes[i]);
+  }
+  expect("  0 samples", call(S16, 4, 2, 1, 0, 1000, 1024), 4, nullptr, false, Family::LpcmMix);
+
+  // ---- positions ----
+  const struct {
+    int64_t pos;
+    bool fused;
+  } positions[] = {{0, true}, {16, true}, {100, false}, {239, false}, {240, true}, {241, true}, {1100, true}, {((int64_t)1 << 31) + 1, true}};
+  for (const auto &c : positions) {
+    snprintf(what, sizeof(what), "  position %lld: %s", (long long)c.pos, c.fused ? "fused" : "refused (unpacked, the general kernel)");
+    expect(what, call(S16C, 2, 2, 2, 1000, c.pos), 2, nullptr, c.fused);
+  }
+
+  // ---- lpcm_mix names element 1's form and matches lpcm_bytes ----
+  for (const Form &f : kForms) {
+    const int m = f.coupled ? 6 : 4;
+    const RenderParams pf = call(f, m, 2, 1);
+    snprintf(what, sizeof(what), "  %s: lpcm_mix of the other sample size", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.lpcm_mix ^= 4; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: lpcm_mix = 0 (no second element as packets)", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.lpcm_mix = 0; }), m, nullptr, false, Family::Refused);
+    snprintf(what, sizeof(what), "  %s: LP2 = 3", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.lpcm_mix |= 3; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: LP2 = 1 with a second element of 2 channels (two mono runs)", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.m2 = 2; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: LP2 = 1 with a second element of 1 channel: fused", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.m2 = 1; }), m, nullptr, true);
+    snprintf(what, sizeof(what), "  %s: LP2 = 2 with a second element of 4 channels", f.name);
+    expect(what, with(call(f, m, 2, 2), [](RenderParams &p) { p.m2 = 4; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: no second element (in2 null)", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.in2 = nullptr; }), m, nullptr, false);
+  }
+
+  // ---- each form's grid, both elements ----
+  for (const Form &f : kForms) {
+    const int m = f.coupled ? 6 : 4, g = f.bytes == 2 ? 8 : 4;
+    const RenderParams pf = call(f, m, 2, 2);
+    snprintf(what, sizeof(what), "  %s: frame stride + %d B (on the form's grid)", f.name, g);
+    expect(what, with(pf, [&](RenderParams &p) { p.lpcm_frame_stride += g; }), m, nullptr, true);
+    snprintf(what, sizeof(what), "  %s: frame stride + %d B (off it)", f.name, g / 2);
+    expect(what, with(pf, [&](RenderParams &p) { p.lpcm_frame_stride += g / 2; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: stream stride + %d B (on the grid)", f.name, g);
+    expect(what, with(pf, [&](RenderParams &p) { p.lpcm_stream_stride += g; }), m, nullptr, true);
+    snprintf(what, sizeof(what), "  %s: stream stride + %d B (off it)", f.name, g / 2);
+    expect(what, with(pf, [&](RenderParams &p) { p.lpcm_stream_stride += g / 2; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: the mono run of channel 2 + %d B (on the grid)", f.name, g);
+    expect(what, with(pf, [&](RenderParams &p) { p.lpcm_off[2] += g; }), m, nullptr, true);
+    snprintf(what, sizeof(what), "  %s: the mono run of channel 2 + %d B (off it)", f.name, g / 2);
+    expect(what, with(pf, [&](RenderParams &p) { p.lpcm_off[2] += g / 2; }), m, nullptr, false);
+    if (f.coupled) {
+      snprintf(what, sizeof(what), "  %s: the pair (4, 5) + %d B (off the grid)", f.name, g / 2);
+      expect(what, with(pf, [&](RenderParams &p) { p.lpcm_off[4] += g / 2, p.lpcm_off[5] += g / 2; }), m, nullptr, false);
+      snprintf(what, sizeof(what), "  %s: the partner of channel 0 not %d bytes behind it", f.name, f.bytes);
+      expect(what, with(pf, [&](RenderParams &p) { p.lpcm_off[1] += g; }), m, nullptr, false);
+    }
+    snprintf(what, sizeof(what), "  %s: packets + 8 B (d_raw off the 16-byte rule)", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.lpcm += 8, p.in += 2; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: a channel count of the other coding", f.name);
+    expect(what, call(f, f.coupled ? 4 : 6, 2, 2), f.coupled ? 4 : 6, nullptr, false);
+    // element 1
+    snprintf(what, sizeof(what), "  %s: element 1's frame stride + %d B (on the grid)", f.name, g);
+    expect(what, with(pf, [&](RenderParams &p) { p.in2_frame_stride += g; }), m, nullptr, true);
+    snprintf(what, sizeof(what), "  %s: element 1's frame stride + %d B (off it)", f.name, g / 2);
+    expect(what, with(pf, [&](RenderParams &p) { p.in2_frame_stride += g / 2; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: element 1's stream stride + %d B (off the grid)", f.name, g / 2);
+    expect(what, with(pf, [&](RenderParams &p) { p.in2_stream_stride += g / 2; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: element 1's packets + 8 B (d_raw off the 16-byte rule)", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.in2 += 2; }), m, nullptr, false);
+    snprintf(what, sizeof(what), "  %s: element 1's packets + 16 B", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.in2 += 4; }), m, nullptr, true);
+    snprintf(what, sizeof(what), "  %s: element 1's frame stride 0", f.name);
+    expect(what, with(pf, [](RenderParams &p) { p.in2_frame_stride = 0; }), m, nullptr, false);
+  }
+  expect("  sample bytes 3 with the 16-bit coupling (lpcm_coupled == 1): no form", with(call(S24C, 6, 2, 1), [](RenderParams &p) { p.lpcm_coupled = 1; }), 6,
+         nullptr, false);
+  expect("  sample bytes 2 with the 24-bit coupling (lpcm_coupled == 2): no form", with(call(S16C, 6, 2, 1), [](RenderParams &p) { p.lpcm_coupled = 2; }), 6,
+         nullptr, false);
+  expect("  sample bytes 0 (16 bit, as the older entries leave it): fused", with(call(S16, 4, 2, 1), [](RenderParams &p) { p.lpcm_bytes = 0; }), 4, nullptr, true);
+  expect("  M = 14", call(S16, 14, 2, 1), 14, nullptr, false);
+
+  // ---- ramps ----
+  const RenderParams ps = call(S24, 16, 2, 2);
+  expect("  an element ramp: fused", with(ps, [](RenderParams &p) { p.elem_ramp = kRamp, p.ramp_stream_stride = 1000; }), 16, nullptr, true);
+  expect("  a ramp for the second element: fused", with(ps, [](RenderParams &p) { p.elem2_ramp = kRamp, p.ramp_stream_stride = 1000; }), 16, nullptr, true);
+  expect("  an output ramp: fused", with(ps, [](RenderParams &p) { p.out_ramp = kRamp, p.ramp_stream_stride = 1000; }), 16, nullptr, true);
+  expect("  all three ramps: fused",
+         with(ps, [](RenderParams &p) { p.elem_ramp = kRamp, p.elem2_ramp = kRamp + 4096, p.out_ramp = kRamp + 8192, p.ramp_stream_stride = 1004; }), 16,
+         nullptr, true);
+  expect("  a ramp stride that is no multiple of 4", with(ps, [](RenderParams &p) { p.elem2_ramp = kRamp, p.ramp_stream_stride = 1001; }), 16, nullptr, false);
+  expect("  an element ramp off 16 bytes", with(ps, [](RenderParams &p) { p.elem_ramp = kRamp + 1, p.ramp_stream_stride = 1000; }), 16, nullptr, false);
+  expect("  a second element's ramp off 16 bytes", with(ps, [](RenderParams &p) { p.elem2_ramp = kRamp + 2, p.ramp_stream_stride = 1000; }), 16, nullptr, false);
+  expect("  an output ramp off 16 bytes", with(ps, [](RenderParams &p) { p.out_ramp = kRamp + 3, p.ramp_stream_stride = 1000; }), 16, nullptr, false);
+
+  // ---- the first_sample rule, both sides of its bound: first + ((n + 3) & ~3) <= frame_size ----
+  for (const Form &f : kForms) {
+    const int m = f.coupled ? 6 : 4;
+    for (int first : {4, 212}) {
+      snprintf(what, sizeof(what), "  %s: first_sample %d, the rest of a frame of 1000: fused", f.name, first);
+      expect(what, call(f, m, 2, 1, 1000 - first, 0, 1000, first), m, nullptr, true);
+    }
+    snprintf(what, sizeof(what), "  %s: first 4, 997 samples of 1004: the last quad ends with the run: fused", f.name);
+    expect(what, call(f, m, 2, 1, 997, 0, 1004, 4), m, nullptr, true);
+    snprintf(what, sizeof(what), "  %s: first 8, 997 samples of 1004: the last quad would end 4 samples behind the run", f.name);
+    expect(what, call(f, m, 2, 1, 997, 0, 1004, 8), m, nullptr, false);
+  }
+  for (const Form *f : {&S16C, &S24C}) {   // a coupled stereo bed with a coupled stereo second element: on the grid at every even first sample
+    snprintf(what, sizeof(what), "  %s, stereo + stereo: first 2, 994 samples of 1000 (2 + 996 <= 1000): fused", f->name);
+    expect(what, call(*f, 2, 2, 2, 994, 0, 1000, 2), 2, nullptr, true);
+    snprintf(what, sizeof(what), "  %s, stereo + stereo: first 2, 997 samples of 1000 (2 + 1000 > 1000): unpacked", f->name);
+    expect(what, call(*f, 2, 2, 2, 997, 0, 1000, 2), 2, nullptr, false);
+  }
+  expect("  a first sample with whole frames (no trimmed frame has it): not taken", with(call(S16, 4, 2, 1), [](RenderParams &p) { p.demix_i0 = 4; }), 4,
+         nullptr, false);
+  expect("  a negative first sample", with(call(S16, 4, 2, 1, 500, 0, 1000), [](RenderParams &p) { p.demix_i0 = -4; }), 4, nullptr, false);
+  expect("  first_sample 3 (the run starts off the grid)", call(S16, 4, 2, 1, 41, 1000, 1000, 3), 4, nullptr, false);
+  expect("  first_sample 951 (the run starts off the grid)", call(S24, 4, 2, 1, 41, 1000, 1000, 951), 4, nullptr, false);
+
+  // ---- one field changed at a time ----
+  expect("  ragged = 0: as iamf_hip_batch_render_packets_mix", with(ps, [](RenderParams &p) { p.ragged = 0; }), 16, nullptr, false);
+  expect("  ragged = 1 (the f32 entry's mark) with packets: refused as before", with(ps, [](RenderParams &p) { p.ragged = 1; }), 16, nullptr, false);
+  expect("  ragged = 2 (the single-element packet entry's mark) with a second element: refused as before", with(ps, [](RenderParams &p) { p.ragged = 2; }), 16,
+         nullptr, false);
+  expect("  limiter off", with(ps, [](RenderParams &p) { p.limiter_on = 0; }), 16, nullptr, false);
+  expect("  3 output channels", call(S24, 16, 3, 2), 16, nullptr, false);
+  expect("  6 output channels", call(S24, 16, 6, 2), 16, nullptr, false);
+  expect("  output gain on fewer channels than rendered", with(ps, [](RenderParams &p) { p.og_ch = 1; }), 16, nullptr, false);
+  expect("  a limiter table shorter than the staged window", with(ps, [](RenderParams &p) { p.n_end = kFWin - 1; }), 16, nullptr, false);
+  expect("  a limiter table of exactly the staged window", with(ps, [](RenderParams &p) { p.n_end = kFWin; }), 16, nullptr, true);
+  expect("  down-mixer", with(call(S24C, 8, 2, 1), [](RenderParams &p) { p.dmx_on = 1; }), 8, nullptr, false);
+  expect("  demixer", with(ps, [](RenderParams &p) { p.demix_on = 1; }), 16, nullptr, false);
+  expect("  de-mapping matrix", with(ps, [](RenderParams &p) { p.pre_matrix = kRamp; }), 16, nullptr, false);
+  expect("  HRTF stage", with(ps, [](RenderParams &p) { p.fir_taps = 256; }), 16, nullptr, false);
+  expect("  LFE generator", with(ps, [](RenderParams &p) { p.lfe = kRamp; }), 16, nullptr, false);
+  expect("  flush (no input)", with(ps, [](RenderParams &p) { p.in = nullptr; }), 16, nullptr, false);
+  expect("  frame size 1002 (1001 samples)", call(S24, 16, 2, 2, 1001, 1000, 1002), 16, nullptr, false);
+  expect("  frame size 1004 (1001 samples)", call(S24, 16, 2, 2, 1001, 1000, 1004), 16, nullptr, true);
+  expect("  pcm + 2 B", with(ps, [](RenderParams &p) { p.pcm += 2; }), 16, nullptr, false);
+  expect("  pcm + 16 B", with(ps, [](RenderParams &p) { p.pcm += 16; }), 16, nullptr, true);
+  expect("  pcm stream stride + 4 B", with(ps, [](RenderParams &p) { p.pcm_stream_stride += 4; }), 16, nullptr, false);
+  for (int fmt : {IAMF_HIP_FMT_S16, IAMF_HIP_FMT_S24, IAMF_HIP_FMT_S32, IAMF_HIP_FMT_F32}) {
+    snprintf(what, sizeof(what), "  PCM format %d: fused", fmt);
+    expect(what, with(ps, [&](RenderParams &p) { p.out_format = fmt; }), 16, nullptr, true);
+  }
+  {
+    // the 32-bit bound on the packets of either element: (total / frame_size + 2) * frame_stride + 2^24 < 2^31, here 3 frames' worth
+    const int64_t lim = (((int64_t)1 << 31) - ((int64_t)1 << 24)) / 3;
+    const int64_t at = (lim - 1) & ~(int64_t)15;
+    const int64_t beyond = (lim + 16) & ~(int64_t)15;
+    const auto ok = [](int64_t fst) { return 3 * fst + ((int64_t)1 << 24) < ((int64_t)1 << 31); };
+    row("  the 32-bit bound's two test strides lie either side of it", ok(at) && !ok(beyond) && beyond - at <= 32);
+    for (const Form &f : kForms) {
+      const int m = f.coupled ? 6 : 4;
+      snprintf(what, sizeof(what), "  %s: frame stride at the 32-bit bound", f.name);
+      expect(what, with(call(f, m, 2, 1), [&](RenderParams &p) { p.lpcm_frame_stride = at; }), m, nullptr, true);
+      snprintf(what, sizeof(what), "  %s: frame stride beyond the 32-bit bound", f.name);
+      expect(what, with(call(f, m, 2, 1), [&](RenderParams &p) { p.lpcm_frame_stride = beyond; }), m, nullptr, false);
+      snprintf(what, sizeof(what), "  %s: element 1's frame stride at the 32-bit bound", f.name);
+      expect(what, with(call(f, m, 2, 1), [&](RenderParams &p) { p.in2_frame_stride = at; }), m, nullptr, true);
+      snprintf(what, sizeof(what), "  %s: element 1's frame stride beyond the 32-bit bound", f.name);
+      expect(what, with(call(f, m, 2, 1), [&](RenderParams &p) { p.in2_frame_stride = beyond; }), m, nullptr, false);
+    }
+  }
+
+  // ---- the switches ----
+  expect("  IAMF_HIP_FORCE_GENERIC", ps, 16, "IAMF_HIP_FORCE_GENERIC", false);
+  expect("  IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED", ps, 16, "IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED", false);
+  expect("  IAMF_HIP_PACKETS_RAGGED_UNFUSED does not reach the form", ps, 16, "IAMF_HIP_PACKETS_RAGGED_UNFUSED", true);
+  expect("  IAMF_HIP_RAGGED_UNFUSED does not reach the form", ps, 16, "IAMF_HIP_RAGGED_UNFUSED", true);
+  expect("  IAMF_HIP_LP_LATE does nothing to this family", ps, 16, "IAMF_HIP_LP_LATE", true);
+
+  // ---- an unmarked call routes exactly as before: whole blocks and ragged, every form, with and without the new switch ----
+  for (int i = 0; i < 4; ++i) {
+    const int m = kForms[i].coupled ? 6 : 4;
+    for (int total : {4096, 1000}) {
+      RenderParams p = call(kForms[i], m, 2, 1, total, 0, total == 4096 ? 1024 : 1000);
+      p.ragged = 0;
+      const Route a = pick_route(p, m);
+      setenv("IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED", "1", 1);
+      const Route b = pick_route(p, m);
+      unsetenv("IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED");
+      snprintf(what, sizeof(what), "ragged = 0, %s, %d samples: %s, whatever the switch says", kForms[i].name, total,
+               total == 4096 ? "the whole-block mix family" : "refused");
+      row(what, a.family == (total == 4096 ? wholes[i] : Family::Refused) && same_route(a, b) &&
+                    (total == 4096 || a.err == IAMF_HIP_ERR_INVALID_STATE));
+    }
+    // the single-element entry's mark on a single-element call: its own family, as in the parent
+    RenderParams q = call(kForms[i], m, 2, 1);
+    q.ragged = 2, q.in2 = nullptr, q.lpcm_mix = 0, q.m2 = 0, q.in2_frame_stride = q.in2_stream_stride = 0;
+    snprintf(what, sizeof(what), "ragged = 2, %s, one element, 1000 samples: PacketsRagged as before", kForms[i].name);
+    row(what, pick_route(q, m).family == Family::PacketsRagged);
+    q.ragged = 3;
+    snprintf(what, sizeof(what), "ragged = 3, %s, one element, 1000 samples: refused (no second element)", kForms[i].name);
+    row(what, pick_route(q, m).family == Family::Refused);
+  }
+  {
+    // planar f32 through the f32 entries: the mark's value 3 names no planar form
+    RenderParams p;
+    memset(&p, 0, sizeof(p));
+    p.frame_size = p.total = 1000, p.pos0 = 1000, p.in = kRamp, p.in_frame_stride = 4000, p.in_stream_stride = 8000, p.pcm = kPcm, p.out_ch = p.og_ch = 2;
+    p.pcm_stream_stride = 4000, p.n_streams = p.n_launch = 64, p.limiter_on = 1, p.n_atk = 48, p.n_end = 9649, p.ragged = 1;
+    row("planar f32, ragged = 1: FastRagged as before", pick_route(p, 4).family == Family::FastRagged);
+    p.ragged = 3;
+    row("planar f32, ragged = 3: the general kernel", pick_route(p, 4).family == Family::Generic);
+  }
+
+  printf("%d cases, %d wrong\n", g_cases, g_failed);
+  if (!g_failed) printf("OK\n");
+  return g_failed ? 1 : 0;
+}
