@@ -1456,6 +1456,11 @@ static int build_stages(struct IAMF_Decoder *d, int resample, int aux) {
  * element, a mono-coded scene-based element of 1 or 4 channels, or one coupled stereo sub-stream.  Elements are not exchanged to
  * make a pair fit.  The reference to that entry is weak — render_packets_mix below — and a device layer without it keeps the
  * f32 path.)  L: the raw rows of the presentation's elements, [nel] */
+/* (a first stage — the render batch of a handle with a resampler behind it, or of one whose limiter is switched off: the batch
+ * has no limiter, and ONE element's packets go to the packet-fed limiter-less renderer, iamf_hip_batch_render_packets_nolim,
+ * which also reads the coupled 24-bit form; any output layout asks, because the library decides per call.  Two elements on
+ * such a handle, stages in front and gain ramps keep the f32 path.)
+ * mix: the entry that will be asked reads the coupled 24-bit form (the two-element forms, the first stage's) */
 #pragma weak iamf_hip_batch_render_packets_mix_ragged
 static int lp_element_fits(const struct IAMF_Decoder *d, int ei, const iamf_hip_lpcm_layout *L, int mix) {
   const Element *e = d->sel_el[ei];
@@ -1477,12 +1482,14 @@ static int lp_element_fits(const struct IAMF_Decoder *d, int ei, const iamf_hip_
 
 static int lp_worth_asking(const struct IAMF_Decoder *d, const iamf_hip_lpcm_layout *L, const char *env_off) {
   const int nel = d->sel->nel;
-  const int common = (nel == 1 || (nel == 2 && !d->aux && iamf_hip_batch_render_packets_mix_ragged)) && !d->rs && d->little_endian &&
-                     d->limiter_on && d->out_channels <= 2 && d->pcm_stride == d->out_channels && (d->frame_size & 3) == 0 &&
-                     !getenv(env_off);
-  if (!common) return 0;
+  const int first_stage = d->rs || !d->limiter_on;
+  /* (the HOA LFE generator filters what a trimmed frame cuts off as well — ftu_element_stage_args — and reads it from the f32
+   * rows: such a first stage keeps them.  With the limiter on and one or two output channels there is no LFE slot to fill) */
+  const int common = first_stage ? nel == 1 && !d->cfg_sig.lfe_hoa
+                                 : (nel == 1 || (nel == 2 && !d->aux && iamf_hip_batch_render_packets_mix_ragged)) && d->out_channels <= 2;
+  if (!common || !d->little_endian || d->pcm_stride != d->out_channels || (d->frame_size & 3) != 0 || getenv(env_off)) return 0;
   for (int e = 0; e < nel; ++e)
-    if (!lp_element_fits(d, e, &L[e], nel == 2)) return 0;
+    if (!lp_element_fits(d, e, &L[e], nel == 2 || first_stage)) return 0;
   return 1;
 }
 
@@ -1881,10 +1888,34 @@ static int render_packets_any_length(iamf_hip_batch *b, const iamf_hip_packet_ca
   return iamf_hip_batch_render_lpcm_range(b, &c->in, &c->args, stream0, n_streams);
 }
 
-/* the frame's launches: the packets themselves, the f32 form, or render (f32) -> resample -> loudness / limiter / pack.
+/* One element's packets -> a batch without the limiter (a first stage, lp_worth_asking).  iamf_hip_batch_render_packets_nolim is
+ * total: the packet-fed limiter-less renderer where its rules hold, else exactly iamf_hip_batch_render_packets_ragged.  The
+ * reference is weak for the reason given above; a device layer without the entry gets render_packets_any_length. */
+#pragma weak iamf_hip_batch_render_packets_nolim
+static int render_packets_first_stage(iamf_hip_batch *b, const iamf_hip_packet_call *c, int32_t stream0, int32_t n_streams) {
+  if (iamf_hip_batch_render_packets_nolim) return iamf_hip_batch_render_packets_nolim(b, c, stream0, n_streams);
+  return render_packets_any_length(b, c, stream0, n_streams);
+}
+
+/* What the resampler left -> the last stage (a frame_size == 1 batch: loudness, limiter, pack).  iamf_hip_batch_render_interleaved is
+ * total and bit-identical to iamf_hip_batch_render_range on such a batch, and runs the four-samples-per-lane kernel for mono and
+ * stereo; weak like the others, with the older call behind it.  a3: ftu_last_stage_args */
+#pragma weak iamf_hip_batch_render_interleaved
+static int render_last_stage(iamf_hip_batch *b3, const iamf_hip_render_args *a3, int32_t stream0, int32_t n_streams) {
+  if (iamf_hip_batch_render_interleaved) {
+    iamf_hip_interleaved_call c;
+    memset(&c, 0, sizeof(c));
+    c.args = *a3;
+    return iamf_hip_batch_render_interleaved(b3, &c, stream0, n_streams);
+  }
+  return iamf_hip_batch_render_range(b3, a3, stream0, n_streams);
+}
+
+/* the frame's launches: the packets themselves, the f32 form, or render (packets or f32) -> resample -> loudness / limiter / pack.
  * Returns the sample-frames in h_pcm, negative if a call failed */
 static int render_launch(struct IAMF_Decoder *d, iamf_hip_render_args *a, int lp, int s0) {
   const int fs = (int)d->frame_size;
+  iamf_hip_render_args a3;
   int n, n2;
   if (!d->rs) {
     a->d_pcm = d->h_pcm;
@@ -1910,17 +1941,25 @@ static int render_launch(struct IAMF_Decoder *d, iamf_hip_render_args *a, int lp
     c.in.first_sample = s0;
     c.in.layout = d->lp_layout[0];
     c.args = *a;
-    return render_packets_any_length(d->batch, &c, 0, 1);
+    if (!d->rs && d->limiter_on) return render_packets_any_length(d->batch, &c, 0, 1);
+    if (d->rs) { /* the first stage of three: into d_mid */
+      c.args.d_pcm = d->d_mid;
+      c.args.pcm_stream_stride_bytes = (int64_t)sizeof(float) * fs * d->out_channels;
+    }
+    n = render_packets_first_stage(d->batch, &c, 0, 1);
+    if (!d->rs) return n;
+  } else {
+    if (!d->rs) return iamf_hip_batch_render_ex(d->batch, a);
+    a->d_pcm = d->d_mid;
+    a->pcm_stream_stride_bytes = (int64_t)sizeof(float) * fs * d->out_channels;
+    n = iamf_hip_batch_render_ex(d->batch, a);
   }
-  if (!d->rs) return iamf_hip_batch_render_ex(d->batch, a);
-  a->d_pcm = d->d_mid;
-  a->pcm_stream_stride_bytes = (int64_t)sizeof(float) * fs * d->out_channels;
-  n = iamf_hip_batch_render_ex(d->batch, a);
   if (n < 0) return n;
   n2 = iamf_hip_resampler_process(d->rs, d->d_mid, (int64_t)fs * d->out_channels, n, d->d_res,
                                   (int64_t)(iamf_hip_resampler_out_capacity(d->rs, fs) + 512) * d->out_channels, d->stream);
   if (n2 <= 0) return n2;
-  return iamf_hip_batch_render(d->batch3, d->d_res, 0, d->out_channels, n2, d->h_pcm, (int64_t)d->pcm_cap, d->stream);
+  ftu_last_stage_args(&a3, d->d_res, 0, d->out_channels, n2, d->h_pcm, (int64_t)d->pcm_cap, d->stream);
+  return render_last_stage(d->batch3, &a3, 0, 1);
 }
 
 static int render_tu(struct IAMF_Decoder *d, void *pcm) {
@@ -2039,7 +2078,11 @@ static int flush_tail(struct IAMF_Decoder *d, void *pcm) { /* iamf_delay_buffer_
       const float one = 1.f;
       if (iamf_hip_batch_set_gains(d->batch3, 0, 0, &one)) return IAMF_ERR_INTERNAL;
     }
-    n = (n2 + extra) ? iamf_hip_batch_render(d->batch3, d->d_res, 0, d->out_channels, n2 + extra, d->h_pcm, (int64_t)d->pcm_cap, d->stream) : 0;
+    if (n2 + extra) {
+      iamf_hip_render_args a3;
+      ftu_last_stage_args(&a3, d->d_res, 0, d->out_channels, n2 + extra, d->h_pcm, (int64_t)d->pcm_cap, d->stream);
+      n = render_last_stage(d->batch3, &a3, 0, 1);
+    }
   }
   if (n < 0) return IAMF_ERR_INTERNAL;
   if (facade_wait(d)) return IAMF_ERR_INTERNAL;

@@ -465,7 +465,8 @@ static int group_create_last(iamf_hip_decoder_group *g, const struct IAMF_Decode
   const int n = g->n;
   if (last_stage_create(d0, n, &g->rs, &g->batch3)) return 1;
   g->mid_stride = (int64_t)g->fs * g->out_ch;
-  g->res_stride = (int64_t)(iamf_hip_resampler_out_capacity(g->rs, g->fs) + iamf_hip_resampler_flush_capacity(g->rs) + 512) * g->out_ch;
+  /* (a multiple of 4 floats: every stream's row on the 16-byte grid, which the last stage's fast form wants — render_last_stage) */
+  g->res_stride = ((int64_t)(iamf_hip_resampler_out_capacity(g->rs, g->fs) + iamf_hip_resampler_flush_capacity(g->rs) + 512) * g->out_ch + 3) & ~(int64_t)3;
   if (hipMalloc((void **)&g->d_mid, sizeof(float) * (size_t)n * g->mid_stride) != hipSuccess ||
       hipMalloc((void **)&g->d_res, sizeof(float) * (size_t)n * g->res_stride) != hipSuccess)
     return 1;
@@ -864,7 +865,7 @@ static int group_last_stage(iamf_hip_decoder_group *g, int i, int j, int n2) {
   iamf_hip_render_args a3;
   if (n2 <= 0) return 0;
   ftu_last_stage_args(&a3, g->d_res, g->res_stride, g->out_ch, n2, g->h_pcm, (int64_t)g->pcm_cap, g->stream);
-  return iamf_hip_batch_render_range(g->batch3, &a3, i, j - i);
+  return render_last_stage(g->batch3, &a3, i, j - i); /* (iamf_hip_batch_render_interleaved where the device layer has it) */
 }
 
 /* iamf_delay_buffer_handle, IAMF_decoder.c:3250-3301: the resampler's tail + the limiter's (flush_tail) */
@@ -887,24 +888,37 @@ static int group_run_flush_resampled(iamf_hip_decoder_group *g, int i, int j) {
   return r < 0;
 }
 
-/* the run's packets straight into the render kernel: first kept sample s0, keep samples (uniform over the run) */
+/* behind the run's render call, which returned r: with a resampler the two stages behind it (d_mid -> d_res -> PCM), and the
+ * run's results and positions */
+static int group_run_behind(iamf_hip_decoder_group *g, int i, int j, int r) {
+  if (r < 0) return 1;
+  if (g->rs) {
+    const int n2 = iamf_hip_resampler_process_range(g->rs, g->d_mid, g->mid_stride, r, g->d_res, g->res_stride, g->stream, i, j - i);
+    if (n2 < 0 || (r = group_last_stage(g, i, j, n2)) < 0) return 1;
+    for (int s = i; s < j; ++s) g->pos3[s] += n2;
+  }
+  for (int s = i; s < j; ++s) {
+    g->result[s] = r;
+    g->pos[s] += g->keep[s];
+  }
+  return 0;
+}
+
+/* the run's packets straight into the render kernel: first kept sample s0, keep samples (uniform over the run).  A first stage
+ * (a resampler behind, or the limiter off: lp_worth_asking) asks the packet-fed limiter-less renderer, into d_mid where the
+ * resampler follows */
 static int group_run_lpcm(iamf_hip_decoder_group *g, int i, int j) {
-  iamf_hip_packet_call c; /* (the entry is total: any number of kept samples, render_launch of the single handle) */
-  int r;
+  iamf_hip_packet_call c; /* (the entries are total: any number of kept samples, render_launch of the single handle) */
   memset(&c, 0, sizeof(c));
   c.in.d_raw = g->d_raw[0];
   c.in.raw_stream_stride = c.in.raw_frame_stride = (int64_t)g->raw_stride[0];
   c.in.first_sample = g->s0[i];
   c.in.layout = g->lay[0];
   ftu_element_stage_args(&c.args, 0, 0, g->fs, 0, g->s0[i], g->te[i], g->keep[i], 0, 0, g->stream);
-  c.args.d_pcm = g->h_pcm;
-  c.args.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
-  r = render_packets_any_length(g->batch, &c, i, j - i);
-  for (int s = i; s < j && r >= 0; ++s) {
-    g->result[s] = r;
-    g->pos[s] += g->keep[s];
-  }
-  return r < 0;
+  c.args.d_pcm = g->rs ? (void *)g->d_mid : (void *)g->h_pcm;
+  c.args.pcm_stream_stride_bytes = g->rs ? (int64_t)sizeof(float) * g->mid_stride : (int64_t)g->pcm_cap;
+  return group_run_behind(g, i, j, g->rs || !g->limiter_on ? render_packets_first_stage(g->batch, &c, i, j - i)
+                                                           : render_packets_any_length(g->batch, &c, i, j - i));
 }
 
 /* a two-element run's packets, both elements', straight into the render kernel (lp_worth_asking has seen the entry: no batch
@@ -941,7 +955,6 @@ static int group_run_f32(iamf_hip_decoder_group *g, int i, int j) {
   const struct IAMF_Decoder *d0 = g->d[0];
   const int fs = g->fs, s0 = g->s0[i], te = g->te[i], keep = g->keep[i];
   iamf_hip_render_args a;
-  int r;
   if (group_unpack_once(g)) return 1;
   ftu_element_stage_args(&a, g->d_in[0], g->in_ch[0], fs, g->lfe[0], s0, te, keep, d0->pre[0].use_dmx ? g->d_dmx : 0,
                          d0->pre[0].use_demix ? g->d_demix : 0, g->stream);
@@ -970,18 +983,7 @@ static int group_run_f32(iamf_hip_decoder_group *g, int i, int j) {
   a.ramp_stream_stride = fs;
   a.d_pcm = g->rs ? (void *)g->d_mid : (void *)g->h_pcm;
   a.pcm_stream_stride_bytes = g->rs ? (int64_t)sizeof(float) * g->mid_stride : (int64_t)g->pcm_cap;
-  r = iamf_hip_batch_render_range(g->batch, &a, i, j - i);
-  if (r < 0) return 1;
-  if (g->rs) {
-    const int n2 = iamf_hip_resampler_process_range(g->rs, g->d_mid, g->mid_stride, r, g->d_res, g->res_stride, g->stream, i, j - i);
-    if (n2 < 0 || (r = group_last_stage(g, i, j, n2)) < 0) return 1;
-    for (int s = i; s < j; ++s) g->pos3[s] += n2;
-  }
-  for (int s = i; s < j; ++s) {
-    g->result[s] = r;
-    g->pos[s] += g->keep[s];
-  }
-  return 0;
+  return group_run_behind(g, i, j, iamf_hip_batch_render_range(g->batch, &a, i, j - i));
 }
 
 /* the end of the run that starts at stream i: neighbouring streams that do the same thing from the same position */

@@ -413,6 +413,9 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
       else
         launched = p.lpcm_coupled ? iamf_hip_fast_packets_mix_ragged_coupled_launch(&p, m, r.variant, st) : iamf_hip_fast_packets_mix_ragged_launch(&p, m, r.variant, st);
       break;
+    case Family::NolimPackets:   // the limiter-less renderer over packets: a unit per sample size
+      launched = p.lpcm_bytes == 3 ? iamf_hip_nolim_packets24_launch(&p, m, st) : iamf_hip_nolim_packets_launch(&p, m, st);
+      break;
     case Family::FirSplit: {
       const int e = launch_fir_split(p, m, grid, st);
       if (e != IAMF_HIP_OK) return e;
@@ -538,10 +541,13 @@ struct PreparedCall {
 // rag (iamf_hip_batch_render_ragged): the call may take the planar ragged form; everything else as without.
 // prag (with lp, iamf_hip_batch_render_packets_ragged; first: iamf_hip_lpcm_input::first_sample): the call may take the ragged
 // packet form; everything else as without.  With lp2 (iamf_hip_batch_render_packets_mix_ragged): the ragged two-element form.
+// nlp (with lp and prag, iamf_hip_batch_render_packets_nolim): the call may take the packet-fed limiter-less renderer; everything
+// else as with prag alone.
 int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc,
-                   const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0) {
+                   const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0, bool nlp = false) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
-  if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || !b->lp_scale_ok || getenv("IAMF_HIP_LPCM_UNFUSED")))
+  // (the weights' range: the limiter-less packet form converts the samples first and needs no rule, so it asks further down)
+  if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || (!b->lp_scale_ok && !nlp) || getenv("IAMF_HIP_LPCM_UNFUSED")))
     return kNotFused;
   // a second element or ramps: the two-element packet form only, which also keeps away from a fixed PCM channel stride
   if (lp && !lp2 && (b->has2 || a.d_element_ramp || a.d_element2_ramp || a.d_output_ramp)) return kNotFused;
@@ -658,9 +664,20 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     for (int m = 0; m < 16; ++m) p.lpcm_off[m] = lp->off[m];
     p.lpcm_bytes = lp->bytes;
     p.lpcm_coupled = lp->coupled;
+    // the mark of iamf_hip_batch_render_packets_nolim, with the trimmed frame's first sample where pick_route looks for it
+    // (render_route.hpp, nolim_packets_shape_ok).  The form packs into the caller's buffer itself: a fixed PCM channel stride
+    // stays unfused.  Where the rule does not hold the mark is taken back, and the call is iamf_hip_batch_render_packets_ragged's
+    bool nolim_lp = false;
+    if (nlp && !lp2 && !(b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) && nolim_packets_fused(cnt)) {
+      p.ragged = 4;
+      p.demix_i0 = first;
+      nolim_lp = pick_route(p, m_eff).family == Family::NolimPackets;
+      if (!nolim_lp) p.ragged = 0, p.demix_i0 = 0;
+    }
+    if (!nolim_lp && !b->lp_scale_ok) return kNotFused;
     // (the size cuts of the whole-block forms say nothing about a ragged call of iamf_hip_batch_render_packets_ragged, which no
     //  whole-block form takes: the ragged packet form has its own measurement and its own cut, packets_ragged_fused below)
-    const bool whole_blocks = !(prag && (total & 63));
+    const bool whole_blocks = !nolim_lp && !(prag && (total & 63));
     if (whole_blocks && lp->bytes == 3 && !lp->coupled && !lp2 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     if (whole_blocks && lp->coupled == 1 && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
     if (whole_blocks && lp->coupled == 2 && !lp2 && !lpcm24_coupled_fused(cnt)) return kNotFused;
@@ -681,7 +698,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     // the mark of iamf_hip_batch_render_packets_ragged, with the trimmed frame's first sample where pick_route looks for it
     // (render_route.hpp, packets_ragged_shape_ok).  The form packs into the caller's buffer itself: a fixed PCM channel stride
     // stays unfused, as for the coupled 24-bit form
-    if (prag && !lp2 && !(b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) && packets_ragged_fused(cnt)) {
+    if (!nolim_lp && prag && !lp2 && !(b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) && packets_ragged_fused(cnt)) {
       p.ragged = 2;
       p.demix_i0 = first;
     }
@@ -691,7 +708,7 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       p.ragged = 3;
       p.demix_i0 = first;
     }
-    if (pick_route(p, m_eff).family != lpcm_family(lp, lp2, p.ragged >= 2 && (total & 63))) return kNotFused;
+    if (!nolim_lp && pick_route(p, m_eff).family != lpcm_family(lp, lp2, p.ragged >= 2 && (total & 63))) return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -793,11 +810,11 @@ int render_finish(iamf_hip_batch *b, const PreparedCall &pc) {
   return r != IAMF_HIP_OK ? r : render_commit(b, pc);
 }
 
-// the whole call (lp, lp2, il, rag, prag, first: as render_prepare, whose kNotFused comes back before anything is changed or launched)
+// the whole call (lp, lp2, il, rag, prag, first, nlp: as render_prepare, whose kNotFused comes back before anything is changed or launched)
 int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr,
-                const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0) {
+                const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0, bool nlp = false) {
   PreparedCall pc;
-  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il, rag, prag, first);
+  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il, rag, prag, first, nlp);
   return r != IAMF_HIP_OK ? r : render_finish(b, pc);
 }
 
@@ -1183,13 +1200,13 @@ static int range_args_check(const iamf_hip_batch *b, const iamf_hip_render_args 
   return IAMF_HIP_OK;
 }
 
-// (prag, first: as render_prepare — iamf_hip_batch_render_packets_ragged)
+// (prag, first, nlp: as render_prepare — iamf_hip_batch_render_packets_ragged, iamf_hip_batch_render_packets_nolim)
 static int render_range_impl(iamf_hip_batch *b, const iamf_hip_render_args *a, int32_t stream0, int32_t n_streams, const LpcmIn *lp,
-                             bool prag = false, int first = 0) {
+                             bool prag = false, int first = 0, bool nlp = false) {
   int64_t total = 0;
   const int rc = range_args_check(b, a, stream0, n_streams, &total);
   if (rc != IAMF_HIP_OK || total == 0) return rc;
-  return render_call(b, *a, (int)total, stream0, n_streams, lp, nullptr, false, false, prag, first);
+  return render_call(b, *a, (int)total, stream0, n_streams, lp, nullptr, false, false, prag, first, nlp);
 }
 
 int iamf_hip_batch_render_range(iamf_hip_batch *b, const iamf_hip_render_args *a, int32_t stream0, int32_t n_streams) {
@@ -1291,9 +1308,10 @@ static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, i
 }
 
 // (packets: iamf_hip_batch_render_packets — the form is asked of lpcm_form_packets(); everything else is the one path.
-//  prag: iamf_hip_batch_render_packets_ragged — the fused attempt carries its mark; everything else is the one path)
+//  prag: iamf_hip_batch_render_packets_ragged — the fused attempt carries its mark; everything else is the one path.
+//  nlp: iamf_hip_batch_render_packets_nolim — the fused attempt asks for the packet-fed limiter-less renderer first)
 static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
-                                  int32_t stream0, int32_t n_streams, bool packets, bool prag = false) {
+                                  int32_t stream0, int32_t n_streams, bool packets, bool prag = false, bool nlp = false) {
   if (!b || !in || !args || !in->d_raw || args->d_in || !args->d_pcm || args->n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
   if (!range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
@@ -1309,7 +1327,7 @@ static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *
     lpcm_in_of(in, ch, first, form, lp);
     a.d_in = reinterpret_cast<const float *>(in->d_raw);   // not read by the fused kernel; non-null = "not a flush"
     a.in_stream_stride = a.in_frame_stride = 0;
-    const int r = render_range_impl(b, &a, stream0, n_streams, &lp, prag, first);
+    const int r = render_range_impl(b, &a, stream0, n_streams, &lp, prag, first, nlp);
     if (r != kNotFused) return r;
   }
   // Unfused: unpack, then the f32 path.  Everything the render call would refuse is refused here first, so that no unpack
@@ -1348,6 +1366,16 @@ int iamf_hip_batch_render_packets_ragged(iamf_hip_batch *b, const iamf_hip_packe
   if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
   if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
   return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, true, true);
+}
+
+// Element 0 as LPCM packets on a limiter-less batch (include/iamf_hip.h): iamf_hip_batch_render_packets_ragged with leave to take
+// render_nolim_kernel<M, LPB, LPC> (Family::NolimPackets) where the batch is of the plain limiter-less kind, the packets
+// have one of the four fused forms and render_prepare and pick_route let the call through.  The same checks in the same order,
+// the same path for everything else.
+int iamf_hip_batch_render_packets_nolim(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, true, true, true);
 }
 
 // Both elements of a mix as LPCM packets (include/iamf_hip.h).  Fused (render_fast_kernel<.., LP2>: Family::LpcmMix) when

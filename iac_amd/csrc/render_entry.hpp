@@ -57,6 +57,11 @@ IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged_launch(const void *params, in
 IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged_coupled_launch(const void *params, int m, int lp2, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged24_launch(const void *params, int m, int lp2, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged24_coupled_launch(const void *params, int m, int lp2, hipStream_t st);
+// iamf_render_nolim_packets.hip, _nolim_packets24.hip: render_nolim_kernel<M, LPB, LPC> (render_nolim.hpp), the limiter-less
+// renderer over one element's packets (params->ragged == 4); 16- / 24-bit samples by unit, mono-coded or coupled by
+// params->lpcm_coupled (0 / 1 with 16-bit samples, 2 with 24-bit ones).  Their launcher: render_nolim_unit.hpp
+IAMF_INTERNAL int iamf_hip_nolim_packets_launch(const void *params, int m, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_nolim_packets24_launch(const void *params, int m, hipStream_t st);
 // iamf_render_fir_m2b.hip: render_fast_kernel<M, 2, stage> / the FFT stage alone (fir_fft_kernel)
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch(const void *params, int m, int stage, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch_fft(const void *params, int m, hipStream_t st);

@@ -133,7 +133,7 @@ IAMF_HD constexpr int wide_lds_floats(int c, int m) {
   return kWPos * c + 2 * kWPos + kWPos / 16 + 3 * kWChunk + 2 * kWWin + ((c + 3) & ~3) * m + 16;
 }
 
-// render_nolim.hpp
+// render_nolim.hpp (both kernels)
 constexpr int kNlChunk = 1024;                       // sample-frames per workgroup
 constexpr int kNlMaxFrameBytes = 60;                 // out_ch * bytes per sample-frame the LDS tile takes (60 KiB)
 
@@ -144,6 +144,44 @@ inline bool nolim_shape_ok(const RenderParams &p) {
   if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
   if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
   if (((p.out_ch * bytes) & 3) || p.out_ch * bytes > kNlMaxFrameBytes) return false;  // a lane's 4 sample-frames = whole 16-byte pieces
+  return true;
+}
+
+// What the packet-fed form of the limiter-less renderer (render_nolim.hpp, render_nolim_kernel) needs of a call that came
+// through iamf_hip_batch_render_packets_nolim (RenderParams::ragged == 4, which that entry alone sets): the plain kind
+// render_nolim_kernel takes (pick_route's Family::Nolim rule: limiter off, one matrix-rendered element, no second element, ramps,
+// down-mixer, demixer, pre-matrix, HRTF stage or LFE generator, no reduced out_gain_channels); the packet form named by
+// (lpcm_bytes, lpcm_coupled) as the ragged packet family names it, with an instance for m, on that form's own grid (lpcm_form.hpp:
+// 8 bytes for 16-bit samples, 4 for 24-bit ones — strides and every run's start, first_sample included); frame size and the call's
+// samples per stream multiples of 4 and at least 4, so that a lane's quad never straddles a frame; for a trimmed frame
+// first + total <= frame_size (`first`, iamf_hip_lpcm_input::first_sample, travels in demix_i0 as for packets_ragged_shape_ok), so
+// that no byte outside the samples of the call is read; PCM rows on the 16-byte grid and a sample-frame of whole dwords that fits
+// the tile, as nolim_shape_ok has it.  The kernel addresses with 64-bit pointers: no bound on the call's extent.
+// IAMF_HIP_NOLIM_PACKETS_UNFUSED=1, IAMF_HIP_LPCM_UNFUSED=1 and IAMF_HIP_FORCE_GENERIC=1 send every such call down the other rules.
+inline bool nolim_packets_shape_ok(const RenderParams &p, int m, bool force_generic) {
+  if (p.ragged != 4 || !p.lpcm || force_generic || getenv("IAMF_HIP_NOLIM_PACKETS_UNFUSED") || getenv("IAMF_HIP_LPCM_UNFUSED")) return false;
+  if (p.limiter_on || !p.in || p.og_ch < p.out_ch) return false;
+  if (p.in2 || p.lpcm_mix || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe)
+    return false;
+  if (p.total < 4 || (p.total & 3) || p.frame_size < 4 || (p.frame_size & 3)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.lpcm) & 15) || (reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
+  if (p.out_ch < 1 || ((p.out_ch * bytes) & 3) || p.out_ch * bytes > kNlMaxFrameBytes) return false;
+  // the form: 16-bit mono-coded (LpcmM), 16-bit coupled (lpcm_coupled == 1), 24-bit mono-coded, 24-bit coupled (== 2)
+  const bool s24 = p.lpcm_bytes == 3;
+  if (!s24 && p.lpcm_bytes != 2) return false;
+  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (s24 ? 2 : 1)) return false;
+  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
+  const int grid = s24 ? 3 : 7;
+  if ((p.lpcm_stream_stride & grid) || (p.lpcm_frame_stride & grid) || p.lpcm_frame_stride <= 0) return false;
+  for (int c = 0; c < m; ++c) {   // a pair's second channel lies sample_bytes behind its first: the pair's one run starts at the first
+    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
+      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + (s24 ? 3 : 2)) return false;
+    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
+  }
+  // a trimmed frame: every quad that starts below `total` ends inside the samples of the call
+  if (p.demix_i0 < 0 || (p.demix_i0 > 0 && p.total >= p.frame_size)) return false;
+  if (p.total < p.frame_size && (int64_t)p.demix_i0 + p.total > p.frame_size) return false;
   return true;
 }
 
@@ -400,6 +438,9 @@ enum class Family {
                 // both elements of a mix as packets of any call length that is no whole number of 64-sample blocks,
                 // RenderParams::ragged == 3, which only iamf_hip_batch_render_packets_mix_ragged sets; variant = LP2.  Set 10
                 // (kRouteSetsListed), listed by family only
+  NolimPackets,  // render_nolim_kernel<M, LPB, LPC> (iamf_render_nolim_packets*.hip): the limiter-less renderer over one
+                // element's packets, RenderParams::ragged == 4, which only iamf_hip_batch_render_packets_nolim sets; variant 0.
+                // Set 11 (kRouteSetsEvery), listed by family only
 };
 struct Route {
   Family family;
@@ -562,6 +603,21 @@ inline bool packets_mix_ragged_fused(int n_launch) {
   return true;
 }
 
+// Whether a range of n_launch streams that came through iamf_hip_batch_render_packets_nolim takes the packet-fed limiter-less
+// renderer at all (render_prepare asks), under the rule of lpcm_coupled_fused(): a (shape, size) at which it does not beat what the
+// call ran before — iamf_hip_batch_render_packets_ragged on a twin batch in the same process: iamf_hip_lpcm_unpack, then
+// render_nolim_kernel — by more than that baseline's own run-to-run spread is not fused (tools/nolim_packets_rate.py,
+// profiles/r19_nolim_packets_rate.json).
+// Measured on an MI355X, limiter off, 64 frames of 1024 per stream and step (5 steps per region, 5 regions after a discarded one): the
+// baseline takes 2.43 / 3.47 / 6.02 (3rd order, 16-bit mono-coded, into stereo f32: a rate-converting stream's first stage) and
+// 2.31 / 3.49 / 4.86 (7.1.4, 24-bit coupled, into stereo s16) times the new entry's time in one-frame calls at 512 / 2048 / 4096
+// streams, and 5.22 / 5.40 / 5.83 and 5.01 / 4.56 / 5.13 in one call of 64 frames; its spread against itself at most 0.0039 — every
+// measured (shape, size) wins, so every size is fused; this is where one that stops winning would be cut.
+inline bool nolim_packets_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
 // rules.  The environment switches are read at every call (the tests set and unset them within one process).
@@ -586,6 +642,9 @@ inline Route pick_route(const RenderParams &p, int m) {
   // both elements of a mix as packets, no whole number of 64-sample blocks (RenderParams::ragged == 3, which only
   // iamf_hip_batch_render_packets_mix_ragged sets): the same way, in front of the packet-mix rules, which refuse such a length
   if (packets_mix_ragged_shape_ok(p, m, force_generic)) return take(Family::PacketsMixRagged, p.lpcm_mix & 3);
+  // one element as packets on a limiter-less batch (RenderParams::ragged == 4, which only iamf_hip_batch_render_packets_nolim sets):
+  // the same way, in front of the packet rules, which refuse a batch without the limiter
+  if (nolim_packets_shape_ok(p, m, force_generic)) return take(Family::NolimPackets);
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
@@ -874,6 +933,28 @@ void for_each_instance_of_listed_set(int set, F &&f) {
   else for_each_instance_of_launched_set(set, f);
 }
 
+// The packet-fed limiter-less renderer (iamf_hip_route_family_instances), walking LpcmM, then LpcmCoupledM as its launchers do, the
+// 16-bit unit first; k = bytes per packet sample (m tells mono-coded from coupled: the two lists share no number).  The output
+// channel count and format are run-time values of the kernel: c = 0, as for the f32 form's rows.
+template <class F>
+void for_each_render_instance_nolim_packets(F &&f) {
+  for (int k = 2; k <= 3; ++k) {
+    const auto rows = [&](int m) { f(IAMF_HIP_ROUTE_NOLIM_PACKETS, 0, m, 0, k); };
+    for_each_int(LpcmM{}, rows);
+    for_each_int(LpcmCoupledM{}, rows);
+  }
+}
+
+// The answers of for_each_instance_of_listed_set are pinned like the others — eleven sets, "no row" for every other number — so
+// the sets added since are walked by a sixth walker: numbers kRouteSetsListed .. kRouteSetsEvery - 1, listed by family only.
+// What iamf_route.hip builds and counts by.
+constexpr int kRouteSetsEvery = 12;
+template <class F>
+void for_each_instance_of_every_set(int set, F &&f) {
+  if (set == 11) for_each_render_instance_nolim_packets(f);
+  else for_each_instance_of_listed_set(set, f);
+}
+
 // the row of the kernel launch() runs for a route, and the set that lists it: what iamf_hip_route_count takes (a FirSplit
 // call launches render_fast_kernel<2, 2> behind it as well: launch() counts that row too)
 struct RouteKey {
@@ -906,6 +987,7 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::PacketsRagged: return {IAMF_HIP_ROUTE_PACKETS_RAGGED, 0, m, p.out_ch, p.lpcm_bytes == 3 ? 3 : 2, 9};   // a family listing's row, k = sample bytes
     case Family::PacketsMixRagged:   // a family listing's row, variant = sample bytes, k = LP2
       return {IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED, p.lpcm_bytes == 3 ? 3 : 2, m, p.out_ch, r.variant, 10};
+    case Family::NolimPackets: return {IAMF_HIP_ROUTE_NOLIM_PACKETS, 0, m, 0, p.lpcm_bytes == 3 ? 3 : 2, 11};   // a family listing's row, k = sample bytes
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

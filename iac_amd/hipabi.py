@@ -113,7 +113,9 @@ ROUTE_FAMILY_MORE = dict(LPCM24_MIX=33)
 ROUTE_FAMILY_LATER = dict(PACKETS_RAGGED=37)
 # (and so is that one)
 ROUTE_FAMILY_NEWER = dict(PACKETS_MIX_RAGGED=39)
-_ROUTE_NAME_MORE = {v: k for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER) for k, v in names.items()}
+# (and that one: families added from here on go into this dict, which no caller pins)
+ROUTE_FAMILY_OPEN = dict(NOLIM_PACKETS=43)
+_ROUTE_NAME_MORE = {v: k for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER, ROUTE_FAMILY_OPEN) for k, v in names.items()}
 
 
 def _family_name(fam):
@@ -217,6 +219,7 @@ def lib():
         L.iamf_hip_batch_render_ragged.argtypes = [C.c_void_p, C.POINTER(RaggedCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets_ragged.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_packets_nolim.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets_mix.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets_mix_ragged.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
@@ -405,10 +408,10 @@ def _family_id(family):
         for names in (ROUTE, ROUTE_BY_FAMILY_ONLY):
             if family in names:
                 return names[family]
-        for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER):
+        for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER):
             if family in names:
                 return names[family]
-        return ROUTE_FAMILY_NEWER[family]
+        return ROUTE_FAMILY_OPEN[family]
     return int(family)
 
 
@@ -653,6 +656,17 @@ class Batch:
         r = lib().iamf_hip_batch_render_packets_ragged(self.h, C.byref(call), stream0, n)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_packets_ragged")
+        return r
+
+    def render_packets_nolim(self, inp, args, stream0=0, n_streams=None):
+        """iamf_hip_batch_render_packets_nolim: as render_packets_ragged, with leave to run the packet-fed limiter-less kernel on
+        a batch without the limiter; the whole batch unless a range is named"""
+        call = PacketCall()
+        call.in_, call.args = inp, args
+        n = self.cfg.n_streams - stream0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_packets_nolim(self.h, C.byref(call), stream0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_packets_nolim")
         return r
 
     def render_packets_mix(self, in0, in1, args, stream0=0, n_streams=None):

@@ -878,6 +878,30 @@ int iamf_hip_batch_render_packets_mix(iamf_hip_batch *b, const iamf_hip_packet_m
 int iamf_hip_batch_render_packets_mix_ragged(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0,
                                              int32_t n_streams);
 
+/* Element 0 as LPCM packets on a batch WITHOUT the peak limiter: the first stage of a rate-converting stream (render ->
+ * resampler -> limiter) and the whole render of a stream whose limiter is switched off.  On any batch, any packet layout and
+ * any length the call leaves the batch, d_pcm and its return value exactly as
+ *   iamf_hip_batch_render_packets_ragged(b, call, stream0, n_streams)
+ * does, bit for bit, the stream position included.
+ *   call      as for iamf_hip_batch_render_packets.
+ * One pass of the four-samples-per-lane limiter-less kernel over the packets as they lie (IAMF_HIP_ROUTE_NOLIM_PACKETS), with no
+ * f32 copy of the element, when:
+ *   - the batch has the limiter off and one matrix-rendered element: no second element, ramps, down-mixer, demixer, projection,
+ *     pre-matrix, HRTF stage, LFE generator, reduced out_gain_channels or fixed PCM channel stride;
+ *   - the packets have one of the four forms iamf_hip_batch_render_packets_ragged lists (16- or 24-bit little-endian, mono-coded
+ *     1, 4, 9 or 16 runs or the coupled 2, 6, 8, 10 or 12 channels, on the form's grid with first_sample counted in);
+ *   - frame_size and the call's samples per stream (n_frames * frame_size, or n_samples) are multiples of 4 and at least 4;
+ *     for a frame trimmed to n_samples, first_sample + n_samples <= frame_size (which every accepted call has);
+ *   - d_pcm and pcm_stream_stride_bytes are multiples of 16; out_channels * bytes per PCM sample is a multiple of 4 and at
+ *     most 60 (any of the four PCM formats, up to 15 channels of f32).
+ * The kernel reads no byte outside the samples of the call.  The weights need no rule: the samples are converted to f32 as
+ * iamf_hip_lpcm_unpack converts them and every product is the f32 path's.  Every other call — a limiter-on batch included —
+ * takes exactly the path of iamf_hip_batch_render_packets_ragged; IAMF_HIP_NOLIM_PACKETS_UNFUSED=1 forces that, and
+ * IAMF_HIP_LPCM_UNFUSED=1 the unpacker and the f32 kernels, as everywhere.
+ * Returns the sample-frames emitted per stream.  Refusals are those of iamf_hip_batch_render_packets_ragged, with their
+ * codes, before anything is queued, allocated or changed. */
+int iamf_hip_batch_render_packets_nolim(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams);
+
 /* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
  * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
  *
@@ -964,6 +988,9 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *                          (iamf_hip_route_family_instances only)
  *     PACKETS_MIX_RAGGED   both elements as packets of any call length (iamf_hip_batch_render_packets_mix_ragged): m, c, k as
  *                          LPCM_MIX; variant = bytes per packet sample (2, 3) (iamf_hip_route_family_instances only)
+ *     NOLIM_PACKETS        the limiter-less renderer over one element's packets (iamf_hip_batch_render_packets_nolim): m (1,
+ *                          4, 9, 16: mono-coded; 2, 6, 8, 10, 12: coupled), k = bytes per packet sample (2, 3); variant 0,
+ *                          c 0 (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -1003,7 +1030,8 @@ enum {
   IAMF_HIP_ROUTE_LPCM24_COUPLED = 31,    /* no table either (30 stays unused) */
   IAMF_HIP_ROUTE_LPCM24_MIX = 33,        /* no table either (32 stays unused) */
   IAMF_HIP_ROUTE_PACKETS_RAGGED = 37,    /* no table either (34, 35 and 36 stay unused) */
-  IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED = 39 /* no table either (38 stays unused) */
+  IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED = 39, /* no table either (38 stays unused) */
+  IAMF_HIP_ROUTE_NOLIM_PACKETS = 43      /* no table either (40, 41 and 42 stay unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -1036,7 +1064,7 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
  * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED, LPCM24_COUPLED,
- * LPCM24_MIX, PACKETS_RAGGED and PACKETS_MIX_RAGGED. */
+ * LPCM24_MIX, PACKETS_RAGGED, PACKETS_MIX_RAGGED and NOLIM_PACKETS. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
