@@ -1458,10 +1458,13 @@ static int build_stages(struct IAMF_Decoder *d, int resample, int aux) {
  * f32 path.)  L: the raw rows of the presentation's elements, [nel] */
 /* (a first stage — the render batch of a handle with a resampler behind it, or of one whose limiter is switched off: the batch
  * has no limiter, and ONE element's packets go to the packet-fed limiter-less renderer, iamf_hip_batch_render_packets_nolim,
- * which also reads the coupled 24-bit form; any output layout asks, because the library decides per call.  Two elements on
- * such a handle, stages in front and gain ramps keep the f32 path.)
+ * which also reads the coupled 24-bit form; any output layout asks, because the library decides per call.  Stages in front
+ * and, for one element, gain ramps keep the f32 path.  TWO elements on such a handle — the pairs the limiter-on two-element case
+ * takes, with no batch of its own for element 1 — go to iamf_hip_batch_render_packets_mix_nolim, ramps included; that reference is
+ * weak too, and a device layer without the entry keeps the f32 path for them.)
  * mix: the entry that will be asked reads the coupled 24-bit form (the two-element forms, the first stage's) */
 #pragma weak iamf_hip_batch_render_packets_mix_ragged
+#pragma weak iamf_hip_batch_render_packets_mix_nolim
 static int lp_element_fits(const struct IAMF_Decoder *d, int ei, const iamf_hip_lpcm_layout *L, int mix) {
   const Element *e = d->sel_el[ei];
   const int sb = L->sample_bytes, grid = sb == 3 ? 3 : 7;
@@ -1485,7 +1488,7 @@ static int lp_worth_asking(const struct IAMF_Decoder *d, const iamf_hip_lpcm_lay
   const int first_stage = d->rs || !d->limiter_on;
   /* (the HOA LFE generator filters what a trimmed frame cuts off as well — ftu_element_stage_args — and reads it from the f32
    * rows: such a first stage keeps them.  With the limiter on and one or two output channels there is no LFE slot to fill) */
-  const int common = first_stage ? nel == 1 && !d->cfg_sig.lfe_hoa
+  const int common = first_stage ? (nel == 1 || (nel == 2 && !d->aux && iamf_hip_batch_render_packets_mix_nolim)) && !d->cfg_sig.lfe_hoa
                                  : (nel == 1 || (nel == 2 && !d->aux && iamf_hip_batch_render_packets_mix_ragged)) && d->out_channels <= 2;
   if (!common || !d->little_endian || d->pcm_stride != d->out_channels || (d->frame_size & 3) != 0 || getenv(env_off)) return 0;
   for (int e = 0; e < nel; ++e)
@@ -1931,9 +1934,16 @@ static int render_launch(struct IAMF_Decoder *d, iamf_hip_render_args *a, int lp
       c.in[e].layout = d->lp_layout[e];
     }
     c.args = *a;
-    return iamf_hip_batch_render_packets_mix_ragged(d->batch, &c, 0, 1);
-  }
-  if (lp) {
+    if (!d->rs && d->limiter_on) return iamf_hip_batch_render_packets_mix_ragged(d->batch, &c, 0, 1);
+    if (d->rs) { /* the first stage of three: into d_mid */
+      c.args.d_pcm = d->d_mid;
+      c.args.pcm_stream_stride_bytes = (int64_t)sizeof(float) * fs * d->out_channels;
+    }
+    /* (a first stage: the entry is total — the two-element form of the limiter-less renderer where its rules hold, else exactly
+     * iamf_hip_batch_render_packets_mix_ragged; lp_worth_asking has seen it) */
+    n = iamf_hip_batch_render_packets_mix_nolim(d->batch, &c, 0, 1);
+    if (!d->rs) return n;
+  } else if (lp) {
     iamf_hip_packet_call c; /* (any number of kept samples: render_packets_any_length) */
     memset(&c, 0, sizeof(c));
     c.in.d_raw = d->h_raw[0];

@@ -923,10 +923,10 @@ static int group_run_lpcm(iamf_hip_decoder_group *g, int i, int j) {
 
 /* a two-element run's packets, both elements', straight into the render kernel (lp_worth_asking has seen the entry: no batch
  * of its own for element 1).  Element 1 takes its gain through its ramp row, constant or not, as in group_run_f32; the other two
- * stages through theirs where the round applies them so (rampu) */
+ * stages through theirs where the round applies them so (rampu).  A first stage (a resampler behind, or the limiter off:
+ * lp_worth_asking, which has seen that entry too) asks iamf_hip_batch_render_packets_mix_nolim */
 static int group_run_lpcm_mix(iamf_hip_decoder_group *g, int i, int j) {
   iamf_hip_packet_mix_call c;
-  int r;
   memset(&c, 0, sizeof(c));
   for (int e = 0; e < 2; ++e) {
     c.in[e].d_raw = g->d_raw[e];
@@ -939,14 +939,11 @@ static int group_run_lpcm_mix(iamf_hip_decoder_group *g, int i, int j) {
   if (g->rampu & 1) c.args.d_element_ramp = g->d_ramp[0];
   if (g->rampu & 4) c.args.d_output_ramp = g->d_ramp[2];
   c.args.ramp_stream_stride = g->fs;
-  c.args.d_pcm = g->h_pcm;
-  c.args.pcm_stream_stride_bytes = (int64_t)g->pcm_cap;
-  r = iamf_hip_batch_render_packets_mix_ragged(g->batch, &c, i, j - i);
-  for (int s = i; s < j && r >= 0; ++s) {
-    g->result[s] = r;
-    g->pos[s] += g->keep[s];
-  }
-  return r < 0;
+  c.args.d_pcm = g->rs ? (void *)g->d_mid : (void *)g->h_pcm;
+  c.args.pcm_stream_stride_bytes = g->rs ? (int64_t)sizeof(float) * g->mid_stride : (int64_t)g->pcm_cap;
+  /* (a first stage asks the two-element form of the limiter-less renderer, into d_mid where the resampler follows) */
+  return group_run_behind(g, i, j, g->rs || !g->limiter_on ? iamf_hip_batch_render_packets_mix_nolim(g->batch, &c, i, j - i)
+                                                           : iamf_hip_batch_render_packets_mix_ragged(g->batch, &c, i, j - i));
 }
 
 /* the run from unpacked f32: element 1 through its own batch first (stage, matrix, its gain row -> planar f32), the render

@@ -416,6 +416,9 @@ int launch(const RenderMixParams &p, int m, size_t lds_bytes, hipStream_t st) {
     case Family::NolimPackets:   // the limiter-less renderer over packets: a unit per sample size
       launched = p.lpcm_bytes == 3 ? iamf_hip_nolim_packets24_launch(&p, m, st) : iamf_hip_nolim_packets_launch(&p, m, st);
       break;
+    case Family::NolimPacketsMix:   // the same over both elements' packets
+      launched = p.lpcm_bytes == 3 ? iamf_hip_nolim_packets24_mix_launch(&p, m, r.variant, st) : iamf_hip_nolim_packets_mix_launch(&p, m, r.variant, st);
+      break;
     case Family::FirSplit: {
       const int e = launch_fir_split(p, m, grid, st);
       if (e != IAMF_HIP_OK) return e;
@@ -543,15 +546,18 @@ struct PreparedCall {
 // packet form; everything else as without.  With lp2 (iamf_hip_batch_render_packets_mix_ragged): the ragged two-element form.
 // nlp (with lp and prag, iamf_hip_batch_render_packets_nolim): the call may take the packet-fed limiter-less renderer; everything
 // else as with prag alone.
+// nlm (with lp, lp2 and prag, iamf_hip_batch_render_packets_mix_nolim): the call may take the two-element packet form of the
+// limiter-less renderer; everything else as with lp2 and prag alone.
 int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc,
-                   const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0, bool nlp = false) {
+                   const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0, bool nlp = false,
+                   bool nlm = false) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
-  // (the weights' range: the limiter-less packet form converts the samples first and needs no rule, so it asks further down)
-  if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || (!b->lp_scale_ok && !nlp) || getenv("IAMF_HIP_LPCM_UNFUSED")))
+  // (the weights' range: the limiter-less packet forms convert the samples first and need no rule, so they ask further down)
+  if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || (!b->lp_scale_ok && !nlp && !nlm) || getenv("IAMF_HIP_LPCM_UNFUSED")))
     return kNotFused;
   // a second element or ramps: the two-element packet form only, which also keeps away from a fixed PCM channel stride
   if (lp && !lp2 && (b->has2 || a.d_element_ramp || a.d_element2_ramp || a.d_output_ramp)) return kNotFused;
-  if (lp2 && (!lp || !b->has2 || !b->lp2_scale_ok ||
+  if (lp2 && (!lp || !b->has2 || (!b->lp2_scale_ok && !nlm) ||
               (b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels)))
     return kNotFused;
   // the coupled 24-bit form (iamf_hip_batch_render_packets) keeps away from a fixed PCM channel stride as well
@@ -667,14 +673,14 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     // the mark of iamf_hip_batch_render_packets_nolim, with the trimmed frame's first sample where pick_route looks for it
     // (render_route.hpp, nolim_packets_shape_ok).  The form packs into the caller's buffer itself: a fixed PCM channel stride
     // stays unfused.  Where the rule does not hold the mark is taken back, and the call is iamf_hip_batch_render_packets_ragged's
-    bool nolim_lp = false;
+    bool nolim_lp = false, nolim_mix = false;
     if (nlp && !lp2 && !(b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) && nolim_packets_fused(cnt)) {
       p.ragged = 4;
       p.demix_i0 = first;
       nolim_lp = pick_route(p, m_eff).family == Family::NolimPackets;
       if (!nolim_lp) p.ragged = 0, p.demix_i0 = 0;
     }
-    if (!nolim_lp && !b->lp_scale_ok) return kNotFused;
+    if (!nolim_lp && !(nlm && lp2) && !b->lp_scale_ok) return kNotFused;   // (nlm: asked in the lp2 block below)
     // (the size cuts of the whole-block forms say nothing about a ragged call of iamf_hip_batch_render_packets_ragged, which no
     //  whole-block form takes: the ragged packet form has its own measurement and its own cut, packets_ragged_fused below)
     const bool whole_blocks = !nolim_lp && !(prag && (total & 63));
@@ -685,7 +691,6 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       // 24-bit packets on both elements (iamf_hip_batch_render_packets_mix alone hands them over): the form's own values
       if (lp->bytes != lp2->bytes) return kNotFused;
       p.lpcm_mix = (lp->bytes == 3 ? 4 : 0) | (lp2->coupled ? 2 : 1);
-      if (whole_blocks && lp->bytes == 3 && !lpcm24_mix_fused(cnt)) return kNotFused;
       p.in2 = reinterpret_cast<const float *>(lp2->raw);
       p.in2_stream_stride = lp2->stream_stride;
       p.in2_frame_stride = lp2->frame_stride;
@@ -693,7 +698,19 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       pc.p.lpcm2_stream_stride = lp2->stream_stride;
       pc.p.lpcm2_frame_stride = lp2->frame_stride;
       for (int m = 0; m < 4; ++m) pc.p.lpcm2_off[m] = lp2->off[m];
-      if (whole_blocks && lp->bytes != 3 && !lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
+      // the mark of iamf_hip_batch_render_packets_mix_nolim, with the trimmed frame's first sample where pick_route looks for it
+      // (render_route.hpp, nolim_packets_mix_shape_ok; a fixed PCM channel stride has been sent away above).  Where the rule does
+      // not hold the mark is taken back, and the call is iamf_hip_batch_render_packets_mix_ragged's.  (The returns below change
+      // nothing: with the block filled in first they come back as they did.)
+      if (nlm && nolim_packets_mix_fused(cnt)) {
+        p.ragged = 5;
+        p.demix_i0 = first;
+        nolim_mix = pick_route(pc.p, m_eff).family == Family::NolimPacketsMix;
+        if (!nolim_mix) p.ragged = 0, p.demix_i0 = 0;
+      }
+      if (!nolim_mix && (!b->lp_scale_ok || !b->lp2_scale_ok)) return kNotFused;
+      if (!nolim_mix && whole_blocks && lp->bytes == 3 && !lpcm24_mix_fused(cnt)) return kNotFused;
+      if (!nolim_mix && whole_blocks && lp->bytes != 3 && !lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     }
     // the mark of iamf_hip_batch_render_packets_ragged, with the trimmed frame's first sample where pick_route looks for it
     // (render_route.hpp, packets_ragged_shape_ok).  The form packs into the caller's buffer itself: a fixed PCM channel stride
@@ -704,11 +721,11 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     }
     // the mark of iamf_hip_batch_render_packets_mix_ragged, the same way (packets_mix_ragged_shape_ok; a fixed PCM channel
     // stride has been sent away above, with every two-element packet call)
-    if (prag && lp2 && packets_mix_ragged_fused(cnt)) {
+    if (!nolim_mix && prag && lp2 && packets_mix_ragged_fused(cnt)) {
       p.ragged = 3;
       p.demix_i0 = first;
     }
-    if (!nolim_lp && pick_route(p, m_eff).family != lpcm_family(lp, lp2, p.ragged >= 2 && (total & 63))) return kNotFused;
+    if (!nolim_lp && !nolim_mix && pick_route(p, m_eff).family != lpcm_family(lp, lp2, p.ragged >= 2 && (total & 63))) return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -810,11 +827,12 @@ int render_finish(iamf_hip_batch *b, const PreparedCall &pc) {
   return r != IAMF_HIP_OK ? r : render_commit(b, pc);
 }
 
-// the whole call (lp, lp2, il, rag, prag, first, nlp: as render_prepare, whose kNotFused comes back before anything is changed or launched)
+// the whole call (lp, lp2, il, rag, prag, first, nlp, nlm: as render_prepare, whose kNotFused comes back before anything is changed or launched)
 int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr,
-                const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0, bool nlp = false) {
+                const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0, bool nlp = false,
+                bool nlm = false) {
   PreparedCall pc;
-  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il, rag, prag, first, nlp);
+  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il, rag, prag, first, nlp, nlm);
   return r != IAMF_HIP_OK ? r : render_finish(b, pc);
 }
 
@@ -1385,9 +1403,11 @@ int iamf_hip_batch_render_packets_nolim(iamf_hip_batch *b, const iamf_hip_packet
 // give the same PCM and leave the same stream state, bit for bit.  Every refusal comes before the first launch.
 // (packets: iamf_hip_batch_render_packets_mix — the forms are asked of lpcm_form_packets(), and 24-bit packets on both
 //  elements are a fused form as well; everything else is the one path.
-//  prag: iamf_hip_batch_render_packets_mix_ragged — the fused attempt carries its mark; everything else is the one path)
+//  prag: iamf_hip_batch_render_packets_mix_ragged — the fused attempt carries its mark; everything else is the one path.
+//  nlm: iamf_hip_batch_render_packets_mix_nolim — the fused attempt asks for the limiter-less renderer's two-element form first)
 static int render_lpcm_mix_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in0, const iamf_hip_lpcm_input *in1,
-                                const iamf_hip_render_args *args, int32_t stream0, int32_t n_streams, bool packets, bool prag = false) {
+                                const iamf_hip_render_args *args, int32_t stream0, int32_t n_streams, bool packets, bool prag = false,
+                                bool nlm = false) {
   if (!b->has2 || args->d_in || args->d_in2 || !in0->d_raw || !in1->d_raw || in0->first_sample != in1->first_sample ||
       !args->d_pcm || args->n_frames < 0)
     return IAMF_HIP_ERR_BAD_ARG;
@@ -1421,7 +1441,7 @@ static int render_lpcm_mix_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in
     LpcmIn lp0, lp1;
     lpcm_in_of(in0, ch, first, form0, lp0);
     lpcm_in_of(in1, b->m2, first, form1, lp1);
-    const int r = render_call(b, a, (int)total, stream0, n_streams, &lp0, &lp1, false, false, prag, first);
+    const int r = render_call(b, a, (int)total, stream0, n_streams, &lp0, &lp1, false, false, prag, first, false, nlm);
     if (r != kNotFused) return r;
   }
   const hipStream_t st = static_cast<hipStream_t>(args->stream);
@@ -1456,6 +1476,16 @@ int iamf_hip_batch_render_packets_mix_ragged(iamf_hip_batch *b, const iamf_hip_p
   if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
   if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
   return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, true, true);
+}
+
+// Both elements of a mix as LPCM packets on a limiter-less batch (include/iamf_hip.h): iamf_hip_batch_render_packets_mix_ragged with
+// leave to take render_nolim_kernel<M, LPB, LPC, LP2> (Family::NolimPacketsMix) where the batch is of the limiter-less kind without
+// stages in front, both elements' packets have a form the mix kernels read and render_prepare and pick_route let the call through.
+// The same checks in the same order, the same path for everything else.
+int iamf_hip_batch_render_packets_mix_nolim(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, true, true, true);
 }
 
 // Interleaved f32 of any call length (include/iamf_hip.h): iamf_hip_batch_render_range with leave to take

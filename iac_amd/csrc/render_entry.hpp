@@ -62,6 +62,10 @@ IAMF_INTERNAL int iamf_hip_fast_packets_mix_ragged24_coupled_launch(const void *
 // params->lpcm_coupled (0 / 1 with 16-bit samples, 2 with 24-bit ones).  Their launcher: render_nolim_unit.hpp
 IAMF_INTERNAL int iamf_hip_nolim_packets_launch(const void *params, int m, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_nolim_packets24_launch(const void *params, int m, hipStream_t st);
+// iamf_render_nolim_packets_mix.hip, _nolim_packets24_mix.hip: render_nolim_kernel<M, LPB, LPC, LP2>, the same renderer over both
+// elements' packets (params->ragged == 5; params a RenderMixParams); lp2 = the second element's form (LpcmMixK)
+IAMF_INTERNAL int iamf_hip_nolim_packets_mix_launch(const void *params, int m, int lp2, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_nolim_packets24_mix_launch(const void *params, int m, int lp2, hipStream_t st);
 // iamf_render_fir_m2b.hip: render_fast_kernel<M, 2, stage> / the FFT stage alone (fir_fft_kernel)
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch(const void *params, int m, int stage, hipStream_t st);
 IAMF_INTERNAL int iamf_hip_fir_m2b_launch_fft(const void *params, int m, hipStream_t st);

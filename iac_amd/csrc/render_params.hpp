@@ -118,6 +118,10 @@ struct RenderParams {
                             // 4: the call came through iamf_hip_batch_render_packets_nolim with element 0 as packets (`lpcm`) and
                             // takes render_nolim_kernel<M, LPB, LPC> (pick_route: Family::NolimPackets) — render_prepare keeps the
                             // mark only where that rule holds, and otherwise goes on as for 2; demix_i0 as for 2
+                            // 5: the call came through iamf_hip_batch_render_packets_mix_nolim with both elements as packets
+                            // (`lpcm`, `lpcm_mix`, RenderMixParams) and takes render_nolim_kernel<M, LPB, LPC, LP2> (pick_route:
+                            // Family::NolimPacketsMix) — render_prepare keeps the mark only where that rule holds, and otherwise
+                            // goes on as for 3; demix_i0 as for 2
   double lfe_div;           // sqrt(n) of h2m_rdr.c:1162; 0 = the `* 0.5` form (n <= 2)
   int32_t lfe_mask;         // bit c: output slot c is an LFE slot (src_feed[c] == -2), for render_wide4.hpp
   // ---- HRTF FIR renderer (render_fast_kernel<M, 2, true>): matrix = h[2][M][fir_taps] ----

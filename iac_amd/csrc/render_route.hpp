@@ -185,6 +185,62 @@ inline bool nolim_packets_shape_ok(const RenderParams &p, int m, bool force_gene
   return true;
 }
 
+// What the two-element packet form of the limiter-less renderer (render_nolim_kernel<M, LPB, LPC, LP2>) needs of a call that came
+// through iamf_hip_batch_render_packets_mix_nolim (RenderParams::ragged == 5, which that entry alone sets, on a RenderMixParams):
+// limiter off; no down-mixer, demixer, pre-matrix, HRTF stage, LFE generator or reduced out_gain_channels; a second element given
+// as packets — lpcm_mix names a form (LP2, or 4 | LP2 with 24-bit samples) with lpcm_mix_m2_ok, of element 0's sample size;
+// element 0's form exactly as nolim_packets_shape_ok checks it; element 1 on the same grid (8 bytes for 16-bit samples, 4 for
+// 24-bit ones): the buffer on 16 bytes, the strides, every run's start with first_sample counted in, and a pair's partner one
+// sample behind; ramps, where given, on the 16-byte grid with a stride that is a multiple of 4 (one float4 per lane); frame size
+// and the call's samples per stream multiples of 4 and at least 4; for a trimmed frame first + total <= frame_size, which holds
+// for both elements (one first_sample, in demix_i0); the PCM rules of nolim_shape_ok.  64-bit addressing: no bound on the extent.
+// IAMF_HIP_NOLIM_PACKETS_MIX_UNFUSED=1, IAMF_HIP_LPCM_UNFUSED=1 and IAMF_HIP_FORCE_GENERIC=1 send every such call down the other rules.
+inline bool nolim_packets_mix_shape_ok(const RenderMixParams &p, int m, bool force_generic) {
+  if (p.ragged != 5 || !p.lpcm || force_generic || getenv("IAMF_HIP_NOLIM_PACKETS_MIX_UNFUSED") || getenv("IAMF_HIP_LPCM_UNFUSED")) return false;
+  if (p.limiter_on || !p.in || p.og_ch < p.out_ch) return false;
+  if (p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe) return false;
+  if (p.total < 4 || (p.total & 3) || p.frame_size < 4 || (p.frame_size & 3)) return false;
+  if ((reinterpret_cast<uintptr_t>(p.lpcm) & 15) || (reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
+  if (p.out_ch < 1 || ((p.out_ch * bytes) & 3) || p.out_ch * bytes > kNlMaxFrameBytes) return false;
+  // element 0's form: 16-bit mono-coded (LpcmM), 16-bit coupled (lpcm_coupled == 1), 24-bit mono-coded, 24-bit coupled (== 2)
+  const bool s24 = p.lpcm_bytes == 3;
+  if (!s24 && p.lpcm_bytes != 2) return false;
+  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (s24 ? 2 : 1)) return false;
+  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
+  const int grid = s24 ? 3 : 7;
+  if ((p.lpcm_stream_stride & grid) || (p.lpcm_frame_stride & grid) || p.lpcm_frame_stride <= 0) return false;
+  for (int c = 0; c < m; ++c) {   // a pair's second channel lies sample_bytes behind its first: the pair's one run starts at the first
+    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
+      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + (s24 ? 3 : 2)) return false;
+    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
+  }
+  // element 1: the form lpcm_mix names, of the same sample size, where pick_route's fields and the kernel's agree
+  const int lp2 = p.lpcm_mix & 3;
+  if (p.lpcm_mix != ((s24 ? 4 : 0) | lp2) || !LpcmMixK::has(lp2)) return false;
+  if (!p.in2 || !p.lpcm2 || reinterpret_cast<const uint8_t *>(p.in2) != p.lpcm2 || !lpcm_mix_m2_ok(lp2, p.m2)) return false;
+  if (!p.matrix2 || !p.src_feed2 || !p.gains2) return false;
+  if (p.in2_stream_stride != p.lpcm2_stream_stride || p.in2_frame_stride != p.lpcm2_frame_stride) return false;
+  if ((reinterpret_cast<uintptr_t>(p.lpcm2) & 15) || (p.lpcm2_stream_stride & grid) || (p.lpcm2_frame_stride & grid) || p.lpcm2_frame_stride <= 0)
+    return false;
+  if (lp2 == 2) {
+    if (p.lpcm2_off[0] < 0 || (p.lpcm2_off[0] & grid) || p.lpcm2_off[1] != p.lpcm2_off[0] + (s24 ? 3 : 2)) return false;
+  } else {
+    for (int c = 0; c < p.m2; ++c)
+      if (p.lpcm2_off[c] < 0 || (p.lpcm2_off[c] & grid)) return false;
+  }
+  // per-sample gains: one float4 per lane
+  if (p.elem_ramp || p.elem2_ramp || p.out_ramp) {
+    if (p.ramp_stream_stride & 3) return false;
+    if ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) | reinterpret_cast<uintptr_t>(p.out_ramp)) & 15)
+      return false;
+  }
+  // a trimmed frame: every quad that starts below `total` ends inside the samples of the call, in both elements
+  if (p.demix_i0 < 0 || (p.demix_i0 > 0 && p.total >= p.frame_size)) return false;
+  if (p.total < p.frame_size && (int64_t)p.demix_i0 + p.total > p.frame_size) return false;
+  return true;
+}
+
 // which HRTF stage a FIR call runs (host): 3 = overlap-save FFT (default), 2 = split-f16 MFMA, 1 = f32 MFMA
 // 4 = the FFT stage as a kernel of its own + the two-channel matrix kernel behind it (default); IAMF_HIP_FIR_FUSED=1 keeps
 // the FFT stage inside render_fast_kernel<M, 2, 3> (one pass over HBM, but the hops of a stream run one pass after the other
@@ -441,6 +497,9 @@ enum class Family {
   NolimPackets,  // render_nolim_kernel<M, LPB, LPC> (iamf_render_nolim_packets*.hip): the limiter-less renderer over one
                 // element's packets, RenderParams::ragged == 4, which only iamf_hip_batch_render_packets_nolim sets; variant 0.
                 // Set 11 (kRouteSetsEvery), listed by family only
+  NolimPacketsMix,  // render_nolim_kernel<M, LPB, LPC, LP2> (iamf_render_nolim_packets*_mix.hip): the limiter-less renderer over both
+                // elements' packets, RenderParams::ragged == 5, which only iamf_hip_batch_render_packets_mix_nolim sets; variant =
+                // LP2.  Set 12 (kRouteSetsTotal), listed by family only
 };
 struct Route {
   Family family;
@@ -618,6 +677,21 @@ inline bool nolim_packets_fused(int n_launch) {
   return true;
 }
 
+// Whether a range of n_launch streams that came through iamf_hip_batch_render_packets_mix_nolim takes the two-element packet form of
+// the limiter-less renderer at all (render_prepare asks), under the rule of lpcm_coupled_fused(): a (shape, size) at which it does
+// not beat what the call ran before — iamf_hip_batch_render_packets_mix_ragged on a twin batch in the same process: two
+// iamf_hip_lpcm_unpack passes, then the general kernel — by more than that baseline's own run-to-run spread is not fused
+// (tools/nolim_packets_mix_rate.py, profiles/r20_nolim_packets_mix_rate.json).
+// Measured on an MI355X, limiter off, 64 frames of 1024 per stream and step (5 steps per region, 5 regions after a discarded one): the
+// baseline takes 3.98 / 4.38 / 6.04 (3rd-order bed + coupled stereo, 16 bit, into stereo f32: a rate-converting stream's first stage)
+// and 3.36 / 3.65 / 5.24 (7.1.4 coupled + mono, 24 bit, into stereo s16) times the new entry's time in one-frame calls at 512 / 2048 /
+// 4096 streams, and 7.25 / 5.89 / 5.78 and 6.23 / 5.23 / 5.21 in one call of 64 frames; its spread against itself at most 0.0040 — every
+// measured (shape, size) wins, so every size is fused and nothing is cut; this is where one that stops winning would be.
+inline bool nolim_packets_mix_fused(int n_launch) {
+  (void)n_launch;
+  return true;
+}
+
 // Which kernel launch() runs for p with m inputs.  The rules in priority order: the first that holds decides.  Every
 // kernel is exact, so a call that misses its rule still renders right, only slower: tests/test_route_host.py pins the
 // rules.  The environment switches are read at every call (the tests set and unset them within one process).
@@ -645,6 +719,8 @@ inline Route pick_route(const RenderParams &p, int m) {
   // one element as packets on a limiter-less batch (RenderParams::ragged == 4, which only iamf_hip_batch_render_packets_nolim sets):
   // the same way, in front of the packet rules, which refuse a batch without the limiter
   if (nolim_packets_shape_ok(p, m, force_generic)) return take(Family::NolimPackets);
+  // (both elements as packets on such a batch, RenderParams::ragged == 5: the rule reads the second element's run starts, which
+  //  travel behind this block — pick_route(const RenderMixParams &) below asks it, here, in front of the packet rules)
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
@@ -955,6 +1031,37 @@ void for_each_instance_of_every_set(int set, F &&f) {
   else for_each_instance_of_listed_set(set, f);
 }
 
+// The same for the block launch() holds: both elements as packets on a limiter-less batch (RenderParams::ragged == 5, which only
+// iamf_hip_batch_render_packets_mix_nolim sets) take the two-element form of the limiter-less renderer where
+// nolim_packets_mix_shape_ok holds — the marks exclude one another, so its place among the marked rules above does not matter —
+// and every other block is routed by the rules above, the mark meaning nothing to them.
+inline Route pick_route(const RenderMixParams &p, int m) {
+  if (nolim_packets_mix_shape_ok(p, m, getenv("IAMF_HIP_FORCE_GENERIC") != nullptr)) return Route{Family::NolimPacketsMix, p.lpcm_mix & 3, IAMF_HIP_OK};
+  return pick_route(static_cast<const RenderParams &>(p), m);
+}
+
+// The two-element packet form of the limiter-less renderer (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x
+// LpcmMixK as its launchers do, the 16-bit unit first; variant = bytes per packet sample, k = LP2, c = 0 (the output channel count
+// and format are run-time values of the kernel).
+template <class F>
+void for_each_render_instance_nolim_packets_mix(F &&f) {
+  for (int v = 2; v <= 3; ++v) {
+    const auto rows = [&](int m) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX, v, m, 0, k); }); };
+    for_each_int(LpcmM{}, rows);
+    for_each_int(LpcmCoupledM{}, rows);
+  }
+}
+
+// The answers of for_each_instance_of_every_set are pinned like the others — twelve sets, "no row" for every other number — so
+// the sets added since are walked by a seventh walker: numbers kRouteSetsEvery .. kRouteSetsTotal - 1, listed by family only.
+// What iamf_route.hip builds and counts by.
+constexpr int kRouteSetsTotal = 13;
+template <class F>
+void for_each_instance_of_total_set(int set, F &&f) {
+  if (set == 12) for_each_render_instance_nolim_packets_mix(f);
+  else for_each_instance_of_every_set(set, f);
+}
+
 // the row of the kernel launch() runs for a route, and the set that lists it: what iamf_hip_route_count takes (a FirSplit
 // call launches render_fast_kernel<2, 2> behind it as well: launch() counts that row too)
 struct RouteKey {
@@ -988,6 +1095,8 @@ inline RouteKey route_key(const Route &r, const RenderParams &p, int m) {
     case Family::PacketsMixRagged:   // a family listing's row, variant = sample bytes, k = LP2
       return {IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED, p.lpcm_bytes == 3 ? 3 : 2, m, p.out_ch, r.variant, 10};
     case Family::NolimPackets: return {IAMF_HIP_ROUTE_NOLIM_PACKETS, 0, m, 0, p.lpcm_bytes == 3 ? 3 : 2, 11};   // a family listing's row, k = sample bytes
+    case Family::NolimPacketsMix:   // a family listing's row, variant = sample bytes, k = LP2
+      return {IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX, p.lpcm_bytes == 3 ? 3 : 2, m, 0, r.variant, 12};
   }
   return {IAMF_HIP_ROUTE_NONE, 0, 0, 0, 0};
 }

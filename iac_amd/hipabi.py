@@ -114,7 +114,7 @@ ROUTE_FAMILY_LATER = dict(PACKETS_RAGGED=37)
 # (and so is that one)
 ROUTE_FAMILY_NEWER = dict(PACKETS_MIX_RAGGED=39)
 # (and that one: families added from here on go into this dict, which no caller pins)
-ROUTE_FAMILY_OPEN = dict(NOLIM_PACKETS=43)
+ROUTE_FAMILY_OPEN = dict(NOLIM_PACKETS=43, NOLIM_PACKETS_MIX=47)
 _ROUTE_NAME_MORE = {v: k for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER, ROUTE_FAMILY_OPEN) for k, v in names.items()}
 
 
@@ -222,6 +222,7 @@ def lib():
         L.iamf_hip_batch_render_packets_nolim.argtypes = [C.c_void_p, C.POINTER(PacketCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets_mix.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_render_packets_mix_ragged.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
+        L.iamf_hip_batch_render_packets_mix_nolim.argtypes = [C.c_void_p, C.POINTER(PacketMixCall), C.c_int32, C.c_int32]
         L.iamf_hip_batch_set_second_element.argtypes = [C.c_void_p, C.POINTER(Matrix), FP]
         L.iamf_hip_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.iamf_hip_resampler_destroy.argtypes = [C.c_void_p]
@@ -689,6 +690,17 @@ class Batch:
         r = lib().iamf_hip_batch_render_packets_mix_ragged(self.h, C.byref(call), stream0, n)
         if r < 0:
             raise IamfHipError(r, "iamf_hip_batch_render_packets_mix_ragged")
+        return r
+
+    def render_packets_mix_nolim(self, in0, in1, args, stream0=0, n_streams=None):
+        """iamf_hip_batch_render_packets_mix_nolim: as render_packets_mix_ragged, with leave to run the two-element packet form of
+        the limiter-less kernel on a batch without the limiter; the whole batch unless a range is named"""
+        call = PacketMixCall()
+        call.in_[0], call.in_[1], call.args = in0, in1, args
+        n = self.cfg.n_streams - stream0 if n_streams is None else n_streams
+        r = lib().iamf_hip_batch_render_packets_mix_nolim(self.h, C.byref(call), stream0, n)
+        if r < 0:
+            raise IamfHipError(r, "iamf_hip_batch_render_packets_mix_nolim")
         return r
 
     def render_range(self, args, stream0, n_streams):

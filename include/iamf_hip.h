@@ -902,6 +902,34 @@ int iamf_hip_batch_render_packets_mix_ragged(iamf_hip_batch *b, const iamf_hip_p
  * codes, before anything is queued, allocated or changed. */
 int iamf_hip_batch_render_packets_nolim(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams);
 
+/* Both elements of a mix as LPCM packets on a batch WITHOUT the peak limiter: a bed plus dialogue or commentary as the first
+ * stage of a rate-converting stream, or as the whole render of a stream whose limiter is switched off.  On any batch, any pair
+ * of packet layouts and any length the call leaves the batch, d_pcm and its return value exactly as
+ *   iamf_hip_batch_render_packets_mix_ragged(b, call, stream0, n_streams)
+ * does, bit for bit, the stream position included.
+ *   call      as for iamf_hip_batch_render_packets_mix.
+ * One pass of the four-samples-per-lane limiter-less kernel over both elements' packets as they lie
+ * (IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX), with no f32 copy of either element, when:
+ *   - the batch has the limiter off and a second element, and no down-mixer, demixer, projection, pre-matrix, HRTF stage, LFE
+ *     generator, reduced out_gain_channels or fixed PCM channel stride;
+ *   - both elements hold little-endian samples of one size, 16 or 24 bit: element 0 in one of the four forms
+ *     iamf_hip_batch_render_packets_nolim lists, element 1 as 1 or 4 mono-coded runs or as ONE coupled stereo pair, each on its
+ *     form's grid (8 bytes for 16-bit samples, 4 for 24-bit ones) with first_sample counted in, in[1].d_raw a multiple of 16;
+ *   - d_element_ramp, d_element2_ramp and d_output_ramp, where given, are multiples of 16 and ramp_stream_stride is a
+ *     multiple of 4 (any of the three, or none);
+ *   - frame_size and the call's samples per stream (n_frames * frame_size, or n_samples) are multiples of 4 and at least 4;
+ *     for a frame trimmed to n_samples, first_sample + n_samples <= frame_size (which every accepted call has);
+ *   - d_pcm and pcm_stream_stride_bytes are multiples of 16; out_channels * bytes per PCM sample is a multiple of 4 and at
+ *     most 60 (any of the four PCM formats, up to 15 channels of f32).
+ * The kernel reads no byte outside the samples of the call, and no float of a ramp behind the call's last sample.  The weights
+ * need no rule: the samples are converted to f32 as iamf_hip_lpcm_unpack converts them and every product is the f32 path's.
+ * Every other call — a limiter-on batch, 16-bit packets beside 24-bit ones, big-endian samples, a stereo second element held
+ * as two mono runs, a trim that is no multiple of 4 — takes exactly the path of iamf_hip_batch_render_packets_mix_ragged;
+ * IAMF_HIP_NOLIM_PACKETS_MIX_UNFUSED=1 forces that, and IAMF_HIP_LPCM_UNFUSED=1 the unpacker and the f32 kernels, as everywhere.
+ * Returns the sample-frames emitted per stream.  Refusals are those of iamf_hip_batch_render_packets_mix_ragged, with their
+ * codes, before anything is queued, allocated or changed. */
+int iamf_hip_batch_render_packets_mix_nolim(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams);
+
 /* One element, held as LPCM packets, rendered into several batches with ONE pass over the packets where that is possible:
  * iamf_hip_batch_render_fanout for the input form of iamf_hip_batch_render_lpcm, over a range of streams.
  *
@@ -991,6 +1019,9 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *     NOLIM_PACKETS        the limiter-less renderer over one element's packets (iamf_hip_batch_render_packets_nolim): m (1,
  *                          4, 9, 16: mono-coded; 2, 6, 8, 10, 12: coupled), k = bytes per packet sample (2, 3); variant 0,
  *                          c 0 (iamf_hip_route_family_instances only)
+ *     NOLIM_PACKETS_MIX    the limiter-less renderer over both elements' packets (iamf_hip_batch_render_packets_mix_nolim): m as
+ *                          NOLIM_PACKETS, variant = bytes per packet sample (2, 3), k = the second element's form (1: mono-
+ *                          coded runs, 2: one coupled pair); c 0 (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
@@ -1031,7 +1062,8 @@ enum {
   IAMF_HIP_ROUTE_LPCM24_MIX = 33,        /* no table either (32 stays unused) */
   IAMF_HIP_ROUTE_PACKETS_RAGGED = 37,    /* no table either (34, 35 and 36 stay unused) */
   IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED = 39, /* no table either (38 stays unused) */
-  IAMF_HIP_ROUTE_NOLIM_PACKETS = 43      /* no table either (40, 41 and 42 stay unused) */
+  IAMF_HIP_ROUTE_NOLIM_PACKETS = 43,     /* no table either (40, 41 and 42 stay unused) */
+  IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX = 47  /* no table either (44, 45 and 46 stay unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -1064,7 +1096,7 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
  * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED, LPCM24_COUPLED,
- * LPCM24_MIX, PACKETS_RAGGED, PACKETS_MIX_RAGGED and NOLIM_PACKETS. */
+ * LPCM24_MIX, PACKETS_RAGGED, PACKETS_MIX_RAGGED, NOLIM_PACKETS and NOLIM_PACKETS_MIX. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
