@@ -479,12 +479,24 @@ struct LpcmIn {
   int32_t coupled; // 1: LpcmForm::S16C, off[] of a pair's two channels 2 bytes apart; 2: LpcmForm::S24C, 3 bytes apart
 };
 constexpr int kNotFused = INT32_MIN;
+// Which entry a call came through: what that entry's own kernel form may take, everything else as without.  Ordered — each
+// packet form may take what the one in front of it takes: a limiter-less packet call is a ragged packet call is a packet call.
+// Whether the call is a mix is a matter of a second element's packets being there (lp2), not of the form.
+enum class CallForm {
+  Plain,           // iamf_hip_batch_render_range and every entry on top of it
+  Interleaved,     // iamf_hip_batch_render_interleaved: the interleaved form of the fast kernel
+  Ragged,          // iamf_hip_batch_render_ragged: the planar ragged form
+  Lpcm,            // iamf_hip_batch_render_lpcm_range, _lpcm_mix: the forms lpcm_form() names
+  Packets,         // iamf_hip_batch_render_packets, _packets_mix: the forms lpcm_form_packets() names (24-bit coupled, 24-bit mix)
+  PacketsRagged,   // iamf_hip_batch_render_packets_ragged, _packets_mix_ragged: and the ragged packet forms (kCallPacketsRagged,
+                   // kCallPacketsMixRagged)
+  PacketsNolim,    // iamf_hip_batch_render_packets_nolim, _packets_mix_nolim: and, first, the packet-fed limiter-less renderer
+                   // (kCallPacketsNolim, kCallPacketsMixNolim)
+};
 // the family a packet call must route to for a fused kernel to read its packets (lp2: the second element's, or null;
-// prag: the call carries the mark of iamf_hip_batch_render_packets_ragged — RenderParams::ragged == 2 — and is no whole number
-// of 64-sample blocks, which only the ragged packet form takes; with lp2, the mark of iamf_hip_batch_render_packets_mix_ragged —
-// ragged == 3 — and the ragged two-element form)
-Family lpcm_family(const LpcmIn *lp, const LpcmIn *lp2, bool prag = false) {
-  if (prag) return lp2 ? Family::PacketsMixRagged : Family::PacketsRagged;
+// ragged: the call carries the mark of a ragged packet form and is no whole number of 64-sample blocks, which only that form takes)
+Family lpcm_family(const LpcmIn *lp, const LpcmIn *lp2, bool ragged) {
+  if (ragged) return lp2 ? Family::PacketsMixRagged : Family::PacketsRagged;
   if (lp2) return lp->bytes == 3 ? Family::Lpcm24Mix : Family::LpcmMix;   // (24-bit: iamf_hip_batch_render_packets_mix only)
   if (lp->coupled == 2) return Family::Lpcm24Coupled;
   if (lp->coupled) return Family::LpcmCoupled;
@@ -539,29 +551,24 @@ struct PreparedCall {
   int total, s0, cnt;
 };
 
-// lp2 (with lp, iamf_hip_batch_render_lpcm_mix): the second element as packets too; a.d_in2 is then a non-null placeholder.
-// il (iamf_hip_batch_render_interleaved): the call may take the interleaved form of the fast kernel; everything else as without.
-// rag (iamf_hip_batch_render_ragged): the call may take the planar ragged form; everything else as without.
-// prag (with lp, iamf_hip_batch_render_packets_ragged; first: iamf_hip_lpcm_input::first_sample): the call may take the ragged
-// packet form; everything else as without.  With lp2 (iamf_hip_batch_render_packets_mix_ragged): the ragged two-element form.
-// nlp (with lp and prag, iamf_hip_batch_render_packets_nolim): the call may take the packet-fed limiter-less renderer; everything
-// else as with prag alone.
-// nlm (with lp, lp2 and prag, iamf_hip_batch_render_packets_mix_nolim): the call may take the two-element packet form of the
-// limiter-less renderer; everything else as with lp2 and prag alone.
-int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, PreparedCall &pc,
-                   const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0, bool nlp = false,
-                   bool nlm = false) {
+// lp: element 0 as packets of a fusable form, or null; lp2 (with lp): the second element as packets too, a.d_in2 then being a
+// non-null placeholder.  form: the entry the call came through (CallForm); first: iamf_hip_lpcm_input::first_sample of a packet call.
+// kNotFused comes back before anything is changed or launched.
+int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, const LpcmIn *lp2,
+                   CallForm form, int first, PreparedCall &pc) {
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
+  const bool nolim = form == CallForm::PacketsNolim;
+  // a fixed PCM channel stride: the call packs into scratch and is re-laid behind the kernel
+  const int sc = b->cfg.pcm_stride_channels;
+  const bool restride = sc > 0 && sc != b->cfg.out_channels;
   // (the weights' range: the limiter-less packet forms convert the samples first and need no rule, so they ask further down)
-  if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || (!b->lp_scale_ok && !nlp && !nlm) || getenv("IAMF_HIP_LPCM_UNFUSED")))
+  if (lp && (b->fir || b->lfe || b->d_pre || b->demix || b->dmx || (!b->lp_scale_ok && !nolim) || getenv("IAMF_HIP_LPCM_UNFUSED")))
     return kNotFused;
   // a second element or ramps: the two-element packet form only, which also keeps away from a fixed PCM channel stride
   if (lp && !lp2 && (b->has2 || a.d_element_ramp || a.d_element2_ramp || a.d_output_ramp)) return kNotFused;
-  if (lp2 && (!lp || !b->has2 || (!b->lp2_scale_ok && !nlm) ||
-              (b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels)))
-    return kNotFused;
+  if (lp2 && (!lp || !b->has2 || (!b->lp2_scale_ok && !nolim) || restride)) return kNotFused;
   // the coupled 24-bit form (iamf_hip_batch_render_packets) keeps away from a fixed PCM channel stride as well
-  if (lp && lp->coupled == 2 && b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) return kNotFused;
+  if (lp && lp->coupled == 2 && restride) return kNotFused;
   if (!range_ok(b, s0, cnt)) return IAMF_HIP_ERR_BAD_ARG;
   if (a.lfe_pre_samples < 0 || a.lfe_post_samples < 0 ||
       ((a.lfe_pre_samples || a.lfe_post_samples) &&
@@ -670,23 +677,6 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     for (int m = 0; m < 16; ++m) p.lpcm_off[m] = lp->off[m];
     p.lpcm_bytes = lp->bytes;
     p.lpcm_coupled = lp->coupled;
-    // the mark of iamf_hip_batch_render_packets_nolim, with the trimmed frame's first sample where pick_route looks for it
-    // (render_route.hpp, nolim_packets_shape_ok).  The form packs into the caller's buffer itself: a fixed PCM channel stride
-    // stays unfused.  Where the rule does not hold the mark is taken back, and the call is iamf_hip_batch_render_packets_ragged's
-    bool nolim_lp = false, nolim_mix = false;
-    if (nlp && !lp2 && !(b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) && nolim_packets_fused(cnt)) {
-      p.ragged = 4;
-      p.demix_i0 = first;
-      nolim_lp = pick_route(p, m_eff).family == Family::NolimPackets;
-      if (!nolim_lp) p.ragged = 0, p.demix_i0 = 0;
-    }
-    if (!nolim_lp && !(nlm && lp2) && !b->lp_scale_ok) return kNotFused;   // (nlm: asked in the lp2 block below)
-    // (the size cuts of the whole-block forms say nothing about a ragged call of iamf_hip_batch_render_packets_ragged, which no
-    //  whole-block form takes: the ragged packet form has its own measurement and its own cut, packets_ragged_fused below)
-    const bool whole_blocks = !nolim_lp && !(prag && (total & 63));
-    if (whole_blocks && lp->bytes == 3 && !lp->coupled && !lp2 && !lpcm24_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
-    if (whole_blocks && lp->coupled == 1 && !lp2 && !lpcm_coupled_fused(cnt)) return kNotFused;
-    if (whole_blocks && lp->coupled == 2 && !lp2 && !lpcm24_coupled_fused(cnt)) return kNotFused;
     if (lp2) {   // the kernel reads RenderMixParams; pick_route the packets' place in the in2 fields (strides in bytes)
       // 24-bit packets on both elements (iamf_hip_batch_render_packets_mix alone hands them over): the form's own values
       if (lp->bytes != lp2->bytes) return kNotFused;
@@ -698,34 +688,35 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
       pc.p.lpcm2_stream_stride = lp2->stream_stride;
       pc.p.lpcm2_frame_stride = lp2->frame_stride;
       for (int m = 0; m < 4; ++m) pc.p.lpcm2_off[m] = lp2->off[m];
-      // the mark of iamf_hip_batch_render_packets_mix_nolim, with the trimmed frame's first sample where pick_route looks for it
-      // (render_route.hpp, nolim_packets_mix_shape_ok; a fixed PCM channel stride has been sent away above).  Where the rule does
-      // not hold the mark is taken back, and the call is iamf_hip_batch_render_packets_mix_ragged's.  (The returns below change
-      // nothing: with the block filled in first they come back as they did.)
-      if (nlm && nolim_packets_mix_fused(cnt)) {
-        p.ragged = 5;
-        p.demix_i0 = first;
-        nolim_mix = pick_route(pc.p, m_eff).family == Family::NolimPacketsMix;
-        if (!nolim_mix) p.ragged = 0, p.demix_i0 = 0;
-      }
-      if (!nolim_mix && (!b->lp_scale_ok || !b->lp2_scale_ok)) return kNotFused;
-      if (!nolim_mix && whole_blocks && lp->bytes == 3 && !lpcm24_mix_fused(cnt)) return kNotFused;
-      if (!nolim_mix && whole_blocks && lp->bytes != 3 && !lpcm_mix_fused(cnt)) return kNotFused;   // a size at which the fused form measured no faster
     }
-    // the mark of iamf_hip_batch_render_packets_ragged, with the trimmed frame's first sample where pick_route looks for it
-    // (render_route.hpp, packets_ragged_shape_ok).  The form packs into the caller's buffer itself: a fixed PCM channel stride
-    // stays unfused, as for the coupled 24-bit form
-    if (!nolim_lp && prag && !lp2 && !(b->cfg.pcm_stride_channels > 0 && b->cfg.pcm_stride_channels != b->cfg.out_channels) && packets_ragged_fused(cnt)) {
-      p.ragged = 2;
+    // The call's mark (render_params.hpp, CallMark), decided once: the limiter-less form's where the entry asks for it and its rule
+    // holds (nolim_packets_shape_ok, nolim_packets_mix_shape_ok: asked of a copy that carries the mark), else the ragged form's
+    // where the entry asks for it, else none.  These forms pack into the caller's buffer themselves: a fixed PCM channel stride
+    // stays unfused.  Each has its own measurement and its own size cut.
+    int32_t mark = kCallPlain;
+    if (nolim && !restride && (lp2 ? nolim_packets_mix_fused(cnt) : nolim_packets_fused(cnt))) {
+      RenderMixParams q = pc.p;
+      q.ragged = lp2 ? kCallPacketsMixNolim : kCallPacketsNolim;
+      q.demix_i0 = first;
+      if (pick_route(q, m_eff).family == (lp2 ? Family::NolimPacketsMix : Family::NolimPackets)) mark = q.ragged;
+    }
+    const bool nolim_taken = mark != kCallPlain;
+    if (!nolim_taken && (!b->lp_scale_ok || (lp2 && !b->lp2_scale_ok))) return kNotFused;
+    // (the size cuts of the whole-block forms say nothing about a ragged call of a ragged packet entry, which no whole-block form
+    //  takes, nor about a call the limiter-less renderer takes)
+    if (!nolim_taken && !(form >= CallForm::PacketsRagged && (total & 63))) {   // a size at which the fused form measured no faster
+      if (!lp2 && lp->bytes == 3 && !lp->coupled && !lpcm24_fused(cnt)) return kNotFused;
+      if (!lp2 && lp->coupled == 1 && !lpcm_coupled_fused(cnt)) return kNotFused;
+      if (!lp2 && lp->coupled == 2 && !lpcm24_coupled_fused(cnt)) return kNotFused;
+      if (lp2 && !(lp->bytes == 3 ? lpcm24_mix_fused(cnt) : lpcm_mix_fused(cnt))) return kNotFused;
+    }
+    if (!nolim_taken && form >= CallForm::PacketsRagged && !restride && (lp2 ? packets_mix_ragged_fused(cnt) : packets_ragged_fused(cnt)))
+      mark = lp2 ? kCallPacketsMixRagged : kCallPacketsRagged;
+    if (mark != kCallPlain) {   // with the trimmed frame's first sample where the marked rules look for it (call_first_sample)
+      p.ragged = mark;
       p.demix_i0 = first;
     }
-    // the mark of iamf_hip_batch_render_packets_mix_ragged, the same way (packets_mix_ragged_shape_ok; a fixed PCM channel
-    // stride has been sent away above, with every two-element packet call)
-    if (!nolim_mix && prag && lp2 && packets_mix_ragged_fused(cnt)) {
-      p.ragged = 3;
-      p.demix_i0 = first;
-    }
-    if (!nolim_lp && !nolim_mix && pick_route(p, m_eff).family != lpcm_family(lp, lp2, p.ragged >= 2 && (total & 63))) return kNotFused;
+    if (!nolim_taken && pick_route(p, m_eff).family != lpcm_family(lp, lp2, mark != kCallPlain && (total & 63))) return kNotFused;
   }
   if (b->fir) {
     p.fir_taps = b->fir_taps;
@@ -765,8 +756,6 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
   }
   const size_t lds = sizeof(float) * ((size_t)(p.out_ch + 2) * kRing + 3 * kChunk + kHead + 4 +
                                       ((b->dmx || b->demix) ? (size_t)kChCount * kChunk : 0));
-  const int sc = b->cfg.pcm_stride_channels;
-  const bool restride = sc > 0 && sc != p.out_ch;
   const int bps = iamf_hip_format_bytes(p.out_format);
   if (restride) {  // pack naturally into scratch, then re-lay with the fixed channel stride
     const size_t per_stream = (size_t)(total > kDelay ? total : kDelay) * p.out_ch * bps;
@@ -776,9 +765,9 @@ int render_prepare(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, 
     p.pcm_stream_stride = (int64_t)per_stream;
   }
   // the interleaved form packs into the caller's buffer itself and knows no LFE slot; pick_route has the call's other rules
-  p.interleaved = (il && !restride && !b->lfe && interleaved_fused(cnt)) ? 1 : 0;
+  p.interleaved = (form == CallForm::Interleaved && !restride && !b->lfe && interleaved_fused(cnt)) ? 1 : 0;
   // so does the planar ragged form (an LFE slot: pick_route sees p.lfe)
-  if (p.ragged < 2) p.ragged = (rag && !restride && ragged_fused(cnt)) ? 1 : 0;
+  if (form == CallForm::Ragged && !restride && ragged_fused(cnt)) p.ragged = kCallRagged;
   pc.a = a;
   pc.m_eff = m_eff;
   pc.lds = lds;
@@ -827,13 +816,20 @@ int render_finish(iamf_hip_batch *b, const PreparedCall &pc) {
   return r != IAMF_HIP_OK ? r : render_commit(b, pc);
 }
 
-// the whole call (lp, lp2, il, rag, prag, first, nlp, nlm: as render_prepare, whose kNotFused comes back before anything is changed or launched)
-int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp = nullptr,
-                const LpcmIn *lp2 = nullptr, bool il = false, bool rag = false, bool prag = false, int first = 0, bool nlp = false,
-                bool nlm = false) {
+// the whole call (lp, lp2, form, first: as render_prepare, whose kNotFused comes back before anything is changed or launched)
+int render_call(iamf_hip_batch *b, const iamf_hip_render_args &a, int total, int s0, int cnt, const LpcmIn *lp, const LpcmIn *lp2,
+                CallForm form, int first) {
   PreparedCall pc;
-  const int r = render_prepare(b, a, total, s0, cnt, lp, pc, lp2, il, rag, prag, first, nlp, nlm);
+  const int r = render_prepare(b, a, total, s0, cnt, lp, lp2, form, first, pc);
   return r != IAMF_HIP_OK ? r : render_finish(b, pc);
+}
+
+// What the six packet entries (iamf_hip_packet_call, iamf_hip_packet_mix_call) ask of their call block in front of everything else:
+// the reserved words zero, and no f32 input beside the packets
+template <class Call>
+bool packet_call_ok(const iamf_hip_batch *b, const Call *call) {
+  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return false;
+  return !call->args.d_in && !call->args.d_in2;
 }
 
 // feed-major copy of a renderer matrix and its output-slot map (h2m_rdr.c:1114-1150 keeps the
@@ -1218,17 +1214,17 @@ static int range_args_check(const iamf_hip_batch *b, const iamf_hip_render_args 
   return IAMF_HIP_OK;
 }
 
-// (prag, first, nlp: as render_prepare — iamf_hip_batch_render_packets_ragged, iamf_hip_batch_render_packets_nolim)
+// a range call of one element: the argument checks, then the call (lp, form, first: as render_prepare)
 static int render_range_impl(iamf_hip_batch *b, const iamf_hip_render_args *a, int32_t stream0, int32_t n_streams, const LpcmIn *lp,
-                             bool prag = false, int first = 0, bool nlp = false) {
+                             CallForm form, int first) {
   int64_t total = 0;
   const int rc = range_args_check(b, a, stream0, n_streams, &total);
   if (rc != IAMF_HIP_OK || total == 0) return rc;
-  return render_call(b, *a, (int)total, stream0, n_streams, lp, nullptr, false, false, prag, first, nlp);
+  return render_call(b, *a, (int)total, stream0, n_streams, lp, nullptr, form, first);
 }
 
 int iamf_hip_batch_render_range(iamf_hip_batch *b, const iamf_hip_render_args *a, int32_t stream0, int32_t n_streams) {
-  return render_range_impl(b, a, stream0, n_streams, nullptr);
+  return render_range_impl(b, a, stream0, n_streams, nullptr, CallForm::Plain, 0);
 }
 
 // Element 0 as LPCM packets.  Fused (render_fast_kernel<.., LP>: the packets' samples are converted where the render
@@ -1249,7 +1245,7 @@ int iamf_hip_batch_render_lpcm(iamf_hip_batch *b, const iamf_hip_lpcm_input *in,
 // (ch: the channels of the element the packets hold — element 0's, or the second element's for iamf_hip_batch_render_lpcm_mix;
 //  packets: the call came through iamf_hip_batch_render_packets or _packets_mix, which also take LpcmForm::S24C)
 static int lpcm_form_check_ch(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int ch, int nf, int n_samples, LpcmForm *form_out,
-                              int *first_out, int *count_out, bool packets = false) {
+                              int *first_out, int *count_out, bool packets) {
   const iamf_hip_lpcm_layout &L = in->layout;
   const int fs = b->cfg.frame_size;
   if (L.sample_bytes < 2 || L.sample_bytes > 4 || L.channels != ch || ch > IAMF_HIP_LPCM_MAX_CHANNELS || L.frame_size != fs ||
@@ -1272,7 +1268,7 @@ static int lpcm_form_check_ch(const iamf_hip_batch *b, const iamf_hip_lpcm_input
 }
 
 static int lpcm_form_check(const iamf_hip_batch *b, const iamf_hip_lpcm_input *in, int nf, int n_samples, LpcmForm *form_out,
-                           int *first_out, int *count_out, bool packets = false) {
+                           int *first_out, int *count_out, bool packets) {
   return lpcm_form_check_ch(b, in, element_channels(b), nf, n_samples, form_out, first_out, count_out, packets);
 }
 
@@ -1325,11 +1321,10 @@ static int lpcm_unpack_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, i
   return IAMF_HIP_OK;
 }
 
-// (packets: iamf_hip_batch_render_packets — the form is asked of lpcm_form_packets(); everything else is the one path.
-//  prag: iamf_hip_batch_render_packets_ragged — the fused attempt carries its mark; everything else is the one path.
-//  nlp: iamf_hip_batch_render_packets_nolim — the fused attempt asks for the packet-fed limiter-less renderer first)
+// (form, CallForm::Lpcm and on: from Packets on the form is asked of lpcm_form_packets(), and the fused attempt carries what the
+//  entry may take; everything else is the one path)
 static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
-                                  int32_t stream0, int32_t n_streams, bool packets, bool prag = false, bool nlp = false) {
+                                  int32_t stream0, int32_t n_streams, CallForm call_form) {
   if (!b || !in || !args || !in->d_raw || args->d_in || !args->d_pcm || args->n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
   if (!range_ok(b, stream0, n_streams)) return IAMF_HIP_ERR_BAD_ARG;
   if (!on_batch_device(b)) return IAMF_HIP_ERR_INVALID_STATE;
@@ -1337,7 +1332,7 @@ static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *
   const int ch = element_channels(b), nf = args->n_frames;
   LpcmForm form = LpcmForm::None;
   int first = 0, count = 0;
-  const int fc = lpcm_form_check(b, in, nf, args->n_samples, &form, &first, &count, packets);
+  const int fc = lpcm_form_check(b, in, nf, args->n_samples, &form, &first, &count, call_form >= CallForm::Packets);
   if (fc != IAMF_HIP_OK) return fc;
   iamf_hip_render_args a = *args;
   if (form != LpcmForm::None) {
@@ -1345,7 +1340,7 @@ static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *
     lpcm_in_of(in, ch, first, form, lp);
     a.d_in = reinterpret_cast<const float *>(in->d_raw);   // not read by the fused kernel; non-null = "not a flush"
     a.in_stream_stride = a.in_frame_stride = 0;
-    const int r = render_range_impl(b, &a, stream0, n_streams, &lp, prag, first, nlp);
+    const int r = render_range_impl(b, &a, stream0, n_streams, &lp, call_form, first);
     if (r != kNotFused) return r;
   }
   // Unfused: unpack, then the f32 path.  Everything the render call would refuse is refused here first, so that no unpack
@@ -1358,12 +1353,12 @@ static int render_lpcm_range_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *
   }
   const int ur = lpcm_unpack_range(b, in, nf, first, count, stream0, n_streams, static_cast<hipStream_t>(args->stream), a);
   if (ur != IAMF_HIP_OK) return ur;
-  return render_range_impl(b, &a, stream0, n_streams, nullptr);
+  return render_range_impl(b, &a, stream0, n_streams, nullptr, CallForm::Plain, 0);
 }
 
 int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_input *in, const iamf_hip_render_args *args,
                                      int32_t stream0, int32_t n_streams) {
-  return render_lpcm_range_impl(b, in, args, stream0, n_streams, false);
+  return render_lpcm_range_impl(b, in, args, stream0, n_streams, CallForm::Lpcm);
 }
 
 // Element 0 as LPCM packets of every form a fused kernel reads (include/iamf_hip.h): iamf_hip_batch_render_lpcm_range with
@@ -1371,9 +1366,8 @@ int iamf_hip_batch_render_lpcm_range(iamf_hip_batch *b, const iamf_hip_lpcm_inpu
 // form (lpcm_form_packets) and render_prepare and pick_route let the call through.  The same checks in the same order, the
 // same path for everything else.
 int iamf_hip_batch_render_packets(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams) {
-  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
-  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
-  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, true);
+  if (!packet_call_ok(b, call)) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, CallForm::Packets);
 }
 
 // Element 0 as LPCM packets of any call length (include/iamf_hip.h): iamf_hip_batch_render_packets with leave to take
@@ -1381,9 +1375,8 @@ int iamf_hip_batch_render_packets(iamf_hip_batch *b, const iamf_hip_packet_call 
 // blocks, the packets have one of the four fused forms and render_prepare and pick_route let the call through.  The same
 // checks in the same order, the same path for everything else.
 int iamf_hip_batch_render_packets_ragged(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams) {
-  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
-  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
-  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, true, true);
+  if (!packet_call_ok(b, call)) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, CallForm::PacketsRagged);
 }
 
 // Element 0 as LPCM packets on a limiter-less batch (include/iamf_hip.h): iamf_hip_batch_render_packets_ragged with leave to take
@@ -1391,9 +1384,8 @@ int iamf_hip_batch_render_packets_ragged(iamf_hip_batch *b, const iamf_hip_packe
 // have one of the four fused forms and render_prepare and pick_route let the call through.  The same checks in the same order,
 // the same path for everything else.
 int iamf_hip_batch_render_packets_nolim(iamf_hip_batch *b, const iamf_hip_packet_call *call, int32_t stream0, int32_t n_streams) {
-  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
-  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
-  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, true, true, true);
+  if (!packet_call_ok(b, call)) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_range_impl(b, &call->in, &call->args, stream0, n_streams, CallForm::PacketsNolim);
 }
 
 // Both elements of a mix as LPCM packets (include/iamf_hip.h).  Fused (render_fast_kernel<.., LP2>: Family::LpcmMix) when
@@ -1401,13 +1393,11 @@ int iamf_hip_batch_render_packets_nolim(iamf_hip_batch *b, const iamf_hip_packet
 // S16 with 1 or 4 channels or S16C with 2 (lpcm_form() on each element's own layout) — and pick_route takes the call; in
 // every other case both elements are unpacked, each into a buffer of the batch, and the f32 path renders them.  Both ways
 // give the same PCM and leave the same stream state, bit for bit.  Every refusal comes before the first launch.
-// (packets: iamf_hip_batch_render_packets_mix — the forms are asked of lpcm_form_packets(), and 24-bit packets on both
-//  elements are a fused form as well; everything else is the one path.
-//  prag: iamf_hip_batch_render_packets_mix_ragged — the fused attempt carries its mark; everything else is the one path.
-//  nlm: iamf_hip_batch_render_packets_mix_nolim — the fused attempt asks for the limiter-less renderer's two-element form first)
+// (call_form, CallForm::Lpcm and on: from Packets on the forms are asked of lpcm_form_packets(), 24-bit packets on both elements
+//  are a fused form as well, and the fused attempt carries what the entry may take; everything else is the one path)
 static int render_lpcm_mix_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in0, const iamf_hip_lpcm_input *in1,
-                                const iamf_hip_render_args *args, int32_t stream0, int32_t n_streams, bool packets, bool prag = false,
-                                bool nlm = false) {
+                                const iamf_hip_render_args *args, int32_t stream0, int32_t n_streams, CallForm call_form) {
+  const bool packets = call_form >= CallForm::Packets;
   if (!b->has2 || args->d_in || args->d_in2 || !in0->d_raw || !in1->d_raw || in0->first_sample != in1->first_sample ||
       !args->d_pcm || args->n_frames < 0)
     return IAMF_HIP_ERR_BAD_ARG;
@@ -1441,7 +1431,7 @@ static int render_lpcm_mix_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in
     LpcmIn lp0, lp1;
     lpcm_in_of(in0, ch, first, form0, lp0);
     lpcm_in_of(in1, b->m2, first, form1, lp1);
-    const int r = render_call(b, a, (int)total, stream0, n_streams, &lp0, &lp1, false, false, prag, first, false, nlm);
+    const int r = render_call(b, a, (int)total, stream0, n_streams, &lp0, &lp1, call_form, first);
     if (r != kNotFused) return r;
   }
   const hipStream_t st = static_cast<hipStream_t>(args->stream);
@@ -1449,12 +1439,12 @@ static int render_lpcm_mix_impl(iamf_hip_batch *b, const iamf_hip_lpcm_input *in
   if (ur != IAMF_HIP_OK) return ur;
   ur = lpcm_unpack_range(b, in1, nf, first, count, stream0, n_streams, st, a, true);
   if (ur != IAMF_HIP_OK) return ur;
-  return render_range_impl(b, &a, stream0, n_streams, nullptr);
+  return render_range_impl(b, &a, stream0, n_streams, nullptr, CallForm::Plain, 0);
 }
 
 int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_call *call, int32_t stream0, int32_t n_streams) {
   if (!b || !call) return IAMF_HIP_ERR_BAD_ARG;
-  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, false);
+  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, CallForm::Lpcm);
 }
 
 // Both elements of a mix as LPCM packets of every form a fused kernel reads (include/iamf_hip.h): iamf_hip_batch_render_lpcm_mix
@@ -1463,9 +1453,8 @@ int iamf_hip_batch_render_lpcm_mix(iamf_hip_batch *b, const iamf_hip_lpcm_mix_ca
 // each element's own layout) — and render_prepare and pick_route let the call through.  The same checks in the same order,
 // the same path for everything else.
 int iamf_hip_batch_render_packets_mix(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams) {
-  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
-  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
-  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, true);
+  if (!packet_call_ok(b, call)) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, CallForm::Packets);
 }
 
 // Both elements of a mix as LPCM packets of any call length (include/iamf_hip.h): iamf_hip_batch_render_packets_mix with leave to
@@ -1473,9 +1462,8 @@ int iamf_hip_batch_render_packets_mix(iamf_hip_batch *b, const iamf_hip_packet_m
 // 64-sample blocks, both elements' packets have a form the whole-block mix kernels read and render_prepare and pick_route let the
 // call through.  The same checks in the same order, the same path for everything else.
 int iamf_hip_batch_render_packets_mix_ragged(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams) {
-  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
-  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
-  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, true, true);
+  if (!packet_call_ok(b, call)) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, CallForm::PacketsRagged);
 }
 
 // Both elements of a mix as LPCM packets on a limiter-less batch (include/iamf_hip.h): iamf_hip_batch_render_packets_mix_ragged with
@@ -1483,9 +1471,8 @@ int iamf_hip_batch_render_packets_mix_ragged(iamf_hip_batch *b, const iamf_hip_p
 // stages in front, both elements' packets have a form the mix kernels read and render_prepare and pick_route let the call through.
 // The same checks in the same order, the same path for everything else.
 int iamf_hip_batch_render_packets_mix_nolim(iamf_hip_batch *b, const iamf_hip_packet_mix_call *call, int32_t stream0, int32_t n_streams) {
-  if (!b || !call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
-  if (call->args.d_in || call->args.d_in2) return IAMF_HIP_ERR_BAD_ARG;
-  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, true, true, true);
+  if (!packet_call_ok(b, call)) return IAMF_HIP_ERR_BAD_ARG;
+  return render_lpcm_mix_impl(b, &call->in[0], &call->in[1], &call->args, stream0, n_streams, CallForm::PacketsNolim);
 }
 
 // Interleaved f32 of any call length (include/iamf_hip.h): iamf_hip_batch_render_range with leave to take
@@ -1497,7 +1484,7 @@ int iamf_hip_batch_render_interleaved(iamf_hip_batch *b, const iamf_hip_interlea
   int64_t total = 0;
   const int rc = range_args_check(b, &call->args, stream0, n_streams, &total);
   if (rc != IAMF_HIP_OK || total == 0) return rc;
-  return render_call(b, call->args, (int)total, stream0, n_streams, nullptr, nullptr, true);
+  return render_call(b, call->args, (int)total, stream0, n_streams, nullptr, nullptr, CallForm::Interleaved, 0);
 }
 
 // Planar f32 of any call length (include/iamf_hip.h): iamf_hip_batch_render_range with leave to take
@@ -1508,7 +1495,7 @@ int iamf_hip_batch_render_ragged(iamf_hip_batch *b, const iamf_hip_ragged_call *
   int64_t total = 0;
   const int rc = range_args_check(b, &call->args, stream0, n_streams, &total);
   if (rc != IAMF_HIP_OK || total == 0) return rc;
-  return render_call(b, call->args, (int)total, stream0, n_streams, nullptr, nullptr, false, true);
+  return render_call(b, call->args, (int)total, stream0, n_streams, nullptr, nullptr, CallForm::Ragged, 0);
 }
 
 int iamf_hip_batch_render_ex(iamf_hip_batch *b, const iamf_hip_render_args *a) {
@@ -1655,7 +1642,7 @@ static int fanout_range_impl(iamf_hip_batch *const *batches, int32_t n_batches, 
     if (k >= kFanFuseMax || b->fir || b->lfe || b->d_pre || (sc > 0 && sc != b->cfg.out_channels) || !b->cfg.limiter_enable ||
         b->cfg.out_channels > 2)
       continue;
-    const int rc = render_prepare(b, args[j], (int)total, stream0, n_streams, nullptr, pcs[j]);
+    const int rc = render_prepare(b, args[j], (int)total, stream0, n_streams, nullptr, nullptr, CallForm::Plain, 0, pcs[j]);
     if (rc != IAMF_HIP_OK) return rc;
     const Route r = pick_route(pcs[j].p, pcs[j].m_eff);
     fuse[j] = r.family == Family::Fast && r.variant == 0 && pcs[j].m_eff == b0->m && FanM::has(pcs[j].m_eff);
@@ -1696,7 +1683,7 @@ static int fanout_range_impl(iamf_hip_batch *const *batches, int32_t n_batches, 
   // ---- every other member: the single call, in member order, on the same stream ----
   for (int j = 0; j < n_batches; ++j) {
     if (k && fuse[j]) continue;
-    const int r = render_call(batches[j], args[j], (int)total, stream0, n_streams);
+    const int r = render_call(batches[j], args[j], (int)total, stream0, n_streams, nullptr, nullptr, CallForm::Plain, 0);
     if (r < 0) return r;
     n_emitted[j] = r;
   }
@@ -1753,7 +1740,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
   // ---- the packets (channels and frame size are the same for every member), then every member's own argument checks ----
   LpcmForm form = LpcmForm::None;
   int first = 0, count = 0;
-  const int fc = lpcm_form_check(b0, in, n_frames, n_samples, &form, &first, &count);
+  const int fc = lpcm_form_check(b0, in, n_frames, n_samples, &form, &first, &count, false);
   if (fc != IAMF_HIP_OK) return fc;
   // "the form the single call fuses" is the 16-bit one here: render_fanout_kernel<.., LP> reads no other, and 24-bit
   // packets and coupled 16-bit ones (LpcmForm::S16C) keep sharing one unpack pass and the f32 fan-out (include/iamf_hip.h)
@@ -1789,7 +1776,7 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
     if (pk_form) {
       LpcmIn lp;
       lpcm_in_of(in, ch, first, form, lp);
-      const int rc = render_prepare(b, args[j], (int)total, stream0, n_streams, &lp, pcs[j]);
+      const int rc = render_prepare(b, args[j], (int)total, stream0, n_streams, &lp, nullptr, CallForm::Lpcm, 0, pcs[j]);
       if (rc != kNotFused && rc != IAMF_HIP_OK) return rc;
       if (rc == IAMF_HIP_OK) {   // the member's single call takes Family::Lpcm (render_prepare has asked pick_route)
         // what the f32 fan-out asks on top: nothing re-laid behind the kernel; then an instance of this kernel
@@ -1894,7 +1881,7 @@ int iamf_hip_batch_flush_range(iamf_hip_batch *b, void *d_pcm, int64_t pcm_strea
   a.d_pcm = d_pcm;
   a.pcm_stream_stride_bytes = pcm_stream_stride_bytes;
   a.stream = stream;
-  const int r = render_call(b, a, kDelay, stream0, n_streams);
+  const int r = render_call(b, a, kDelay, stream0, n_streams, nullptr, nullptr, CallForm::Plain, 0);
   if (r >= 0)
     for (int i = stream0; i < stream0 + n_streams; ++i) b->sflushed[(size_t)i] = 1;
   return r;

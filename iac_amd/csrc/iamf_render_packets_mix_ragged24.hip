@@ -10,7 +10,7 @@
 int iamf_hip_fast_packets_mix_ragged24_launch(const void *params, int m, int lp2, hipStream_t st) {
   RenderMixParams p;
   memcpy(&p, params, sizeof(p));
-  if (p.ragged != 3 || !p.lpcm || !p.lpcm2 || p.lpcm_coupled || p.lpcm_bytes != 3 || p.lpcm_mix != (4 | lp2) || p.total < 1 ||
+  if (p.ragged != kCallPacketsMixRagged || !p.lpcm || !p.lpcm2 || p.lpcm_coupled || p.lpcm_bytes != 3 || p.lpcm_mix != (4 | lp2) || p.total < 1 ||
       p.frame_size < 4 || (p.frame_size & 3))
     return 0;
   return launch_fast_lp_mix_rag<LpcmM, LpcmOC, false, LpcmMixK, 3>(p, m, lp2, st);

@@ -9,6 +9,6 @@
 int iamf_hip_fast_packets_ragged24_coupled_launch(const void *params, int m, hipStream_t st) {
   RenderParams p;
   memcpy(&p, params, sizeof(p));
-  if (p.ragged != 2 || !p.lpcm || p.lpcm_coupled != 2 || p.lpcm_bytes != 3 || p.total < 1 || p.frame_size < 4 || (p.frame_size & 3)) return 0;
+  if (p.ragged != kCallPacketsRagged || !p.lpcm || p.lpcm_coupled != 2 || p.lpcm_bytes != 3 || p.total < 1 || p.frame_size < 4 || (p.frame_size & 3)) return 0;
   return launch_fast_lp_rag<LpcmCoupledM, LpcmOC, 3, true>(p, m, st);
 }

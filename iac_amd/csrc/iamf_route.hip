@@ -1,6 +1,6 @@
 // iamf_route.hip — which kernel ran (include/iamf_hip.h: iamf_hip_route_instances, iamf_hip_route_tally and their indexed and
 // per-family forms).  Host code only.  One array of row sets, each built by walking the lists the launchers dispatch over
-// (for_each_instance_of_total_set, render_route.hpp), so a kernel instance added to a list — or a set added to that walker — is
+// (for_each_instance_of_set, render_route.hpp), so a kernel instance added to a list — or a set added to that walker — is
 // listed and counted without a change here.  Every launcher counts through the one entry iamf_hip_route_count(set, ..), the
 // set being RouteKey::set of the route it ran.  Counting is one relaxed atomic add per launch on a fixed array: no lock and no
 // allocation on the call path (the decoder groups launch from several threads).
@@ -34,7 +34,7 @@ struct RouteTable {
   int32_t index[kRouteCap];    // row of key[i]
   int n = 0, dropped = 0;
   void build(int set) {
-    for_each_instance_of_total_set(set, [&](int family, int variant, int m, int c, int k) {
+    for_each_instance_of_set(set, [&](int family, int variant, int m, int c, int k) {
       if (n == kRouteCap) {
         ++dropped;
         return;
@@ -66,20 +66,16 @@ struct RouteTable {
 
 // One row set and its counters (slot kRouteCap: IAMF_HIP_ROUTE_NONE).  Sets 0 .. kRouteTables - 1 ARE the numbered tables
 // of iamf_hip_route_table_instances (0: the base listing, 1: the extension, 2: the 24-bit LPCM form), whose count is pinned;
-// the sets behind them are listed by family only (iamf_hip_route_family_instances).  render_route.hpp says which walker
-// fills which set (for_each_instance_of_set, and for_each_instance_of_any_set / for_each_instance_of_built_set /
-// for_each_instance_of_launched_set / for_each_instance_of_listed_set / for_each_instance_of_every_set / for_each_instance_of_total_set for the sets added behind the
-// pinned seven: set 7, the coupled 24-bit LPCM form, set 8, the two-element 24-bit form, set 9, the ragged packet form, set 10, the
-// ragged two-element packet form, set 11, the packet-fed limiter-less renderer, and set 12, its two-element form): a set added there is listed and counted without
-// a change here.
+// the sets behind them are listed by family only (iamf_hip_route_family_instances).  for_each_instance_of_set
+// (render_route.hpp) says which rows fill which of the kRouteSets sets.
 struct RouteSet {
   RouteTable table;
   std::atomic<int64_t> launches[kRouteCap + 1];
 };
 RouteSet *route_sets() {
   static RouteSet *const sets = [] {
-    static RouteSet s[kRouteSetsTotal];   // (static storage: every counter starts at zero)
-    for (int set = 0; set < kRouteSetsTotal; ++set) s[set].table.build(set);
+    static RouteSet s[kRouteSets];   // (static storage: every counter starts at zero)
+    for (int set = 0; set < kRouteSets; ++set) s[set].table.build(set);
     return s;
   }();
   return sets;
@@ -113,7 +109,7 @@ int tally_of(RouteSet &s, iamf_hip_route_row *rows, int cap, int reset) {
 int family_rows(int family, bool tally, iamf_hip_route_row *rows, int cap, int reset) {
   int cnt = 0;
   bool known = false;
-  for (int set = 0; set < kRouteSetsTotal; ++set) {
+  for (int set = 0; set < kRouteSets; ++set) {
     RouteSet &s = route_sets()[set];
     const RouteTable &t = s.table;
     for (int i = 0; i < t.n; ++i) {
@@ -139,7 +135,7 @@ int family_rows(int family, bool tally, iamf_hip_route_row *rows, int cap, int r
 // A key its set does not hold counts in that set's own NONE slot where the set is a numbered table, else (the sets listed by
 // family only have no tally of their own to show it) in the base table's.
 void iamf_hip_route_count(int set, int family, int variant, int m, int c, int k) {
-  if (set < 0 || set >= kRouteSetsTotal) return;
+  if (set < 0 || set >= kRouteSets) return;
   RouteSet *sets = route_sets();
   const int i = sets[set].table.find(pack_key(family, variant, m, c, k));
   sets[i == kRouteCap && set >= kRouteTables ? 0 : set].launches[i].fetch_add(1, std::memory_order_relaxed);

@@ -37,7 +37,7 @@ bool launch_nolim_lp(const RenderParams &p, int m, hipStream_t st) {
 // what both units refuse before they launch: a block that does not carry the form's mark or would index outside the tile
 inline bool nolim_lp_params_ok(const RenderParams &p, int lpb) {
   const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
-  if (p.ragged != 4 || !p.lpcm || p.limiter_on || (lpb == 3) != (p.lpcm_bytes == 3)) return false;
+  if (p.ragged != kCallPacketsNolim || !p.lpcm || p.limiter_on || (lpb == 3) != (p.lpcm_bytes == 3)) return false;
   if (p.total < 4 || (p.total & 3) || p.frame_size < 4 || (p.frame_size & 3)) return false;
   return p.out_ch >= 1 && !((p.out_ch * bytes) & 3) && p.out_ch * bytes <= kNlMaxFrameBytes;
 }
@@ -60,7 +60,7 @@ bool launch_nolim_lp_mix(const RenderMixParams &p, int m, int lp2, hipStream_t s
 // kernel reads, or would index outside the tile
 inline bool nolim_lp_mix_params_ok(const RenderMixParams &p, int lpb, int lp2) {
   const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
-  if (p.ragged != 5 || !p.lpcm || !p.lpcm2 || p.limiter_on || (lpb == 3) != (p.lpcm_bytes == 3)) return false;
+  if (p.ragged != kCallPacketsMixNolim || !p.lpcm || !p.lpcm2 || p.limiter_on || (lpb == 3) != (p.lpcm_bytes == 3)) return false;
   if (p.lpcm_mix != ((lpb == 3 ? 4 : 0) | lp2) || !lpcm_mix_m2_ok(lp2, p.m2) || !p.matrix2 || !p.src_feed2 || !p.gains2) return false;
   if (p.total < 4 || (p.total & 3) || p.frame_size < 4 || (p.frame_size & 3)) return false;
   if ((p.elem_ramp || p.elem2_ramp || p.out_ramp) && (p.ramp_stream_stride & 3)) return false;

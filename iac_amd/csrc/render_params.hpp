@@ -104,24 +104,10 @@ struct RenderParams {
   int32_t og_ch;            // output channels the OUTPUT gain multiplies (iamf_hip_batch_config::out_gain_channels; = out_ch: all)
   int32_t lfe_k0;           // the generator's output of the call's first sample sits at index lfe_k0 (trimmed frames: the
                             // filter also ran over the lfe_k0 samples cut off in front, iamf_hip_render_args)
-  int32_t ragged;           // 1: the call came through iamf_hip_batch_render_ragged and, where it is no whole number of 64-sample
-                            // blocks, may take render_fast_kernel<.., IL = false, RAG = true> (pick_route: Family::FastRagged); 0:
-                            // every rule as it stood.  Host only, and kept HERE, in the 4 bytes of padding in front of the
-                            // double, like lpcm_bytes: the block keeps its size and every other field its offset
-                            // 2: the call came through iamf_hip_batch_render_packets_ragged with element 0 as packets (`lpcm`) and,
-                            // where it is no whole number of blocks, may take render_fast_kernel<.., LP, .., RAG = true> (pick_route:
-                            // Family::PacketsRagged); demix_i0 then holds iamf_hip_lpcm_input::first_sample (no demixer runs
-                            // beside packets)
-                            // 3: the call came through iamf_hip_batch_render_packets_mix_ragged with both elements as packets
-                            // (`lpcm`, `lpcm_mix`) and, where it is no whole number of blocks, may take render_fast_kernel<.., IN2,
-                            // LP, .., LP2, false, RAG = true> (pick_route: Family::PacketsMixRagged); demix_i0 as for 2
-                            // 4: the call came through iamf_hip_batch_render_packets_nolim with element 0 as packets (`lpcm`) and
-                            // takes render_nolim_kernel<M, LPB, LPC> (pick_route: Family::NolimPackets) — render_prepare keeps the
-                            // mark only where that rule holds, and otherwise goes on as for 2; demix_i0 as for 2
-                            // 5: the call came through iamf_hip_batch_render_packets_mix_nolim with both elements as packets
-                            // (`lpcm`, `lpcm_mix`, RenderMixParams) and takes render_nolim_kernel<M, LPB, LPC, LP2> (pick_route:
-                            // Family::NolimPacketsMix) — render_prepare keeps the mark only where that rule holds, and otherwise
-                            // goes on as for 3; demix_i0 as for 2
+  int32_t ragged;           // the call's mark, a CallMark (below): which entry the call came through, where that entry's own kernel
+                            // form may take it; kCallPlain: every rule as it stood.  Host only, and kept HERE, in the 4 bytes of
+                            // padding in front of the double, like lpcm_bytes: the block keeps its size and every other field
+                            // its offset
   double lfe_div;           // sqrt(n) of h2m_rdr.c:1162; 0 = the `* 0.5` form (n <= 2)
   int32_t lfe_mask;         // bit c: output slot c is an LFE slot (src_feed[c] == -2), for render_wide4.hpp
   // ---- HRTF FIR renderer (render_fast_kernel<M, 2, true>): matrix = h[2][M][fir_taps] ----
@@ -155,6 +141,29 @@ struct RenderParams {
   int64_t lpcm_stream_stride, lpcm_frame_stride;
   int32_t lpcm_off[16];
 };
+
+// The values of RenderParams::ragged.  Each is set by one entry alone (render_prepare, iamf_render.hip) and read by one rule of
+// pick_route (render_route.hpp); a call whose rule does not hold routes as the entry named behind "else".
+enum CallMark : int32_t {
+  kCallPlain = 0,
+  kCallRagged = 1,            // iamf_hip_batch_render_ragged: planar f32 that is no whole number of 64-sample blocks may take
+                              // render_fast_kernel<.., IL = false, RAG = true> (Family::FastRagged)
+  kCallPacketsRagged = 2,     // iamf_hip_batch_render_packets_ragged: element 0 as packets (`lpcm`), no whole number of blocks, may
+                              // take render_fast_kernel<.., LP, .., RAG = true> (Family::PacketsRagged)
+  kCallPacketsMixRagged = 3,  // iamf_hip_batch_render_packets_mix_ragged: both elements as packets (`lpcm`, `lpcm_mix`), no whole
+                              // number of blocks, may take render_fast_kernel<.., IN2, LP, .., LP2, false, RAG = true>
+                              // (Family::PacketsMixRagged)
+  kCallPacketsNolim = 4,      // iamf_hip_batch_render_packets_nolim: element 0 as packets takes render_nolim_kernel<M, LPB, LPC>
+                              // (Family::NolimPackets) — render_prepare sets the mark only where that rule holds, else
+                              // kCallPacketsRagged
+  kCallPacketsMixNolim = 5,   // iamf_hip_batch_render_packets_mix_nolim: both elements as packets (RenderMixParams) take
+                              // render_nolim_kernel<M, LPB, LPC, LP2> (Family::NolimPacketsMix) — set only where that rule holds,
+                              // else kCallPacketsMixRagged
+};
+// The frame position of a packet call's first sample (iamf_hip_lpcm_input::first_sample; the two inputs of a mix share it).  It
+// travels in demix_i0, which no packet-fed kernel reads: no demixer runs beside packets.  Set with every mark from
+// kCallPacketsRagged on.
+inline int32_t call_first_sample(const RenderParams &p) { return p.demix_i0; }
 
 // render_fast_kernel<.., LP2> (iamf_hip_batch_render_lpcm_mix): the block above and, behind it, the SECOND element as 16-bit
 // little-endian LPCM packets.  Sample i of its channel m, frame f, stream s: lpcm2 + s * lpcm2_stream_stride + f *

@@ -137,108 +137,130 @@ IAMF_HD constexpr int wide_lds_floats(int c, int m) {
 constexpr int kNlChunk = 1024;                       // sample-frames per workgroup
 constexpr int kNlMaxFrameBytes = 60;                 // out_ch * bytes per sample-frame the LDS tile takes (60 KiB)
 
+// ------------------------------------------------------------------------------------------
+// what the shape rules share: each check stated once.  A wrong answer here is a misaligned or stray load on the GPU, not a
+// slower rate (tests/route_host pins every rule, tests/route_host/route_host_sweep_check.cpp the whole decision)
+// ------------------------------------------------------------------------------------------
+
+inline bool on_grid16(const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
+// PCM rows on the 16-byte grid: every kernel but the general one stores a lane's sample-frames as whole 16-byte pieces
+inline bool pcm_rows_ok(const RenderParams &p) { return on_grid16(p.pcm) && !(p.pcm_stream_stride & 15); }
+// per-sample gains, where given: rows on the 16-byte grid with a stride that is a multiple of 4 (one float4 per lane)
+inline bool ramp_quads_ok(const RenderParams &p) {
+  if (!p.elem_ramp && !p.elem2_ramp && !p.out_ramp) return true;
+  return !(p.ramp_stream_stride & 3) && on_grid16(p.elem_ramp) && on_grid16(p.elem2_ramp) && on_grid16(p.out_ramp);
+}
+// the stream position of a kernel that places its ring per call (render_fast.hpp `base`, render_wide4.hpp): a multiple of 16,
+// or — a trimmed first frame — any position from 240 samples on
+inline bool pos_ok(const RenderParams &p) { return !(p.pos0 & 15) || p.pos0 >= kDelay; }
+// the fast kernel addresses a stream's packets of one call with 32-bit byte offsets (buffer loads, render_fast.hpp): the
+// call's frames and two more at `frame_stride` bytes, and 2^24 bytes for what one frame's runs span, stay below 2^31
+inline bool packet_offsets32_ok(const RenderParams &p, int64_t frame_stride) {
+  return ((int64_t)p.total / p.frame_size + 2) * frame_stride + ((int64_t)1 << 24) < (int64_t)1 << 31;
+}
+// the same for planar f32 rows, the stride in floats
+inline bool f32_offsets32_ok(const RenderParams &p) {
+  return ((int64_t)p.total / p.frame_size + 2) * p.in_frame_stride * 4 + 100 * (int64_t)p.frame_size < (int64_t)1 << 31;
+}
+// the grid of a packet form as a mask (lpcm_form.hpp: 8 bytes for 16-bit samples, 4 for 24-bit ones) and its sample size
+inline int lpcm_grid(const RenderParams &p) { return p.lpcm_bytes == 3 ? 3 : 7; }
+inline int lpcm_sample_bytes(const RenderParams &p) { return p.lpcm_bytes == 3 ? 3 : 2; }
+// one element's packets: the buffer on 16 bytes, both strides on the form's grid, frames one behind the other
+inline bool packet_rows_ok(const void *raw, int64_t stream_stride, int64_t frame_stride, int grid) {
+  return on_grid16(raw) && !(stream_stride & grid) && !(frame_stride & grid) && frame_stride > 0;
+}
+// Element 0's packets have one of the four forms the marked packet rules read: 16-bit mono-coded (LpcmM), 16-bit coupled
+// (lpcm_coupled == 1), 24-bit mono-coded, 24-bit coupled (== 2), with an instance for m, on the form's grid — the rows and every
+// run's start, first_sample included; a pair's second channel lies one sample behind its first, the pair's one run starts at the
+// first.  zero_is_16: the rule reads lpcm_bytes == 0 as 16 bit (the ragged forms; the limiter-less ones require 2).
+inline bool lpcm_elem0_form_ok(const RenderParams &p, int m, bool zero_is_16) {
+  if (p.lpcm_bytes != 3 && p.lpcm_bytes != 2 && !(zero_is_16 && p.lpcm_bytes == 0)) return false;
+  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (p.lpcm_bytes == 3 ? 2 : 1)) return false;
+  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
+  const int grid = lpcm_grid(p);
+  if (!packet_rows_ok(p.lpcm, p.lpcm_stream_stride, p.lpcm_frame_stride, grid)) return false;
+  for (int c = 0; c < m; ++c) {
+    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
+      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + lpcm_sample_bytes(p)) return false;
+    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
+  }
+  return true;
+}
+// lpcm_mix names element 1's form (LP2, or 4 | LP2 with 24-bit samples) of element 0's sample size, and the second element given
+// has a channel count that form takes
+inline bool lpcm_mix_form_ok(const RenderParams &p) {
+  const int lp2 = p.lpcm_mix & 3;
+  return p.lpcm_mix == ((p.lpcm_bytes == 3 ? 4 : 0) | lp2) && LpcmMixK::has(lp2) && p.in2 && lpcm_mix_m2_ok(lp2, p.m2);
+}
+// A trimmed frame (`first`, iamf_hip_lpcm_input::first_sample, is call_first_sample(p): one for both elements of a mix): only a
+// call shorter than a frame has one, and every quad that starts below `total` ends inside the run of frame_size samples.
+// round_up: the kernel's last quad may be ragged, so the total counts rounded up to a quad (the ragged forms); else the rule has
+// asked for whole quads, and no byte outside the samples of the call is read (the limiter-less forms).
+inline bool trimmed_frame_ok(const RenderParams &p, bool round_up) {
+  const int first = call_first_sample(p);
+  if (first < 0 || (first > 0 && p.total >= p.frame_size)) return false;
+  return p.total >= p.frame_size || (int64_t)first + (round_up ? (p.total + 3) & ~3 : p.total) <= p.frame_size;
+}
+// what the LDS tile of render_nolim.hpp takes: a lane's 4 sample-frames are whole 16-byte pieces, a sample-frame at most 60 bytes
+inline bool nolim_frame_bytes_ok(const RenderParams &p) {
+  const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
+  return !((p.out_ch * bytes) & 3) && p.out_ch * bytes <= kNlMaxFrameBytes;
+}
+// the early per-channel prefetch of a whole-block packet form: as measured per size (the form's *_early), unless
+// IAMF_HIP_LP_LATE=1 forces the late variant or IAMF_HIP_LP_EARLY=1 the early one
+inline bool lp_early_variant(bool measured_early) { return !getenv("IAMF_HIP_LP_LATE") && (getenv("IAMF_HIP_LP_EARLY") || measured_early); }
+
 // what render_nolim_kernel's addressing needs; the caller has checked that the call is of the plain kind
 inline bool nolim_shape_ok(const RenderParams &p) {
-  const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
   if ((p.frame_size & 3) || (p.total & 3) || p.total <= 0) return false;
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  if (((p.out_ch * bytes) & 3) || p.out_ch * bytes > kNlMaxFrameBytes) return false;  // a lane's 4 sample-frames = whole 16-byte pieces
-  return true;
+  if (!on_grid16(p.in) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
+  return pcm_rows_ok(p) && nolim_frame_bytes_ok(p);
 }
 
 // What the packet-fed form of the limiter-less renderer (render_nolim.hpp, render_nolim_kernel) needs of a call that came
-// through iamf_hip_batch_render_packets_nolim (RenderParams::ragged == 4, which that entry alone sets): the plain kind
-// render_nolim_kernel takes (pick_route's Family::Nolim rule: limiter off, one matrix-rendered element, no second element, ramps,
-// down-mixer, demixer, pre-matrix, HRTF stage or LFE generator, no reduced out_gain_channels); the packet form named by
-// (lpcm_bytes, lpcm_coupled) as the ragged packet family names it, with an instance for m, on that form's own grid (lpcm_form.hpp:
-// 8 bytes for 16-bit samples, 4 for 24-bit ones — strides and every run's start, first_sample included); frame size and the call's
-// samples per stream multiples of 4 and at least 4, so that a lane's quad never straddles a frame; for a trimmed frame
-// first + total <= frame_size (`first`, iamf_hip_lpcm_input::first_sample, travels in demix_i0 as for packets_ragged_shape_ok), so
-// that no byte outside the samples of the call is read; PCM rows on the 16-byte grid and a sample-frame of whole dwords that fits
-// the tile, as nolim_shape_ok has it.  The kernel addresses with 64-bit pointers: no bound on the call's extent.
+// through iamf_hip_batch_render_packets_nolim (kCallPacketsNolim, which that entry alone sets): the plain kind render_nolim_kernel
+// takes (pick_route's Family::Nolim rule: limiter off, one matrix-rendered element, no second element, ramps, down-mixer, demixer,
+// pre-matrix, HRTF stage or LFE generator, no reduced out_gain_channels); element 0's form (lpcm_elem0_form_ok, lpcm_bytes == 2 or
+// 3); frame size and the call's samples per stream multiples of 4 and at least 4, so that a lane's quad never straddles a frame;
+// a trimmed frame inside its run (trimmed_frame_ok, whole quads); PCM rows and a sample-frame the tile takes, as nolim_shape_ok
+// has it.  The kernel addresses with 64-bit pointers: no bound on the call's extent, no n_end, no rule on the position.
 // IAMF_HIP_NOLIM_PACKETS_UNFUSED=1, IAMF_HIP_LPCM_UNFUSED=1 and IAMF_HIP_FORCE_GENERIC=1 send every such call down the other rules.
 inline bool nolim_packets_shape_ok(const RenderParams &p, int m, bool force_generic) {
-  if (p.ragged != 4 || !p.lpcm || force_generic || getenv("IAMF_HIP_NOLIM_PACKETS_UNFUSED") || getenv("IAMF_HIP_LPCM_UNFUSED")) return false;
+  if (p.ragged != kCallPacketsNolim || !p.lpcm || force_generic || getenv("IAMF_HIP_NOLIM_PACKETS_UNFUSED") || getenv("IAMF_HIP_LPCM_UNFUSED")) return false;
   if (p.limiter_on || !p.in || p.og_ch < p.out_ch) return false;
   if (p.in2 || p.lpcm_mix || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe)
     return false;
   if (p.total < 4 || (p.total & 3) || p.frame_size < 4 || (p.frame_size & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.lpcm) & 15) || (reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
-  if (p.out_ch < 1 || ((p.out_ch * bytes) & 3) || p.out_ch * bytes > kNlMaxFrameBytes) return false;
-  // the form: 16-bit mono-coded (LpcmM), 16-bit coupled (lpcm_coupled == 1), 24-bit mono-coded, 24-bit coupled (== 2)
-  const bool s24 = p.lpcm_bytes == 3;
-  if (!s24 && p.lpcm_bytes != 2) return false;
-  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (s24 ? 2 : 1)) return false;
-  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
-  const int grid = s24 ? 3 : 7;
-  if ((p.lpcm_stream_stride & grid) || (p.lpcm_frame_stride & grid) || p.lpcm_frame_stride <= 0) return false;
-  for (int c = 0; c < m; ++c) {   // a pair's second channel lies sample_bytes behind its first: the pair's one run starts at the first
-    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
-      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + (s24 ? 3 : 2)) return false;
-    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
-  }
-  // a trimmed frame: every quad that starts below `total` ends inside the samples of the call
-  if (p.demix_i0 < 0 || (p.demix_i0 > 0 && p.total >= p.frame_size)) return false;
-  if (p.total < p.frame_size && (int64_t)p.demix_i0 + p.total > p.frame_size) return false;
-  return true;
+  if (!pcm_rows_ok(p) || p.out_ch < 1 || !nolim_frame_bytes_ok(p)) return false;
+  return lpcm_elem0_form_ok(p, m, false) && trimmed_frame_ok(p, false);
 }
 
 // What the two-element packet form of the limiter-less renderer (render_nolim_kernel<M, LPB, LPC, LP2>) needs of a call that came
-// through iamf_hip_batch_render_packets_mix_nolim (RenderParams::ragged == 5, which that entry alone sets, on a RenderMixParams):
-// limiter off; no down-mixer, demixer, pre-matrix, HRTF stage, LFE generator or reduced out_gain_channels; a second element given
-// as packets — lpcm_mix names a form (LP2, or 4 | LP2 with 24-bit samples) with lpcm_mix_m2_ok, of element 0's sample size;
-// element 0's form exactly as nolim_packets_shape_ok checks it; element 1 on the same grid (8 bytes for 16-bit samples, 4 for
-// 24-bit ones): the buffer on 16 bytes, the strides, every run's start with first_sample counted in, and a pair's partner one
-// sample behind; ramps, where given, on the 16-byte grid with a stride that is a multiple of 4 (one float4 per lane); frame size
-// and the call's samples per stream multiples of 4 and at least 4; for a trimmed frame first + total <= frame_size, which holds
-// for both elements (one first_sample, in demix_i0); the PCM rules of nolim_shape_ok.  64-bit addressing: no bound on the extent.
+// through iamf_hip_batch_render_packets_mix_nolim (kCallPacketsMixNolim, which that entry alone sets, on a RenderMixParams):
+// everything nolim_packets_shape_ok asks, with a second element given as packets in place of "no second element, no ramps" —
+// lpcm_mix names its form (lpcm_mix_form_ok); pick_route's fields and the kernel's (the block behind RenderParams) agree; element 1
+// on element 0's grid: its rows, every run's start with first_sample counted in, and a pair's partner one sample behind — and
+// ramps, where given, as ramp_quads_ok has them.  The trimmed frame's rule holds for both elements (one first_sample).
 // IAMF_HIP_NOLIM_PACKETS_MIX_UNFUSED=1, IAMF_HIP_LPCM_UNFUSED=1 and IAMF_HIP_FORCE_GENERIC=1 send every such call down the other rules.
 inline bool nolim_packets_mix_shape_ok(const RenderMixParams &p, int m, bool force_generic) {
-  if (p.ragged != 5 || !p.lpcm || force_generic || getenv("IAMF_HIP_NOLIM_PACKETS_MIX_UNFUSED") || getenv("IAMF_HIP_LPCM_UNFUSED")) return false;
+  if (p.ragged != kCallPacketsMixNolim || !p.lpcm || force_generic || getenv("IAMF_HIP_NOLIM_PACKETS_MIX_UNFUSED") || getenv("IAMF_HIP_LPCM_UNFUSED")) return false;
   if (p.limiter_on || !p.in || p.og_ch < p.out_ch) return false;
   if (p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe) return false;
   if (p.total < 4 || (p.total & 3) || p.frame_size < 4 || (p.frame_size & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.lpcm) & 15) || (reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  const int bytes = p.out_format == IAMF_HIP_FMT_S16 ? 2 : (p.out_format == IAMF_HIP_FMT_S24 ? 3 : 4);
-  if (p.out_ch < 1 || ((p.out_ch * bytes) & 3) || p.out_ch * bytes > kNlMaxFrameBytes) return false;
-  // element 0's form: 16-bit mono-coded (LpcmM), 16-bit coupled (lpcm_coupled == 1), 24-bit mono-coded, 24-bit coupled (== 2)
-  const bool s24 = p.lpcm_bytes == 3;
-  if (!s24 && p.lpcm_bytes != 2) return false;
-  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (s24 ? 2 : 1)) return false;
-  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
-  const int grid = s24 ? 3 : 7;
-  if ((p.lpcm_stream_stride & grid) || (p.lpcm_frame_stride & grid) || p.lpcm_frame_stride <= 0) return false;
-  for (int c = 0; c < m; ++c) {   // a pair's second channel lies sample_bytes behind its first: the pair's one run starts at the first
-    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
-      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + (s24 ? 3 : 2)) return false;
-    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
-  }
-  // element 1: the form lpcm_mix names, of the same sample size, where pick_route's fields and the kernel's agree
-  const int lp2 = p.lpcm_mix & 3;
-  if (p.lpcm_mix != ((s24 ? 4 : 0) | lp2) || !LpcmMixK::has(lp2)) return false;
-  if (!p.in2 || !p.lpcm2 || reinterpret_cast<const uint8_t *>(p.in2) != p.lpcm2 || !lpcm_mix_m2_ok(lp2, p.m2)) return false;
-  if (!p.matrix2 || !p.src_feed2 || !p.gains2) return false;
+  if (!pcm_rows_ok(p) || p.out_ch < 1 || !nolim_frame_bytes_ok(p)) return false;
+  if (!lpcm_elem0_form_ok(p, m, false) || !lpcm_mix_form_ok(p)) return false;
+  // element 1: where pick_route's fields and the kernel's agree, on element 0's grid
+  const int grid = lpcm_grid(p);
+  if (!p.lpcm2 || reinterpret_cast<const uint8_t *>(p.in2) != p.lpcm2 || !p.matrix2 || !p.src_feed2 || !p.gains2) return false;
   if (p.in2_stream_stride != p.lpcm2_stream_stride || p.in2_frame_stride != p.lpcm2_frame_stride) return false;
-  if ((reinterpret_cast<uintptr_t>(p.lpcm2) & 15) || (p.lpcm2_stream_stride & grid) || (p.lpcm2_frame_stride & grid) || p.lpcm2_frame_stride <= 0)
-    return false;
-  if (lp2 == 2) {
-    if (p.lpcm2_off[0] < 0 || (p.lpcm2_off[0] & grid) || p.lpcm2_off[1] != p.lpcm2_off[0] + (s24 ? 3 : 2)) return false;
+  if (!packet_rows_ok(p.lpcm2, p.lpcm2_stream_stride, p.lpcm2_frame_stride, grid)) return false;
+  if ((p.lpcm_mix & 3) == 2) {
+    if (p.lpcm2_off[0] < 0 || (p.lpcm2_off[0] & grid) || p.lpcm2_off[1] != p.lpcm2_off[0] + lpcm_sample_bytes(p)) return false;
   } else {
     for (int c = 0; c < p.m2; ++c)
       if (p.lpcm2_off[c] < 0 || (p.lpcm2_off[c] & grid)) return false;
   }
-  // per-sample gains: one float4 per lane
-  if (p.elem_ramp || p.elem2_ramp || p.out_ramp) {
-    if (p.ramp_stream_stride & 3) return false;
-    if ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) | reinterpret_cast<uintptr_t>(p.out_ramp)) & 15)
-      return false;
-  }
-  // a trimmed frame: every quad that starts below `total` ends inside the samples of the call, in both elements
-  if (p.demix_i0 < 0 || (p.demix_i0 > 0 && p.total >= p.frame_size)) return false;
-  if (p.total < p.frame_size && (int64_t)p.demix_i0 + p.total > p.frame_size) return false;
-  return true;
+  return ramp_quads_ok(p) && trimmed_frame_ok(p, false);
 }
 
 // which HRTF stage a FIR call runs (host): 3 = overlap-save FFT (default), 2 = split-f16 MFMA, 1 = f32 MFMA
@@ -265,24 +287,15 @@ inline bool fast_shape_ok(const RenderParams &p, bool force_generic) {
   if (!p.limiter_on || !p.in || p.out_ch > 2 || p.n_end < kFWin) return false;
   if (p.pre_matrix || p.demix_on) return false;
   if (p.elem_ramp || p.elem2_ramp || p.out_ramp) {  // per-sample gains: the mixing variant reads them 4 at a time
-    if (p.dmx_on || p.fir_taps > 0 || (p.ramp_stream_stride & 3) || (p.elem2_ramp && !p.in2)) return false;
-    if ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) |
-         reinterpret_cast<uintptr_t>(p.out_ramp)) & 15)
-      return false;
+    if (p.dmx_on || p.fir_taps > 0 || (p.elem2_ramp && !p.in2) || !ramp_quads_ok(p)) return false;
   }
-  if (p.in2 && (p.dmx_on || p.fir_taps > 0 || p.m2 > kFIn2 || (reinterpret_cast<uintptr_t>(p.in2) & 15) ||
-                (p.in2_stream_stride & 3) || (p.in2_frame_stride & 3)))
+  if (p.in2 && (p.dmx_on || p.fir_taps > 0 || p.m2 > kFIn2 || !on_grid16(p.in2) || (p.in2_stream_stride & 3) || (p.in2_frame_stride & 3)))
     return false;  // a second element of up to 4 channels rides along (render_fast_kernel<.., IN2>)
-  // (a position that is not a multiple of 16 — a trimmed first frame — from 240 samples on: render_fast.hpp `base`)
-  if (((p.pos0 & 15) && p.pos0 < kDelay) || (p.total & 63) || (p.frame_size & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  {  // the kernel addresses a stream's input of one call with 32-bit byte offsets (buffer loads, render_fast.hpp)
-    const int64_t frames = (int64_t)p.total / p.frame_size + 2;
-    if (frames * p.in_frame_stride * 4 + 100 * (int64_t)p.frame_size >= (int64_t)1 << 31) return false;
-    if (p.lpcm && frames * p.lpcm_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
-  }
-  return true;
+  if (!pos_ok(p) || (p.total & 63) || (p.frame_size & 3)) return false;
+  if (!on_grid16(p.in) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
+  if (!pcm_rows_ok(p)) return false;
+  // the kernel addresses a stream's input of one call with 32-bit byte offsets
+  return f32_offsets32_ok(p) && (!p.lpcm || packet_offsets32_ok(p, p.lpcm_frame_stride));
 }
 
 // What the interleaved, ragged form of the fast kernel (render_fast.hpp, IL and RAG) needs of a call that came through
@@ -296,9 +309,7 @@ inline bool interleaved_shape_ok(const RenderParams &p, int m, bool force_generi
   if (p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe || p.lpcm)
     return false;
   if (p.frame_size != 1 || p.in_frame_stride != m) return false;   // dense: sample-frame k of the call at float k * m
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  if ((p.pos0 & 15) && p.pos0 < kDelay) return false;
+  if (!on_grid16(p.in) || (p.in_stream_stride & 3) || !pcm_rows_ok(p) || !pos_ok(p)) return false;
   // the kernel addresses a stream's input of one call with 32-bit byte offsets, and its buffer resource ends with the call
   if (p.total < 1 || (int64_t)p.total * m * 4 + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
   return true;
@@ -313,110 +324,50 @@ inline bool interleaved_shape_ok(const RenderParams &p, int m, bool force_generi
 // below `total` ends inside its row (iamf_render_ragged.hip).  IAMF_HIP_RAGGED_UNFUSED=1 sends every such call down the
 // rules below.
 inline bool ragged_shape_ok(const RenderParams &p, int m, bool force_generic) {
-  if (p.ragged != 1 || force_generic || getenv("IAMF_HIP_RAGGED_UNFUSED")) return false;   // (2: the packet entry's mark, below)
+  if (p.ragged != kCallRagged || force_generic || getenv("IAMF_HIP_RAGGED_UNFUSED")) return false;
   if (!p.limiter_on || !p.in || !RaggedOC::has(p.out_ch) || !RaggedM::has(m) || p.og_ch < p.out_ch || p.n_end < kFWin) return false;
   if (p.in2 || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe || p.lpcm)
     return false;
-  if (p.total < 1 || !(p.total & 63) || (p.frame_size & 3)) return false;
-  if ((p.pos0 & 15) && p.pos0 < kDelay) return false;
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  // the kernel addresses a stream's input of one call with 32-bit byte offsets: fast_shape_ok's bound
-  const int64_t frames = (int64_t)p.total / p.frame_size + 2;
-  if (frames * p.in_frame_stride * 4 + 100 * (int64_t)p.frame_size >= (int64_t)1 << 31) return false;
-  return true;
+  if (p.total < 1 || !(p.total & 63) || (p.frame_size & 3) || !pos_ok(p)) return false;
+  if (!on_grid16(p.in) || (p.in_stream_stride & 3) || (p.in_frame_stride & 3) || !pcm_rows_ok(p)) return false;
+  return f32_offsets32_ok(p);   // 32-bit byte offsets: fast_shape_ok's bound
 }
 
 // What the ragged packet form of the fast kernel (render_fast.hpp, RAG with LP) needs of a call that came through
-// iamf_hip_batch_render_packets_ragged (RenderParams::ragged == 2, which that entry alone sets): everything fast_shape_ok asks
-// of a single packet-fed element, with "whole 64-sample blocks" replaced by "any length >= 1 that is NOT a whole number of
-// blocks"; the packet form named by (lpcm_bytes, lpcm_coupled) as the four whole-block families name it, on that form's own
-// grid (lpcm_form.hpp: 8 bytes for 16-bit samples, 4 for 24-bit ones — strides and every run's start, first_sample included);
-// and, what keeps the loads of a trimmed frame inside its runs, first + ((total + 3) & ~3) <= frame_size where the call is
-// shorter than a frame (one frame, n_samples set; `first`, iamf_hip_lpcm_input::first_sample, travels in demix_i0 — "frame
-// position of the call's first sample" — which no packet-fed kernel reads).  A call of whole blocks, and every call this
-// rule does not take, is left to the rules below.  IAMF_HIP_PACKETS_RAGGED_UNFUSED=1 sends every such call down them.
+// iamf_hip_batch_render_packets_ragged (kCallPacketsRagged, which that entry alone sets): everything fast_shape_ok asks of a
+// single packet-fed element, with "whole 64-sample blocks" replaced by "any length >= 1 that is NOT a whole number of blocks";
+// element 0's form (lpcm_elem0_form_ok; lpcm_bytes == 0 reads as 16 bit, as the whole-block families read it); a trimmed frame
+// inside its run with the total rounded up to a quad (trimmed_frame_ok); the packets inside the kernel's 32-bit offsets.  A call
+// of whole blocks, and every call this rule does not take, is left to the rules below.  IAMF_HIP_PACKETS_RAGGED_UNFUSED=1 sends
+// every such call down them.
 inline bool packets_ragged_shape_ok(const RenderParams &p, int m, bool force_generic) {
-  if (p.ragged != 2 || !p.lpcm || force_generic || getenv("IAMF_HIP_PACKETS_RAGGED_UNFUSED")) return false;
+  if (p.ragged != kCallPacketsRagged || !p.lpcm || force_generic || getenv("IAMF_HIP_PACKETS_RAGGED_UNFUSED")) return false;
   if (!p.limiter_on || !p.in || !LpcmOC::has(p.out_ch) || p.og_ch < p.out_ch || p.n_end < kFWin) return false;
   if (p.in2 || p.lpcm_mix || p.elem_ramp || p.elem2_ramp || p.out_ramp || p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe)
     return false;
-  if (p.total < 1 || !(p.total & 63) || p.frame_size < 4 || (p.frame_size & 3)) return false;
-  if ((p.pos0 & 15) && p.pos0 < kDelay) return false;
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (reinterpret_cast<uintptr_t>(p.lpcm) & 15)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  // the form: 16-bit mono-coded (LpcmM), 16-bit coupled (lpcm_coupled == 1), 24-bit mono-coded, 24-bit coupled (== 2)
-  const bool s24 = p.lpcm_bytes == 3;
-  if (!s24 && p.lpcm_bytes != 0 && p.lpcm_bytes != 2) return false;
-  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (s24 ? 2 : 1)) return false;
-  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
-  const int grid = s24 ? 3 : 7;
-  if ((p.lpcm_stream_stride & grid) || (p.lpcm_frame_stride & grid) || p.lpcm_frame_stride <= 0) return false;
-  for (int c = 0; c < m; ++c) {   // a pair's second channel lies sample_bytes behind its first: the pair's one run starts at the first
-    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
-      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + (s24 ? 3 : 2)) return false;
-    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
-  }
-  // a trimmed frame: the last quad that starts below `total` ends inside the run of frame_size samples
-  if (p.demix_i0 < 0 || (p.demix_i0 > 0 && p.total >= p.frame_size)) return false;
-  if (p.total < p.frame_size && (int64_t)p.demix_i0 + ((p.total + 3) & ~3) > p.frame_size) return false;
-  // the kernel addresses a stream's packets of one call with 32-bit byte offsets: fast_shape_ok's bound
-  const int64_t frames = (int64_t)p.total / p.frame_size + 2;
-  if (frames * p.lpcm_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
-  return true;
+  if (p.total < 1 || !(p.total & 63) || p.frame_size < 4 || (p.frame_size & 3) || !pos_ok(p)) return false;
+  if (!on_grid16(p.in) || !pcm_rows_ok(p)) return false;
+  return lpcm_elem0_form_ok(p, m, true) && trimmed_frame_ok(p, true) && packet_offsets32_ok(p, p.lpcm_frame_stride);
 }
 
 // What the ragged two-element packet form of the fast kernel (render_fast.hpp, RAG with LP and LP2) needs of a call that came
-// through iamf_hip_batch_render_packets_mix_ragged (RenderParams::ragged == 3, which that entry alone sets): everything the
-// whole-block mix rules (Family::LpcmMix, Family::Lpcm24Mix) ask of the call, with "whole 64-sample blocks" replaced by "any
-// length >= 1 that is NOT a whole number of blocks".  lpcm_mix names element 1's form (LP2, or 4 | LP2 with 24-bit samples on
-// both elements) and matches lpcm_bytes; the bed is in LpcmM or LpcmCoupledM, element 1 as lpcm_mix_m2_ok() has it; both
-// elements on their sample size's grid (8 bytes / 4 bytes: the buffers, the strides, element 0's run starts with first_sample in
-// them — element 1's run starts travel behind this block, RenderMixParams::lpcm2_off, and are held to the same grid by the
-// form check that let the call come here, lpcm_form.hpp); ramp rows on the 16-byte grid with a stride that is a multiple of
-// 4; and, what keeps the loads of a trimmed frame inside the runs of both elements, first + ((total + 3) & ~3) <= frame_size
-// where the call is shorter than a frame (`first` travels in demix_i0, as for packets_ragged_shape_ok: the two inputs of a
-// mix call share it).  A call of whole blocks, and every call this rule does not take, is left to the rules below.
-// IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED=1 sends every such call down them.
+// through iamf_hip_batch_render_packets_mix_ragged (kCallPacketsMixRagged, which that entry alone sets): everything
+// packets_ragged_shape_ok asks, with a second element given as packets in place of "no second element, no ramps" — lpcm_mix names
+// its form (lpcm_mix_form_ok); its rows on element 0's grid (its run starts travel behind this block, RenderMixParams::lpcm2_off,
+// and are held to the same grid by the form check that let the call come here, lpcm_form.hpp) and inside the same 32-bit bound —
+// and ramps, where given, as ramp_quads_ok has them (the call's last quad is read float by float).  The trimmed frame's rule holds
+// for both elements (one first_sample).  A call of whole blocks, and every call this rule does not take, is left to the rules
+// below.  IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED=1 sends every such call down them.
 inline bool packets_mix_ragged_shape_ok(const RenderParams &p, int m, bool force_generic) {
-  if (p.ragged != 3 || !p.lpcm || force_generic || getenv("IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED")) return false;
+  if (p.ragged != kCallPacketsMixRagged || !p.lpcm || force_generic || getenv("IAMF_HIP_PACKETS_MIX_RAGGED_UNFUSED")) return false;
   if (!p.limiter_on || !p.in || !LpcmOC::has(p.out_ch) || p.og_ch < p.out_ch || p.n_end < kFWin) return false;
   if (p.dmx_on || p.demix_on || p.pre_matrix || p.fir_taps > 0 || p.lfe) return false;
-  if (p.total < 1 || !(p.total & 63) || p.frame_size < 4 || (p.frame_size & 3)) return false;
-  if ((p.pos0 & 15) && p.pos0 < kDelay) return false;
-  if ((reinterpret_cast<uintptr_t>(p.in) & 15) || (reinterpret_cast<uintptr_t>(p.lpcm) & 15)) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
-  // the forms: 16 bit (lpcm_mix == LP2) or 24 bit (lpcm_mix == 4 | LP2) on both elements, the bed mono-coded or coupled
-  const bool s24 = p.lpcm_bytes == 3;
-  if (!s24 && p.lpcm_bytes != 0 && p.lpcm_bytes != 2) return false;
-  const int lp2 = p.lpcm_mix & 3;
-  if (p.lpcm_mix != ((s24 ? 4 : 0) | lp2) || !LpcmMixK::has(lp2)) return false;
-  if (!p.in2 || !lpcm_mix_m2_ok(lp2, p.m2)) return false;
-  if (p.lpcm_coupled != 0 && p.lpcm_coupled != (s24 ? 2 : 1)) return false;
-  if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m))) return false;
-  const int grid = s24 ? 3 : 7;
-  if ((p.lpcm_stream_stride & grid) || (p.lpcm_frame_stride & grid) || p.lpcm_frame_stride <= 0) return false;
-  for (int c = 0; c < m; ++c) {   // a pair's second channel lies sample_bytes behind its first: the pair's one run starts at the first
-    if (p.lpcm_coupled && lpcm_coupled_paired(m, c) && (c & 1)) {
-      if (p.lpcm_off[c] != p.lpcm_off[c - 1] + (s24 ? 3 : 2)) return false;
-    } else if (p.lpcm_off[c] < 0 || (p.lpcm_off[c] & grid)) return false;
-  }
-  if ((reinterpret_cast<uintptr_t>(p.in2) & 15) || (p.in2_stream_stride & grid) || (p.in2_frame_stride & grid) || p.in2_frame_stride <= 0)
-    return false;
-  // per-sample gains: read four at a time, the call's last quad float by float
-  if (p.elem_ramp || p.elem2_ramp || p.out_ramp) {
-    if (p.ramp_stream_stride & 3) return false;
-    if ((reinterpret_cast<uintptr_t>(p.elem_ramp) | reinterpret_cast<uintptr_t>(p.elem2_ramp) | reinterpret_cast<uintptr_t>(p.out_ramp)) & 15)
-      return false;
-  }
-  // a trimmed frame: the last quad that starts below `total` ends inside the run of frame_size samples, in both elements
-  if (p.demix_i0 < 0 || (p.demix_i0 > 0 && p.total >= p.frame_size)) return false;
-  if (p.total < p.frame_size && (int64_t)p.demix_i0 + ((p.total + 3) & ~3) > p.frame_size) return false;
-  // the kernel addresses a stream's packets of one call with 32-bit byte offsets, either element's: fast_shape_ok's bound
-  const int64_t frames = (int64_t)p.total / p.frame_size + 2;
-  if (frames * p.lpcm_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
-  if (frames * p.in2_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31) return false;
-  return true;
+  if (p.total < 1 || !(p.total & 63) || p.frame_size < 4 || (p.frame_size & 3) || !pos_ok(p)) return false;
+  if (!on_grid16(p.in) || !pcm_rows_ok(p)) return false;
+  if (!lpcm_elem0_form_ok(p, m, true) || !lpcm_mix_form_ok(p)) return false;
+  if (!packet_rows_ok(p.in2, p.in2_stream_stride, p.in2_frame_stride, lpcm_grid(p))) return false;
+  if (!ramp_quads_ok(p) || !trimmed_frame_ok(p, true)) return false;
+  return packet_offsets32_ok(p, p.lpcm_frame_stride) && packet_offsets32_ok(p, p.in2_frame_stride);
 }
 
 // What the wide kernels (render_wide.hpp, render_wide4.hpp) share: 3..24 output channels, limiter on, aligned calls.
@@ -426,8 +377,7 @@ inline bool wide_shape_ok(const RenderParams &p, int m, bool force_generic) {
   if (force_generic || p.og_ch < p.out_ch) return false;
   if (!p.limiter_on || !p.in || p.out_ch <= 2 || p.out_ch > kMaxOut || p.n_end < kWWin) return false;
   if (p.pre_matrix) return false;
-  if (p.total & 63) return false;
-  if ((reinterpret_cast<uintptr_t>(p.pcm) & 15) || (p.pcm_stream_stride & 15)) return false;
+  if ((p.total & 63) || !pcm_rows_ok(p)) return false;
   return sizeof(float) * (size_t)wide_lds_floats(p.out_ch, m) <= 80 * 1024;
 }
 
@@ -483,23 +433,23 @@ enum class Family {
   FastRagged,   // render_fast_kernel<M, OC, .., IL = false, RAG = true> (iamf_render_ragged.hip): planar f32 of any call length that
                 // is no whole number of 64-sample blocks, RenderParams::ragged.  Set 6, listed by family only
   Lpcm24Coupled,  // render_fast_kernel<.., LP, EARLY, 3, LPC> (iamf_render_lpcm24_coupled.hip): RenderParams::lpcm_coupled == 2,
-                // which only iamf_hip_batch_render_packets sets; variant as Lpcm.  Set 7 (kRouteSetsAll), listed by family only
+                // which only iamf_hip_batch_render_packets sets; variant as Lpcm.  Set 7, listed by family only
   Lpcm24Mix,    // render_fast_kernel<.., LP, true, 3, LPC, LP2> (iamf_render_lpcm24_mix.hip, iamf_render_lpcm24_mix_coupled.hip): both
                 // elements of a mix as 24-bit packets, RenderParams::lpcm_mix == (4 | LP2), which only
-                // iamf_hip_batch_render_packets_mix sets; variant = LP2.  Set 8 (kRouteSetsBuilt), listed by family only
+                // iamf_hip_batch_render_packets_mix sets; variant = LP2.  Set 8, listed by family only
   PacketsRagged,  // render_fast_kernel<.., LP, true, LPB, LPC, 0, false, RAG = true> (iamf_render_packets_ragged*.hip): one element as
-                // packets of any call length that is no whole number of 64-sample blocks, RenderParams::ragged == 2, which only
-                // iamf_hip_batch_render_packets_ragged sets; variant 0.  Set 9 (kRouteSetsLaunched), listed by family only
+                // packets of any call length that is no whole number of 64-sample blocks, kCallPacketsRagged, which only
+                // iamf_hip_batch_render_packets_ragged sets; variant 0.  Set 9, listed by family only
   PacketsMixRagged,  // render_fast_kernel<.., IN2, LP, true, LPB, LPC, LP2, false, RAG = true> (iamf_render_packets_mix_ragged*.hip):
                 // both elements of a mix as packets of any call length that is no whole number of 64-sample blocks,
-                // RenderParams::ragged == 3, which only iamf_hip_batch_render_packets_mix_ragged sets; variant = LP2.  Set 10
-                // (kRouteSetsListed), listed by family only
+                // kCallPacketsMixRagged, which only iamf_hip_batch_render_packets_mix_ragged sets; variant = LP2.  Set 10, listed by
+                // family only
   NolimPackets,  // render_nolim_kernel<M, LPB, LPC> (iamf_render_nolim_packets*.hip): the limiter-less renderer over one
-                // element's packets, RenderParams::ragged == 4, which only iamf_hip_batch_render_packets_nolim sets; variant 0.
-                // Set 11 (kRouteSetsEvery), listed by family only
+                // element's packets, kCallPacketsNolim, which only iamf_hip_batch_render_packets_nolim sets; variant 0.  Set 11,
+                // listed by family only
   NolimPacketsMix,  // render_nolim_kernel<M, LPB, LPC, LP2> (iamf_render_nolim_packets*_mix.hip): the limiter-less renderer over both
-                // elements' packets, RenderParams::ragged == 5, which only iamf_hip_batch_render_packets_mix_nolim sets; variant =
-                // LP2.  Set 12 (kRouteSetsTotal), listed by family only
+                // elements' packets, kCallPacketsMixNolim, which only iamf_hip_batch_render_packets_mix_nolim sets; variant = LP2.
+                // Set 12, listed by family only
 };
 struct Route {
   Family family;
@@ -710,68 +660,53 @@ inline Route pick_route(const RenderParams &p, int m) {
   // it): the same way
   if (ragged_shape_ok(p, m, force_generic)) return take(Family::FastRagged);
 
-  // one element as packets, no whole number of 64-sample blocks (RenderParams::ragged == 2, which only
+  // one element as packets, no whole number of 64-sample blocks (kCallPacketsRagged, which only
   // iamf_hip_batch_render_packets_ragged sets): the same way, in front of the packet rules, which refuse such a length
   if (packets_ragged_shape_ok(p, m, force_generic)) return take(Family::PacketsRagged);
-  // both elements of a mix as packets, no whole number of 64-sample blocks (RenderParams::ragged == 3, which only
+  // both elements of a mix as packets, no whole number of 64-sample blocks (kCallPacketsMixRagged, which only
   // iamf_hip_batch_render_packets_mix_ragged sets): the same way, in front of the packet-mix rules, which refuse such a length
   if (packets_mix_ragged_shape_ok(p, m, force_generic)) return take(Family::PacketsMixRagged, p.lpcm_mix & 3);
-  // one element as packets on a limiter-less batch (RenderParams::ragged == 4, which only iamf_hip_batch_render_packets_nolim sets):
+  // one element as packets on a limiter-less batch (kCallPacketsNolim, which only iamf_hip_batch_render_packets_nolim sets):
   // the same way, in front of the packet rules, which refuse a batch without the limiter
   if (nolim_packets_shape_ok(p, m, force_generic)) return take(Family::NolimPackets);
-  // (both elements as packets on such a batch, RenderParams::ragged == 5: the rule reads the second element's run starts, which
+  // (both elements as packets on such a batch, kCallPacketsMixNolim: the rule reads the second element's run starts, which
   //  travel behind this block — pick_route(const RenderMixParams &) below asks it, here, in front of the packet rules)
 
   // element 0 as LPCM packets: only the fused kernel reads them (render_prepare asks here and unpacks to f32 otherwise)
   if (p.lpcm) {
-    // both elements as 16-bit packets (RenderParams::lpcm_mix, zero unless iamf_hip_batch_render_lpcm_mix set it): the
-    // refusals of the single-element forms, element 1's packets on the same grid and inside the same 32-bit offset bound as
-    // element 0's (fast_shape_ok), ramps under fast_shape_ok's rules
-    // both elements as 24-bit packets (lpcm_mix == (4 | LP2) with lpcm_bytes == 3, lpcm_coupled == 2 for a coupled bed: values of
-    // the form's own, set by iamf_hip_batch_render_packets_mix alone — 4 | LP2 with any other sample size or coupling names
-    // no form): the refusals of Family::LpcmMix, element 1's packets on the dword grid and inside the same 32-bit bound
-    if (p.lpcm_mix >= 4) {
-      const int lp2 = p.lpcm_mix - 4;
-      if (p.lpcm_bytes != 3 || (p.lpcm_coupled != 0 && p.lpcm_coupled != 2) ||
-          !(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m)) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on)
-        return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      if (!p.in2 || !LpcmMixK::has(lp2) || !lpcm_mix_m2_ok(lp2, p.m2)) return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      if ((reinterpret_cast<uintptr_t>(p.in2) & 15) || (p.in2_stream_stride & 3) || (p.in2_frame_stride & 3))
-        return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      if (((int64_t)p.total / p.frame_size + 2) * p.in2_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31)
-        return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      return take(Family::Lpcm24Mix, lp2);
-    }
+    const bool elem0_listed = p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m);
+    const bool fast_call = LpcmOC::has(p.out_ch) && fast_shape && !p.dmx_on;   // what every whole-block packet form refuses otherwise
+    // both elements as packets (RenderParams::lpcm_mix, zero unless an entry of the two-element forms set it): LP2 with 16-bit
+    // samples (iamf_hip_batch_render_lpcm_mix), 4 | LP2 with 24-bit samples on both elements and lpcm_coupled == 2 for a coupled bed
+    // (values of the form's own, set by iamf_hip_batch_render_packets_mix alone — 4 | LP2 with any other sample size or coupling
+    // names no form).  The refusals of the single-element forms; element 1's packets on the sample size's grid (8 bytes / 4 bytes) and
+    // inside the same 32-bit offset bound as element 0's (fast_shape_ok); ramps under fast_shape_ok's rules
     if (p.lpcm_mix) {
-      if (!(p.lpcm_coupled ? LpcmCoupledM::has(m) : LpcmM::has(m)) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on ||
-          p.lpcm_bytes == 3)
-        return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      if (!p.in2 || !LpcmMixK::has(p.lpcm_mix) || !lpcm_mix_m2_ok(p.lpcm_mix, p.m2)) return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      if ((reinterpret_cast<uintptr_t>(p.in2) & 15) || (p.in2_stream_stride & 7) || (p.in2_frame_stride & 7))
-        return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      if (((int64_t)p.total / p.frame_size + 2) * p.in2_frame_stride + ((int64_t)1 << 24) >= (int64_t)1 << 31)
-        return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      return take(Family::LpcmMix, p.lpcm_mix);
+      const bool s24 = p.lpcm_mix >= 4;
+      const int lp2 = s24 ? p.lpcm_mix - 4 : p.lpcm_mix;
+      const bool sizes = s24 ? p.lpcm_bytes == 3 && (p.lpcm_coupled == 0 || p.lpcm_coupled == 2) : p.lpcm_bytes != 3;
+      if (!sizes || !elem0_listed || !fast_call) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if (!p.in2 || !LpcmMixK::has(lp2) || !lpcm_mix_m2_ok(lp2, p.m2)) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if (!on_grid16(p.in2) || (p.in2_stream_stride & (s24 ? 3 : 7)) || (p.in2_frame_stride & (s24 ? 3 : 7))) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      if (!packet_offsets32_ok(p, p.in2_frame_stride)) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      return take(s24 ? Family::Lpcm24Mix : Family::LpcmMix, lp2);
     }
     // the coupled 24-bit form (lpcm_coupled == 2, set by iamf_hip_batch_render_packets alone, and 24-bit samples — 2 with any
     // other sample size names no form): the coupled instances' lists under exactly the refusals of Family::Lpcm24
     if (p.lpcm_coupled == 2) {
-      if (p.lpcm_bytes != 3 || !LpcmCoupledM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on)
-        return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      return take(Family::Lpcm24Coupled, !getenv("IAMF_HIP_LP_LATE") && (getenv("IAMF_HIP_LP_EARLY") || lpcm24_coupled_early(p.n_launch)));
+      if (p.lpcm_bytes != 3 || !elem0_listed || !fast_call) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      return take(Family::Lpcm24Coupled, lp_early_variant(lpcm24_coupled_early(p.n_launch)));
     }
     // the coupled 16-bit form: its own instances (the pairing is a function of m: lpcm_form.hpp), the same refusals
     if (p.lpcm_coupled) {
-      if (!LpcmCoupledM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on || p.lpcm_bytes == 3)
-        return refuse(IAMF_HIP_ERR_INVALID_STATE);
-      return take(Family::LpcmCoupled, !getenv("IAMF_HIP_LP_LATE") && (getenv("IAMF_HIP_LP_EARLY") || lpcm_coupled_early(p.n_launch)));
+      if (!elem0_listed || !fast_call || p.lpcm_bytes == 3) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+      return take(Family::LpcmCoupled, lp_early_variant(lpcm_coupled_early(p.n_launch)));
     }
-    if (!LpcmM::has(m) || !LpcmOC::has(p.out_ch) || !fast_shape || p.dmx_on) return refuse(IAMF_HIP_ERR_INVALID_STATE);
+    if (!elem0_listed || !fast_call) return refuse(IAMF_HIP_ERR_INVALID_STATE);
     // 24-bit samples (lpcm_bytes: 0 or 2 = 16 bit): the same instances and refusals, the kernel's LPB = 3 form
     // (IAMF_HIP_LP_EARLY=1 forces the early variant as IAMF_HIP_LP_LATE=1 forces the late one: tools/lpcm24_rate.py times both
     //  at every size, and the tests run both whatever the cut)
-    if (p.lpcm_bytes == 3)
-      return take(Family::Lpcm24, !getenv("IAMF_HIP_LP_LATE") && (getenv("IAMF_HIP_LP_EARLY") || lpcm24_early(p.n_launch)));
+    if (p.lpcm_bytes == 3) return take(Family::Lpcm24, lp_early_variant(lpcm24_early(p.n_launch)));
     // up to four workgroups a CU: the early per-channel prefetch (latency bound); beyond: the plain one (issue bound).
     // Measured on MI355X, 512 / 4096 streams: 117 against 109 / 136 against 145 Gsamples/s (profiles/r04_ab_fast.txt)
     return take(Family::Lpcm, p.n_launch <= 1024 && !getenv("IAMF_HIP_LP_LATE"));
@@ -798,7 +733,7 @@ inline Route pick_route(const RenderParams &p, int m) {
   // of 16 from 240 samples on; the 256-sample kernel of render_wide.hpp keeps absolute ring positions and needs the
   // stream at a multiple of 16
   const bool pos16 = !(p.pos0 & 15);
-  const bool pos_any = pos16 || p.pos0 >= kDelay;
+  const bool pos_any = pos_ok(p);
 
   // an LFE slot is filled by render_wide4_kernel<.., LFE> where that exists, else by the generic kernel
   if (p.lfe) {
@@ -827,6 +762,15 @@ inline Route pick_route(const RenderParams &p, int m) {
   // everything else: ragged calls, flush, wide second elements, exact two-stage projection, demixer + down-mixer
   // together, other PCM formats of the stages above
   return GenericM::has(m) ? take(Family::Generic) : refuse(IAMF_HIP_ERR_UNIMPLEMENTED);
+}
+
+// The same for the block launch() holds: both elements as packets on a limiter-less batch (kCallPacketsMixNolim, which only
+// iamf_hip_batch_render_packets_mix_nolim sets) take the two-element form of the limiter-less renderer where
+// nolim_packets_mix_shape_ok holds — the marks exclude one another, so its place among the marked rules above does not matter —
+// and every other block is routed by the rules above, the mark meaning nothing to them.
+inline Route pick_route(const RenderMixParams &p, int m) {
+  if (nolim_packets_mix_shape_ok(p, m, getenv("IAMF_HIP_FORCE_GENERIC") != nullptr)) return Route{Family::NolimPacketsMix, p.lpcm_mix & 3, IAMF_HIP_OK};
+  return pick_route(static_cast<const RenderParams &>(p), m);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -870,6 +814,14 @@ void for_each_render_instance_ext(F &&f) {
   for_each_int(FanLpM{}, [&](int m) { for_each_int(FanLpK{}, [&](int k) { f(IAMF_HIP_ROUTE_FANOUT_LPCM, 0, m, 0, k); }); });
 }
 
+// The rows of a packet form over element 0's shapes: f(m) for LpcmM (mono-coded), then LpcmCoupledM (coupled) — the two lists
+// share no number, so m tells the one from the other — as the form's launchers walk them.
+template <class F>
+void for_each_packet_m(F &&rows) {
+  for_each_int(LpcmM{}, rows);
+  for_each_int(LpcmCoupledM{}, rows);
+}
+
 // Table 2 (iamf_hip_route_table_instances): the 24-bit LPCM form, walking LpcmM x LpcmOC as its launcher does.
 template <class F>
 void for_each_render_instance_lpcm24(F &&f) {
@@ -877,49 +829,88 @@ void for_each_render_instance_lpcm24(F &&f) {
     for_each_int(LpcmM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM24, early, m, oc, 0); }); });
 }
 
-// The coupled 16-bit LPCM form (iamf_hip_route_family_instances), walking LpcmCoupledM x LpcmOC as its launcher does.
+// The forms below are listed by family only (iamf_hip_route_family_instances), each walking its lists as its launchers do.
+// The coupled 16-bit LPCM form: LpcmCoupledM x LpcmOC.
 template <class F>
 void for_each_render_instance_lpcm_coupled(F &&f) {
   for (int early = 0; early < 2; ++early)
     for_each_int(LpcmCoupledM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM_COUPLED, early, m, oc, 0); }); });
 }
 
-// The two-element packet form (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x LpcmOC x LpcmMixK as its
-// two launchers do; k = LP2.
+// The two-element packet form: element 0's shapes x LpcmOC x LpcmMixK; k = LP2.
 template <class F>
 void for_each_render_instance_lpcm_mix(F &&f) {
-  const auto rows = [&](int m) {
+  for_each_packet_m([&](int m) {
     for_each_int(LpcmOC{}, [&](int oc) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_LPCM_MIX, 0, m, oc, k); }); });
-  };
-  for_each_int(LpcmM{}, rows);
-  for_each_int(LpcmCoupledM{}, rows);
+  });
 }
 
-// The interleaved form (iamf_hip_route_family_instances), walking InterleavedM x InterleavedOC as its launcher does.
+// The interleaved form: InterleavedM x InterleavedOC.
 template <class F>
 void for_each_render_instance_interleaved(F &&f) {
   for_each_int(InterleavedM{}, [&](int m) { for_each_int(InterleavedOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_FAST_INTERLEAVED, 0, m, oc, 0); }); });
 }
 
-// The planar ragged form (iamf_hip_route_family_instances), walking RaggedM x RaggedOC as its launcher does.
+// The planar ragged form: RaggedM x RaggedOC.
 template <class F>
 void for_each_render_instance_ragged(F &&f) {
   for_each_int(RaggedM{}, [&](int m) { for_each_int(RaggedOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_FAST_RAGGED, 0, m, oc, 0); }); });
 }
 
-// The coupled 24-bit LPCM form (iamf_hip_route_family_instances), walking LpcmCoupledM x LpcmOC as its launcher does.
+// The coupled 24-bit LPCM form: LpcmCoupledM x LpcmOC.
 template <class F>
 void for_each_render_instance_lpcm24_coupled(F &&f) {
   for (int early = 0; early < 2; ++early)
     for_each_int(LpcmCoupledM{}, [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_LPCM24_COUPLED, early, m, oc, 0); }); });
 }
 
-// The row sets behind the listing, by number: f as above for every instance of set `set`.  Sets 0 .. kRouteTables - 1 are
-// the numbered tables of iamf_hip_route_table_instances — their count and the rows of each are pinned — and the sets behind
-// them are listed by family only (iamf_hip_route_family_instances), in this order.  The only place that maps a set number
-// to a walker: iamf_route.hip builds and counts by it, and every key is in exactly one set (tests/route_host).
+// The two-element 24-bit packet form: element 0's shapes x LpcmOC x LpcmMixK; k = LP2.
+template <class F>
+void for_each_render_instance_lpcm24_mix(F &&f) {
+  for_each_packet_m([&](int m) {
+    for_each_int(LpcmOC{}, [&](int oc) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_LPCM24_MIX, 0, m, oc, k); }); });
+  });
+}
+
+// The ragged packet form: element 0's shapes x LpcmOC, the 16-bit units first; k = bytes per packet sample.
+template <class F>
+void for_each_render_instance_packets_ragged(F &&f) {
+  for (int k = 2; k <= 3; ++k)
+    for_each_packet_m([&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_PACKETS_RAGGED, 0, m, oc, k); }); });
+}
+
+// The ragged two-element packet form: element 0's shapes x LpcmOC x LpcmMixK, the 16-bit units first; variant = bytes per packet
+// sample, k = LP2.
+template <class F>
+void for_each_render_instance_packets_mix_ragged(F &&f) {
+  for (int v = 2; v <= 3; ++v)
+    for_each_packet_m([&](int m) {
+      for_each_int(LpcmOC{}, [&](int oc) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED, v, m, oc, k); }); });
+    });
+}
+
+// The packet-fed limiter-less renderer: element 0's shapes, the 16-bit unit first; k = bytes per packet sample.  The output
+// channel count and format are run-time values of the kernel: c = 0, as for the f32 form's rows.
+template <class F>
+void for_each_render_instance_nolim_packets(F &&f) {
+  for (int k = 2; k <= 3; ++k) for_each_packet_m([&](int m) { f(IAMF_HIP_ROUTE_NOLIM_PACKETS, 0, m, 0, k); });
+}
+
+// The two-element packet form of the limiter-less renderer: element 0's shapes x LpcmMixK, the 16-bit unit first; variant = bytes
+// per packet sample, k = LP2, c = 0 (the output channel count and format are run-time values of the kernel).
+template <class F>
+void for_each_render_instance_nolim_packets_mix(F &&f) {
+  for (int v = 2; v <= 3; ++v)
+    for_each_packet_m([&](int m) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX, v, m, 0, k); }); });
+}
+
+// The row sets behind the listing, by number: f as above for every instance of set `set`, no row for any other number.  Sets
+// 0 .. kRouteTables - 1 are the numbered tables of iamf_hip_route_table_instances — their count and the rows of each are pinned —
+// and the sets behind them are listed by family only (iamf_hip_route_family_instances), in this order.  The only place that maps
+// a set number to a walker: iamf_route.hip builds and counts by it, and every key is in exactly one set (tests/route_host).  A
+// form added later is one more case and one more set; the numbers in front of it stay.
 constexpr int kRouteTables = 3;
-constexpr int kRouteSets = 7;
+constexpr int kRouteSets = 13;
 template <class F>
 void for_each_instance_of_set(int set, F &&f) {
   switch (set) {
@@ -930,136 +921,13 @@ void for_each_instance_of_set(int set, F &&f) {
     case 4: for_each_render_instance_lpcm_mix(f); break;
     case 5: for_each_render_instance_interleaved(f); break;
     case 6: for_each_render_instance_ragged(f); break;
+    case 7: for_each_render_instance_lpcm24_coupled(f); break;
+    case 8: for_each_render_instance_lpcm24_mix(f); break;
+    case 9: for_each_render_instance_packets_ragged(f); break;
+    case 10: for_each_render_instance_packets_mix_ragged(f); break;
+    case 11: for_each_render_instance_nolim_packets(f); break;
+    case 12: for_each_render_instance_nolim_packets_mix(f); break;
   }
-}
-
-// The sets for_each_instance_of_set walks are pinned at seven, and so is the answer "no row" for every other number.  Sets added
-// since are walked here: numbers kRouteSets .. kRouteSetsAll - 1, listed by family only like the sets behind the numbered
-// tables.  What iamf_route.hip builds and counts by.
-constexpr int kRouteSetsAll = 8;
-template <class F>
-void for_each_instance_of_any_set(int set, F &&f) {
-  if (set == 7) for_each_render_instance_lpcm24_coupled(f);
-  else for_each_instance_of_set(set, f);
-}
-
-// The two-element 24-bit packet form (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x LpcmOC x LpcmMixK
-// as its two launchers do; k = LP2.
-template <class F>
-void for_each_render_instance_lpcm24_mix(F &&f) {
-  const auto rows = [&](int m) {
-    for_each_int(LpcmOC{}, [&](int oc) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_LPCM24_MIX, 0, m, oc, k); }); });
-  };
-  for_each_int(LpcmM{}, rows);
-  for_each_int(LpcmCoupledM{}, rows);
-}
-
-// The answers of for_each_instance_of_any_set are pinned in their turn — eight sets, "no row" for every other number — so the
-// sets added since are walked by a third walker: numbers kRouteSetsAll .. kRouteSetsBuilt - 1, listed by family only.  What
-// iamf_route.hip builds and counts by.
-constexpr int kRouteSetsBuilt = 9;
-template <class F>
-void for_each_instance_of_built_set(int set, F &&f) {
-  if (set == 8) for_each_render_instance_lpcm24_mix(f);
-  else for_each_instance_of_any_set(set, f);
-}
-
-// The ragged packet form (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x LpcmOC as its launchers do, the
-// 16-bit units first; k = bytes per packet sample (m tells mono-coded from coupled: the two lists share no number).
-template <class F>
-void for_each_render_instance_packets_ragged(F &&f) {
-  for (int k = 2; k <= 3; ++k) {
-    const auto rows = [&](int m) { for_each_int(LpcmOC{}, [&](int oc) { f(IAMF_HIP_ROUTE_PACKETS_RAGGED, 0, m, oc, k); }); };
-    for_each_int(LpcmM{}, rows);
-    for_each_int(LpcmCoupledM{}, rows);
-  }
-}
-
-// The answers of for_each_instance_of_built_set are pinned as well — nine sets, "no row" for every other number — so the sets
-// added since are walked by a fourth walker: numbers kRouteSetsBuilt .. kRouteSetsLaunched - 1, listed by family only.  What
-// iamf_route.hip builds and counts by.
-constexpr int kRouteSetsLaunched = 10;
-template <class F>
-void for_each_instance_of_launched_set(int set, F &&f) {
-  if (set == 9) for_each_render_instance_packets_ragged(f);
-  else for_each_instance_of_built_set(set, f);
-}
-
-// The ragged two-element packet form (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x LpcmOC x LpcmMixK as
-// its launchers do, the 16-bit units first; variant = bytes per packet sample, k = LP2 (m tells a mono-coded bed from a coupled
-// one: the two lists share no number).
-template <class F>
-void for_each_render_instance_packets_mix_ragged(F &&f) {
-  for (int v = 2; v <= 3; ++v) {
-    const auto rows = [&](int m) {
-      for_each_int(LpcmOC{}, [&](int oc) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED, v, m, oc, k); }); });
-    };
-    for_each_int(LpcmM{}, rows);
-    for_each_int(LpcmCoupledM{}, rows);
-  }
-}
-
-// The answers of for_each_instance_of_launched_set are pinned too — ten sets, "no row" for every other number — so the sets
-// added since are walked by a fifth walker: numbers kRouteSetsLaunched .. kRouteSetsListed - 1, listed by family only.  What
-// iamf_route.hip builds and counts by.
-constexpr int kRouteSetsListed = 11;
-template <class F>
-void for_each_instance_of_listed_set(int set, F &&f) {
-  if (set == 10) for_each_render_instance_packets_mix_ragged(f);
-  else for_each_instance_of_launched_set(set, f);
-}
-
-// The packet-fed limiter-less renderer (iamf_hip_route_family_instances), walking LpcmM, then LpcmCoupledM as its launchers do, the
-// 16-bit unit first; k = bytes per packet sample (m tells mono-coded from coupled: the two lists share no number).  The output
-// channel count and format are run-time values of the kernel: c = 0, as for the f32 form's rows.
-template <class F>
-void for_each_render_instance_nolim_packets(F &&f) {
-  for (int k = 2; k <= 3; ++k) {
-    const auto rows = [&](int m) { f(IAMF_HIP_ROUTE_NOLIM_PACKETS, 0, m, 0, k); };
-    for_each_int(LpcmM{}, rows);
-    for_each_int(LpcmCoupledM{}, rows);
-  }
-}
-
-// The answers of for_each_instance_of_listed_set are pinned like the others — eleven sets, "no row" for every other number — so
-// the sets added since are walked by a sixth walker: numbers kRouteSetsListed .. kRouteSetsEvery - 1, listed by family only.
-// What iamf_route.hip builds and counts by.
-constexpr int kRouteSetsEvery = 12;
-template <class F>
-void for_each_instance_of_every_set(int set, F &&f) {
-  if (set == 11) for_each_render_instance_nolim_packets(f);
-  else for_each_instance_of_listed_set(set, f);
-}
-
-// The same for the block launch() holds: both elements as packets on a limiter-less batch (RenderParams::ragged == 5, which only
-// iamf_hip_batch_render_packets_mix_nolim sets) take the two-element form of the limiter-less renderer where
-// nolim_packets_mix_shape_ok holds — the marks exclude one another, so its place among the marked rules above does not matter —
-// and every other block is routed by the rules above, the mark meaning nothing to them.
-inline Route pick_route(const RenderMixParams &p, int m) {
-  if (nolim_packets_mix_shape_ok(p, m, getenv("IAMF_HIP_FORCE_GENERIC") != nullptr)) return Route{Family::NolimPacketsMix, p.lpcm_mix & 3, IAMF_HIP_OK};
-  return pick_route(static_cast<const RenderParams &>(p), m);
-}
-
-// The two-element packet form of the limiter-less renderer (iamf_hip_route_family_instances), walking (LpcmM, then LpcmCoupledM) x
-// LpcmMixK as its launchers do, the 16-bit unit first; variant = bytes per packet sample, k = LP2, c = 0 (the output channel count
-// and format are run-time values of the kernel).
-template <class F>
-void for_each_render_instance_nolim_packets_mix(F &&f) {
-  for (int v = 2; v <= 3; ++v) {
-    const auto rows = [&](int m) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX, v, m, 0, k); }); };
-    for_each_int(LpcmM{}, rows);
-    for_each_int(LpcmCoupledM{}, rows);
-  }
-}
-
-// The answers of for_each_instance_of_every_set are pinned like the others — twelve sets, "no row" for every other number — so
-// the sets added since are walked by a seventh walker: numbers kRouteSetsEvery .. kRouteSetsTotal - 1, listed by family only.
-// What iamf_route.hip builds and counts by.
-constexpr int kRouteSetsTotal = 13;
-template <class F>
-void for_each_instance_of_total_set(int set, F &&f) {
-  if (set == 12) for_each_render_instance_nolim_packets_mix(f);
-  else for_each_instance_of_every_set(set, f);
 }
 
 // the row of the kernel launch() runs for a route, and the set that lists it: what iamf_hip_route_count takes (a FirSplit

@@ -18,6 +18,7 @@
 namespace {
 #include "../../iac_amd/csrc/render_params.hpp"
 #include "../../iac_amd/csrc/render_route.hpp"
+#include "route_sets.hpp"
 #include "../../iac_amd/csrc/lpcm_form.hpp"
 
 int g_failed = 0, g_cases = 0;
@@ -67,14 +68,12 @@ void expect(const char *what, const RenderParams &p, int m, const char *env, Fam
   if (env) setenv(env, "1", 1);
   const Route r = pick_route(p, m);
   if (env) unsetenv(env);
-  bool listed = true;   // a route of the form names a row of the family's listing, its set, and no row of the pinned seven sets
+  bool listed = true;   // a route of the form names a row of the family's listing, its set, and no row of any other set
   if (r.family == Family::Lpcm24Coupled) {
     const RouteKey k = route_key(r, p, m);
     listed = false;
     for_each_render_instance_lpcm24_coupled([&](int f, int v, int km, int kc, int kk) { listed = listed || same_key(k, f, v, km, kc, kk); });
-    listed = listed && k.set == 7 && k.set >= kRouteSets && k.set < kRouteSetsAll;
-    for (int s = 0; s < kRouteSets; ++s)
-      for_each_instance_of_set(s, [&](int f, int v, int km, int kc, int kk) { listed = listed && !same_key(k, f, v, km, kc, kk); });
+    listed = listed && k.set == 7 && k.set >= kRouteTables && sets_of_key(k.family, k.variant, k.m, k.c, k.k) == 1 << 7;
   }
   row(what, r.family == family && r.variant == variant && r.err == err && listed);
 }
@@ -127,7 +126,7 @@ int main() {
 
   static_assert(IAMF_HIP_ROUTE_LPCM24_COUPLED == 31, "stable number");
   static_assert((int)Family::Lpcm24Coupled == (int)Family::FastRagged + 1, "added at the end of the enum");
-  static_assert(kRouteSets == 7 && kRouteSetsAll == 8 && kRouteTables == 3, "the pinned seven sets, three tables, one set behind them");
+  static_assert(kRouteSets >= 7 + 1 && kRouteTables == 3, "set 7 behind the three tables; sets added later leave it alone");
   static_assert((int)LpcmForm::S24C == (int)LpcmForm::S16C + 1, "appended to the enum");
   static_assert(sizeof(RenderParams) == 616, "the block keeps its size");
 
@@ -236,20 +235,9 @@ int main() {
     rows += (f == IAMF_HIP_ROUTE_LPCM24_COUPLED && (v == 0 || v == 1) && LpcmCoupledM::has(m) && LpcmOC::has(oc) && k == 0) ? 1 : 1000;
   });
   row("the family's listing: LpcmCoupledM x LpcmOC x {late, early} = 20 rows of family 31", rows == 20);
-  int rows_any = 0, rows_pinned = 0, rows_outside = 0;
-  for_each_instance_of_any_set(7, [&](int f, int, int, int, int) { rows_any += f == IAMF_HIP_ROUTE_LPCM24_COUPLED ? 1 : 1000; });
-  for_each_instance_of_set(7, [&](int, int, int, int, int) { ++rows_pinned; });
-  for_each_instance_of_any_set(8, [&](int, int, int, int, int) { ++rows_outside; });
-  for_each_instance_of_any_set(-1, [&](int, int, int, int, int) { ++rows_outside; });
-  row("set 7 of for_each_instance_of_any_set is the listing; the pinned walker has no set 7; no set 8 or -1", rows_any == 20 && rows_pinned == 0 && rows_outside == 0);
-  int same = 0;
-  for (int s = 0; s < kRouteSets; ++s) {
-    int a = 0, b = 0;
-    for_each_instance_of_set(s, [&](int, int, int, int, int) { ++a; });
-    for_each_instance_of_any_set(s, [&](int, int, int, int, int) { ++b; });
-    same += (a == b && a > 0) ? 1 : 0;
-  }
-  row("sets 0 .. 6 are the pinned walker's", same == kRouteSets);
+  row("set 7 of for_each_instance_of_set is the listing: 20 rows, family 31 alone, which no other set lists", family_in_one_set(IAMF_HIP_ROUTE_LPCM24_COUPLED, 7, 20));
+  row("no row for a set number outside the listing (-1, kRouteSets)", no_rows_outside());
+  row("every set keeps its row count and its family (sets 0 .. 12)", pinned_sets_ok());
   expect("  lpcm_coupled = 2 with 16-bit samples: refused", call(6, 2, 2, 2), 6, nullptr, Family::Refused, 0, STATE);
   expect("  lpcm_coupled = 2 with lpcm_bytes = 0 (16 bit): refused", call(6, 2, 2, 0), 6, nullptr, Family::Refused, 0, STATE);
   expect("  lpcm_coupled = 2 with 32-bit samples: refused", call(2, 2, 2, 4), 2, nullptr, Family::Refused, 0, STATE);

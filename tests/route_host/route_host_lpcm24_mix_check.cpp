@@ -18,6 +18,7 @@
 namespace {
 #include "../../iac_amd/csrc/render_params.hpp"
 #include "../../iac_amd/csrc/render_route.hpp"
+#include "route_sets.hpp"
 #include "../../iac_amd/csrc/lpcm_form.hpp"
 
 int g_failed = 0, g_cases = 0;
@@ -78,9 +79,7 @@ void expect(const char *what, const RenderParams &p, int m, const char *env, Fam
     const RouteKey k = route_key(r, p, m);
     listed = false;
     for_each_render_instance_lpcm24_mix([&](int f, int v, int km, int kc, int kk) { listed = listed || same_key(k, f, v, km, kc, kk); });
-    listed = listed && k.set == 8 && k.set >= kRouteSetsAll && k.set < kRouteSetsBuilt;
-    for (int s = 0; s < kRouteSetsAll; ++s)
-      for_each_instance_of_any_set(s, [&](int f, int v, int km, int kc, int kk) { listed = listed && !same_key(k, f, v, km, kc, kk); });
+    listed = listed && k.set == 8 && k.set >= kRouteTables && sets_of_key(k.family, k.variant, k.m, k.c, k.k) == 1 << 8;
     listed = listed && k.family == IAMF_HIP_ROUTE_LPCM24_MIX && k.variant == 0 && k.k == p.lpcm_mix - 4;
   }
   row(what, r.family == family && r.variant == variant && r.err == err && listed);
@@ -127,8 +126,7 @@ int main() {
   // ---- the numbers and the pinned sizes ----
   static_assert(IAMF_HIP_ROUTE_LPCM24_MIX == 33, "stable number (32 stays unused)");
   static_assert((int)Family::Lpcm24Mix == (int)Family::Lpcm24Coupled + 1, "added at the end of the enum");
-  static_assert(kRouteSets == 7 && kRouteSetsAll == 8 && kRouteSetsBuilt == 9 && kRouteTables == 3,
-                "the pinned seven and eight sets, three tables, one set behind them");
+  static_assert(kRouteSets >= 8 + 1 && kRouteTables == 3, "set 8 behind the three tables; sets added later leave it alone");
   static_assert(sizeof(RenderParams) == 616 && sizeof(RenderMixParams) == 656, "the blocks keep their sizes");
   static_assert(offsetof(RenderParams, interleaved) == 380 && offsetof(RenderParams, dump) == 384 && offsetof(RenderParams, ragged) == 412 &&
                     offsetof(RenderParams, lfe_div) == 416 && offsetof(RenderParams, lpcm) == 528 && offsetof(RenderParams, lpcm_off) == 552,
@@ -184,22 +182,9 @@ int main() {
     expect(what, call(m, oc, LpcmCoupledM::has(m) ? 2 : 0, k, k == 2 ? 2 : (m & 1 ? 1 : 4)), m, nullptr, Family::Lpcm24Mix, k);
   });
   row("the family's listing: (LpcmM + LpcmCoupledM) x LpcmOC x {1, 2} = 36 rows of family 33", rows == 36);
-  int rows_built = 0, rows_any = 0, rows_pinned = 0, rows_outside = 0;
-  for_each_instance_of_built_set(8, [&](int f, int, int, int, int) { rows_built += f == IAMF_HIP_ROUTE_LPCM24_MIX ? 1 : 1000; });
-  for_each_instance_of_any_set(8, [&](int, int, int, int, int) { ++rows_any; });
-  for_each_instance_of_set(8, [&](int, int, int, int, int) { ++rows_pinned; });
-  for_each_instance_of_built_set(9, [&](int, int, int, int, int) { ++rows_outside; });
-  for_each_instance_of_built_set(-1, [&](int, int, int, int, int) { ++rows_outside; });
-  row("set 8 of for_each_instance_of_built_set is the listing; the pinned walkers answer no row for 8; no set 9 or -1",
-      rows_built == 36 && rows_any == 0 && rows_pinned == 0 && rows_outside == 0);
-  int same = 0;
-  for (int s = 0; s < kRouteSetsAll; ++s) {
-    int a = 0, b = 0;
-    for_each_instance_of_any_set(s, [&](int, int, int, int, int) { ++a; });
-    for_each_instance_of_built_set(s, [&](int, int, int, int, int) { ++b; });
-    same += (a == b && a > 0) ? 1 : 0;
-  }
-  row("sets 0 .. 7 are the pinned walkers'", same == kRouteSetsAll);
+  row("set 8 of for_each_instance_of_set is the listing: 36 rows, family 33 alone, which no other set lists", family_in_one_set(IAMF_HIP_ROUTE_LPCM24_MIX, 8, 36));
+  row("no row for a set number outside the listing (-1, kRouteSets)", no_rows_outside());
+  row("every set keeps its row count and its family (sets 0 .. 12)", pinned_sets_ok());
   row("lpcm24_mix_fused: one answer per size, whatever it is, and the route does not depend on it", [&] {
     bool ok = true;
     for (int n = 1; n <= 65536; n += 97) ok = ok && (lpcm24_mix_fused(n) == true || lpcm24_mix_fused(n) == false);

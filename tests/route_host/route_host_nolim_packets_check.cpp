@@ -20,6 +20,7 @@
 namespace {
 #include "../../iac_amd/csrc/render_params.hpp"
 #include "../../iac_amd/csrc/render_route.hpp"
+#include "route_sets.hpp"
 #include "../../iac_amd/csrc/lpcm_form.hpp"
 
 int g_failed = 0, g_cases = 0;
@@ -111,8 +112,8 @@ bool same_key(const RouteKey &k, int f, int v, int m, int c, int kk) {
 }
 int sets_of(const RouteKey &k) {
   int mask = 0;
-  for (int s = 0; s < kRouteSetsEvery; ++s)
-    for_each_instance_of_every_set(s, [&](int f, int v, int km, int kc, int kk) { mask |= same_key(k, f, v, km, kc, kk) ? 1 << s : 0; });
+  for (int s = 0; s < kRouteSets; ++s)
+    for_each_instance_of_set(s, [&](int f, int v, int km, int kc, int kk) { mask |= same_key(k, f, v, km, kc, kk) ? 1 << s : 0; });
   return mask;
 }
 bool same_route(const Route &a, const Route &b) { return a.family == b.family && a.variant == b.variant && a.err == b.err; }
@@ -165,9 +166,7 @@ int main() {
   static_assert(IAMF_HIP_ROUTE_NOLIM_PACKETS == 43 && IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED == 39 && IAMF_HIP_ROUTE_PACKETS_RAGGED == 37, "stable numbers");
   static_assert(sizeof(RenderParams) == 616 && offsetof(RenderParams, ragged) == 412, "the block keeps its size: the mark is a new VALUE of `ragged`");
   static_assert((int)Family::NolimPackets == (int)Family::PacketsMixRagged + 1, "added at the end of the enum");
-  static_assert(kRouteSets == 7 && kRouteSetsAll == 8 && kRouteSetsBuilt == 9 && kRouteSetsLaunched == 10 && kRouteSetsListed == 11 &&
-                    kRouteSetsEvery == 12 && kRouteTables == 3,
-                "a twelfth set behind the pinned walkers, three tables");
+  static_assert(kRouteSets >= 11 + 1 && kRouteTables == 3, "set 11 behind the three tables; sets added later leave it alone");
   static_assert(kNlChunk == 1024 && kNlMaxFrameBytes == 60, "the tile");
 
   // ---- every instance: 18 rows, each fused into every PCM format ----
@@ -183,16 +182,9 @@ int main() {
   });
   row("the family lists 18 rows", rows == 18);
   {
-    int n11 = 0, before = 0, after = 0, outside = 0;
-    for_each_instance_of_every_set(11, [&](int f, int, int, int, int) { n11 += f == IAMF_HIP_ROUTE_NOLIM_PACKETS ? 1 : 1000; });
-    for (int s = 0; s < kRouteSetsListed; ++s) {
-      for_each_instance_of_listed_set(s, [&](int, int, int, int, int) { ++before; });
-      for_each_instance_of_every_set(s, [&](int f, int, int, int, int) { after += f != IAMF_HIP_ROUTE_NOLIM_PACKETS ? 1 : 1000; });
-    }
-    for_each_instance_of_listed_set(11, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_every_set(12, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_every_set(-1, [&](int, int, int, int, int) { ++outside; });
-    row("set 11 of for_each_instance_of_every_set is the listing; sets 0 .. 10 are the pinned walkers'; no set 12 or -1", n11 == 18 && before == after && outside == 0);
+    row("set 11 of for_each_instance_of_set is the listing: 18 rows, family 43 alone, which no other set lists", family_in_one_set(IAMF_HIP_ROUTE_NOLIM_PACKETS, 11, 18));
+    row("no row for a set number outside the listing (-1, kRouteSets)", no_rows_outside());
+    row("every set keeps its row count and its family (sets 0 .. 12)", pinned_sets_ok());
   }
 
   const Call toa = call(16, 2, false), b714 = call(12, 3, true), b51 = call(6, 2, true), st = call(2, 2, true);

@@ -21,6 +21,7 @@
 namespace {
 #include "../../iac_amd/csrc/render_params.hpp"
 #include "../../iac_amd/csrc/render_route.hpp"
+#include "route_sets.hpp"
 #include "../../iac_amd/csrc/lpcm_form.hpp"
 
 int g_failed = 0, g_cases = 0;
@@ -156,8 +157,8 @@ bool same_key(const RouteKey &k, int f, int v, int m, int c, int kk) {
 }
 int sets_of(const RouteKey &k) {
   int mask = 0;
-  for (int s = 0; s < kRouteSetsTotal; ++s)
-    for_each_instance_of_total_set(s, [&](int f, int v, int km, int kc, int kk) { mask |= same_key(k, f, v, km, kc, kk) ? 1 << s : 0; });
+  for (int s = 0; s < kRouteSets; ++s)
+    for_each_instance_of_set(s, [&](int f, int v, int km, int kc, int kk) { mask |= same_key(k, f, v, km, kc, kk) ? 1 << s : 0; });
   return mask;
 }
 bool same_route(const Route &a, const Route &b) { return a.family == b.family && a.variant == b.variant && a.err == b.err; }
@@ -215,9 +216,7 @@ int main() {
   static_assert(sizeof(RenderParams) == 616 && offsetof(RenderParams, ragged) == 412, "the block keeps its size: the mark is a new VALUE of `ragged`");
   static_assert(sizeof(RenderMixParams) == 616 + 8 + 16 + 16, "and so does the block behind it");
   static_assert((int)Family::NolimPacketsMix == (int)Family::NolimPackets + 1, "added at the end of the enum");
-  static_assert(kRouteSets == 7 && kRouteSetsAll == 8 && kRouteSetsBuilt == 9 && kRouteSetsLaunched == 10 && kRouteSetsListed == 11 &&
-                    kRouteSetsEvery == 12 && kRouteSetsTotal == 13 && kRouteTables == 3,
-                "a thirteenth set behind the pinned walkers, three tables");
+  static_assert(kRouteSets >= 12 + 1 && kRouteTables == 3, "set 12 behind the three tables; sets added later leave it alone");
   static_assert(kNlChunk == 1024 && kNlMaxFrameBytes == 60, "the tile");
 
   // ---- every instance: 36 rows, each fused into every PCM format ----
@@ -233,23 +232,9 @@ int main() {
   });
   row("the family lists 36 rows", rows == 36);
   {
-    int n12 = 0, before = 0, after = 0, outside = 0;
-    for_each_instance_of_total_set(12, [&](int f, int, int, int, int) { n12 += f == IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX ? 1 : 1000; });
-    for (int s = 0; s < kRouteSetsEvery; ++s) {
-      for_each_instance_of_every_set(s, [&](int, int, int, int, int) { ++before; });
-      for_each_instance_of_total_set(s, [&](int f, int, int, int, int) { after += f != IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX ? 1 : 1000; });
-    }
-    // the six older walkers answer "no row" for 12
-    for_each_instance_of_set(12, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_any_set(12, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_built_set(12, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_launched_set(12, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_listed_set(12, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_every_set(12, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_total_set(13, [&](int, int, int, int, int) { ++outside; });
-    for_each_instance_of_total_set(-1, [&](int, int, int, int, int) { ++outside; });
-    row("set 12 of for_each_instance_of_total_set is the listing; sets 0 .. 11 are the pinned walkers'; the six older walkers have no set 12",
-        n12 == 36 && before == after && outside == 0);
+    row("set 12 of for_each_instance_of_set is the listing: 36 rows, family 47 alone, which no other set lists", family_in_one_set(IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX, 12, 36));
+    row("no row for a set number outside the listing (-1, kRouteSets)", no_rows_outside());
+    row("every set keeps its row count and its family (sets 0 .. 12)", pinned_sets_ok());
   }
 
   const Call toa = call(16, 2, 2), b714 = call(12, 3, 1), b51 = call(6, 2, 1), foa4 = call(4, 2, 1);

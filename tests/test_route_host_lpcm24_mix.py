@@ -3,8 +3,8 @@ and lpcm_form.hpp with the host compiler and pins one row per rule — the secon
 answers them (mono runs, one pair, the dword grid with trimmed starts, two mono runs for stereo, 16- and 32-bit samples, byte
 order, d_raw, the strides), and pick_route(): every (M, OC, LP2) takes Family::Lpcm24Mix; lpcm_mix 1 / 2 with 24-bit samples and
 lpcm_mix 3 are refused as before; 4 | LP2 with another sample size or coupling names no form; each refusal of Family::LpcmMix
-with one pointer, stride, bound or flag changed; the route_key's set is 8 and holds a row of none of sets 0 .. 7; the pinned
-walkers answer "no row" for 8; sizeof and offsetof of the parameter blocks are as pinned."""
+with one pointer, stride, bound or flag changed; the route_key's set is 8 and no other set holds its row; every
+set keeps its pinned row count, no row for a number outside the listing; sizeof and offsetof of the parameter blocks are as pinned."""
 import os
 import re
 import subprocess

@@ -2,8 +2,8 @@
 render_route.hpp and lpcm_form.hpp with the host compiler and pins one row per rule of nolim_packets_shape_ok behind
 lpcm_form_packets, each flipped alone — limiter on, total = 6, frame size = 6, d_pcm off 16, out_ch * bytes = 2 and 64,
 first + n > fs, a 16-bit run off the 8-byte grid, big-endian, 32 bit, mono-coded 5.1, each off-switch, every stage that keeps
-the f32 form away; every (sample size, M) takes Family::NolimPackets, a row of set 11 and of no other set; the pinned walkers
-answer "no row" for 11; a block without the mark, or a limiter-on one with it, routes as in the parent."""
+the f32 form away; every (sample size, M) takes Family::NolimPackets, a row of set 11 and of no other set; every set
+keeps its pinned row count, no row for a number outside the listing; a block without the mark, or a limiter-on one with it, routes as in the parent."""
 import os
 import re
 import subprocess

@@ -4,7 +4,7 @@ one row per rule of nolim_packets_mix_shape_ok behind lpcm_form_packets on each 
 frame size 6, first + n > fs, element 1 off its grid (16 and 24 bit), the pair's partner misplaced, m2 = 2 as mono runs, m2 = 3,
 sample sizes that differ, a ramp off 16 bytes, a ramp stride of 4k + 1, out_ch * bytes of 2 and 64, d_pcm off 16, each
 off-switch, each stage that keeps the form away; every (sample size, M, LP2) takes Family::NolimPacketsMix, a row of set 12 and of
-no other set; the six older walkers answer "no row" for 12; a block without the mark, or with mark 4, routes as in the parent."""
+no other set; every set keeps its pinned row count, no row for a number outside the listing; a block without the mark, or with mark 4, routes as in the parent."""
 import os
 import re
 import subprocess

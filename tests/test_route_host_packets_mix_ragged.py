@@ -2,8 +2,8 @@
 render_route.hpp with the host compiler and pins one row per term of packets_mix_ragged_shape_ok — the length, the position,
 lpcm_mix against lpcm_bytes and m2, the bed's lists, both elements' grids and 32-bit bounds, the ramp rows' alignment and
 stride, the trimmed frame's inequality, every stage and flag that keeps a call away, the three switches — each with that term
-changed alone; every (sample size, M, OC, LP2) takes Family::PacketsMixRagged, a row of set 10 and of no other set; the pinned
-walkers answer "no row" for 10; a call without the mark routes as in the parent, as do the marks 1 and 2; sizeof and offsetof of
+changed alone; every (sample size, M, OC, LP2) takes Family::PacketsMixRagged, a row of set 10 and of no other set; every set
+keeps its pinned row count, no row for a number outside the listing; a call without the mark routes as in the parent, as do the marks 1 and 2; sizeof and offsetof of
 the parameter blocks are as pinned."""
 import os
 import re
