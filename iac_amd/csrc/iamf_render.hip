@@ -1713,10 +1713,38 @@ static int fan_lp_fuse_max(int workgroups) {
   return IAMF_HIP_FANOUT_MAX;
 }
 
-int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_batches, const iamf_hip_lpcm_input *in,
-                                      int32_t n_frames, int32_t n_samples, void *const *d_pcm,
-                                      const int64_t *pcm_stream_stride_bytes, void *stream, int32_t stream0, int32_t n_streams,
-                                      int32_t *n_emitted, iamf_hip_fanout_report *report) {
+// How many of k packet-fusable members one launch of render_fanout_kernel<.., LP, LPB, LPC> takes for a range of `workgroups`
+// streams, under the rule of fan_lp_fuse_max(): a (form, K, size) that does not beat the better of its two baselines — K single
+// iamf_hip_batch_render_packets calls, and iamf_hip_batch_render_fanout_lpcm (one unpack pass and the f32 fan-out) — by more
+// than that baseline's spread against itself is not fused (tools/fanout_packets_rate.py, profiles/r21_fanout_packets_rate.json).
+// The rule may look at the form, at K and at the number of workgroups only.
+// Measured on an MI355X, 64 frames x 1024 samples per stream, the hot programme, members {A, A with gains, mono} s16 and mono
+// s24, at 512 / 2048 / 4096 streams; in every row the better baseline is the K single calls (the old entry takes 1.13 to 3.85
+// times the new launch's time everywhere), whose spread against itself is at most 0.0062:
+//   3rd order, 24 bit      K = 2: 1.52 / 1.51 / 1.54 times as fast as its single calls, K = 3: 1.68 / 1.70 / 1.73,
+//                          K = 4: 1.017 / 0.979 / 1.009 — fused up to 512 workgroups; above, three members share the launch (the
+//                          2048 triple has to stay unfused, and the 0.9 % of the 4096 one are not worth a fourth member there);
+//   5.1 coupled, 16 bit    K = 2: 1.025 / 0.547 / 0.542, K = 3: 1.014 / 0.537 / 0.533, K = 4: 0.549 / 0.293 / 0.290;
+//   7.1.4 coupled, 24 bit  K = 2: 1.073 / 0.631 / 0.609, K = 3: 1.073 / 0.620 / 0.600, K = 4: 0.584 / 0.345 / 0.335
+//                          — the coupled forms: two or three members up to 512 workgroups, nothing above.  (A loudspeaker
+//                          layout's down-mix of the hot programme triggers the limiter in nearly every block; the members' limiter
+//                          rounds run one after the other in a workgroup, at two workgroups per CU — one for K = 4 — where the
+//                          single calls run four.  512 workgroups are the one round of two per CU: the cut lies there.)
+// Not measured: fewer than 512 workgroups (the rule keeps its starting value there, IAMF_HIP_FANOUT_MAX, except that a coupled
+// K = 4 at exactly the measured 512 is capped) and the sizes between the measured ones, which take the side of the larger.
+static int fan_pk_fuse_max(LpcmForm form, int k, int workgroups) {
+  if (k > IAMF_HIP_FANOUT_MAX) k = IAMF_HIP_FANOUT_MAX;
+  if (workgroups < 512) return k;
+  if (form == LpcmForm::S24) return (k == 4 && workgroups > 512) ? 3 : k;
+  if (workgroups > 512) return 0;
+  return k == 4 ? 3 : k;
+}
+
+// iamf_hip_batch_render_fanout_lpcm and, with `packets`, iamf_hip_batch_render_fanout_packets: the same checks in the same order,
+// the same routes and report for every call whose packets the latter's kernel does not read.
+static int fanout_lpcm_impl(iamf_hip_batch *const *batches, int32_t n_batches, const iamf_hip_lpcm_input *in, int32_t n_frames,
+                            int32_t n_samples, void *const *d_pcm, const int64_t *pcm_stream_stride_bytes, void *stream,
+                            int32_t stream0, int32_t n_streams, int32_t *n_emitted, iamf_hip_fanout_report *report, bool packets) {
   // ---- checks that need no device ----
   if (n_batches < 1 || n_batches > IAMF_HIP_FANOUT_MAX) return IAMF_HIP_ERR_BAD_ARG;
   if (!batches || !in || !in->d_raw || !d_pcm || !pcm_stream_stride_bytes || !n_emitted || n_frames < 0) return IAMF_HIP_ERR_BAD_ARG;
@@ -1740,11 +1768,18 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
   // ---- the packets (channels and frame size are the same for every member), then every member's own argument checks ----
   LpcmForm form = LpcmForm::None;
   int first = 0, count = 0;
-  const int fc = lpcm_form_check(b0, in, n_frames, n_samples, &form, &first, &count, false);
+  // (packets: the form is asked of lpcm_form_packets(), which also names S24C; IAMF_HIP_FANOUT_PACKETS_UNFUSED=1 makes the
+  //  call iamf_hip_batch_render_fanout_lpcm's)
+  if (packets && getenv("IAMF_HIP_FANOUT_PACKETS_UNFUSED")) packets = false;
+  const int fc = lpcm_form_check(b0, in, n_frames, n_samples, &form, &first, &count, packets);
   if (fc != IAMF_HIP_OK) return fc;
-  // "the form the single call fuses" is the 16-bit one here: render_fanout_kernel<.., LP> reads no other, and 24-bit
-  // packets and coupled 16-bit ones (LpcmForm::S16C) keep sharing one unpack pass and the f32 fan-out (include/iamf_hip.h)
-  const bool pk_form = form == LpcmForm::S16;
+  // "the form the single call fuses" is the 16-bit one for iamf_hip_batch_render_fanout_lpcm: render_fanout_kernel<.., LP>
+  // reads no other there, and 24-bit packets and coupled 16-bit ones (LpcmForm::S16C) keep sharing one unpack pass and the f32
+  // fan-out (include/iamf_hip.h).  iamf_hip_batch_render_fanout_packets adds the three forms render_fanout_kernel<.., LP, LPB,
+  // LPC> reads (pk_more); a call of any other form (S16, None) takes the same path through either entry.
+  const bool pk_more = packets && (form == LpcmForm::S24 || form == LpcmForm::S16C || form == LpcmForm::S24C);
+  const int pk_variant = pk_more ? fan_pk_variant(lpcm_form_bytes(form), form != LpcmForm::S24) : 0;
+  const bool pk_form = form == LpcmForm::S16 || pk_more;
   iamf_hip_render_args args[IAMF_HIP_FANOUT_MAX];
   int64_t total = 0;
   for (int j = 0; j < n_batches; ++j) {
@@ -1776,9 +1811,15 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
     if (pk_form) {
       LpcmIn lp;
       lpcm_in_of(in, ch, first, form, lp);
-      const int rc = render_prepare(b, args[j], (int)total, stream0, n_streams, &lp, nullptr, CallForm::Lpcm, 0, pcs[j]);
+      const int rc = pk_more ? render_prepare(b, args[j], (int)total, stream0, n_streams, &lp, nullptr, CallForm::Packets, first, pcs[j])
+                             : render_prepare(b, args[j], (int)total, stream0, n_streams, &lp, nullptr, CallForm::Lpcm, 0, pcs[j]);
       if (rc != kNotFused && rc != IAMF_HIP_OK) return rc;
-      if (rc == IAMF_HIP_OK) {   // the member's single call takes Family::Lpcm (render_prepare has asked pick_route)
+      if (rc == IAMF_HIP_OK && pk_more) {
+        // the member's single call takes the form's family (Lpcm24, LpcmCoupled, Lpcm24Coupled: render_prepare has asked
+        // pick_route); on top, nothing re-laid behind the kernel.  How many of these share the launch is decided below
+        cls[j] = (!pcs[j].restride && pcs[j].m_eff == b0->m) ? 2 : 1;
+        if (cls[j] == 2) ++k;
+      } else if (rc == IAMF_HIP_OK) {   // the member's single call takes Family::Lpcm (render_prepare has asked pick_route)
         // what the f32 fan-out asks on top: nothing re-laid behind the kernel; then an instance of this kernel
         cls[j] = (!pcs[j].restride && k < k_max && pcs[j].m_eff == b0->m && FanLpM::has(pcs[j].m_eff)) ? 2 : 1;
         if (cls[j] == 2) ++k;
@@ -1786,7 +1827,16 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
     }
     if (cls[j] == 0) ++n_f32;
   }
-  if (k < 2 || !FanLpK::has(k)) {
+  if (pk_more) {
+    // the first k' candidates share the launch, k' the largest count within the measured cap that the form's list holds for M
+    int kk = fan_pk_fuse_max(form, k, n_streams);
+    while (kk >= 2 && !fan_pk_has(pk_variant, b0->m, kk)) --kk;
+    if (kk < 2) kk = 0;
+    k = 0;
+    for (int j = 0; j < n_batches; ++j)
+      if (cls[j] == 2 && k++ >= kk) cls[j] = 1;
+    k = kk;
+  } else if (k < 2 || !FanLpK::has(k)) {
     for (int j = 0; j < n_batches; ++j)
       if (cls[j] == 2) cls[j] = 1;
     k = 0;
@@ -1816,9 +1866,13 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
       }
       fp.mem[n++] = fan_member_of(p);
     }
-    if (!iamf_hip_fanout_lp_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
+    const auto fan_launch = !pk_more ? iamf_hip_fanout_lp_launch
+                            : (form == LpcmForm::S24 ? iamf_hip_fanout_pk24_launch
+                                                     : (form == LpcmForm::S16C ? iamf_hip_fanout_pk16c_launch : iamf_hip_fanout_pk24c_launch));
+    if (!fan_launch(&fp, b0->m, k, static_cast<hipStream_t>(stream))) return IAMF_HIP_ERR_INTERNAL;
     HIPCHK(hipGetLastError());
-    iamf_hip_route_count(1, IAMF_HIP_ROUTE_FANOUT_LPCM, 0, b0->m, 0, k);   // the extension table
+    if (pk_more) iamf_hip_route_count(kRouteSetFanoutPackets, IAMF_HIP_ROUTE_FANOUT_PACKETS, pk_variant, b0->m, 0, k);   // by family only
+    else iamf_hip_route_count(1, IAMF_HIP_ROUTE_FANOUT_LPCM, 0, b0->m, 0, k);   // the extension table
     for (int j = 0; j < n_batches; ++j) {
       if (cls[j] != 2) continue;
       const int r = render_commit(batches[j], pcs[j]);
@@ -1867,6 +1921,32 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
   for (int j = 0; j < n_batches; ++j) n_emitted[j] = emitted[j];
   if (report) *report = rep;
   return IAMF_HIP_OK;
+}
+
+int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_batches, const iamf_hip_lpcm_input *in,
+                                      int32_t n_frames, int32_t n_samples, void *const *d_pcm,
+                                      const int64_t *pcm_stream_stride_bytes, void *stream, int32_t stream0, int32_t n_streams,
+                                      int32_t *n_emitted, iamf_hip_fanout_report *report) {
+  return fanout_lpcm_impl(batches, n_batches, in, n_frames, n_samples, d_pcm, pcm_stream_stride_bytes, stream, stream0, n_streams,
+                          n_emitted, report, false);
+}
+
+// The same with leave to read 24-bit and coupled packets in the shared launch (include/iamf_hip.h): render_fanout_kernel<..,
+// LP, LPB, LPC>, IAMF_HIP_ROUTE_FANOUT_PACKETS.
+// The call block is iamf_hip_batch_render_packets': the packets, and of its args the frames, the samples and the stream — the
+// members' PCM buffers travel beside it, and a fan-out takes no ramps, frame records or f32 input, so every other field is 0.
+int iamf_hip_batch_render_fanout_packets(iamf_hip_batch *const *batches, int32_t n_batches, const iamf_hip_packet_call *call,
+                                         void *const *d_pcm, const int64_t *pcm_stream_stride_bytes, int32_t stream0, int32_t n_streams,
+                                         int32_t *n_emitted, iamf_hip_fanout_report *report) {
+  if (n_batches < 1 || n_batches > IAMF_HIP_FANOUT_MAX) return IAMF_HIP_ERR_BAD_ARG;   // (the first answer of the shared checks)
+  if (!call || call->reserved[0] || call->reserved[1] || call->reserved[2] || call->reserved[3]) return IAMF_HIP_ERR_BAD_ARG;
+  const iamf_hip_render_args &a = call->args;   // every field but n_frames, n_samples and stream: NULL / 0
+  if (a.d_in || a.in_stream_stride || a.in_frame_stride || a.d_in2 || a.in2_stream_stride || a.in2_frame_stride || a.d_element_ramp ||
+      a.d_element2_ramp || a.d_output_ramp || a.ramp_stream_stride || a.d_dmx_frames || a.d_pcm || a.pcm_stream_stride_bytes ||
+      a.d_demix_frames || a.demix_sample0 || a.lfe_pre_samples || a.lfe_post_samples || a.reserved0)
+    return IAMF_HIP_ERR_BAD_ARG;
+  return fanout_lpcm_impl(batches, n_batches, &call->in, call->args.n_frames, call->args.n_samples, d_pcm, pcm_stream_stride_bytes,
+                          call->args.stream, stream0, n_streams, n_emitted, report, true);
 }
 
 int iamf_hip_batch_flush_range(iamf_hip_batch *b, void *d_pcm, int64_t pcm_stream_stride_bytes, void *stream,

@@ -34,7 +34,7 @@ struct RouteTable {
   int32_t index[kRouteCap];    // row of key[i]
   int n = 0, dropped = 0;
   void build(int set) {
-    for_each_instance_of_set(set, [&](int family, int variant, int m, int c, int k) {
+    const auto add = [&](int family, int variant, int m, int c, int k) {
       if (n == kRouteCap) {
         ++dropped;
         return;
@@ -49,7 +49,9 @@ struct RouteTable {
       key[n] = pack_key(family, variant, m, c, k);
       index[n] = n;
       ++n;
-    });
+    };
+    if (set < kRouteSets) for_each_instance_of_set(set, add);
+    else for_each_instance_of_later_set(set - kRouteSets, add);   // (the sets behind: render_route.hpp)
     int32_t order[kRouteCap];
     for (int i = 0; i < n; ++i) order[i] = i;
     std::sort(order, order + n, [&](int a, int b) { return key[a] < key[b]; });
@@ -67,15 +69,17 @@ struct RouteTable {
 // One row set and its counters (slot kRouteCap: IAMF_HIP_ROUTE_NONE).  Sets 0 .. kRouteTables - 1 ARE the numbered tables
 // of iamf_hip_route_table_instances (0: the base listing, 1: the extension, 2: the 24-bit LPCM form), whose count is pinned;
 // the sets behind them are listed by family only (iamf_hip_route_family_instances).  for_each_instance_of_set
-// (render_route.hpp) says which rows fill which of the kRouteSets sets.
+// (render_route.hpp) says which rows fill which of the kRouteSets sets, for_each_instance_of_later_set which fill the
+// kRouteLaterSets sets behind them (also listed by family only).
+constexpr int kRouteSetsAll = kRouteSets + kRouteLaterSets;
 struct RouteSet {
   RouteTable table;
   std::atomic<int64_t> launches[kRouteCap + 1];
 };
 RouteSet *route_sets() {
   static RouteSet *const sets = [] {
-    static RouteSet s[kRouteSets];   // (static storage: every counter starts at zero)
-    for (int set = 0; set < kRouteSets; ++set) s[set].table.build(set);
+    static RouteSet s[kRouteSetsAll];   // (static storage: every counter starts at zero)
+    for (int set = 0; set < kRouteSetsAll; ++set) s[set].table.build(set);
     return s;
   }();
   return sets;
@@ -109,7 +113,7 @@ int tally_of(RouteSet &s, iamf_hip_route_row *rows, int cap, int reset) {
 int family_rows(int family, bool tally, iamf_hip_route_row *rows, int cap, int reset) {
   int cnt = 0;
   bool known = false;
-  for (int set = 0; set < kRouteSets; ++set) {
+  for (int set = 0; set < kRouteSetsAll; ++set) {
     RouteSet &s = route_sets()[set];
     const RouteTable &t = s.table;
     for (int i = 0; i < t.n; ++i) {
@@ -135,7 +139,7 @@ int family_rows(int family, bool tally, iamf_hip_route_row *rows, int cap, int r
 // A key its set does not hold counts in that set's own NONE slot where the set is a numbered table, else (the sets listed by
 // family only have no tally of their own to show it) in the base table's.
 void iamf_hip_route_count(int set, int family, int variant, int m, int c, int k) {
-  if (set < 0 || set >= kRouteSets) return;
+  if (set < 0 || set >= kRouteSetsAll) return;
   RouteSet *sets = route_sets();
   const int i = sets[set].table.find(pack_key(family, variant, m, c, k));
   sets[i == kRouteCap && set >= kRouteTables ? 0 : set].launches[i].fetch_add(1, std::memory_order_relaxed);

@@ -19,6 +19,12 @@ IAMF_INTERNAL int iamf_hip_wide4_lfe_launch(const void *params, int m, hipStream
 IAMF_INTERNAL int iamf_hip_fanout_launch(const void *params, int m, int k, hipStream_t st);
 // iamf_render_fanout_lp.hip; params: a FanLpParams whose first k members are set
 IAMF_INTERNAL int iamf_hip_fanout_lp_launch(const void *params, int m, int k, hipStream_t st);
+// iamf_render_fanout_pk24.hip, _fanout_pk16c.hip, _fanout_pk24c.hip: render_fanout_kernel<M, K, true, LPB, LPC>, the fan-out fed
+// with 24-bit mono-coded, coupled 16-bit and coupled 24-bit packets; params as above, (m, k) in the unit's list
+// (FanPk24MK, FanPk16cMK, FanPk24cMK of render_route.hpp)
+IAMF_INTERNAL int iamf_hip_fanout_pk24_launch(const void *params, int m, int k, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_fanout_pk16c_launch(const void *params, int m, int k, hipStream_t st);
+IAMF_INTERNAL int iamf_hip_fanout_pk24c_launch(const void *params, int m, int k, hipStream_t st);
 // iamf_render_lpcm.hip; early: Route::variant of Family::Lpcm
 IAMF_INTERNAL int iamf_hip_fast_lpcm_launch(const void *params, int m, int early, hipStream_t st);
 // iamf_render_lpcm24.hip: the same for 24-bit samples (params->lpcm_bytes == 3); early: Route::variant of Family::Lpcm24

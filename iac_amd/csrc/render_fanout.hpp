@@ -34,7 +34,19 @@
 //     w * (s * 2^-15) for the matrices the host admits (iamf_hip_batch::lp_scale_ok: a power of two commutes with
 //     rounding as long as neither the scaled weight nor a product leaves the normal range), so each product and each sum
 //     is rounded once, in ascending channel order: the reference's arithmetic.
-// A member has one or two output channels (a run-time property: the instantiations are <M, K, LP> only; a mono member's
+// LP with LPB / LPC (their meaning in render_fast_kernel; iamf_hip_batch_render_fanout_packets): the other three packet forms
+// of lpcm_form.hpp, in the same six places and nowhere else.
+//   - LPB == 3 (S24): three dwords per channel (four 24-bit samples as they lie in memory), one 12-byte load per channel and
+//     lane at 3 * i, cut where channel m is consumed — a[23:0], {b[15:0], a[31:24]}, {c[7:0], b[31:16]}, c[31:8], sign-extended —
+//     and "/ 2^23" folded into the staged weights (the argument at mat[t] in render_fast.hpp, under the same host check);
+//   - LPC (S16C, S24C): the pairs of lpcm_coupled_paired(M, m) lie interleaved sample by sample.  A pair is loaded once, when
+//     its first channel is named — one 16-byte load at 4 * i, or two 12-byte loads at 6 * i — into its two channels'
+//     registers; L is cut out of the low halves (triples 0 and 2) where channel m is consumed, R one channel later out of the
+//     high halves (triples 1 and 3), and the pair's next chunk is requested once its SECOND channel has been consumed.  C and
+//     LFE are mono runs under the form's mono rule.
+//   The cut and convert expressions restate render_fast.hpp's (LP3, LPC there): that kernel keeps them inline, between its own
+//   ordering fences, and lifting them into device functions moved its instances' instructions.
+// A member has one or two output channels (a run-time property: the instantiations are <M, K, LP, LPB, LPC> only; a mono member's
 // second slot carries zero weights).  The rings and the staged limiter-table window / head are per member; the array of
 // window maxima the limiter walk reads — and overwrites, block by block, with its gains — is transient and serves the
 // members in turn.  Of max |y| only what the next call needs is kept (the last 256 samples; the window maximum reads the
@@ -95,9 +107,12 @@ __host__ __device__ constexpr int fan_lds_floats(int k, int m) {
   return k * fan_member_floats() + kFChunk + ((2 * k * m + 15) & ~15) + 16;
 }
 
-template <int M, int K, bool LP>
+template <int M, int K, bool LP, int LPB = 2, bool LPC = false>
 __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(const std::conditional_t<LP, FanLpParams, FanParams> p) {
   static_assert(!LP || M <= 16, "one run offset per channel");
+  static_assert(LPB == 2 || (LP && LPB == 3), "packet samples of 16 or 24 bits");
+  static_assert(!LPC || (LP && lpcm_coupled_m(M)), "coupled pairs: 16- or 24-bit packets of a loudspeaker layout");
+  constexpr bool LP3 = LP && LPB == 3;
   static_assert(K >= 2 && K <= kFanMax, "two to four members");
   extern __shared__ float lds[];
   constexpr int R = kFRing;
@@ -154,7 +169,9 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
     if (t < 2 * M) {
       const int c = t / M, m = t - c * M;
       const int f = c < oc ? mb.src_feed[c] : -1;
-      if constexpr (LP)   // the LPCM decoder's "sample / 32768.f" folded into the weight (the host has checked lp_scale_ok)
+      if constexpr (LP3)  // 24-bit samples: "/ 2^23", by the same argument and under the same host check
+        mat[2 * j * M + t] = (f >= 0 ? mb.matrix[f * M + m] : 0.f) * (1.0f / 8388608.0f);
+      else if constexpr (LP)   // the LPCM decoder's "sample / 32768.f" folded into the weight (the host has checked lp_scale_ok)
         mat[2 * j * M + t] = (f >= 0 ? mb.matrix[f * M + m] : 0.f) * (1.0f / 32768.0f);
       else
         mat[2 * j * M + t] = f >= 0 ? mb.matrix[f * M + m] : 0.f;
@@ -182,7 +199,13 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
   // ---- the element's input: buffer loads, one resource per stream (render_fast.hpp).  Per channel a float4, or (LP) the
   //      packets' samples as they lie in memory: four 16-bit samples in two dwords ----
   using lp_u2 = __attribute__((ext_vector_type(2))) unsigned;
-  std::conditional_t<LP, lp_u2, float4> x[M];
+  std::conditional_t<LP, lp_u2, float4> x[LP3 ? 1 : M];
+  // LPB == 3: four 24-bit samples in three dwords.  (LPC: a pair's {L0:R0} .. {L3:R3} in x[m], x[m + 1], m even; with 24-bit
+  // samples L0 R0 L1 R1 in x3[m] and L2 R2 L3 R3 in x3[m + 1])
+  struct lp_u3 {
+    unsigned a, b, c;
+  };
+  lp_u3 x3[LP3 ? M : 1];
   const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(in_s), 0, 0x7fffffff, 0x00020000);
   // (zero records: every load through it is answered with zeros — the requests for "the next chunk" when there is none)
   const __amdgpu_buffer_rsrc_t rs_none = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(in_s), 0, 0, 0x00020000);
@@ -198,7 +221,44 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
     }
   };
   auto load_one = [&](int m, int f, int i, __amdgpu_buffer_rsrc_t rs) {
-    if constexpr (LP) {
+    if constexpr (LP3 && LPC) {
+      // (24 bytes on the dword grid: the pair's run offset is a multiple of 4 — lpcm_form.hpp, S24C — and 6 * i one of 24;
+      //  M is even for every coupled layout, so a pair's second channel exists)
+      if (lpcm_coupled_paired(M, m)) {
+        if (!(m & 1)) {
+          const int vo = f * (int)p.lpcm_frame_stride + 6 * i;
+          const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, vo, p.lpcm_off[m], 2 /* nt */);
+          const auto w = __builtin_amdgcn_raw_buffer_load_b96(rs, vo + 12, p.lpcm_off[m], 2 /* nt */);
+          const int m1 = m + 1 < M ? m + 1 : m;
+          x3[m].a = v[0], x3[m].b = v[1], x3[m].c = v[2];
+          x3[m1].a = w[0], x3[m1].b = w[1], x3[m1].c = w[2];
+        }
+      } else {
+        const int vo = f * (int)p.lpcm_frame_stride + 3 * i;
+        const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, vo, p.lpcm_off[m], 2 /* nt */);
+        x3[m] = lp_u3{v[0], v[1], v[2]};
+      }
+    } else if constexpr (LP3) {
+      // (dword-aligned: the stream's base, the frame stride and the run offsets are multiples of 4 — lpcm_form.hpp, S24 —
+      //  and 3 * i is one of 12)
+      const int vo = f * (int)p.lpcm_frame_stride + 3 * i;
+      const auto v = __builtin_amdgcn_raw_buffer_load_b96(rs, vo, p.lpcm_off[m], 2 /* nt */);
+      x3[m] = lp_u3{v[0], v[1], v[2]};
+    } else if constexpr (LPC) {
+      // (16 bytes on the 8-byte grid: the pair's run offset is a multiple of 8 — lpcm_form.hpp, S16C — and 4 * i one of 16)
+      if (lpcm_coupled_paired(M, m)) {
+        if (!(m & 1)) {
+          const int vo = f * (int)p.lpcm_frame_stride + 4 * i;
+          const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, vo, p.lpcm_off[m], 2 /* nt */);
+          x[m] = lp_u2{v[0], v[1]};
+          x[m + 1 < M ? m + 1 : m] = lp_u2{v[2], v[3]};
+        }
+      } else {
+        const int vo = f * (int)p.lpcm_frame_stride + 2 * i;
+        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, p.lpcm_off[m], 2 /* nt */);
+        x[m] = lp_u2{v[0], v[1]};
+      }
+    } else if constexpr (LP) {
       const int vo = f * (int)p.lpcm_frame_stride + 2 * i;
       const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, vo, p.lpcm_off[m], 2 /* nt */);
       x[m] = lp_u2{v[0], v[1]};
@@ -218,7 +278,9 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
     } else {
 #pragma unroll
       for (int m = 0; m < M; ++m) {
-        if constexpr (LP)
+        if constexpr (LP3)
+          x3[m] = lp_u3{0u, 0u, 0u};
+        else if constexpr (LP)
           x[m] = lp_u2{0u, 0u};
         else
           x[m] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -297,7 +359,53 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
 #pragma unroll
         for (int c = 0; c < 2 * NS; ++c) asm volatile("" : "+v"(prj[c]));
         f2 xa, xb;
-        if constexpr (LP) {
+        if constexpr (LP3 && LPC) {
+          if (lpcm_coupled_paired(M, m)) {   // (m is a constant of the unrolled loop)
+            // half m & 1 of the pair whose six dwords lie in x3[m & ~1], x3[m | 1]: the fence covers all six (the partner's half
+            // is still to be, or has just been, cut out of them); each triple is cut as the 24-bit form's, L takes its samples 0
+            // and 2, R 1 and 3
+            const int m0 = m & ~1, m1 = (m | 1) < M ? (m | 1) : m;
+            asm volatile("" : "+v"(x3[m0].a), "+v"(x3[m0].b), "+v"(x3[m0].c), "+v"(x3[m1].a), "+v"(x3[m1].b), "+v"(x3[m1].c));
+            const unsigned a = x3[m0].a, b = x3[m0].b, c = x3[m0].c, d = x3[m1].a, e = x3[m1].b, g = x3[m1].c;
+            if ((m & 1) == 0) {
+              xa = f2{(float)((int)(a << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(c, b, 16) << 8) >> 8)};
+              xb = f2{(float)((int)(d << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(g, e, 16) << 8) >> 8)};
+            } else {
+              xa = f2{(float)((int)(__builtin_amdgcn_alignbit(b, a, 24) << 8) >> 8), (float)((int)c >> 8)};
+              xb = f2{(float)((int)(__builtin_amdgcn_alignbit(e, d, 24) << 8) >> 8), (float)((int)g >> 8)};
+            }
+          } else {   // C, LFE: a mono run, the 24-bit form's conversion below
+            asm volatile("" : "+v"(x3[m].a), "+v"(x3[m].b), "+v"(x3[m].c));
+            const unsigned a = x3[m].a, b = x3[m].b, c = x3[m].c;
+            xa = f2{(float)((int)(a << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(b, a, 24) << 8) >> 8)};
+            xb = f2{(float)((int)(__builtin_amdgcn_alignbit(c, b, 16) << 8) >> 8), (float)((int)c >> 8)};
+          }
+        } else if constexpr (LP3) {
+          asm volatile("" : "+v"(x3[m].a), "+v"(x3[m].b), "+v"(x3[m].c));
+          const unsigned a = x3[m].a, b = x3[m].b, c = x3[m].c;   // (the scale 2^-23 sits in the weights)
+          // sign-extended from 24 bits: a bit-field extract of the dword (or of the two dwords' funnel) the sample lies in
+          xa = f2{(float)((int)(a << 8) >> 8), (float)((int)(__builtin_amdgcn_alignbit(b, a, 24) << 8) >> 8)};
+          xb = f2{(float)((int)(__builtin_amdgcn_alignbit(c, b, 16) << 8) >> 8), (float)((int)c >> 8)};
+        } else if constexpr (LPC) {
+          if (lpcm_coupled_paired(M, m)) {   // (m is a constant of the unrolled loop)
+            // half m & 1 of the pair whose four dwords lie in x[m & ~1], x[m | 1]: the fence covers all four
+            const int m0 = m & ~1, m1 = (m | 1) < M ? (m | 1) : m;
+            asm volatile("" : "+v"(x[m0].x), "+v"(x[m0].y), "+v"(x[m1].x), "+v"(x[m1].y));
+            const unsigned a = x[m0].x, b = x[m0].y, c = x[m1].x, d = x[m1].y;   // (the scale 2^-15 sits in the weights)
+            if ((m & 1) == 0) {
+              xa = f2{(float)(int)(short)(a & 0xffffu), (float)(int)(short)(b & 0xffffu)};
+              xb = f2{(float)(int)(short)(c & 0xffffu), (float)(int)(short)(d & 0xffffu)};
+            } else {
+              xa = f2{(float)((int)a >> 16), (float)((int)b >> 16)};
+              xb = f2{(float)((int)c >> 16), (float)((int)d >> 16)};
+            }
+          } else {   // C, LFE: a mono run, the 16-bit form's conversion below
+            asm volatile("" : "+v"(x[m].x), "+v"(x[m].y));
+            const unsigned pa = x[m].x, pb = x[m].y;
+            xa = f2{(float)(int)(short)(pa & 0xffffu), (float)((int)pa >> 16)};
+            xb = f2{(float)(int)(short)(pb & 0xffffu), (float)((int)pb >> 16)};
+          }
+        } else if constexpr (LP) {
           asm volatile("" : "+v"(x[m].x), "+v"(x[m].y));
           const unsigned pa = x[m].x, pb = x[m].y;   // (the scale 2^-15 sits in the weights: see where `mat` is filled)
           xa = f2{(float)(int)(short)(pa & 0xffffu), (float)((int)pa >> 16)};
@@ -314,8 +422,14 @@ __global__ __launch_bounds__(256, K <= 3 ? 2 : 1) void render_fanout_kernel(cons
           prj[2 * c] = prj[2 * c] + w2 * xa;
           prj[2 * c + 1] = prj[2 * c + 1] + w2 * xb;
         }
-        // channel m's registers are free: its samples of the next chunk are requested now
-        load_one(m, pf_f, pf_i, rs_pf);
+        // channel m's registers are free: its samples of the next chunk are requested now (LPC: a pair's, once its SECOND
+        // channel has been consumed)
+        if constexpr (LPC) {
+          if (!lpcm_coupled_paired(M, m)) load_one(m, pf_f, pf_i, rs_pf);
+          else if (m & 1) load_one(m - 1, pf_f, pf_i, rs_pf);
+        } else {
+          load_one(m, pf_f, pf_i, rs_pf);
+        }
       }
     }
 

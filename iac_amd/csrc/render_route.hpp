@@ -112,6 +112,21 @@ using RaggedOC = Ints<1, 2>;
 // elements are the only ones whose channels are contiguous 16-bit runs), K within FanK
 using FanLpM = Ints<4, 9, 16>;
 using FanLpK = Ints<2, 3, 4>;
+// render_fanout_kernel<M, K, LP, LPB, LPC>: the fan-out fed with the other three packet forms of lpcm_form.hpp
+// (iamf_hip_batch_render_fanout_packets), one list of (M, K) pairs — mc(m, k) — per form and translation unit: 24-bit
+// mono-coded ambisonics (S24: FanLpM), coupled 5.1 / 7.1 / 5.1.4 / 7.1.4 with 16-bit (S16C) and 24-bit samples (S24C), K within
+// FanK.  Stereo is left out: its 4 or 6 bytes per sample-frame are less than what its members write.  Every instance listed
+// runs without scratch and without a vector spill under the kernel's launch bounds (DESIGN.md 4.1n has the table); one that
+// stops doing so is taken out of its list here, and the listing, the host rule and the tests follow.
+using FanPk24MK = Ints<mc(4, 2), mc(4, 3), mc(4, 4), mc(9, 2), mc(9, 3), mc(9, 4), mc(16, 2), mc(16, 3), mc(16, 4)>;
+using FanPk16cMK = Ints<mc(6, 2), mc(6, 3), mc(6, 4), mc(8, 2), mc(8, 3), mc(8, 4), mc(10, 2), mc(10, 3), mc(10, 4), mc(12, 2), mc(12, 3), mc(12, 4)>;
+using FanPk24cMK = FanPk16cMK;
+// variant of an IAMF_HIP_ROUTE_FANOUT_PACKETS row: bit 0 = 24-bit samples, bit 1 = coupled pairs (1 / 2 / 3 = S24 / S16C / S24C)
+IAMF_HD constexpr int fan_pk_variant(int lpb, bool lpc) { return (lpb == 3 ? 1 : 0) | (lpc ? 2 : 0); }
+// whether the form `variant` has an instance for an element of m channels into k members
+IAMF_HD constexpr bool fan_pk_has(int variant, int m, int k) {
+  return variant == 1 ? FanPk24MK::has(mc(m, k)) : (variant == 2 ? FanPk16cMK::has(mc(m, k)) : (variant == 3 && FanPk24cMK::has(mc(m, k))));
+}
 // the HRTF stage: ambisonics elements (iamf_render.hip) and channel-based ones, the loudspeaker layouts' channel counts
 // (iamf_render_fir_m2b.hip)
 using FirHomeM = Ints<1, 4, 9, 16>;
@@ -904,6 +919,14 @@ void for_each_render_instance_nolim_packets_mix(F &&f) {
     for_each_packet_m([&](int m) { for_each_int(LpcmMixK{}, [&](int k) { f(IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX, v, m, 0, k); }); });
 }
 
+// The fan-out fed with 24-bit and coupled packets: the three forms' (M, K) lists, variant = fan_pk_variant, k = members.
+template <class F>
+void for_each_render_instance_fanout_packets(F &&f) {
+  for_each_int(FanPk24MK{}, [&](int v) { f(IAMF_HIP_ROUTE_FANOUT_PACKETS, fan_pk_variant(3, false), mc_m(v), 0, mc_c(v)); });
+  for_each_int(FanPk16cMK{}, [&](int v) { f(IAMF_HIP_ROUTE_FANOUT_PACKETS, fan_pk_variant(2, true), mc_m(v), 0, mc_c(v)); });
+  for_each_int(FanPk24cMK{}, [&](int v) { f(IAMF_HIP_ROUTE_FANOUT_PACKETS, fan_pk_variant(3, true), mc_m(v), 0, mc_c(v)); });
+}
+
 // The row sets behind the listing, by number: f as above for every instance of set `set`, no row for any other number.  Sets
 // 0 .. kRouteTables - 1 are the numbered tables of iamf_hip_route_table_instances — their count and the rows of each are pinned —
 // and the sets behind them are listed by family only (iamf_hip_route_family_instances), in this order.  The only place that maps
@@ -927,6 +950,18 @@ void for_each_instance_of_set(int set, F &&f) {
     case 10: for_each_render_instance_packets_mix_ragged(f); break;
     case 11: for_each_render_instance_nolim_packets(f); break;
     case 12: for_each_render_instance_nolim_packets_mix(f); break;
+  }
+}
+// Row sets behind those: kernels that no call of pick_route names (the fan-out entry decides for itself) and that were added
+// after the rows of the sets above had been counted by their callers (tests/golden/route_sweep.txt counts the rows of sets
+// 0 .. kRouteSets - 1 that pick_route does not name).  Set kRouteSets + i is walked by for_each_instance_of_later_set(i, f);
+// iamf_route.hip builds, lists (by family only) and counts these exactly as the sets above.
+constexpr int kRouteLaterSets = 1;
+constexpr int kRouteSetFanoutPackets = kRouteSets + 0;   // what the fan-out entry counts its packet launch in (it has no Route to ask)
+template <class F>
+void for_each_instance_of_later_set(int i, F &&f) {
+  switch (i) {
+    case 0: for_each_render_instance_fanout_packets(f); break;
   }
 }
 

@@ -115,7 +115,10 @@ ROUTE_FAMILY_LATER = dict(PACKETS_RAGGED=37)
 ROUTE_FAMILY_NEWER = dict(PACKETS_MIX_RAGGED=39)
 # (and that one: families added from here on go into this dict, which no caller pins)
 ROUTE_FAMILY_OPEN = dict(NOLIM_PACKETS=43, NOLIM_PACKETS_MIX=47)
-_ROUTE_NAME_MORE = {v: k for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER, ROUTE_FAMILY_OPEN) for k, v in names.items()}
+# (the fan-out families added behind the single-call ones)
+ROUTE_FAMILY_FANOUT = dict(FANOUT_PACKETS=51)
+_ROUTE_NAME_MORE = {v: k for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER, ROUTE_FAMILY_OPEN, ROUTE_FAMILY_FANOUT)
+                    for k, v in names.items()}
 
 
 def _family_name(fam):
@@ -195,6 +198,9 @@ def lib():
         L.iamf_hip_batch_render_fanout_lpcm.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(LpcmInput), C.c_int32, C.c_int32,
                                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.c_int32, C.c_int32,
                                                         C.POINTER(C.c_int32), C.POINTER(FanoutReport)]
+        L.iamf_hip_batch_render_fanout_packets.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(PacketCall), C.POINTER(C.c_void_p),
+                                                           C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                           C.POINTER(FanoutReport)]
         L.iamf_hip_batch_reset.argtypes = [C.c_void_p]
         L.iamf_hip_batch_render_range.argtypes = [C.c_void_p, C.POINTER(RenderArgs), C.c_int32, C.c_int32]
         L.iamf_hip_batch_flush_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32]
@@ -409,7 +415,7 @@ def _family_id(family):
         for names in (ROUTE, ROUTE_BY_FAMILY_ONLY):
             if family in names:
                 return names[family]
-        for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER):
+        for names in (ROUTE_FAMILY_MORE, ROUTE_FAMILY_LATER, ROUTE_FAMILY_NEWER, ROUTE_FAMILY_FANOUT):
             if family in names:
                 return names[family]
         return ROUTE_FAMILY_OPEN[family]
@@ -502,6 +508,30 @@ def render_fanout_lpcm(batches, lpcm_input, n_frames, d_pcms, pcm_strides, strea
                                                 n_streams, emitted, C.byref(rep))
     if r < 0:
         raise IamfHipError(r, "iamf_hip_batch_render_fanout_lpcm")
+    return list(emitted[:n]), (rep.n_fused, rep.input_fused, rep.n_unpacks)
+
+
+def render_fanout_packets(batches, lpcm_input, n_frames, d_pcms, pcm_strides, stream=None, n_samples=0, stream0=0, n_streams=None,
+                          report=None):
+    """iamf_hip_batch_render_fanout_packets: render_fanout_lpcm with leave to read 24-bit and coupled packets in the shared
+    launch (the FANOUT_PACKETS family); every member is left as its own iamf_hip_batch_render_packets call leaves it.  The
+    same arguments and the same return value: (n_emitted per member, (n_fused, input_fused, n_unpacks))."""
+    n = len(batches)
+    if len(d_pcms) != n or len(pcm_strides) != n:
+        raise ValueError("render_fanout_packets: one PCM buffer and one stride per batch")
+    if n_streams is None:
+        n_streams = batches[0].cfg.n_streams if n else 1
+    hs = (C.c_void_p * n)(*[b.h for b in batches])
+    pcms = (C.c_void_p * n)(*d_pcms)
+    strides = (C.c_int64 * n)(*pcm_strides)
+    emitted = (C.c_int32 * max(n, 1))()
+    rep = FanoutReport() if report is None else report
+    call = PacketCall()     # the entry's call block: the packets, and of the args the frames, the samples and the stream
+    call.in_ = lpcm_input
+    call.args.n_frames, call.args.n_samples, call.args.stream = n_frames, n_samples, stream
+    r = lib().iamf_hip_batch_render_fanout_packets(hs, n, C.byref(call), pcms, strides, stream0, n_streams, emitted, C.byref(rep))
+    if r < 0:
+        raise IamfHipError(r, "iamf_hip_batch_render_fanout_packets")
     return list(emitted[:n]), (rep.n_fused, rep.input_fused, rep.n_unpacks)
 
 

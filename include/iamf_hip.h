@@ -954,7 +954,8 @@ int iamf_hip_batch_render_packets_mix_nolim(iamf_hip_batch *b, const iamf_hip_pa
  *
  * Errors: those of iamf_hip_batch_render_fanout_range plus those of iamf_hip_batch_render_lpcm_range.  Every argument and
  * state check runs before the first launch; a refused call changes no member and writes neither n_emitted nor *report.
- * The count, NULL and n_streams <= 0 checks need no device. */
+ * The count, NULL and n_streams <= 0 checks need no device.
+ * (24-bit packets and coupled 5.1 / 7.1 / 7.1.4 elements are read once by iamf_hip_batch_render_fanout_packets, below.) */
 typedef struct iamf_hip_fanout_report {
   int32_t n_fused;      /* members the shared launch rendered: 0 or 2..IAMF_HIP_FANOUT_MAX (the packet launch's where both
                            a packet launch and an f32 launch ran) */
@@ -966,6 +967,43 @@ int iamf_hip_batch_render_fanout_lpcm(iamf_hip_batch *const *batches, int32_t n_
                                       int32_t n_frames, int32_t n_samples, void *const *d_pcm,
                                       const int64_t *pcm_stream_stride_bytes, void *stream, int32_t stream0, int32_t n_streams,
                                       int32_t *n_emitted /* host, [n_batches] */, iamf_hip_fanout_report *report /* may be NULL */);
+
+/* The same for every packet form a fused kernel reads: iamf_hip_batch_render_fanout for the input form of
+ * iamf_hip_batch_render_packets.  It takes that entry's call block, as every packet entry since does — the packets in call->in,
+ * and of call->args n_frames, n_samples and stream; every other field of call->args is NULL / 0 (the members' PCM buffers travel
+ * beside the block, one per member), as are the reserved words — and otherwise the parameters of
+ * iamf_hip_batch_render_fanout_lpcm.
+ *
+ * Meaning: for every j the call leaves batches[j], d_pcm[j] and n_emitted[j] exactly as
+ *   iamf_hip_batch_render_packets(batches[j], &call_j, stream0, n_streams)
+ * with call_j = *call but args.d_pcm = d_pcm[j], args.pcm_stream_stride_bytes = pcm_stream_stride_bytes[j] would, called for j = 0 .. in turn:
+ * bit for bit, PCM and persisted stream state.  The entry is total — it takes every call the entry above takes — and may be
+ * mixed freely with it, the f32 fan-out and the single-batch calls on the same batches.
+ *
+ * What runs is decided from what the call can observe, in this order:
+ *   1. Where the packets have the 24-bit mono-coded, the coupled 16-bit or the coupled 24-bit form (little-endian; what
+ *      iamf_hip_batch_render_packets fuses), a member is packet-fusable when its single call would run that form's packet-fed
+ *      kernel (IAMF_HIP_ROUTE_LPCM24 / _LPCM_COUPLED / _LPCM24_COUPLED), nothing is re-laid behind the kernel (no fixed PCM
+ *      channel stride) and the element has 4, 9 or 16 channels (24-bit mono-coded) or 6, 8, 10 or 12 (coupled).  Two or more such
+ *      members share one launch (IAMF_HIP_ROUTE_FANOUT_PACKETS) that reads the packets once: 3 * M (2 * M) + sum of the
+ *      members' output bytes per sample-frame instead of 3 * M (2 * M) per member.  *report: input_fused = 1.  How many share
+ *      it at a given number of streams follows a measured rule (a size at which the launch does not beat the
+ *      single calls is not fused); the members left over go by 2.
+ *   2. A remaining member whose single call runs a packet-fed kernel gets that call.
+ *   3. Every other member takes the path of iamf_hip_batch_render_fanout_lpcm: one unpack pass and the f32 fan-out.
+ *   4. A call whose packets have the 16-bit mono-coded form or none a kernel reads (big-endian, 32 bit, a loudspeaker layout as
+ *      mono sub-streams, runs off the grid, a call that is not whole 64-sample blocks) is iamf_hip_batch_render_fanout_lpcm's,
+ *      whole: its routes, its report.
+ * Not fused (out of scope): stereo elements, members of more than two output channels, calls that are not whole 64-sample
+ * blocks.  IAMF_HIP_FANOUT_PACKETS_UNFUSED=1 forces the path of iamf_hip_batch_render_fanout_lpcm for every call, and
+ * IAMF_HIP_LPCM_UNFUSED=1 the unpacker and the f32 kernels, as everywhere.
+ *
+ * Errors, the order of the checks and *report: as iamf_hip_batch_render_fanout_lpcm, a NULL call block, a non-zero reserved word
+ * or a field of call->args other than the three named answering IAMF_HIP_ERR_BAD_ARG behind the member count.  Every check runs
+ * before the first launch; a refused call changes no member and writes neither n_emitted nor *report. */
+int iamf_hip_batch_render_fanout_packets(iamf_hip_batch *const *batches, int32_t n_batches, const iamf_hip_packet_call *call,
+                                         void *const *d_pcm, const int64_t *pcm_stream_stride_bytes, int32_t stream0, int32_t n_streams,
+                                         int32_t *n_emitted /* host, [n_batches] */, iamf_hip_fanout_report *report /* may be NULL */);
 
 /* Host -> device by a kernel that reads pinned host memory (hipHostMalloc) over PCIe, 16 bytes per lane: the bytes of a
  * hipMemcpyAsync without leaving the compute queue, for callers that put a small upload between kernels (a pinned
@@ -1024,6 +1062,9 @@ int iamf_hip_deinterleave_f32(const float *d_src, int64_t src_stream_stride, int
  *                          coded runs, 2: one coupled pair); c 0 (iamf_hip_route_family_instances only)
  *     FANOUT               m, k = members of the fused launch
  *     FANOUT_LPCM          m, k = members of the fused launch (extension table: iamf_hip_route_instances_ext)
+ *     FANOUT_PACKETS       the fan-out fed with 24-bit or coupled packets (iamf_hip_batch_render_fanout_packets): m, k = members
+ *                          of the fused launch; variant bit 0 = 24-bit samples, bit 1 = coupled pairs (1 / 2 / 3 = 24-bit
+ *                          mono-coded / 16-bit coupled / 24-bit coupled); c 0 (iamf_hip_route_family_instances only)
  *     FIR_SPLIT            m (the FFT stage as its own kernel; the FAST <2, 2> launch behind it is counted as FAST)
  *     FIR_FUSED            variant = stage (3 FFT, 2 split-f16 MFMA, 1 f32 MFMA), m
  *     RS_PLAIN             resample_kernel
@@ -1063,7 +1104,8 @@ enum {
   IAMF_HIP_ROUTE_PACKETS_RAGGED = 37,    /* no table either (34, 35 and 36 stay unused) */
   IAMF_HIP_ROUTE_PACKETS_MIX_RAGGED = 39, /* no table either (38 stays unused) */
   IAMF_HIP_ROUTE_NOLIM_PACKETS = 43,     /* no table either (40, 41 and 42 stay unused) */
-  IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX = 47  /* no table either (44, 45 and 46 stay unused) */
+  IAMF_HIP_ROUTE_NOLIM_PACKETS_MIX = 47, /* no table either (44, 45 and 46 stay unused) */
+  IAMF_HIP_ROUTE_FANOUT_PACKETS = 51     /* no table either (48, 49 and 50 stay unused) */
 };
 typedef struct {
   int32_t family, variant, m, c, k;
@@ -1096,7 +1138,7 @@ int iamf_hip_route_table_tally(int table, iamf_hip_route_row *rows, int cap, int
  * _tally: the rows launched since their last reset (reset != 0 clears them).  Both return the number of such rows and
  * fill at most cap of them (rows may be NULL); -1 for a family no instance belongs to.  No GPU needed.  LPCM_MIX is listed
  * the same way: rows and counters of its own, in no table; so are FAST_INTERLEAVED, FAST_RAGGED, LPCM24_COUPLED,
- * LPCM24_MIX, PACKETS_RAGGED, PACKETS_MIX_RAGGED, NOLIM_PACKETS and NOLIM_PACKETS_MIX. */
+ * LPCM24_MIX, PACKETS_RAGGED, PACKETS_MIX_RAGGED, NOLIM_PACKETS, NOLIM_PACKETS_MIX and FANOUT_PACKETS. */
 int iamf_hip_route_family_instances(int family, iamf_hip_route_row *rows, int cap);
 int iamf_hip_route_family_tally(int family, iamf_hip_route_row *rows, int cap, int reset);
 
